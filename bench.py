@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: Mrays/s (primary + bounce + shadow rays) on the Cornell box.
 
-  python bench.py --gpus 1 --steps K --warmup W [--config c2|c3|c4|c5]
+  python bench.py --gpus 1 --steps K --warmup W [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
   python bench.py --gpus N ...                      (N > 1, no launcher: ONE process, one context + host thread per GPU -- trg_group_*)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W     (one process per GPU, torch.distributed over RCCL)
@@ -13,7 +13,13 @@ configs[4] on one GPU.  One STEP = one pass of the hot path over the whole frame
 bounces x [nearest, shade, shadow] -> accumulate for all samples) and, for N > 1, one RCCL all-gather of the row bands.
 The frame is fixed, so N > 1 is STRONG scaling: rank g renders its band of rows.
 
-Rank 0 prints ONE JSON line of about 3 KB.  `value` counts rays actually traversed (in-kernel counters), inputs resident in HBM
+A plain run does only what the headline needs: set up, warm up, time the K steps, print one short JSON line (metric, value, unit,
+ms_per_step = wall milliseconds per timed step, dtype, config).  `--dump-outputs DIR` then writes the frame of the last timed step
+(DIR/frame.npy, float32 [h, w, 4]; inputs are seeded, so two builds can be compared output for output).  Everything below -- the
+roofline with its counters pass and launches alone, the other exchanges, the secondary legs, the plugin leg, the CPU baseline and the
+side file -- is measured with `--full` only.
+
+With `--full`, rank 0 prints ONE JSON line of about 3 KB.  `value` counts rays actually traversed (in-kernel counters), inputs resident in HBM
 before the timed region.  The driver's record keeps the SCALAR values directly under `config`, `roofline` and `cpu_baseline` (nested
 objects and long strings are dropped: BENCH_r04.parsed), so everything a reader needs to recompute a fraction is a flat scalar there:
   * `roofline`: the headline's binding resource -- bound, achieved, peak, unit, frac, traffic -- and beside it valu_insts_per_launch,
@@ -323,8 +329,32 @@ def kernel_name(st, in_lds):
     return k + ("<LDS>" if in_lds else "<HBM>") + ("+head/tail from bounce %d" % st.last_tail_bounce if st.last_tail_bounce else "") + " fast build"
 
 
-def run_torch(config_name, steps, warmup, env, use_imported=True, gpu_build=None):
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+DUMP_SEED = 0x5EED0002
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as <path>/<name>.npy in float32 / float64.  An array larger than its share of DUMP_BUDGET_BYTES is
+    replaced by a fixed, seeded sample of its rows (the same rows every run), <name>_rows.npy names them."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+            # (half the share: room for the row indices beside the sample)
+            k = max(1, (share // 2) // (rows.shape[1] * a.itemsize + 8))
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], size=k, replace=False))
+            np.save(os.path.join(path, "%s_rows.npy" % name), idx.astype(np.float64))
+            a = rows[idx]
+        np.save(os.path.join(path, "%s.npy" % name), a)
+
+
+def run_torch(config_name, steps, warmup, env, use_imported=True, gpu_build=None, full=True, dump=None):
     """One configuration on this process' GPU (N = 1) or on its row band (one process per GPU under torch.distributed.run).
+    full=False: only what the headline needs (no counters pass, no launches alone, no second exchange timings, no roofline).
+    dump = a directory: rank 0 writes the frame of the last timed step there (dump_outputs).
     Returns (result dict, detail dict) on rank 0, (None, None) elsewhere."""
     import torch
     from toyraygun_amd import capi
@@ -355,16 +385,17 @@ def run_torch(config_name, steps, warmup, env, use_imported=True, gpu_build=None
             dist.barrier()
             torch.cuda.synchronize(dev)
 
-    # counters pass (untimed): algorithmic bytes per ray for the roofline object
-    r.ctx.set_option(capi.OPT_TIMING, 1)
-    r.ctx.set_option(capi.OPT_COUNTERS, 1)
-    r.ctx.reset_stats()
-    r.launch_band(0, SPP, BOUNCES)
-    cst = r.ctx.stats()
-    bytes_per_ray, mix = algorithmic_bytes_per_ray(cst, r.owned_rows * W * SPP)
-    rays_per_launch = cst.rays
-    lane_util_nodes = cst.node_fetches / (64.0 * cst.wave_node_iters * (1 if cst.scene_in_lds else 2)) if cst.wave_node_iters else None
-    r.ctx.set_option(capi.OPT_COUNTERS, 0)
+    if full:
+        # counters pass (untimed): algorithmic bytes per ray for the roofline object
+        r.ctx.set_option(capi.OPT_TIMING, 1)
+        r.ctx.set_option(capi.OPT_COUNTERS, 1)
+        r.ctx.reset_stats()
+        r.launch_band(0, SPP, BOUNCES)
+        cst = r.ctx.stats()
+        bytes_per_ray, mix = algorithmic_bytes_per_ray(cst, r.owned_rows * W * SPP)
+        rays_per_launch = cst.rays
+        lane_util_nodes = cst.node_fetches / (64.0 * cst.wave_node_iters * (1 if cst.scene_in_lds else 2)) if cst.wave_node_iters else None
+        r.ctx.set_option(capi.OPT_COUNTERS, 0)
 
     gather = distributed or bool(os.environ.get("TRG_FORCE_GATHER"))
     # untimed priming: one step per render stream, so that every stream's per-launch scratch (traversal-stack overflow, tail-compaction
@@ -375,18 +406,20 @@ def run_torch(config_name, steps, warmup, env, use_imported=True, gpu_build=None
     for _ in range(warmup):
         r.render(0, SPP, BOUNCES, gather=gather)
     sync_all()
-    # launch duration of the megakernel when it runs ALONE: HIP events on the stream it runs on (trg_render brackets the
-    # launch with hipEventRecord on the context's stream), 3 launches -- the event wait is a host sync, which would
-    # serialise the pipeline inside the timed region (and there several launches overlap on purpose).
-    r.ctx.reset_stats()
-    for _ in range(3):
-        r.launch_band(0, SPP, BOUNCES)
-    pst = r.ctx.stats()
-    kernel_ms_alone = pst.total_render_ms / max(pst.renders, 1)
+    kernel_ms_alone = None
+    if full:
+        # launch duration of the megakernel when it runs ALONE: HIP events on the stream it runs on (trg_render brackets the
+        # launch with hipEventRecord on the context's stream), 3 launches -- the event wait is a host sync, which would
+        # serialise the pipeline inside the timed region (and there several launches overlap on purpose).
+        r.ctx.reset_stats()
+        for _ in range(3):
+            r.launch_band(0, SPP, BOUNCES)
+        pst = r.ctx.stats()
+        kernel_ms_alone = pst.total_render_ms / max(pst.renders, 1)
     r.ctx.set_option(capi.OPT_TIMING, 0)
     sync_all()
     r.ctx.reset_stats()
-    r.time_launches = True   # HIP events around every launch, on the stream it runs on, no host sync
+    r.time_launches = full   # HIP events around every launch, on the stream it runs on, no host sync (the roofline's launch times)
     # THE TIMED REGION: `steps` steps, the exchange north_star names behind each (N > 1: the gather of the bands to rank 0, overlapping the
     # renders that follow)
     t0 = time.perf_counter()
@@ -397,6 +430,12 @@ def run_torch(config_name, steps, warmup, env, use_imported=True, gpu_build=None
     r.time_launches = False
     launch_ms = r.launch_ms()
     st = r.ctx.stats()
+    if dump and rank == 0:
+        # the frame of the last timed step (rank 0 holds the whole frame: N = 1, or the gather to the root), before anything renders again
+        dump_outputs(dump, {"frame": r.frame.cpu().numpy()})
+    if not full:
+        cst = st
+        rays_per_launch = st.rays / max(steps, 1)
 
     def timed_again(mode):   # the same steps with another exchange, after the timed region: reported beside the headline
         t1 = time.perf_counter()
@@ -404,8 +443,8 @@ def run_torch(config_name, steps, warmup, env, use_imported=True, gpu_build=None
             r.render(0, SPP, BOUNCES, gather=mode)
         sync_all()
         return time.perf_counter() - t1
-    dt_all = timed_again("all") if gather else None
-    dt_none = timed_again(False) if gather else None
+    dt_all = timed_again("all") if (gather and full) else None
+    dt_none = timed_again(False) if (gather and full) else None
 
     rays_local = float(st.rays)
     # average launch duration over the timed region (what rocprofv3 --kernel-trace reports for the same command).  With
@@ -422,7 +461,7 @@ def run_torch(config_name, steps, warmup, env, use_imported=True, gpu_build=None
         tsum = t.clone()
         dist.all_reduce(tsum, op=dist.ReduceOp.SUM)
         # the slowest rank's band: its device time per launch and ITS rays (for the derived roofline)
-        mine = torch.tensor([kernel_ms / concurrency, band_rays, kernel_ms, concurrency, kernel_ms_alone], dtype=torch.float64, device="cpu" if cpu else dev)
+        mine = torch.tensor([kernel_ms / concurrency, band_rays, kernel_ms, concurrency, kernel_ms_alone or 0.0], dtype=torch.float64, device="cpu" if cpu else dev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         slow = max(range(world), key=lambda k: float(allr[k][0]))
@@ -438,8 +477,10 @@ def run_torch(config_name, steps, warmup, env, use_imported=True, gpu_build=None
     out, detail = None, None
     if rank == 0:
         in_lds = bool(cst.scene_in_lds)
-        rf, rf_detail = build_roofline(config_name, cst, band_rays, bytes_per_ray, mix, kernel_ms, concurrency, kernel_eff_ms, kernel_ms_alone, lane_util_nodes,
-                                       use_imported=use_imported, derive=(band_rays, frame_rays) if world > 1 else None)
+        rf, rf_detail = None, None
+        if full:
+            rf, rf_detail = build_roofline(config_name, cst, band_rays, bytes_per_ray, mix, kernel_ms, concurrency, kernel_eff_ms, kernel_ms_alone, lane_util_nodes,
+                                           use_imported=use_imported, derive=(band_rays, frame_rays) if world > 1 else None)
         builder = {0: "host SAH", 1: "device binned SAH", 2: "device LBVH", 3: "device PLOC"}[gpu_build]
         config = {"workload": cfg["short"], "name": config_name, "rays_per_step": rays_total / steps,
                   "sharding": ("none" if not distributed else "%s bands, 1 process/GPU, %s gather to rank 0 per frame" % ("interleaved 8-row" if r.interleaved else "contiguous row", "gloo (host memory: rehearsal)" if env.get("backend") == "gloo" else "RCCL")),
@@ -449,9 +490,10 @@ def run_torch(config_name, steps, warmup, env, use_imported=True, gpu_build=None
                   # geometry-specific leaves, said next to the number: parallelogram pairs tested as one quad, addCube groups that are one box leaf (LDS scenes)
                   "quads": int(cst.bvh_quads), "box_leaves": int(cst.bvh_boxes)}
         if gather:
-            config.update({"exchange": "root gather" if r.gather_mode == "root" else "all-gather",
-                           "gather_root_ms_per_step": sig(max(0.0, (dt - dt_none) / steps * 1e3)), "gather_all_ms_per_step": sig(max(0.0, (dt_all - dt_none) / steps * 1e3)),
-                           "ms_per_step_all_gather": sig(dt_all / steps * 1e3), "ms_per_step_without_gather": sig(dt_none / steps * 1e3)})
+            config["exchange"] = "root gather" if r.gather_mode == "root" else "all-gather"
+            if full:
+                config.update({"gather_root_ms_per_step": sig(max(0.0, (dt - dt_none) / steps * 1e3)), "gather_all_ms_per_step": sig(max(0.0, (dt_all - dt_none) / steps * 1e3)),
+                               "ms_per_step_all_gather": sig(dt_all / steps * 1e3), "ms_per_step_without_gather": sig(dt_none / steps * 1e3)})
             if distributed and env.get("backend") != "gloo":
                 try:
                     v = torch.cuda.nccl.version()
@@ -464,8 +506,10 @@ def run_torch(config_name, steps, warmup, env, use_imported=True, gpu_build=None
             "value": sig(rays_total / dt / 1e6, 7), "unit": "Mrays/s", "n_gpus": world, "steps": steps, "warmup": warmup,
             "ms_per_step": sig(dt / steps * 1e3, 6), "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": config, "roofline": rf,
+            "config": config,
         }
+        if full:
+            out["roofline"] = rf
         detail = {"workload": cfg["workload"], "roofline": rf_detail,
                   "pipeline": "frames in flight on alternating streams: later steps fill the CUs the tail of step k leaves idle (roofline.kernel_ms = average launch duration "
                               "while they overlap; kernel_alone_ms = one launch by itself)",
@@ -474,12 +518,14 @@ def run_torch(config_name, steps, warmup, env, use_imported=True, gpu_build=None
     return out, detail
 
 
-def run_group(args, n=None, use_imported=False):
+def run_group(args, n=None, use_imported=False, full=True):
     """`--gpus N` without a launcher: ONE process, trg_group_* (one context + one host thread per device, row bands, one
     in-place ncclAllGather per frame over xGMI).  Same method as the N = 1 headline (run_torch): TRG_PIPE_DEPTH (4) frames in flight per
     device -- frame i renders on stream i % 4 into buffer i % 4, its exchange follows on the device's exchange stream and overlaps the
     renders behind it (trg_group_set_pipeline) -- HIP events around every launch on its own stream, no host sync inside the timed
-    region.  Same JSON line; `config.bands` carries what each rank did: rays, the band's launch alone, its launches in the pipeline."""
+    region.  Same JSON line; `config.bands` carries what each rank did: rays, the band's launch alone, its launches in the pipeline.
+    full=False: the counters pass (rays per step) and the timed gather only -- no launches alone, no second exchange timings, no roofline.
+    args.dump_outputs = a directory: the frame of the last timed step on device 0 is written there (dump_outputs)."""
     import torch   # device count only: nothing here initialises the GPU before the library does
     from toyraygun_amd import capi
     n = n or args.gpus
@@ -512,15 +558,16 @@ def run_group(args, n=None, use_imported=False):
         rays_per_step = float(cst.rays)
         per_rank_rays = g.rank_rays()
         g.set_option(capi.OPT_COUNTERS, 0)
-        # every band's launch ALONE on its device (HIP events around the launch; the ranks run at the same time, each on its own GPU)
-        g.reset_stats()
-        for _ in range(3):
-            g.render(0, SPP, BOUNCES, capi.GATHER_NONE)
-        alone = []
-        for r in range(n):
-            st = g.rank_stats(r)
-            alone.append(st.total_render_ms / max(st.renders, 1))
-        kernel_ms_alone = max(alone)
+        alone = None
+        if full:
+            # every band's launch ALONE on its device (HIP events around the launch; the ranks run at the same time, each on its own GPU)
+            g.reset_stats()
+            for _ in range(3):
+                g.render(0, SPP, BOUNCES, capi.GATHER_NONE)
+            alone = []
+            for r in range(n):
+                st = g.rank_stats(r)
+                alone.append(st.total_render_ms / max(st.renders, 1))
         depth = 1 if os.environ.get("TRG_BENCH_SERIAL") else int(os.environ.get("TRG_PIPE_DEPTH", "4"))
         g.set_option(capi.OPT_TIMING, 0)          # asynchronous from here on: a step only enqueues
         g.set_pipeline(depth)
@@ -544,13 +591,35 @@ def run_group(args, n=None, use_imported=False):
         # over N - 1 independent xGMI links) -- behind every step; the in-place all-gather and no exchange at all are timed after it and reported beside it
         timed(capi.GATHER_ROOT, max(args.warmup, 1))
         g.reset_stats()
-        dt = timed(capi.GATHER_ROOT, args.steps, timeit=True)
-        launch = [g.launch_ms(r) for r in range(n)]
-        dt_all = timed(capi.GATHER_ALL, args.steps)
-        dt_nogather = timed(capi.GATHER_NONE, args.steps)
+        dt = timed(capi.GATHER_ROOT, args.steps, timeit=full)
+        if getattr(args, "dump_outputs", None):
+            # the frame of the last timed step, gathered to device 0 (before anything renders again)
+            dump_outputs(args.dump_outputs, {"frame": g.read_accum(0)})
         in_lds = bool(cst.scene_in_lds)
         exchange = g.exchange
         st0 = g.rank_stats(0)
+        rccl = g.rccl_info()   # {"version", "ranks": [ncclCommCount per communicator]} -- None without communicators (one device, copy exchange)
+        xname = {capi.EXCHANGE_RCCL: "rccl", capi.EXCHANGE_COPY: "copy"}.get(exchange, "none")
+        config = {"workload": cfg["short"], "name": args.config, "rays_per_step": rays_per_step,
+                  "sharding": "1 process, trg_group: %d contexts + host threads, %s bands" % (n, "interleaved 8-row" if interleaved else "contiguous ceil(h/N)-row"),
+                  "pipeline": "%d frames in flight per device, exchange on its own stream" % depth if depth > 1 else "serial launches",
+                  "exchange": xname, "exchange_mode": "root gather (ncclSend/ncclRecv to device 0)" if xname == "rccl" else ("root gather (peer copies)" if xname == "copy" else "none"),
+                  "rccl_version": rccl["version"] if rccl else None, "rccl_ranks": min(rccl["ranks"]) if rccl else None,
+                  "devices": ",".join(str(d) for d in devices), "shared_device": shared,
+                  "kernel": ("bands of: " if n > 1 else "") + kernel_name(st0, in_lds),
+                  "triangles": int(len(buffers["material_ids"])), "scene_bytes": int(cst.scene_bytes)}
+        out = {
+            "metric": "Mrays/s (primary+shadow+bounce) at %dx%d" % (W, H),
+            "value": sig(rays_per_step * args.steps / dt / 1e6, 7), "unit": "Mrays/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": sig(dt / args.steps * 1e3, 6), "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": config,
+        }
+        if not full:
+            return out, {"workload": cfg["workload"], "kernel": ("per-band launches of: " if n > 1 else "") + kernel_name_long(st0, in_lds)}
+        launch = [g.launch_ms(r) for r in range(n)]
+        dt_all = timed(capi.GATHER_ALL, args.steps)
+        dt_nogather = timed(capi.GATHER_NONE, args.steps)
         piped = [sum(l) / max(len(l), 1) for l in launch]               # mean launch duration per rank while its frames overlap
         conc = [max(1.0, sum(l) / (dt * 1e3)) for l in launch]          # launches of a rank in flight on average
         eff = [p / c for p, c in zip(piped, conc)]                      # device time per launch and rank
@@ -561,27 +630,12 @@ def run_group(args, n=None, use_imported=False):
         def spread(v):
             m = sum(v) / len(v)
             return {"per_rank": [round(x, 4) for x in v], "slowest": max(v), "mean": m, "max_over_mean": (max(v) / m) if m > 0 else None}
-        rccl = g.rccl_info()   # {"version", "ranks": [ncclCommCount per communicator]} -- None without communicators (one device, copy exchange)
-        xname = {capi.EXCHANGE_RCCL: "rccl", capi.EXCHANGE_COPY: "copy"}.get(exchange, "none")
-        config = {"workload": cfg["short"], "name": args.config, "rays_per_step": rays_per_step,
-                  "sharding": "1 process, trg_group: %d contexts + host threads, %s bands" % (n, "interleaved 8-row" if interleaved else "contiguous ceil(h/N)-row"),
-                  "pipeline": "%d frames in flight per device, exchange on its own stream" % depth if depth > 1 else "serial launches",
-                  "exchange": xname, "exchange_mode": "root gather (ncclSend/ncclRecv to device 0)" if xname == "rccl" else ("root gather (peer copies)" if xname == "copy" else "none"),
-                  "rccl_version": rccl["version"] if rccl else None, "rccl_ranks": min(rccl["ranks"]) if rccl else None,
-                  "devices": ",".join(str(d) for d in devices), "shared_device": shared,
+        config.update({
                   "gather_root_ms_per_step": sig(max(0.0, (dt - dt_nogather) / args.steps * 1e3)),
                   "gather_all_ms_per_step": sig(max(0.0, (dt_all - dt_nogather) / args.steps * 1e3)),
                   "ms_per_step_all_gather": sig(dt_all / args.steps * 1e3), "ms_per_step_without_gather": sig(dt_nogather / args.steps * 1e3),
-                  "band_ms_slowest": sig(max(eff)), "band_ms_max_over_mean": sig(max(eff) / (sum(eff) / n)), "band_rays_max_over_mean": sig(max(per_rank_rays) / (sum(per_rank_rays) / n)),
-                  "kernel": ("bands of: " if n > 1 else "") + kernel_name(st0, in_lds),
-                  "triangles": int(len(buffers["material_ids"])), "scene_bytes": int(cst.scene_bytes)}
-        out = {
-            "metric": "Mrays/s (primary+shadow+bounce) at %dx%d" % (W, H),
-            "value": sig(rays_per_step * args.steps / dt / 1e6, 7), "unit": "Mrays/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": sig(dt / args.steps * 1e3, 6), "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": config, "roofline": rf,
-        }
+                  "band_ms_slowest": sig(max(eff)), "band_ms_max_over_mean": sig(max(eff) / (sum(eff) / n)), "band_rays_max_over_mean": sig(max(per_rank_rays) / (sum(per_rank_rays) / n))})
+        out["roofline"] = rf
         detail = {"workload": cfg["workload"], "roofline": rf_detail, "exchange_note": g.exchange_note or None, "rccl": rccl,
                   "per_rank_rays_per_step": per_rank_rays,
                   "bands": {"rays": spread([float(x) for x in per_rank_rays]),
@@ -601,11 +655,17 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C4 / C3 legs the default run adds under `secondary`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (counters pass, launches alone), the other exchanges, the secondary "
+                         "legs, the plugin leg, the CPU baseline, and the side file")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the C4 / C3 / c4xl legs and the plugin leg of the default run")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame of the last timed step to DIR/frame.npy (float32; a seeded sample of its pixels above 64 MB)")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -614,10 +674,11 @@ def main(argv=None):
     if not launched and (args.gpus > 1 or os.environ.get("TRG_BENCH_GROUP")):
         # plain invocation: the single-process design of SURVEY 8(e); nothing is re-executed.  (TRG_BENCH_GROUP=1: N = 1 through the same
         # group path, to check it against the headline)
-        out, detail = run_group(args, use_imported=True)
-        if args.gpus == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"], detail["cpu_baseline"] = cpu_baseline(args.config)
-        out["config"]["detail_file"] = write_detail(args.config, args.gpus, {"line": out, **detail})
+        out, detail = run_group(args, use_imported=True, full=args.full)
+        if args.full:
+            if args.gpus == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"], detail["cpu_baseline"] = cpu_baseline(args.config)
+            out["config"]["detail_file"] = write_detail(args.config, args.gpus, {"line": out, **detail})
         print(json.dumps(out), flush=True)
         return
     if args.gpus != world:
@@ -647,9 +708,9 @@ def main(argv=None):
             dist.init_process_group("gloo")
     env = dict(dist=dist, distributed=distributed, rank=rank, world=world, local_rank=device_index, backend=backend if (distributed or launched) else None)
 
-    out, detail = run_torch(args.config, args.steps, args.warmup, env)
+    out, detail = run_torch(args.config, args.steps, args.warmup, env, full=args.full, dump=args.dump_outputs)
     secondary_failed = []
-    if rank == 0 and world == 1 and args.config == "c2" and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and args.config == "c2" and not args.no_secondary:
         # the configurations where the roofline question lives, timed in the same (driver-witnessed) run: same method, fewer steps.  Their
         # numbers go into `config` as flat scalars (module docstring), their verbose halves into the side file
         detail["secondary"] = {}
@@ -671,9 +732,10 @@ def main(argv=None):
                 out["config"]["plugin_error"] = ("%s: %s" % (type(e).__name__, e))[:110]
                 secondary_failed.append("plugin")
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"], detail["cpu_baseline"] = cpu_baseline(args.config)
-        out["config"]["detail_file"] = write_detail(args.config, world, {"line": out, **detail})
+        if args.full:
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"], detail["cpu_baseline"] = cpu_baseline(args.config)
+            out["config"]["detail_file"] = write_detail(args.config, world, {"line": out, **detail})
         print(json.dumps(out), flush=True)
     if distributed or launched:
         dist.barrier()

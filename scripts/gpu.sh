@@ -9,7 +9,7 @@
 #   slow                  pytest -m "gpu and slow" (whole-frame parity)   -> tests_slow.log
 #   exptests              the whole -m gpu suite against experiments/lib/libtoyraygun_hip_exp.so (all three schedules)
 #   smoke                 __graft_entry__.smoke()                          -> smoke.log
-#   bench[:<cfg>]         python bench.py [--config cfg]                   -> bench_<cfg>.json (+ the detail file)
+#   bench[:<cfg>]         python bench.py --full [--config cfg]            -> bench_<cfg>.json (+ the detail file)
 #   dbench:<cfg>          the same with the device binned-SAH builder
 #   g<N>                  bench.py --gpus N rehearsed on this one device (N contexts, copy exchange)  -> bench_g<N>.json
 #   group1                N = 1 through the group path (TRG_BENCH_GROUP=1)
@@ -40,7 +40,7 @@ for s in "$@"; do
              cfg=${a:-c2}; step "bench $cfg"
              extra=""; [ "$cfg" != c2 ] && extra="--config $cfg --no-cpu-baseline"
              [ "$what" = dbench ] && export TRG_BENCH_GPU_BUILD=1
-             ( time TRG_BENCH_DETAIL=$PWD/$O/bench_${what}_${cfg}_detail.json timeout -k 10 600 python bench.py $extra ) > "$O/bench_${what}_${cfg}.json" 2> "$O/bench_${what}_${cfg}.err"; rc=$?
+             ( time TRG_BENCH_DETAIL=$PWD/$O/bench_${what}_${cfg}_detail.json timeout -k 10 600 python bench.py --full $extra ) > "$O/bench_${what}_${cfg}.json" 2> "$O/bench_${what}_${cfg}.err"; rc=$?
              unset TRG_BENCH_GPU_BUILD
              tail -4 "$O/bench_${what}_${cfg}.err"; [ $rc -eq 0 ] || exit $rc
              python - "$O/bench_${what}_${cfg}.json" <<'PY'
@@ -57,9 +57,9 @@ PY
              ;;
     g[0-9]*) n=${what#g}; step "bench --gpus $n on one device"
              devs=$(python -c "print(','.join(['0']*$n))")
-             TRG_GROUP_EXCHANGE=copy TRG_BENCH_DEVICES=$devs TRG_BENCH_DETAIL=$PWD/$O/bench_g${n}_detail.json timeout -k 10 300 python bench.py --gpus $n --no-cpu-baseline ${a:+--config $a} > "$O/bench_g$n.json" 2> "$O/bench_g$n.err"; rc=$?
+             TRG_GROUP_EXCHANGE=copy TRG_BENCH_DEVICES=$devs TRG_BENCH_DETAIL=$PWD/$O/bench_g${n}_detail.json timeout -k 10 300 python bench.py --gpus $n --full --no-cpu-baseline ${a:+--config $a} > "$O/bench_g$n.json" 2> "$O/bench_g$n.err"; rc=$?
              [ $rc -eq 0 ] || { tail -5 "$O/bench_g$n.err"; exit $rc; } ;;
-    group1)  step "N = 1 through the group path"; TRG_BENCH_GROUP=1 TRG_BENCH_DETAIL=$PWD/$O/bench_group1_detail.json timeout -k 10 300 python bench.py --no-cpu-baseline > "$O/bench_group1.json" 2> "$O/bench_group1.err"; rc=$?; [ $rc -eq 0 ] || exit $rc ;;
+    group1)  step "N = 1 through the group path"; TRG_BENCH_GROUP=1 TRG_BENCH_DETAIL=$PWD/$O/bench_group1_detail.json timeout -k 10 300 python bench.py --full --no-cpu-baseline > "$O/bench_group1.json" 2> "$O/bench_group1.err"; rc=$?; [ $rc -eq 0 ] || exit $rc ;;
     profile) step "profile_round ${a//,/ }"; TRG_COMMIT=$(cat .commit 2>/dev/null) timeout -k 10 1100 bash scripts/profile_round.sh ${a//,/ } > "$O/profile_round.log" 2>&1; rc=$?; tail -12 "$O/profile_round.log"; [ $rc -eq 0 ] || exit $rc ;;
     pmc)     step "$a $b $c"; timeout -k 10 900 bash "scripts/$a.sh" "$b" "$c" > "$O/$a_$b.log" 2>&1; rc=$?; tail -15 "$O/$a_$b.log"; [ $rc -eq 0 ] || exit $rc ;;
     ab)      reps=${c:-2}

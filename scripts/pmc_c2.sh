@@ -5,7 +5,7 @@ export TMPDIR=/tmp GPU_MAX_HW_QUEUES=16
 tag=${1:-shipped}
 [ -n "$2" ] && export TRG_HIP_SO=$PWD/exp_build/$2/libtoyraygun_hip.so
 OUT=$PWD/gpurun_out/pmc_c2_$tag; rm -rf "$OUT"; mkdir -p "$OUT"
-CMD="python3 bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-secondary"
+CMD="python3 bench.py --full --steps 6 --warmup 1 --no-cpu-baseline --no-secondary"
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY --output-format csv -d "$OUT/sq" -- $CMD > "$OUT/sq.log" 2>&1
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections

@@ -11,11 +11,11 @@ export TMPDIR=/tmp
 export GPU_MAX_HW_QUEUES=16
 OUT=$PWD/gpurun_out/profiles; mkdir -p "$OUT"
 WHAT="${*:-c2 c4}"
-C2="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary"
-C4="python3 bench.py --config c4 --steps 5 --warmup 1 --no-cpu-baseline"
-C3="python3 bench.py --config c3 --steps 3 --warmup 1 --no-cpu-baseline"
-C5="python3 bench.py --config c5 --steps 5 --warmup 1 --no-cpu-baseline"
-C4XL="python3 bench.py --config c4xl --steps 3 --warmup 1 --no-cpu-baseline"
+C2="python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-secondary"
+C4="python3 bench.py --full --config c4 --steps 5 --warmup 1 --no-cpu-baseline"
+C3="python3 bench.py --full --config c3 --steps 3 --warmup 1 --no-cpu-baseline"
+C5="python3 bench.py --full --config c5 --steps 5 --warmup 1 --no-cpu-baseline"
+C4XL="python3 bench.py --full --config c4xl --steps 3 --warmup 1 --no-cpu-baseline"
 run() { name=$1; shift; rm -rf "$OUT/$name"; rocprofv3 "$@" > "$OUT/$name.log" 2>&1 || { echo "FAILED $name"; tail -5 "$OUT/$name.log"; }; }
 for cfg in $WHAT; do
   if [ "$cfg" = c2 ]; then CMD=$C2; elif [ "$cfg" = c3 ]; then CMD=$C3; elif [ "$cfg" = c5 ]; then CMD=$C5; elif [ "$cfg" = c4xl ]; then CMD=$C4XL; else CMD=$C4; fi

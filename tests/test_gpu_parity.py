@@ -1593,7 +1593,7 @@ def test_bench_launched_multi_rank_path_rehearsed_on_one_device(capi, tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+                        os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -1604,6 +1604,42 @@ def test_bench_launched_multi_rank_path_rehearsed_on_one_device(capi, tmp_path):
     assert "gloo" in out["config"]["sharding"] and "cpu_baseline" not in out
     assert out["config"]["exchange"] == "root gather" and out["config"]["gather_all_ms_per_step"] >= 0      # north_star's exchange is the timed one
     assert out["roofline"]["derived"] and len(lines[0]) < 4096
+
+
+def test_bench_plain_run_dumps_the_frame_of_its_last_step(capi, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` as a plain run: one short JSON line (no roofline, no CPU baseline, no
+    side file) whose ms_per_step is the wall time per timed step, and DIR/frame.npy = the frame the last timed step computed, which is the
+    frame one context renders from the same seeded inputs with the same options."""
+    import json, subprocess, sys
+    from toyraygun_amd import host
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "TRG_BENCH_GROUP", "TRG_FORCE_GATHER", "TRG_BENCH_DEVICES"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       cwd=root, env=env, capture_output=True, text=True, timeout=280)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 1000 and out["unit"] == "Mrays/s" and out["dtype"] == "f32"
+    assert "roofline" not in out and "cpu_baseline" not in out and "detail_file" not in out["config"]
+    assert sorted(os.listdir(tmp_path)) == ["frame.npy"]
+    got = np.load(tmp_path / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (1080, 1920, 4)
+    b = host.Scene.cornell_box().buffers()
+    ctx = capi.Context(1920, 1080)
+    try:
+        ctx.load_scene(b["positions"], b["normals"], b["colors"], b["indices"], b["material_ids"])
+        ctx.set_option(capi.OPT_LAUNCHES_IN_FLIGHT, 4)        # what bench.py's renderer tells the library (four frames in flight)
+        ctx.set_uniforms(host.uniforms(1920, 1080)[0])
+        ctx.set_pixel_offsets_seed()
+        ctx.render(0, 16, 3)
+        want = ctx.read_accum()
+    finally:
+        ctx.close()
+    assert np.isfinite(got).all() and got[..., :3].max() > 0
+    np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-6)
 
 
 _RCCL_ONE_RANK = r"""
@@ -1674,7 +1710,7 @@ def test_bench_launched_path_through_rccl_with_one_rank(capi):
     frame and the all-gather beside it -- every N > 1 branch, through RCCL."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-secondary"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-secondary"],
                        cwd=root, env=_launched_env(_free_port()), capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -1697,7 +1733,7 @@ def test_bench_single_process_group_path_rehearsed_on_one_device(capi, monkeypat
     monkeypatch.setenv("TRG_GROUP_EXCHANGE", "copy")
     for n in (2, 8):
         monkeypatch.setenv("TRG_BENCH_DEVICES", ",".join(["0"] * n))
-        bench.main(["--gpus", str(n), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+        bench.main(["--gpus", str(n), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"])
         out = json.loads([l for l in capsys.readouterr().out.splitlines() if l.startswith("{")][-1])
         cfgo = out["config"]
         assert out["n_gpus"] == n and cfgo["exchange"] == "copy" and cfgo["devices"] == ",".join(["0"] * n) and cfgo["rccl_ranks"] is None

@@ -757,6 +757,9 @@ def test_bench_runs_plainly_with_several_gpus(built, monkeypatch, capsys, tmp_pa
         def launch_ms(self, rank):
             k, self.timed = (self.timed if rank == self.n - 1 else None), (0 if rank == self.n - 1 else self.timed)
             return [0.25] * (k if k is not None else self.timed)
+        def read_accum(self, rank=0):
+            calls.append(("read", rank))
+            return np.full((self.h, self.w, 4), 0.5, np.float32)
         def close(self): calls.append(("close",))
 
     monkeypatch.setattr(capi, "Group", FakeGroup)
@@ -764,7 +767,7 @@ def test_bench_runs_plainly_with_several_gpus(built, monkeypatch, capsys, tmp_pa
     for k in ("RANK", "WORLD_SIZE", "MASTER_PORT", "LOCAL_RANK"):
         monkeypatch.delenv(k, raising=False)
     monkeypatch.setenv("TRG_BENCH_DETAIL", str(tmp_path / "detail.json"))
-    bench.main(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    bench.main(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"])
     line = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")][-1]
     assert len(line) < 4096                                           # the driver keeps an 8 KB tail: the whole line must sit in it
     out = json.loads(line)
@@ -785,22 +788,58 @@ def test_bench_runs_plainly_with_several_gpus(built, monkeypatch, capsys, tmp_pa
     # the TIMED exchange is north_star's gather to one root: warm-up 1 + timed 3; the all-gather beside it: 3; without an exchange: counters 1 + alone 3 + priming 4 + timed 3
     n_of = lambda mode: sum(1 for c in calls if c == ("render", mode))
     assert n_of(capi.GATHER_ROOT) == 1 + 3 and n_of(capi.GATHER_ALL) == 3 and n_of(capi.GATHER_NONE) == 1 + 3 + 4 + 3
+    # a plain run (no --full) does only what the headline needs: counters 1 + priming 4 without an exchange, warm-up 1 + timed 3 with the
+    # gather; no launches alone, no other exchange, no roofline, no side file.  --dump-outputs writes the frame of the last timed step
+    del calls[:]
+    monkeypatch.setenv("TRG_BENCH_DETAIL", str(tmp_path / "plain_detail.json"))
+    bench.main(["--gpus", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")])
+    out = json.loads([l for l in capsys.readouterr().out.splitlines() if l.startswith("{")][-1])
+    assert out["n_gpus"] == 2 and out["steps"] == 3 and out["ms_per_step"] > 0 and out["unit"] == "Mrays/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and "roofline" not in out and "cpu_baseline" not in out and "detail_file" not in out["config"]
+    assert not (tmp_path / "plain_detail.json").exists()
+    assert n_of(capi.GATHER_ROOT) == 1 + 3 and n_of(capi.GATHER_ALL) == 0 and n_of(capi.GATHER_NONE) == 1 + 4
+    assert ("read", 0) in calls and sorted(os.listdir(tmp_path / "dump")) == ["frame.npy"]
+    frame = np.load(tmp_path / "dump" / "frame.npy")
+    assert frame.dtype == np.float32 and frame.shape == (1080, 1920, 4) and (frame == 0.5).all()
+    monkeypatch.setenv("TRG_BENCH_DETAIL", str(tmp_path / "detail.json"))
     monkeypatch.setattr(torch.cuda, "device_count", lambda: 1)
     with pytest.raises(SystemExit) as e:
-        bench.main(["--gpus", "2", "--no-cpu-baseline"])
+        bench.main(["--gpus", "2", "--full", "--no-cpu-baseline"])
     assert "only 1 GPU" in str(e.value)
     monkeypatch.setenv("TRG_BENCH_DEVICES", "0,0")   # the one-GPU rehearsal: an explicit device list (contexts sharing a device)
-    bench.main(["--gpus", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
+    bench.main(["--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"])
     out = json.loads([l for l in capsys.readouterr().out.splitlines() if l.startswith("{")][-1])
     assert out["config"]["devices"] == "0,0" and out["config"]["shared_device"] is True and ("create", [0, 0], 1920, 1080) in calls
     monkeypatch.setenv("TRG_BENCH_DEVICES", "0")
     with pytest.raises(SystemExit):
-        bench.main(["--gpus", "2", "--no-cpu-baseline"])
+        bench.main(["--gpus", "2", "--full", "--no-cpu-baseline"])
     monkeypatch.delenv("TRG_BENCH_DEVICES")
     monkeypatch.setenv("RANK", "0"); monkeypatch.setenv("MASTER_PORT", "1"); monkeypatch.setenv("WORLD_SIZE", "1")
     with pytest.raises(SystemExit) as e:   # under a launcher the world size must match
-        bench.main(["--gpus", "2", "--no-cpu-baseline"])
+        bench.main(["--gpus", "2", "--full", "--no-cpu-baseline"])
     assert "WORLD_SIZE=1" in str(e.value)
+
+
+def test_bench_dump_outputs_stays_within_budget(monkeypatch, tmp_path):
+    """bench.py --dump-outputs: an array within the budget is written whole in float32; a larger one (a C5 frame is 133 MB) becomes a fixed,
+    seeded sample of its pixels, the same pixels on every run, with their indices beside it."""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    small = np.arange(2 * 3 * 4, dtype=np.float32).reshape(2, 3, 4)
+    bench.dump_outputs(str(tmp_path / "a"), {"frame": small})
+    assert sorted(os.listdir(tmp_path / "a")) == ["frame.npy"] and np.array_equal(np.load(tmp_path / "a" / "frame.npy"), small)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1 << 16)
+    big = np.random.default_rng(1).random((300, 200, 4)).astype(np.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"frame": big})
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= (1 << 16)
+    rows = np.load(tmp_path / "b" / "frame_rows.npy")
+    got = np.load(tmp_path / "b" / "frame.npy")
+    assert got.dtype == np.float32 and rows.dtype == np.float64 and got.shape == (len(rows), 4) and len(rows) > 100
+    assert np.array_equal(got, big.reshape(-1, 4)[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "frame_rows.npy")) and np.array_equal(got, np.load(tmp_path / "c" / "frame.npy"))
 
 
 def test_texture_images_follow_the_native_registration_order(built, tmp_path):
