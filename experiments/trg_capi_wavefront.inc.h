@@ -13,12 +13,7 @@ static int render_wavefront(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint
     // layout of the slot: 7 float4 arrays, two lists of 2 nb entries, the stage counters
     const size_t arr = (size_t)nb_max * 16u, lst = (size_t)nb_max * 2u * 4u;
     const size_t need = 7u * arr + 2u * lst + kWfMaxStages * 16u + 256u;
-    if (need > c->wf_bytes[slot]) {
-        if (c->wf_mem[slot]) { (void)hipDeviceSynchronize(); (void)hipFree(c->wf_mem[slot]); c->wf_mem[slot] = nullptr; c->wf_bytes[slot] = 0; }
-        hipError_t e = hipMalloc((void **)&c->wf_mem[slot], need);
-        if (e != hipSuccess) return fail(c, TRG_ERR_NOMEM, "wavefront buffers hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-        c->wf_bytes[slot] = need;
-    }
+    if (int rc = ensure_slot_buffer(c, c->wf_mem[slot], c->wf_bytes[slot], need, "wavefront buffers")) return rc;
     unsigned char *m = c->wf_mem[slot];
     WfParams p{};
     p.u = c->u; p.sc = c->sc; p.offsets = c->offsets; p.accum = c->accum; p.counters = c->counters;
@@ -32,22 +27,21 @@ static int render_wavefront(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint
     const uint32_t trace_grid = (uint32_t)c->cu_count * 8u;
     if (int rc = ensure_stack_scratch(c, plan, (uint64_t)trace_grid * kBlock, p.stack, slot)) return rc;
     const uint32_t shade_grid = (uint32_t)c->cu_count * 8u;
-    const bool strict = c->opt_strict;
+    const Launchers &L = launchers(c);
     for (uint32_t f0 = 0; f0 < spp; f0 += fb) {
         p.frame0 = frame_begin + f0;
         p.nframes = std::min(fb, spp - f0);
         p.nb = p.npix * p.nframes;
         HIPCHK(c, hipMemsetAsync(p.b.ctr, 0, kWfMaxStages * 16u, c->stream));
-        HIPCHK(c, strict ? launch_wf_raygen_strict(p, c->stream) : launch_wf_raygen_fast(p, c->stream));
+        HIPCHK(c, L.wf_raygen(p, c->stream));
         for (uint32_t b = 0; b <= bounces; ++b) {
             if (bounces == 0) break;
             p.stage = b; p.bounce = b;
-            HIPCHK(c, strict ? launch_wf_trace_strict(p, plan.lds_scene, c->opt_counters, trace_grid, plan.total, c->stream)
-                             : launch_wf_trace_fast(p, plan.lds_scene, c->opt_counters, trace_grid, plan.total, c->stream));
+            HIPCHK(c, L.wf_trace(p, plan.lds_scene, c->opt_counters, trace_grid, plan.total, c->stream));
             if (b == bounces) break;   // that was the trace of the last bounce's shadow rays
-            HIPCHK(c, strict ? launch_wf_shade_strict(p, plan.lds_scene, shade_grid, c->stream) : launch_wf_shade_fast(p, plan.lds_scene, shade_grid, c->stream));
+            HIPCHK(c, L.wf_shade(p, plan.lds_scene, shade_grid, c->stream));
         }
-        HIPCHK(c, strict ? launch_wf_accumulate_strict(p, c->stream) : launch_wf_accumulate_fast(p, c->stream));
+        HIPCHK(c, L.wf_accumulate(p, c->stream));
     }
     return TRG_OK;
 }

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(trg::kBlock, TRG_EXP_WAVES_RTAIL) void render_rtail
     v4f *radbuf = reinterpret_cast<v4f *>(p.tail_radbuf);
     const uint32_t b = p.tail_k;                          // the bounce of this launch (wave-uniform)
     const bool last = b + 1u == p.bounces;                // ... the last one: nothing is queued again
-    constexpr bool TAB = !TRG_STRICT && TRG_HALTON_TABLES;
+    constexpr bool TAB = !TRG_STRICT;
     typedef const __attribute__((address_space(4))) trg_uniforms cu_t;
     cu_t *up = (cu_t *)__builtin_amdgcn_kernarg_segment_ptr();
     PathCounters pc; pc.primary = 0; pc.bounce = 0; pc.shadow = 0; pc.shaded = 0;

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(256) void wf_shade_kernel(const trg::WfParams p) {
     SceneView sc;
     sc.nodes = nullptr; sc.htab = nullptr; sc.meta = nullptr; sc.center = mk(sd.center[0], sd.center[1], sd.center[2]);
     sc.tex = p.tex;
-    sc.tris = FAT ? reinterpret_cast<const v4f *>(sd.blob + (kRecPlanes ? sd.off_fat_planes : sd.off_fat)) : nullptr;
+    sc.tris = FAT ? reinterpret_cast<const v4f *>(sd.blob + (kShipped ? sd.off_fat_planes : sd.off_fat)) : nullptr;
     sc.normals = FAT ? nullptr : reinterpret_cast<const float *>(sd.blob + sd.off_normals);
     sc.colors = FAT ? nullptr : reinterpret_cast<const float *>(sd.blob + sd.off_colors);
     sc.mats = FAT ? nullptr : reinterpret_cast<const uint32_t *>(sd.blob + sd.off_mats);

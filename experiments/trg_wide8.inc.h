@@ -73,8 +73,8 @@ TRG_DEV void trav_step_wide8(const SceneView &sc, Trav &tv, bool any, STK stk, C
     } else {
         // one leaf record: the strict build tests every triangle by itself; the shipped build decides a QUAD (flag bit 29 of its index word) in one test
         uint32_t flags;
-        if (kRecPlanes) {
-            const uint32_t iw = (uint32_t)__float_as_int(kRecMetaFirst ? q3.x : 0.0f);
+        if (kShipped) {
+            const uint32_t iw = (uint32_t)__float_as_int(q3.x);
             flags = iw >> 28;
             const bool quad = (flags & 2u) != 0u;
             stop = trav_tri_planes_rec<COUNT>(q0, q1, q2, (uint32_t)__float_as_int(q3.y), (int)(iw & 0x0FFFFFFFu), tv, any, cnt, rec, sc.tris, sc.center, quad, sc.n_rec);

@@ -198,20 +198,13 @@ static void fill_fat_record_planes(unsigned char *dst, const F4 *rec48, const fl
     fill_fat_record(dst, rec48, nrm, col, n_tris);
     uint16_t meta;
     fill_plane_record(dst, &meta, rec48, center, quad_y);
-    if (TRG_REC_META_FIRST) {   // index and mask right behind the planes (the first 64 bytes are all a test reads), the attributes at floats 14..31
-        memmove(dst + 56, dst + 48, 72);
-        memcpy(dst + 48, &rec48[0].w, 4);   // float 12: original index
-        memcpy(dst + 52, &rec48[1].w, 4);   // float 13: material id = mask
-    } else {
-        memcpy(dst + 120, &rec48[0].w, 4);   // float 30: original index
-        memcpy(dst + 124, &rec48[1].w, 4);   // float 31: material id = mask
-    }
+    // index and mask right behind the planes (the first 64 bytes are all a test reads), the attributes at floats 14..31
+    memmove(dst + 56, dst + 48, 72);
+    memcpy(dst + 48, &rec48[0].w, 4);   // float 12: original index
+    memcpy(dst + 52, &rec48[1].w, 4);   // float 13: material id = mask
 }
 
 constexpr uint32_t kStackLdsLevels = TRG_STACK_LDS_LEVELS;
-#ifndef TRG_TAIL_REFILL_AUTO
-#define TRG_TAIL_REFILL_AUTO 0   // what TRG_OPT_TAIL_REFILL -1 means (set once the refill tail has been measured)
-#endif
 #ifndef TRG_TAIL_AUTO_MIN_BOUNCES
 #define TRG_TAIL_AUTO_MIN_BOUNCES 4
 #endif
@@ -223,9 +216,6 @@ constexpr uint32_t kStackLdsLevels = TRG_STACK_LDS_LEVELS;
 #endif
 constexpr uint32_t kRegenAutoMinTris = 32768u;   // TRG_OPT_REGEN -1: path regeneration from this many triangles on
 constexpr uint32_t kTailAutoMinBounces = TRG_TAIL_AUTO_MIN_BOUNCES, kTailAutoK = TRG_TAIL_AUTO_K, kTailChunkFrames = 16, kTailLevelStep = TRG_TAIL_LEVEL_STEP;
-#ifndef TRG_XCD_AUTO_COLS
-#define TRG_XCD_AUTO_COLS 0   // TRG_OPT_TILE_ORDER -1 for scenes in HBM: 0 = image columns (measured faster, see choose_xcd_cols), 2 = XCD-aware 2 x 4
-#endif
 
 struct LdsPlan { bool lds_scene; uint32_t stack_off, red_off, pool_off, acc_off, total, klds, overflow_levels; };
 static bool plan_lds_as(const trg_ctx *c, LdsPlan &p, bool lds_scene, bool pool, uint32_t fp_slots, uint32_t &limit, bool park = true) {
@@ -259,10 +249,10 @@ static bool plan_lds_as(const trg_ctx *c, LdsPlan &p, bool lds_scene, bool pool,
     // render_kernel on an HBM-resident scene parks the running average in LDS between frames (three VGPRs less across every
     // traversal; an LDS-resident scene has neither the room -- 8 workgroups of 20 KB per CU -- nor the need: it is spill-free)
     p.acc_off = 0;
-    if (park && !p.lds_scene && !pool && !fp_slots) { p.acc_off = p.total; p.total += (uint32_t)kBlock * (TRG_PARK_PATH ? (TRG_PARK_OFFSET ? 40u : 36u) : 12u); }
+    if (park && !p.lds_scene && !pool && !fp_slots) { p.acc_off = p.total; p.total += (uint32_t)kBlock * 40u; }
     // render_fp_kernel on an HBM-resident scene parks throughput, radiance and the Halton offset the same way (seven words per thread; its
     // running average stays in the registers of the one wave per sub-tile that folds)
-    if (park && !p.lds_scene && !pool && fp_slots && TRG_PARK_PATH && TRG_PARK_OFFSET) { p.acc_off = p.total; p.total += (uint32_t)kBlock * 28u; }
+    if (park && !p.lds_scene && !pool && fp_slots) { p.acc_off = p.total; p.total += (uint32_t)kBlock * 28u; }
     limit = (pool || fp_slots) ? 160u * 1024u : 64u * 1024u;  // above 64 KB the launcher opts in per kernel
     return p.total <= limit;
 }
@@ -337,16 +327,22 @@ static uint64_t tile_slots(uint32_t tiles_x, uint32_t tiles_y, uint32_t xcd_cols
 // L2 hit rate from 81 to 86 % and shortens the mean L1 -> L2 round trip from 245 to 199 cycles -- and takes 22.1 ms instead of 19.3: the
 // wavefronts' total lifetime (SQ_WAVE_CYCLES) stays the same, the kernel issues instructions most of the time and what it waits less for
 // memory it waits more for an issue slot, while the eight regions differ in cost and the dispatcher deals workgroups to the XCDs
-// strictly in turn, so the cheap regions' XCDs idle (1 x 8: 23.8 ms, 4 x 2: 37.5, 8 x 1: 35.9 -- the 16:9 side bars).  TRG_XCD_AUTO_COLS
-// (a build flag) would make an XCD-aware layout the automatic choice for scenes traversed from HBM.
-static uint32_t choose_xcd_cols(const trg_ctx *c, bool lds_scene, uint32_t tiles_x, uint32_t tiles_y) {
+// strictly in turn, so the cheap regions' XCDs idle (1 x 8: 23.8 ms, 4 x 2: 37.5, 8 x 1: 35.9 -- the 16:9 side bars).
+static uint32_t choose_xcd_cols(const trg_ctx *c) {
     if (c->opt_tile_order >= (int)kXcdPersist) return (uint32_t)c->opt_tile_order - kXcdPersist;   // 64 + n: the n x (8 / n) regions, dealt through per-XCD queues where the kernel can (regeneration)
     if (c->opt_tile_order >= 0) return (uint32_t)c->opt_tile_order;
-    if (lds_scene || TRG_XCD_AUTO_COLS == 0) return 0u;
-    uint32_t rc = TRG_XCD_AUTO_COLS;
-    while (rc < kXcds && tiles_y < kXcds / rc) rc *= 2u;   // fewer row bands for a launch of few tile rows (a row band of a multi-GPU job)
-    while (rc > 1u && tiles_x < rc) rc /= 2u;
-    return rc;
+    return 0u;
+}
+
+// a per-slot device buffer of at least `need` bytes: a smaller one is replaced (after the device has finished with it)
+template <typename T>
+static int ensure_slot_buffer(trg_ctx *c, T *&mem, size_t &bytes, size_t need, const char *what) {
+    if (need <= bytes) return TRG_OK;
+    if (mem) { (void)hipDeviceSynchronize(); (void)hipFree(mem); mem = nullptr; bytes = 0; }
+    hipError_t e = hipMalloc((void **)&mem, need);
+    if (e != hipSuccess) return fail(c, TRG_ERR_NOMEM, "%s hipMalloc(%zu) failed: %s", what, need, hipGetErrorString(e));
+    bytes = need;
+    return TRG_OK;
 }
 
 // global scratch for the stack levels that do not fit in LDS: overflow_levels x grid_threads ints
@@ -355,15 +351,47 @@ static int ensure_stack_scratch(trg_ctx *c, const LdsPlan &plan, uint64_t grid_t
     out.overflow = nullptr;
     if (plan.overflow_levels == 0) return TRG_OK;
     const size_t need = (size_t)plan.overflow_levels * grid_threads * sizeof(int);
-    if (need > c->stack_scratch_bytes[slot]) {
-        if (c->stack_scratch[slot]) { (void)hipDeviceSynchronize(); (void)hipFree(c->stack_scratch[slot]); c->stack_scratch[slot] = nullptr; c->stack_scratch_bytes[slot] = 0; }
-        hipError_t e = hipMalloc((void **)&c->stack_scratch[slot], need);
-        if (e != hipSuccess) return fail(c, TRG_ERR_NOMEM, "stack scratch hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-        c->stack_scratch_bytes[slot] = need;
-    }
+    if (int rc = ensure_slot_buffer(c, c->stack_scratch[slot], c->stack_scratch_bytes[slot], need, "stack scratch")) return rc;
     out.overflow = c->stack_scratch[slot];
     return TRG_OK;
 }
+
+// The launchers of one build (trg_kernels.h TRG_DECL_LAUNCHERS): the strict or the shipped set, chosen once per call
+struct Launchers {
+    decltype(&launch_render_fast) render;
+    decltype(&launch_render_fp_fast) render_fp;
+    decltype(&launch_render_regen_fast) render_regen;
+    decltype(&launch_regen_accumulate_fast) regen_accumulate;
+    decltype(&launch_render_head_fast) render_head;
+    decltype(&launch_render_tail_fast) render_tail;
+    decltype(&launch_tail_accumulate_fast) tail_accumulate;
+    decltype(&launch_tail_sort_fast) tail_sort;
+    decltype(&launch_trace_fast) trace;
+    decltype(&launch_halton_fast) halton;
+    decltype(&launch_raygen_fast) raygen;
+    decltype(&launch_sample_fast) sample;
+    decltype(&launch_postprocess_fast) postprocess;
+#if TRG_EXPERIMENTS
+    decltype(&launch_render_pool_fast) render_pool;
+    decltype(&launch_render_rtail_fast) render_rtail;
+    decltype(&launch_wf_raygen_fast) wf_raygen;
+    decltype(&launch_wf_trace_fast) wf_trace;
+    decltype(&launch_wf_shade_fast) wf_shade;
+    decltype(&launch_wf_accumulate_fast) wf_accumulate;
+#endif
+};
+#if TRG_EXPERIMENTS
+#define EXP_LAUNCHERS(SFX) , launch_render_pool_##SFX, launch_render_rtail_##SFX, launch_wf_raygen_##SFX, launch_wf_trace_##SFX, launch_wf_shade_##SFX, launch_wf_accumulate_##SFX
+#else
+#define EXP_LAUNCHERS(SFX)
+#endif
+#define LAUNCHERS(SFX) { launch_render_##SFX, launch_render_fp_##SFX, launch_render_regen_##SFX, launch_regen_accumulate_##SFX, launch_render_head_##SFX, \
+                         launch_render_tail_##SFX, launch_tail_accumulate_##SFX, launch_tail_sort_##SFX, launch_trace_##SFX, launch_halton_##SFX,         \
+                         launch_raygen_##SFX, launch_sample_##SFX, launch_postprocess_##SFX EXP_LAUNCHERS(SFX) }
+static const Launchers kLaunchFast = LAUNCHERS(fast), kLaunchStrict = LAUNCHERS(strict);
+#undef LAUNCHERS
+#undef EXP_LAUNCHERS
+static const Launchers &launchers(const trg_ctx *c) { return c->opt_strict ? kLaunchStrict : kLaunchFast; }
 
 #if TRG_EXPERIMENTS
 static int render_wavefront(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint32_t bounces, uint32_t row0, uint32_t rows, int slot);
@@ -567,6 +595,15 @@ static int check_scene_args(trg_ctx *c, const float *pos, const float *nrm, cons
 
 namespace trg {
 // Host SAH build + the image of the device blob.  No device work: a device group calls this once and uploads to every context.
+// the rows (a_k, d_k) of a box's own frame, three float4: l_k = a_k . (P - scene centre) + d_k
+static void box_frame_rows(const BoxLeaf &bl, const float *center, float *rows) {
+    for (int k = 0; k < 3; ++k) {
+        double dk = 0.0;
+        for (int a = 0; a < 3; ++a) { rows[k * 4 + a] = bl.axis[k][a]; dk -= (double)bl.axis[k][a] * ((double)bl.center[a] - (double)center[a]); }
+        rows[k * 4 + 3] = (float)dk;
+    }
+}
+
 int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float *col, const uint32_t *idx, const uint32_t *mat, uint32_t n_verts,
                      uint32_t n_tris, HostScene **out) {
     if (!c || !out) return TRG_ERR_INVALID;
@@ -576,10 +613,7 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
     if (!hs) return fail(c, TRG_ERR_NOMEM, "trg_load_scene: out of host memory");
     const auto host_t0 = std::chrono::steady_clock::now();
     Bvh bvh;
-    // (boxes: only a scene that may be staged in LDS can use them -- 170 triangles at most; the switch is wider so that the answer does not hinge on it)
-    uint32_t box_max_tris = 1024u;
-    if (const char *e = getenv("TRG_BVH_BOXES_MAX_TRIS")) box_max_tris = (uint32_t)strtoul(e, nullptr, 10);   // (measurements: boxes as units of the split rule in larger scenes too)
-    build_bvh(pos, idx, mat, n_tris, bvh, TRG_WIDE8 != 0, TRG_BOX_LEAVES && !TRG_WIDE8 && (TRG_BOX_LEAVES_HBM || n_tris <= box_max_tris));
+    build_bvh(pos, idx, mat, n_tris, bvh, TRG_WIDE8 != 0, !TRG_WIDE8);
     if (TRG_WIDE8 && !bvh.wide8_ok) { delete hs; return fail(c, TRG_ERR_RANGE, "trg_load_scene: the 8-wide layout of this build needs leaves of at most two records (TRG_BVH_MAXLEAF <= 2)"); }
     hs->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
     if (n_tris) {
@@ -618,7 +652,7 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
     const uint32_t n_fat = TRG_WIDE8 ? (uint32_t)bvh.rec8.size() : nt_rec;   // (TRG_WIDE8: two entries per leaf, in the order the 8-wide tree addresses them)
     uint64_t total = 0;
     // the box-leaf flavour of the HBM tree (shipped build): TRG_BVH_BOXES_HBM=0 leaves it out (A/B runs: the kernels then never meet a box code)
-    const bool hbm_boxes = TRG_BOX_LEAVES_HBM && !TRG_WIDE8 && bvh.n_nodes4_box != 0 && !(getenv("TRG_BVH_BOXES_HBM") && atoi(getenv("TRG_BVH_BOXES_HBM")) == 0);
+    const bool hbm_boxes = !TRG_WIDE8 && bvh.n_nodes4_box != 0 && !(getenv("TRG_BVH_BOXES_HBM") && atoi(getenv("TRG_BVH_BOXES_HBM")) == 0);
     if (!plan_scene_layout(sc.n_nodes, node_bytes, lds_candidate ? nt_rec : 0u, lds_candidate ? attr_tris : 0u, lds_candidate, sc.n_nodes4, n_fat, sc, total,
                            hbm_boxes ? bvh.n_nodes4_box : 0u, hbm_boxes ? bvh.boxes.size() : 0u)) {
         delete hs;
@@ -671,11 +705,7 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
         for (const BoxLeaf &bl : bvh.boxes) {
             if (bl.node == ~0u) continue;   // (a lone quad dressed as a box: the HBM flavour's business)
             float rec[12];
-            for (int k = 0; k < 3; ++k) {
-                double dk = 0.0;
-                for (int a = 0; a < 3; ++a) { rec[k * 4 + a] = bl.axis[k][a]; dk -= (double)bl.axis[k][a] * ((double)bl.center[a] - (double)sc.center[a]); }
-                rec[k * 4 + 3] = (float)dk;
-            }
+            box_frame_rows(bl, sc.center, rec);
             memcpy(&host[sc.off_tris_alt + (size_t)(bl.first_rec + 1u) * 48u], rec, 48);
             uint32_t faces[12] = { 0 };
             for (int f = 0; f < 6; ++f) faces[f] = ((uint32_t)bl.face_rec[f] << 16) | ((uint32_t)bl.face_rec[f] * 48u);
@@ -759,11 +789,7 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
         for (size_t b = 0; b < bvh.boxes.size(); ++b) {
             const BoxLeaf &bl = bvh.boxes[b];
             float rec[16];
-            for (int k = 0; k < 3; ++k) {
-                double dk = 0.0;
-                for (int a = 0; a < 3; ++a) { rec[k * 4 + a] = bl.axis[k][a]; dk -= (double)bl.axis[k][a] * ((double)bl.center[a] - (double)sc.center[a]); }
-                rec[k * 4 + 3] = (float)dk;
-            }
+            box_frame_rows(bl, sc.center, rec);
             uint32_t row3[4] = { bl.first_rec, bl.mask, 0u, 0u };
             for (int f = 0; f < 6; ++f) {
                 const uint32_t w7 = (uint32_t)bl.face_rec[f] | ((uint32_t)bl.face_bits[f] << 4);
@@ -936,6 +962,21 @@ int trg_unpack_bands(trg_ctx *c, const void *compact, void *image, uint32_t n_ra
     return TRG_OK;
 }
 
+// the end of every schedule of render_impl: count the render and, with TRG_OPT_TIMING, time it from ev0 (recorded before its first launch)
+static int render_done(trg_ctx *c) {
+    c->renders++;
+    c->launches++;
+    if (c->opt_timing) {
+        HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+        HIPCHK(c, hipEventSynchronize(c->ev1));
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        c->last_ms = ms;
+        c->total_ms += ms;
+    }
+    return TRG_OK;
+}
+
 static int render_impl(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint32_t bounces, uint32_t row0, uint32_t rows, uint32_t il_n, uint32_t il_r) {
     if (!c->scene_loaded) return fail(c, TRG_ERR_INVALID, "trg_render: no scene loaded");
     if (!c->have_uniforms) return fail(c, TRG_ERR_INVALID, "trg_render: uniforms not set");
@@ -946,6 +987,7 @@ static int render_impl(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint32_t 
     HIPCHK(c, hipSetDevice(c->device));
     const int slot = scratch_slot(c);
     if (slot < 0) return fail(c, TRG_ERR_RANGE, "trg_render: more than %d different streams used with this context", trg_ctx::kScratchSlots - 1);
+    const Launchers &L = launchers(c);
     int kernel = c->opt_kernel;
     if (kernel == TRG_KERNEL_AUTO) kernel = TRG_KERNEL_DIRECT;
     if (il_n > 1u && kernel != TRG_KERNEL_DIRECT)
@@ -954,15 +996,8 @@ static int render_impl(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint32_t 
     if (kernel == TRG_KERNEL_WAVEFRONT) {
         if (c->opt_timing) HIPCHK(c, hipEventRecord(c->ev0, c->stream));
         if (int rc = render_wavefront(c, frame_begin, spp, bounces, row0, rows, slot)) return rc;
-        c->renders++; c->launches++; c->last_fsplit = 1; c->last_kernel = TRG_KERNEL_WAVEFRONT;
-        if (c->opt_timing) {
-            HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            float ms = 0.f;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-            c->last_ms = ms; c->total_ms += ms;
-        }
-        return TRG_OK;
+        c->last_fsplit = 1; c->last_kernel = TRG_KERNEL_WAVEFRONT;
+        return render_done(c);
     }
     const bool pool = kernel == TRG_KERNEL_POOL;
 #else
@@ -1004,7 +1039,7 @@ static int render_impl(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint32_t 
     p.tiles_x = (c->w + tile_w - 1) / tile_w;
     const uint32_t tiles_y = (rows + tile_h - 1) / tile_h;
     p.tiles_y = tiles_y;
-    p.xcd_cols = choose_xcd_cols(c, plan.lds_scene, p.tiles_x, tiles_y);
+    p.xcd_cols = choose_xcd_cols(c);
     c->last_xcd_cols = p.xcd_cols;
     const uint64_t slots = tile_slots(p.tiles_x, tiles_y, p.xcd_cols);
     if (slots * std::max(regen_lanes, 1u) > 0x7FFFFFFFull) return fail(c, TRG_ERR_RANGE, "trg_render: grid too large");
@@ -1026,18 +1061,13 @@ static int render_impl(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint32_t 
         const size_t q_bytes = (size_t)(n_waves * cap * 48u), cnt_bytes = (size_t)((n_waves * 4u + 255u) & ~255ull), rad_bytes = (size_t)(band_pixels * fc * 16u);
         // compaction levels: K, K + 2, K + 4 ... while at least two bounces are left (each level halves the live lanes again)
         // (TRG_OPT_TAIL_REFILL: one level per bounce -- every path of a launch is at the same bounce, its lanes refill from the queue)
-        const bool refill = TRG_EXPERIMENTS && (c->opt_tail_refill > 0 || (c->opt_tail_refill < 0 && TRG_TAIL_REFILL_AUTO));
+        const bool refill = TRG_EXPERIMENTS && c->opt_tail_refill > 0;
         uint32_t levels[TRG_MAX_BOUNCES + 1]; int n_levels = 0;
         for (uint32_t k = tail_k; k < bounces && n_levels < (int)TRG_MAX_BOUNCES; k += refill ? 1u : kTailLevelStep) { levels[n_levels++] = k; if (c->opt_tail_levels == 1 && !refill) break; }
         const bool sorted = !refill && c->opt_tail_sort > 0 && cap * kWaves <= 4096u;   // the sort kernel holds a tile's keys in LDS
         const bool two_queues = n_levels > 1 || sorted;
         const size_t need = q_bytes * (two_queues ? 2u : 1u) + cnt_bytes * 2u + rad_bytes;
-        if (need > c->wf_bytes[slot]) {
-            if (c->wf_mem[slot]) { (void)hipDeviceSynchronize(); (void)hipFree(c->wf_mem[slot]); c->wf_mem[slot] = nullptr; c->wf_bytes[slot] = 0; }
-            hipError_t me = hipMalloc((void **)&c->wf_mem[slot], need);
-            if (me != hipSuccess) return fail(c, TRG_ERR_NOMEM, "tail buffers hipMalloc(%zu) failed: %s", need, hipGetErrorString(me));
-            c->wf_bytes[slot] = need;
-        }
+        if (int rc = ensure_slot_buffer(c, c->wf_mem[slot], c->wf_bytes[slot], need, "tail buffers")) return rc;
         p.tail_cap = (uint32_t)cap; p.tail_band_pixels = (uint32_t)band_pixels;
         unsigned char *mem = c->wf_mem[slot];
         void *q[2] = { mem, two_queues ? mem + q_bytes : mem };
@@ -1048,7 +1078,7 @@ static int render_impl(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint32_t 
         for (uint32_t f0 = 0; f0 < spp; f0 += fc) {
             p.frame_begin = frame_begin + f0; p.spp = std::min(fc, spp - f0);
             p.tail_k = levels[0]; p.tail_k_end = levels[0]; p.tail_queue = q[0]; p.tail_count = qc[0];
-            hipError_t te = c->opt_strict ? launch_render_head_strict(p, c->opt_counters, grid, plan.total, c->stream) : launch_render_head_fast(p, c->opt_counters, grid, plan.total, c->stream);
+            hipError_t te = L.render_head(p, c->opt_counters, grid, plan.total, c->stream);
             float inv3[3];
             for (int a = 0; a < 3; ++a) inv3[a] = 1.0f / std::max(c->scene_hi[a] - c->scene_lo[a], 1e-20f);
             for (int l = 0; l < n_levels && te == hipSuccess; ++l) {
@@ -1057,31 +1087,23 @@ static int render_impl(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint32_t 
                     // TRG_OPT_TAIL_SORT: the paths of a tile by direction octant (and origin cell) before a tail launch reads them -- q0 (written by
                     // the head / the previous tail) -> q1 (read by this tail, which compacts into q0 again); the counts stay in qc[l & 1]
                     p.tail_queue = q[0]; p.tail_count = qc[l & 1]; p.tail_queue_out = q[1];
-                    te = c->opt_strict ? launch_tail_sort_strict(p, grid, (uint32_t)c->opt_tail_sort, c->scene_lo, inv3, c->stream)
-                                       : launch_tail_sort_fast(p, grid, (uint32_t)c->opt_tail_sort, c->scene_lo, inv3, c->stream);
+                    te = L.tail_sort(p, grid, (uint32_t)c->opt_tail_sort, c->scene_lo, inv3, c->stream);
                     if (te != hipSuccess) break;
                     p.tail_queue = q[1]; p.tail_queue_out = q[0]; p.tail_count_out = qc[(l + 1) & 1];
                 } else {
                     p.tail_queue = q[l & 1]; p.tail_count = qc[l & 1]; p.tail_queue_out = q[(l + 1) & 1]; p.tail_count_out = qc[(l + 1) & 1];
                 }
 #if TRG_EXPERIMENTS
-                if (refill) te = c->opt_strict ? launch_render_rtail_strict(p, c->opt_counters, grid, plan.total, c->stream) : launch_render_rtail_fast(p, c->opt_counters, grid, plan.total, c->stream);
+                if (refill) te = L.render_rtail(p, c->opt_counters, grid, plan.total, c->stream);
                 else
 #endif
-                te = c->opt_strict ? launch_render_tail_strict(p, c->opt_counters, grid, plan.total, c->stream) : launch_render_tail_fast(p, c->opt_counters, grid, plan.total, c->stream);
+                te = L.render_tail(p, c->opt_counters, grid, plan.total, c->stream);
             }
-            if (te == hipSuccess) te = c->opt_strict ? launch_tail_accumulate_strict(p, c->stream) : launch_tail_accumulate_fast(p, c->stream);
+            if (te == hipSuccess) te = L.tail_accumulate(p, c->stream);
             if (te != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_render: tail-compaction launch failed: %s", hipGetErrorString(te));
         }
-        c->renders++; c->launches++; c->last_fsplit = 1; c->last_tail_k = tail_k;
-        if (c->opt_timing) {
-            HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            float ms = 0.f;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-            c->last_ms = ms; c->total_ms += ms;
-        }
-        return TRG_OK;
+        c->last_fsplit = 1; c->last_tail_k = tail_k;
+        return render_done(c);
     }
     c->last_tail_k = 0;
 
@@ -1098,12 +1120,7 @@ static int render_impl(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint32_t 
         const uint32_t rgrid = grid * regen_lanes;
         const size_t rad_bytes = (size_t)rgrid * kBlock * ((fc + regen_lanes - 1u) / regen_lanes) * 16u;   // one log of 256 x frames records per workgroup
         p.fsplit = regen_lanes;
-        if (rad_bytes > c->wf_bytes[slot]) {
-            if (c->wf_mem[slot]) { (void)hipDeviceSynchronize(); (void)hipFree(c->wf_mem[slot]); c->wf_mem[slot] = nullptr; c->wf_bytes[slot] = 0; }
-            hipError_t me = hipMalloc((void **)&c->wf_mem[slot], rad_bytes);
-            if (me != hipSuccess) return fail(c, TRG_ERR_NOMEM, "radiance buffer hipMalloc(%zu) failed: %s", rad_bytes, hipGetErrorString(me));
-            c->wf_bytes[slot] = rad_bytes;
-        }
+        if (int rc = ensure_slot_buffer(c, c->wf_mem[slot], c->wf_bytes[slot], rad_bytes, "radiance buffer")) return rc;
         p.tail_radbuf = c->wf_mem[slot];
         // TRG_OPT_TILE_ORDER 64 + n: about as many PERSISTENT workgroups as the chip holds (7 per CU) pop the jobs of the n x (8 / n) screen regions
         // from one queue per XCD (trg_regen.inc.h): the heads are zeroed in front of every launch, on its stream
@@ -1114,49 +1131,28 @@ static int render_impl(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint32_t 
         for (uint32_t f0 = 0; f0 < spp; f0 += fc) {
             p.frame_begin = frame_begin + f0; p.spp = std::min(fc, spp - f0);
             if (persist) HIPCHK(c, hipMemsetAsync(p.xq, 0, sizeof(uint32_t) * kXcds, c->stream));
-            hipError_t te = c->opt_strict ? launch_render_regen_strict(p, c->opt_counters, launch_grid, plan.total, c->stream)
-                                          : launch_render_regen_fast(p, c->opt_counters, launch_grid, plan.total, c->stream);
-            if (te == hipSuccess) te = c->opt_strict ? launch_regen_accumulate_strict(p, grid, c->stream) : launch_regen_accumulate_fast(p, grid, c->stream);
+            hipError_t te = L.render_regen(p, c->opt_counters, launch_grid, plan.total, c->stream);
+            if (te == hipSuccess) te = L.regen_accumulate(p, grid, c->stream);
             if (te != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_render: regeneration launch failed: %s", hipGetErrorString(te));
         }
-        c->renders++; c->launches++; c->last_fsplit = regen_lanes;
-        if (c->opt_timing) {
-            HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            float ms = 0.f;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-            c->last_ms = ms; c->total_ms += ms;
-        }
-        return TRG_OK;
+        c->last_fsplit = regen_lanes;
+        return render_done(c);
     }
 
     if (c->opt_timing) HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     hipError_t e;
 #if TRG_EXPERIMENTS
     if (pool)
-        e = c->opt_strict ? launch_render_pool_strict(p, plan.lds_scene, c->opt_counters, grid, plan.total, c->stream)
-                          : launch_render_pool_fast(p, plan.lds_scene, c->opt_counters, grid, plan.total, c->stream);
+        e = L.render_pool(p, plan.lds_scene, c->opt_counters, grid, plan.total, c->stream);
     else
 #endif
     if (fsplit > 1)
-        e = c->opt_strict ? launch_render_fp_strict(p, plan.lds_scene, c->opt_counters, grid, plan.total, c->stream)
-                          : launch_render_fp_fast(p, plan.lds_scene, c->opt_counters, grid, plan.total, c->stream);
+        e = L.render_fp(p, plan.lds_scene, c->opt_counters, grid, plan.total, c->stream);
     else
-        e = c->opt_strict ? launch_render_strict(p, plan.lds_scene, c->opt_counters, grid, plan.total, c->stream)
-                          : launch_render_fast(p, plan.lds_scene, c->opt_counters, grid, plan.total, c->stream);
+        e = L.render(p, plan.lds_scene, c->opt_counters, grid, plan.total, c->stream);
     if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_render: launch failed: %s", hipGetErrorString(e));
-    c->renders++;
-    c->launches++;
     c->last_fsplit = fsplit;
-    if (c->opt_timing) {
-        HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-        HIPCHK(c, hipEventSynchronize(c->ev1));
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        c->last_ms = ms;
-        c->total_ms += ms;
-    }
-    return TRG_OK;
+    return render_done(c);
 }
 
 int trg_read_accum(trg_ctx *c, float *rgba) {
@@ -1324,14 +1320,20 @@ int trg_sync(trg_ctx *c) {
 // ---- host-only introspection: build the BVH exactly as trg_load_scene does and hand back the flattened
 //      arrays (no GPU needed).  nodes_out: 16 floats per node, tris_out: 12 floats per record; either may be
 //      NULL to query sizes only. ----
+// what the trg_debug_* builders share: every index names a vertex, then the tree as trg_load_scene builds it (boxes: as the caller asks)
+static int debug_build(const float *positions3, const uint32_t *indices, const uint32_t *material_ids, uint32_t n_verts, uint32_t n_tris, bool boxes, Bvh &bvh) {
+    for (size_t i = 0; i < (size_t)n_tris * 3; ++i)
+        if (indices[i] >= n_verts) return TRG_ERR_INVALID;
+    build_bvh(positions3, indices, material_ids, n_tris, bvh, false, boxes);
+    return TRG_OK;
+}
+
 int trg_debug_build_bvh(const float *positions3, const uint32_t *indices, const uint32_t *material_ids, uint32_t n_verts,
                         uint32_t n_tris, float *nodes_out, uint32_t nodes_cap, float *tris_out, uint32_t tris_cap,
                         uint32_t *n_nodes, uint32_t *n_tri_records, uint32_t *depth) {
     if (n_tris && (!positions3 || !indices || !material_ids)) return TRG_ERR_INVALID;
-    for (size_t i = 0; i < (size_t)n_tris * 3; ++i)
-        if (indices[i] >= n_verts) return TRG_ERR_INVALID;
     Bvh bvh;
-    build_bvh(positions3, indices, material_ids, n_tris, bvh, false, debug_want_boxes());
+    if (int rc = debug_build(positions3, indices, material_ids, n_verts, n_tris, debug_want_boxes(), bvh)) return rc;
     const uint32_t nrec = (uint32_t)(bvh.tris.size() / 3);
     if (n_nodes) *n_nodes = bvh.n_nodes;
     if (n_tri_records) *n_tri_records = nrec;
@@ -1350,10 +1352,8 @@ int trg_debug_build_bvh(const float *positions3, const uint32_t *indices, const 
 int trg_debug_build_bvh4(const float *positions3, const uint32_t *indices, const uint32_t *material_ids, uint32_t n_verts,
                          uint32_t n_tris, float *nodes4_out, uint32_t nodes4_cap, uint32_t *n_nodes4, uint32_t *depth4) {
     if (n_tris && (!positions3 || !indices || !material_ids)) return TRG_ERR_INVALID;
-    for (size_t i = 0; i < (size_t)n_tris * 3; ++i)
-        if (indices[i] >= n_verts) return TRG_ERR_INVALID;
     Bvh bvh;
-    build_bvh(positions3, indices, material_ids, n_tris, bvh, false, debug_want_boxes());
+    if (int rc = debug_build(positions3, indices, material_ids, n_verts, n_tris, debug_want_boxes(), bvh)) return rc;
     if (n_nodes4) *n_nodes4 = bvh.n_nodes4;
     if (depth4) *depth4 = bvh.depth4;
     if (nodes4_out) {
@@ -1366,10 +1366,8 @@ int trg_debug_build_bvh4(const float *positions3, const uint32_t *indices, const
 int trg_debug_boxes(const float *positions3, const uint32_t *indices, const uint32_t *material_ids, uint32_t n_verts, uint32_t n_tris,
                     float *boxes20_out, uint32_t boxes_cap, uint32_t *n_boxes) {
     if (n_tris && (!positions3 || !indices || !material_ids)) return TRG_ERR_INVALID;
-    for (size_t i = 0; i < (size_t)n_tris * 3; ++i)
-        if (indices[i] >= n_verts) return TRG_ERR_INVALID;
     Bvh bvh;
-    build_bvh(positions3, indices, material_ids, n_tris, bvh, false, true);
+    if (int rc = debug_build(positions3, indices, material_ids, n_verts, n_tris, true, bvh)) return rc;
     if (n_boxes) *n_boxes = bvh.n_boxes_real;
     if (boxes20_out) {
         if (boxes_cap < bvh.n_boxes_real) return TRG_ERR_RANGE;
@@ -1387,10 +1385,8 @@ int trg_debug_boxes(const float *positions3, const uint32_t *indices, const uint
 int trg_debug_build_bvh4q(const float *positions3, const uint32_t *indices, const uint32_t *material_ids, uint32_t n_verts,
                           uint32_t n_tris, uint32_t *nodes4q_out, uint32_t nodes4_cap, uint32_t *n_nodes4) {
     if (n_tris && (!positions3 || !indices || !material_ids)) return TRG_ERR_INVALID;
-    for (size_t i = 0; i < (size_t)n_tris * 3; ++i)
-        if (indices[i] >= n_verts) return TRG_ERR_INVALID;
     Bvh bvh;
-    build_bvh(positions3, indices, material_ids, n_tris, bvh, false, debug_want_boxes());
+    if (int rc = debug_build(positions3, indices, material_ids, n_verts, n_tris, debug_want_boxes(), bvh)) return rc;
     if (n_nodes4) *n_nodes4 = bvh.n_nodes4;
     if (nodes4q_out) {
         if (nodes4_cap < bvh.n_nodes4) return TRG_ERR_RANGE;
@@ -1402,10 +1398,8 @@ int trg_debug_build_bvh4q(const float *positions3, const uint32_t *indices, cons
 int trg_debug_leaf_records(const float *positions3, const float *normals3, const float *colors3, const uint32_t *indices, const uint32_t *material_ids,
                            uint32_t n_verts, uint32_t n_tris, float *records32_out, uint32_t records_cap, uint32_t *n_records) {
     if (n_tris && (!positions3 || !normals3 || !colors3 || !indices || !material_ids)) return TRG_ERR_INVALID;
-    for (size_t i = 0; i < (size_t)n_tris * 3; ++i)
-        if (indices[i] >= n_verts) return TRG_ERR_INVALID;
     Bvh bvh;
-    build_bvh(positions3, indices, material_ids, n_tris, bvh, false, debug_want_boxes());
+    if (int rc = debug_build(positions3, indices, material_ids, n_verts, n_tris, debug_want_boxes(), bvh)) return rc;
     const uint32_t nrec = (uint32_t)(bvh.tris.size() / 3);
     if (n_records) *n_records = nrec;
     if (records32_out) {
@@ -1419,10 +1413,8 @@ int trg_debug_leaf_records(const float *positions3, const float *normals3, const
 int trg_debug_plane_records(const float *positions3, const uint32_t *indices, const uint32_t *material_ids, uint32_t n_verts, uint32_t n_tris,
                             float *planes12_out, uint16_t *meta_out, uint32_t records_cap, uint32_t *n_records, float *center3_out) {
     if (!positions3 || !indices || !material_ids || n_tris == 0) return TRG_ERR_INVALID;
-    for (size_t i = 0; i < (size_t)n_tris * 3; ++i)
-        if (indices[i] >= n_verts) return TRG_ERR_INVALID;
     Bvh bvh;
-    build_bvh(positions3, indices, material_ids, n_tris, bvh, false, debug_want_boxes());
+    if (int rc = debug_build(positions3, indices, material_ids, n_verts, n_tris, debug_want_boxes(), bvh)) return rc;
     const uint32_t nrec = (uint32_t)(bvh.tris.size() / 3);
     if (n_records) *n_records = nrec;
     float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY }, ctr[3];
@@ -1497,7 +1489,7 @@ int trg_trace(trg_ctx *c, const trg_ray *rays, size_t n, int any_hit, void *out)
         // trg_device.h trav_begin) -- all the renderers' ray masks 3 and 1 can ask for.  Rays that carry other mask bits are traced through the
         // HBM records, which hold the whole material id (MetalRenderer.mm:269,276: ray.mask & triangle mask, 32 bits).
         bool wide_mask = false;
-        if (!c->opt_strict && TRG_TRI_PLANES)
+        if (!c->opt_strict)
             for (size_t k = 0; k < n && !wide_mask; ++k) wide_mask = (rays[k].mask & ~3u) != 0u;
         const bool saved = c->opt_force_global;
         if (wide_mask) c->opt_force_global = true;
@@ -1515,8 +1507,7 @@ int trg_trace(trg_ctx *c, const trg_ray *rays, size_t n, int any_hit, void *out)
     const int slot = scratch_slot(c);
     if (slot < 0) return fail(c, TRG_ERR_RANGE, "trg_trace: more than %d different streams used with this context", trg_ctx::kScratchSlots - 1);
     if (int rc = ensure_stack_scratch(c, plan, (uint64_t)((n + kBlock - 1) / kBlock) * kBlock, p.stack, slot)) return rc;
-    hipError_t e = c->opt_strict ? launch_trace_strict(p, plan.lds_scene, any_hit != 0, plan.total, c->stream)
-                                 : launch_trace_fast(p, plan.lds_scene, any_hit != 0, plan.total, c->stream);
+    hipError_t e = launchers(c).trace(p, plan.lds_scene, any_hit != 0, plan.total, c->stream);
     if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_trace: launch failed: %s", hipGetErrorString(e));
     HIPCHK(c, hipMemcpyAsync(out, dout.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1533,8 +1524,7 @@ int trg_halton(trg_ctx *c, const uint32_t *i, const uint32_t *d, size_t n, float
     HIPCHK(c, di.alloc(n * 4)); HIPCHK(c, dd.alloc(n * 4)); HIPCHK(c, dout.alloc(n * 4));
     HIPCHK(c, hipMemcpyAsync(di.p, i, n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(dd.p, d, n * 4, hipMemcpyHostToDevice, c->stream));
-    hipError_t e = c->opt_strict ? launch_halton_strict((const uint32_t *)di.p, (const uint32_t *)dd.p, (uint32_t)n, (float *)dout.p, c->stream)
-                                 : launch_halton_fast((const uint32_t *)di.p, (const uint32_t *)dd.p, (uint32_t)n, (float *)dout.p, c->stream);
+    hipError_t e = launchers(c).halton((const uint32_t *)di.p, (const uint32_t *)dd.p, (uint32_t)n, (float *)dout.p, c->stream);
     if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_halton: launch failed: %s", hipGetErrorString(e));
     HIPCHK(c, hipMemcpyAsync(out, dout.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1571,8 +1561,7 @@ int trg_raygen(trg_ctx *c, uint32_t frameIndex, trg_ray *out) {
     HIPCHK(c, dout.alloc(n * sizeof(trg_ray)));
     trg_uniforms u = c->u;
     u.frameIndex = frameIndex;
-    hipError_t e = c->opt_strict ? launch_raygen_strict(u, c->offsets, (trg_ray *)dout.p, c->stream)
-                                 : launch_raygen_fast(u, c->offsets, (trg_ray *)dout.p, c->stream);
+    hipError_t e = launchers(c).raygen(u, c->offsets, (trg_ray *)dout.p, c->stream);
     if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_raygen: launch failed: %s", hipGetErrorString(e));
     HIPCHK(c, hipMemcpyAsync(out, dout.p, n * sizeof(trg_ray), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1589,8 +1578,7 @@ int trg_sample(trg_ctx *c, const float *p3, const float *n3, const float *r4, si
     HIPCHK(c, hipMemcpyAsync(dp.p, p3, n * 12, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(dn.p, n3, n * 12, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(dr.p, r4, n * 16, hipMemcpyHostToDevice, c->stream));
-    hipError_t e = c->opt_strict ? launch_sample_strict(c->u, (const float *)dp.p, (const float *)dn.p, (const float *)dr.p, (uint32_t)n, (float *)dout.p, c->stream)
-                                 : launch_sample_fast(c->u, (const float *)dp.p, (const float *)dn.p, (const float *)dr.p, (uint32_t)n, (float *)dout.p, c->stream);
+    hipError_t e = launchers(c).sample(c->u, (const float *)dp.p, (const float *)dn.p, (const float *)dr.p, (uint32_t)n, (float *)dout.p, c->stream);
     if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_sample: launch failed: %s", hipGetErrorString(e));
     HIPCHK(c, hipMemcpyAsync(out12, dout.p, n * 48, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1603,8 +1591,7 @@ int trg_postprocess(trg_ctx *c, uint8_t *rgba8, int flip_y) {
     const size_t n = (size_t)c->w * c->h;
     DevBuf dout;
     HIPCHK(c, dout.alloc(n * 4));
-    hipError_t e = c->opt_strict ? launch_postprocess_strict(c->accum, c->w, c->h, (uint8_t *)dout.p, flip_y, c->stream)
-                                 : launch_postprocess_fast(c->accum, c->w, c->h, (uint8_t *)dout.p, flip_y, c->stream);
+    hipError_t e = launchers(c).postprocess(c->accum, c->w, c->h, (uint8_t *)dout.p, flip_y, c->stream);
     if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_postprocess: launch failed: %s", hipGetErrorString(e));
     HIPCHK(c, hipMemcpyAsync(rgba8, dout.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

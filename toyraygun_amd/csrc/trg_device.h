@@ -140,9 +140,6 @@ __host__ __device__ constexpr uint32_t halton_pow(uint32_t b, int k) {
 template <uint32_t D>
 TRG_DEV float halton_c(uint32_t i) {
 #pragma clang fp contract(off)
-#ifdef TRG_EXP_NOHALTON  // timing-only ablation: a cheap hash instead of the radical inverse
-    return (float)((i * 2654435761u + D * 40503u) >> 8) * 0x1p-24f;
-#endif
     constexpr uint32_t B = halton_prime(D);
     if constexpr (B == 2) {
         const uint32_t rev = __brev(i);
@@ -574,17 +571,13 @@ TRG_DEV bool tri_test_planes_quad(const v4f a, const v4f b, const v4f c, V3 o, V
 }
 constexpr uint32_t kLeafQuad = 7u;   // bvh_build.h: the count field of a QUAD leaf (two triangles of a parallelogram, X then Y)
 constexpr uint32_t kLeafBox = 6u;    // ... of a BOX leaf (LDS-resident scenes): twelve records, six quads that bound a parallelepiped
-// the build's triangle test on an LDS-resident scene: planes + the u16 per record (shipped), or the Moeller-Trumbore rows (strict)
-constexpr bool kTriPlanes = !TRG_STRICT && TRG_TRI_PLANES;
-// ... and on a scene traversed from HBM: the leaf records of SceneDesc::off_fat_planes (rows 0..2 planes, words 30 / 31 index and mask)
-constexpr bool kRecPlanes = !TRG_STRICT && TRG_TRI_PLANES_HBM;
-
-constexpr bool kRecMetaFirst = kRecPlanes && TRG_REC_META_FIRST;   // plane records: index / mask = floats 12, 13 (else 30, 31)
-constexpr bool kBoxHbm = kRecPlanes && TRG_BOX_LEAVES && TRG_BOX_LEAVES_HBM;   // box leaves in the tree traversed from HBM (shipped build only)
-static_assert(!kBoxHbm || kRecMetaFirst, "a box record keeps its first record, mask and face table in row 3, which the unified step loads for TRG_REC_META_FIRST");
+// the shipped build: triangles of an LDS-resident scene in their plane form (planes + the u16 per record), scenes traversed from HBM through the
+// plane-form leaf records of SceneDesc::off_fat_planes (index and mask = floats 12, 13) and the tree whose boxes are leaves; the strict build
+// keeps the Moeller-Trumbore rows and the plain tree
+constexpr bool kShipped = !TRG_STRICT;
 // (TRG_WIDE8: the index word of a record carries two flag bits, 28 and 29 -- trav_step_wide8)
-TRG_DEV int fat_prim(const v4f *recs, uint32_t r) { return (TRG_WIDE8 ? 0x0FFFFFFF : -1) & __float_as_int(kRecMetaFirst ? recs[(size_t)r * kRecV4 + 3].x : kRecPlanes ? recs[(size_t)r * kRecV4 + 7].z : recs[(size_t)r * kRecV4].w); }
-TRG_DEV uint32_t fat_mask(const v4f *recs, uint32_t r) { return (uint32_t)__float_as_int(kRecMetaFirst ? recs[(size_t)r * kRecV4 + 3].y : kRecPlanes ? recs[(size_t)r * kRecV4 + 7].w : recs[(size_t)r * kRecV4 + 1].w); }
+TRG_DEV int fat_prim(const v4f *recs, uint32_t r) { return (TRG_WIDE8 ? 0x0FFFFFFF : -1) & __float_as_int(kShipped ? recs[(size_t)r * kRecV4 + 3].x : recs[(size_t)r * kRecV4].w); }
+TRG_DEV uint32_t fat_mask(const v4f *recs, uint32_t r) { return (uint32_t)__float_as_int(kShipped ? recs[(size_t)r * kRecV4 + 3].y : recs[(size_t)r * kRecV4 + 1].w); }
 
 // Per-lane traversal stack, laid out [level][thread] so lane i always hits LDS bank i%32 (no conflicts).
 // Scenes staged in LDS have shallow trees and keep the whole stack in LDS (klds = all levels).  Scenes in
@@ -669,13 +662,13 @@ TRG_DEV void trav_begin(const SceneView &sc, Trav &tv, V3 o, V3 d, float tmax, u
     // |d| < 1e-30 ? copysign(1e-30, d) : d, written on the bit patterns (the magnitudes of non-negative floats order like
     // unsigned integers) so that every constant is a VOP2 literal instead of a VGPR the inner loops would have to carry
     const float dx = clamp_away_from_zero(d.x), dy = clamp_away_from_zero(d.y), dz = clamp_away_from_zero(d.z);
-    tv.o = (kTriPlanes && rel) ? o - sc.center : o; tv.d = d;
+    tv.o = (kShipped && rel) ? o - sc.center : o; tv.d = d;
     tv.idx = rcp_fast(dx); tv.idy = rcp_fast(dy); tv.idz = rcp_fast(dz);
     tv.oix = o.x * tv.idx; tv.oiy = o.y * tv.idy; tv.oiz = o.z * tv.idz;
     // the plane test of an LDS-resident scene reads the mask off the u16 per record, (original index << 2) | (material id & 3): only the two low bits
     // of a ray's mask may take part, or they would match index bits.  (The renderers' rays carry 3 or 1; trg_trace sends rays whose mask has
     // higher bits through the HBM records, which keep the whole material id: trg_capi.cpp.)
-    tv.best = tmax; tv.rmask = (kTriPlanes && rel) ? (rmask & 3u) : rmask;
+    tv.best = tmax; tv.rmask = (kShipped && rel) ? (rmask & 3u) : rmask;
     tv.hit.t = -1.0f; tv.hit.prim = -1; tv.hit.u = 0.0f; tv.hit.v = 0.0f;
     tv.found = false;
     tv.node = 0; tv.sp = sp0;  // sp0 = stk.first(): the empty stack
@@ -843,7 +836,7 @@ TRG_DEV const v4f *lds_records(const SceneView &sc, uint32_t first);
 // the triangle and the weights of a hit that is still a box (h.prim <= -2): the hit point in the box's frame, the face = the axis along which it lies
 // farthest out, that face's own quad planes for (s, t) -- exactly what its quad test would have computed there
 TRG_DEV void lds_box_hit_resolve(const SceneView &sc, const Trav &tv, Hit &h) {
-    if (!(kTriPlanes && TRG_BOX_LEAVES) || h.prim > -2) return;
+    if (!kShipped || h.prim > -2) return;
     const uint32_t first = (uint32_t)(-h.prim - 2);
     const v4f *tr = lds_records(sc, first);
     const v4f b0 = tr[3], b1 = tr[4], b2 = tr[5];
@@ -868,10 +861,10 @@ TRG_DEV void lds_box_hit_resolve(const SceneView &sc, const Trav &tv, Hit &h) {
 // that of the box's first record: a box's triangles are consecutive, so any of them orders it against everything outside the box
 TRG_DEV int held_prim_index(const v4f *recs, uint32_t n_rec, int held) {
     const uint32_t r = (uint32_t)held;
-    return fat_prim(recs, (kBoxHbm && r >= n_rec) ? (uint32_t)__float_as_int(recs[(size_t)r * kRecV4 + 3].x) : r);
+    return fat_prim(recs, (kShipped && r >= n_rec) ? (uint32_t)__float_as_int(recs[(size_t)r * kRecV4 + 3].x) : r);
 }
 // ... and on a leaf RECORD of an HBM-resident scene (the hit keeps the record index; ties go to the lower original index, read back from the
-// held record only then): mask and prim are floats 13 and 12 of the record (TRG_REC_META_FIRST; its last two words before)
+// held record only then): mask and prim are floats 13 and 12 of the record
 template <bool COUNT>
 TRG_DEV bool trav_tri_planes_rec(const v4f a, const v4f b, const v4f c, uint32_t mask, int prim, Trav &tv, bool any, Counters &cnt, uint32_t rec, const v4f *recs, V3 center, bool quad, uint32_t n_rec) {
     const bool masked_in = (mask & tv.rmask) != 0u;
@@ -924,7 +917,7 @@ TRG_DEV bool trav_box_rec(const v4f b0, const v4f b1, const v4f b2, const v4f b3
 // the face = the axis along which it lies farthest out (|l_k| = 1 there, less on the other two; a lone quad dressed as a box of no thickness
 // says so in bit 31 of the table's high word: its l_2 is rounding noise), then (s, t) from the two OTHER coordinates and three bits per face.
 TRG_DEV void box_hit_resolve(const SceneView &sc, const Trav &tv, Hit &h) {
-    if (!kBoxHbm || h.prim < (int)sc.n_rec) return;
+    if (!kShipped || h.prim < (int)sc.n_rec) return;
     const v4f *br = sc.tris + (size_t)(uint32_t)h.prim * kRecV4;
     const v4f b0 = br[0], b1 = br[1], b2 = br[2], b3 = br[3];
     const V3 o = tv.o - sc.center, d = tv.d;
@@ -948,7 +941,7 @@ TRG_DEV void box_hit_resolve(const SceneView &sc, const Trav &tv, Hit &h) {
 // triangle `k` of the records starting at `tr` (LDS-resident scene): whichever test the build uses
 template <bool COUNT>
 TRG_DEV bool trav_tri_lds(const SceneView &sc, const v4f *tr, uint32_t rec, Trav &tv, bool any, Counters &cnt) {
-    if (kTriPlanes) return trav_tri_planes<COUNT>(tr[0], tr[1], tr[2], sc.meta[rec], tv, any, cnt);
+    if (kShipped) return trav_tri_planes<COUNT>(tr[0], tr[1], tr[2], sc.meta[rec], tv, any, cnt);
     return trav_tri_math<COUNT>(tr[0], tr[1], tr[2], tv, any, cnt);
 }
 
@@ -968,14 +961,14 @@ template <bool COUNT, int BLOCK, typename STK>
 TRG_DEV bool trav_leaf_step(const SceneView &sc, Trav &tv, bool any, STK stk, Counters &cnt) {
     const uint32_t code = (uint32_t)~tv.node;
     const bool quad = (code & 7u) == kLeafQuad;   // the two triangles of a parallelogram (bvh_build.h): ONE plane test in the shipped build
-    const bool box = TRG_BOX_LEAVES && (code & 7u) == kLeafBox;   // the twelve of a parallelepiped: ONE slab test in the shipped build
+    const bool box = (code & 7u) == kLeafBox;   // the twelve of a parallelepiped: ONE slab test in the shipped build
     const uint32_t first = code >> 3, count = quad ? 2u : box ? 12u : (code & 7u) + 1u;
     bool stop = false;
     {   // leaves of the host builder hold a quad, or one or two triangles: those without a loop (-2 %); more only from other builders
         const v4f *tr = lds_records(sc, first);
-        if (kTriPlanes && TRG_BOX_LEAVES && box) {
+        if (kShipped && box) {
             stop = trav_box_planes<COUNT>(sc, tr, first, tv, any, cnt);
-        } else if (kTriPlanes && quad) {
+        } else if (kShipped && quad) {
             stop = trav_quad_planes<COUNT>(sc, tr, first, tv, any, cnt);
         } else {
             stop = trav_tri_lds<COUNT>(sc, tr, first, tv, any, cnt);
@@ -1075,19 +1068,17 @@ TRG_DEV void trav_step_wide(const SceneView &sc, Trav &tv, bool any, STK stk, Co
     const uint32_t first = code >> 3, left = code & 7u;
     // one wave-uniform base + a 32-bit byte offset per lane (the scene blob is below 4 GiB and the records follow the nodes in it):
     // the loads take the SGPR-base form, no 64-bit address arithmetic per lane
-    const bool boxleaf = kBoxHbm && !inner && left == kLeafBox;   // (shipped build: ONE leaf for a parallelepiped's twelve triangles; its 64-byte record -- addressed like a
-                                                                  //  leaf record behind the leaf records -- is all the test reads)
+    const bool boxleaf = kShipped && !inner && left == kLeafBox;   // (shipped build: ONE leaf for a parallelepiped's twelve triangles; its 64-byte record -- addressed like a
+                                                                   //  leaf record behind the leaf records -- is all the test reads)
     const uint32_t off = inner ? (uint32_t)tv.node * 64u : (code & ~7u) * (uint32_t)(kRecV4 * 16 / 8) + sc.rec_delta;
     const v4f *ptr = reinterpret_cast<const v4f *>(reinterpret_cast<const char *>(sc.nodes) + off);
     const v4f q0 = ptr[0], q1 = ptr[1], q2 = ptr[2];
-    // the fourth load: the children of a node, or -- plane records -- the last row of the leaf record (its index and mask); one instruction for both kinds
+    // the fourth load: the children of a node, or -- plane records -- row 3 of the leaf record (its index and mask); one instruction for both kinds
     v4f q3;
-    if (kRecMetaFirst) q3 = ptr[3];          // (the record's first 64 bytes hold all a test reads: one line half, like a node)
-    else if (kRecPlanes) q3 = ptr[inner ? 3 : 7];
-    else if (inner) q3 = ptr[3];
+    if (kShipped || inner) q3 = ptr[3];   // (the record's first 64 bytes hold all a test reads: one line half, like a node)
     if (inner) {
         trav_node4_math<COUNT, BLOCK>(q0, q1, q2, q3, tv, stk, cnt);
-    } else if (kBoxHbm && boxleaf) {
+    } else if (boxleaf) {
         const bool stop = trav_box_rec<COUNT>(q0, q1, q2, q3, tv, any, cnt, first, sc.center, sc.tris, sc.n_rec);
         const int sp = tv.sp - (stop ? 0 : STK::unit);
         const int popped = stk.pop(sp);
@@ -1097,15 +1088,15 @@ TRG_DEV void trav_step_wide(const SceneView &sc, Trav &tv, bool any, STK stk, Co
         // a QUAD leaf (count field 7, bvh_build.h): the shipped build decides both triangles with one parallelogram test; the strict build
         // tests record `first`, then advances to the single-triangle code of record first + 1
         const bool quad = left == kLeafQuad;
-        const bool stop = kRecPlanes ? trav_tri_planes_rec<COUNT>(q0, q1, q2, (uint32_t)__float_as_int(kRecMetaFirst ? q3.y : q3.w), __float_as_int(kRecMetaFirst ? q3.x : q3.z), tv, any, cnt, first, sc.tris, sc.center, quad, sc.n_rec)
-                                     : trav_tri_math<COUNT, true>(q0, q1, q2, tv, any, cnt, first, sc.tris);
-        const bool more = kRecPlanes ? (left != 0u && !quad) : (left != 0u);
+        const bool stop = kShipped ? trav_tri_planes_rec<COUNT>(q0, q1, q2, (uint32_t)__float_as_int(q3.y), __float_as_int(q3.x), tv, any, cnt, first, sc.tris, sc.center, quad, sc.n_rec)
+                                   : trav_tri_math<COUNT, true>(q0, q1, q2, tv, any, cnt, first, sc.tris);
+        const bool more = kShipped ? (left != 0u && !quad) : (left != 0u);
         const bool do_pop = !stop && !more;
         const int sp = tv.sp - (do_pop ? STK::unit : 0);
         const int popped = stk.pop(sp);  // the sentinel at level 0 when nothing is pending
         // the next triangle of the leaf: ~(((first + 1) << 3) | (left - 1)) = node - 7 for left >= 1; after the first triangle of a quad
         // (strict build) ~(((first + 1) << 3) | 0) = node - 1
-        const int advanced = tv.node - ((!kRecPlanes && quad) ? 1 : 7);
+        const int advanced = tv.node - ((!kShipped && quad) ? 1 : 7);
         tv.node = stop ? kNodeDone : (more ? advanced : popped);
         tv.sp = sp;
     }
@@ -1118,7 +1109,6 @@ TRG_DEV void trav_step_wide(const SceneView &sc, Trav &tv, bool any, STK stk, Co
 template <bool COUNT, int BLOCK, typename STK>
 TRG_DEV void trav_step_hbm(const SceneView &sc, Trav &tv, bool any, STK stk, Counters &cnt) {
 #if TRG_WIDE8
-    static_assert(!kRecPlanes || kRecMetaFirst, "TRG_WIDE8 reads a plane record's index word and mask from floats 12, 13");
     trav_step_wide8<COUNT, BLOCK>(sc, tv, any, stk, cnt);
 #else
     trav_step_wide<COUNT, BLOCK>(sc, tv, any, stk, cnt);
@@ -1144,12 +1134,8 @@ TRG_DEV uint32_t lds_node_base(const SceneView &sc) {
 template <bool ANY, bool COUNT, int BLOCK, bool UNIFIED = false, typename STK>
 TRG_DEV bool traverse(const SceneView &sc, V3 o, V3 d, float tmax_ray, uint32_t rmask, Hit &hit, STK stk,
                       Counters &cnt) {
-#ifdef TRG_EXP_NOTRAVERSE  // timing-only ablation: a made-up hit, no traversal
-    hit.t = 0.5f + 0.001f * (float)(threadIdx.x & 15); hit.prim = ANY ? -1 : (int)((threadIdx.x * 7u + (uint32_t)(o.x * 64.0f)) % 34u); hit.u = 0.3f; hit.v = 0.3f;
-    return !ANY;
-#endif
 #if TRG_EXPERIMENTS
-    if (!UNIFIED && kTriPlanes && sc.n_flat != 0u) return traverse_flat<ANY, COUNT>(sc, o, d, tmax_ray, rmask, hit, cnt);   // (wave-uniform: a property of the scene)
+    if (!UNIFIED && kShipped && sc.n_flat != 0u) return traverse_flat<ANY, COUNT>(sc, o, d, tmax_ray, rmask, hit, cnt);   // (wave-uniform: a property of the scene)
 #endif
     Trav tv;
     trav_begin(sc, tv, o, d, tmax_ray, rmask, stk.first(), lds_node_base<UNIFIED>(sc), !UNIFIED);
@@ -1244,7 +1230,7 @@ TRG_DEV Surf<FAT> surf_fetch(const SceneView &sc, int ref) {
     s.ref = ref;
     if (FAT) {
         const v4f *rec = sc.tris + (size_t)(uint32_t)ref * kRecV4;
-        s.mat = (uint32_t)__float_as_int(kRecMetaFirst ? rec[3].y : kRecPlanes ? rec[7].w : rec[1].w);
+        s.mat = (uint32_t)__float_as_int(kShipped ? rec[3].y : rec[1].w);
         s.r3 = rec[3]; s.r4 = rec[4]; s.r5 = rec[5]; s.r6 = rec[6]; s.r7 = rec[7];
     } else {
         s.mat = sc.mats[ref];
@@ -1257,11 +1243,11 @@ TRG_DEV void surf_interp(const SceneView &sc, const Surf<FAT> &s, float cx, floa
     int prim = s.ref;
     if (FAT) {
         const float cz = 1.0f - cx - cy;
-        // (attributes at floats 12..29 of the record, or -- plane records with index / mask first -- at 14..31)
-        const V3 N0 = kRecMetaFirst ? mk(s.r3.z, s.r3.w, s.r4.x) : mk(s.r3.x, s.r3.y, s.r3.z), N1 = kRecMetaFirst ? mk(s.r4.y, s.r4.z, s.r4.w) : mk(s.r3.w, s.r4.x, s.r4.y);
-        const V3 N2 = kRecMetaFirst ? mk(s.r5.x, s.r5.y, s.r5.z) : mk(s.r4.z, s.r4.w, s.r5.x);
-        const V3 C0 = kRecMetaFirst ? mk(s.r5.w, s.r6.x, s.r6.y) : mk(s.r5.y, s.r5.z, s.r5.w), C1 = kRecMetaFirst ? mk(s.r6.z, s.r6.w, s.r7.x) : mk(s.r6.x, s.r6.y, s.r6.z);
-        const V3 C2 = kRecMetaFirst ? mk(s.r7.y, s.r7.z, s.r7.w) : mk(s.r6.w, s.r7.x, s.r7.y);
+        // (attributes at floats 12..29 of the record, or -- plane records: index / mask first -- at 14..31)
+        const V3 N0 = kShipped ? mk(s.r3.z, s.r3.w, s.r4.x) : mk(s.r3.x, s.r3.y, s.r3.z), N1 = kShipped ? mk(s.r4.y, s.r4.z, s.r4.w) : mk(s.r3.w, s.r4.x, s.r4.y);
+        const V3 N2 = kShipped ? mk(s.r5.x, s.r5.y, s.r5.z) : mk(s.r4.z, s.r4.w, s.r5.x);
+        const V3 C0 = kShipped ? mk(s.r5.w, s.r6.x, s.r6.y) : mk(s.r5.y, s.r5.z, s.r5.w), C1 = kShipped ? mk(s.r6.z, s.r6.w, s.r7.x) : mk(s.r6.x, s.r6.y, s.r6.z);
+        const V3 C2 = kShipped ? mk(s.r7.y, s.r7.z, s.r7.w) : mk(s.r6.w, s.r7.x, s.r7.y);
         vcol = cx * C0 + cy * C1 + cz * C2;
         nraw = cx * N0 + cy * N1 + cz * N2;
         if (sc.tex.uv) prim = fat_prim(sc.tris, (uint32_t)s.ref);   // textures are addressed by the original index

@@ -32,13 +32,8 @@ constexpr int kCounterWords = 8;   // primary, bounce, shadow, shaded, node_fetc
 #endif
 constexpr uint32_t kMaxLdsScene = TRG_MAX_LDS_SCENE_KB * 1024u;  // scenes up to this size are staged in LDS per workgroup
 // render_kernel on an HBM-resident scene: park throughput + radiance in LDS while a ray pair is traced (6 floats per thread next
-// to the 3 of the running average), and keep this many traversal-stack levels in LDS (deeper ones go to global scratch)
-#ifndef TRG_PARK_PATH
-#define TRG_PARK_PATH 1
-#endif
-#ifndef TRG_PARK_OFFSET
-#define TRG_PARK_OFFSET 1   // ... and the pixel's Halton offset behind them (one more word per thread)
-#endif
+// to the 3 of the running average, then the pixel's Halton offset), and keep this many traversal-stack levels in LDS (deeper ones go to
+// global scratch)
 #ifndef TRG_STACK_LDS_LEVELS
 #define TRG_STACK_LDS_LEVELS 12
 #endif
@@ -54,19 +49,20 @@ struct SceneDesc {
     uint32_t lds_stage_bytes;       // bytes a workgroup stages into LDS (everything before the 4-wide nodes)
     uint32_t off_htab;              // Halton group tables (kHtabFloats floats), inside the staged region
     uint32_t off_fat, n_fat;        // leaf records of the HBM traversal: geometry + attributes, 128 bytes each, 128-byte aligned, leaf order
-    // LDS-resident scenes, shipped build (TRG_TRI_PLANES, round 4): the triangle test on three precomputed PLANES per triangle -- 48 bytes in
+    // LDS-resident scenes, shipped build (round 4): the triangle test on three precomputed PLANES per triangle -- 48 bytes in
     // leaf order like the Moeller-Trumbore records (off_tris), kept outside the staged part and copied over them at staging time --
     // and, inside the staged part, one u16 per record: (original index << 2) | (material id & 3), the test's mask and the hit's primitive
     uint32_t off_tris_alt, off_meta, n_tris_rec;   // n_tris_rec = 48-byte records of the staged part (leaf order)
-    // scenes traversed from HBM, shipped build (TRG_TRI_PLANES_HBM): a second set of 128-byte leaf records whose rows 0..2 are the triangle's
-    // three planes, then the original index and the material id (floats 12, 13: TRG_REC_META_FIRST), then the attributes (floats 14..31)
+    // scenes traversed from HBM, shipped build: a second set of 128-byte leaf records whose rows 0..2 are the triangle's three planes, then
+    // the original index and the material id (floats 12, 13: everything a triangle TEST reads sits in the first 64 bytes), then the attributes
+    // (floats 14..31)
     uint32_t off_fat_planes;
     // FLAT primitive list (round-5 EXPERIMENT, experiments library with TRG_FLAT_PRIMS=1 only; scenes of at most kFlatMaxPrims primitives after the quads are paired -- the Cornell box has 18):
     // n_flat x 64 bytes in the blob, outside the staged part -- rows 0..2 the plane record of the triangle or of the quad's parallelogram (as
     // off_tris_alt), row 3 = (original index of the triangle / of the quad's X, original index of the quad's Y or ~0, material id = mask, 1 = quad).
     // Such a scene is not walked through its tree at all: every ray tests every primitive in record order (trg_device.h traverse_flat).
     uint32_t off_flat, n_flat;
-    // BOX leaves of the shipped build's HBM traversal (TRG_BOX_LEAVES_HBM, round 5): a second array of quantised 4-wide nodes in which a box's subtree is
+    // BOX leaves of the shipped build's HBM traversal (round 5; the strict build keeps the plain tree): a second array of quantised 4-wide nodes in which a box's subtree is
     // ONE leaf -- child code ~(((n_fat + box index) << 3) | 6): a box is addressed like a leaf record behind the plane records, same 128-byte stride, so the
     // traversal's address arithmetic does not know about boxes -- and 64 bytes per box: rows 0..2 = (a_k, d_k), l_k = a_k . (P - center) + d_k the box's own
     // frame, row 3 = (its first leaf record, material id, face table low, high: 7 bits per face f = 2 k + (l_k > 0), 0..3 in the low word, 4..5 in
@@ -223,28 +219,9 @@ struct TraceParams {
 // samples of bounce 0), staged in LDS with the scene: T_b[r] = radical inverse of r read as a K-digit base-b number.
 // The shipped megakernel on an LDS-resident scene takes K digits per lookup instead of one digit per five VALU
 // instructions (trg_device.h halton_c); everything else (strict build, HBM scenes, other dimensions) keeps the digits.
-// The shipped build's triangle test on an LDS-resident scene: 1 = three planes per triangle (17 arithmetic instructions), 0 = Moeller-Trumbore
-// on (v0, e1, e2) like the strict build (31).  trg_device.h tri_test_planes.
-#ifndef TRG_TRI_PLANES
-#define TRG_TRI_PLANES 1
-#endif
-#ifndef TRG_REC_META_FIRST
-#define TRG_REC_META_FIRST 1   // plane-form leaf records: 1 = the original index and the material id are floats 12, 13 -- everything a triangle TEST reads
-                               // sits in the first 64 bytes of the record, the attributes follow at floats 14..31; 0 = attributes at 12..29, index / mask last
-#endif
-#ifndef TRG_TRI_PLANES_HBM
-#define TRG_TRI_PLANES_HBM 1   // the same for scenes traversed from HBM (their own set of leaf records, SceneDesc::off_fat_planes)
-#endif
-#ifndef TRG_BOX_LEAVES
-#define TRG_BOX_LEAVES 1       // scenes staged in LDS: addCube's twelve triangles become ONE leaf (bvh_build.h kLeafBox): twelve triangle tests in the strict
-                               // build, one slab test in the parallelepiped's own frame in the shipped one (trg_device.h trav_box_planes)
-#endif
-#ifndef TRG_BOX_LEAVES_HBM
-#define TRG_BOX_LEAVES_HBM 1   // the same box leaf for scenes traversed from HBM (shipped build: SceneDesc::off_nodes4_box / off_boxrec; the strict build keeps the plain tree)
-#endif
-#ifndef TRG_HALTON_TABLES
-#define TRG_HALTON_TABLES 1
-#endif
+// The shipped build tests triangles by three planes each (17 arithmetic instructions against Moeller-Trumbore's 31 on (v0, e1, e2), which the
+// strict build keeps: trg_device.h tri_test_planes), and addCube's twelve triangles are ONE box leaf (bvh_build.h kLeafBox): one slab test in the
+// parallelepiped's own frame in the shipped build (trg_device.h trav_box_planes, trav_box_rec), twelve triangle tests in the strict one.
 struct HtabSpec { uint32_t base, digits, radix, offset; };
 constexpr HtabSpec kHtab[5] = { { 3, 4, 81, 0 }, { 5, 3, 125, 81 }, { 7, 2, 49, 206 }, { 11, 2, 121, 255 }, { 13, 2, 169, 376 } };
 constexpr uint32_t kHtabFloats = 545, kHtabBytes = 2192;  // 545 * 4 rounded up to 16

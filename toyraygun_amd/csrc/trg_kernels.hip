@@ -18,9 +18,6 @@ using namespace trgdev;
 #define SFX(name) name##_fast
 #endif
 
-#ifndef TRG_UNIFORMS_AT_USE
-#define TRG_UNIFORMS_AT_USE 1
-#endif
 #ifndef TRG_EXPERIMENTS
 #define TRG_EXPERIMENTS 0   // 1: experiments/lib/libtoyraygun_hip_exp.so -- the product library + the schedules in experiments/
 #endif
@@ -50,7 +47,7 @@ TRG_DEV SceneView scene_view(const trg::SceneDesc &sc, unsigned char *smem) {
         const uint32_t n16 = sc.lds_stage_bytes >> 4;
         for (uint32_t i = threadIdx.x; i < n16; i += trg::kBlock) dst[i] = src[i];
         __syncthreads();
-        if (kTriPlanes) {   // the shipped build tests triangles in their PLANE form: those records over the Moeller-Trumbore ones
+        if (kShipped) {   // the shipped build tests triangles in their PLANE form: those records over the Moeller-Trumbore ones
             const uint4 *alt = reinterpret_cast<const uint4 *>(sc.blob + sc.off_tris_alt);
             uint4 *tr = reinterpret_cast<uint4 *>(smem + sc.off_tris);
             for (uint32_t i = threadIdx.x; i < sc.n_tris_rec * 3u; i += trg::kBlock) tr[i] = alt[i];
@@ -65,17 +62,17 @@ TRG_DEV SceneView scene_view(const trg::SceneDesc &sc, unsigned char *smem) {
         v.htab = reinterpret_cast<const float *>(smem + sc.off_htab);
     } else {
         // traversed from HBM: the quantised 4-wide nodes and the 128-byte leaf records (geometry + attributes, trg_device.h kRecV4)
-        v.nodes = reinterpret_cast<const v4f *>(sc.blob + (kBoxHbm ? sc.off_nodes4_box : sc.off_nodes4));   // (shipped build: the flavour whose boxes are leaves)
-        v.tris = reinterpret_cast<const v4f *>(sc.blob + (kRecPlanes ? sc.off_fat_planes : sc.off_fat));
+        v.nodes = reinterpret_cast<const v4f *>(sc.blob + (kShipped ? sc.off_nodes4_box : sc.off_nodes4));   // (shipped build: the flavour whose boxes are leaves)
+        v.tris = reinterpret_cast<const v4f *>(sc.blob + (kShipped ? sc.off_fat_planes : sc.off_fat));
         v.normals = nullptr; v.colors = nullptr; v.mats = nullptr; v.meta = nullptr;
         v.htab = nullptr;
     }
     v.flat = reinterpret_cast<const v4f *>(sc.blob + sc.off_flat);
-    v.n_flat = (LDS_SCENE && kTriPlanes) ? sc.n_flat : 0u;
+    v.n_flat = (LDS_SCENE && kShipped) ? sc.n_flat : 0u;
     v.center = mk(sc.center[0], sc.center[1], sc.center[2]);
     v.tex.uv = nullptr; v.tex.ids = nullptr; v.tex.table = nullptr; v.tex.texels = nullptr;
     v.n_rec = sc.n_fat;
-    v.rec_delta = LDS_SCENE ? 0u : (kRecPlanes ? sc.off_fat_planes : sc.off_fat) - (kBoxHbm ? sc.off_nodes4_box : sc.off_nodes4);   // (>= 0: both node arrays sit before the records, trg_capi.cpp plan_scene_layout)
+    v.rec_delta = LDS_SCENE ? 0u : (kShipped ? sc.off_fat_planes : sc.off_fat) - (kShipped ? sc.off_nodes4_box : sc.off_nodes4);   // (>= 0: both node arrays sit before the records, trg_capi.cpp plan_scene_layout)
     return v;
 }
 
@@ -174,21 +171,17 @@ TRG_DEV V3 path_radiance(const trg::RenderParams &p, const SceneView &sc, STK st
     // Halton index of this pixel-sample (Raytracing.metal:67: offset + uniforms.frameIndex, wraps mod 2^32).  `frame` is wave-uniform:
     // the sum is re-formed where it is used instead of living in a VGPR of its own across the traversals.
     // (HBM scenes: the offset itself is parked in LDS behind the path state and read back where the index is formed)
-#define TRG_HIDX ((TRG_PARK_OFFSET && path_park ? (uint32_t)__float_as_int(path_park[6 * trg::kBlock]) : offset) + frame)
+#define TRG_HIDX ((path_park ? (uint32_t)__float_as_int(path_park[6 * trg::kBlock]) : offset) + frame)
     V3 o, d;
-    constexpr bool TAB = LDS_SCENE && !TRG_STRICT && TRG_HALTON_TABLES;  // Halton group tables staged with the scene
+    constexpr bool TAB = LDS_SCENE && !TRG_STRICT;  // Halton group tables staged with the scene
     // The 176-byte uniform block is read from the kernel-argument segment WHERE IT IS USED (scalar loads, cached) through a pointer
     // the optimiser cannot see through: loaded once at kernel entry its 44 dwords sat in SGPRs across every traversal, and with
     // 80 (LDS scenes) / 96 (HBM scenes) SGPRs per wave about 60 of them were spilled to VGPR lanes and, from there, to scratch.
-#if TRG_UNIFORMS_AT_USE
     typedef const __attribute__((address_space(4))) trg_uniforms cu_t;
     cu_t *up = (cu_t *)__builtin_amdgcn_kernarg_segment_ptr();   // RenderParams::u is the first member
     static_assert(offsetof(trg::RenderParams, u) == 0, "uniforms must lead the kernel arguments");
     asm volatile("" : "+s"(up));
 #define TRG_U (*(const trg_uniforms *)up)
-#else
-#define TRG_U p.u
-#endif
     raygen<TAB>(TRG_U, x, y, TRG_HIDX, o, d, sc.htab);
     V3 thr = mk(1.0f, 1.0f, 1.0f);  // ray.color
     V3 rad = mk(0.0f, 0.0f, 0.0f);  // the render target texel of this frame
@@ -205,9 +198,7 @@ TRG_DEV V3 path_radiance(const trg::RenderParams &p, const SceneView &sc, STK st
         for (uint32_t b = 0; b < p.bounces; ++b) {
             if (__ballot(active) == 0ull) break;  // whole wavefront terminated
             const bool last = (b + 1u == p.bounces);  // wave-uniform
-#if TRG_UNIFORMS_AT_USE
             asm volatile("" : "+s"(up));   // the uniforms of this bounce's shading event are loaded after this point
-#endif
             if (b > 0) pc.bounce += wave_count(active);
             ShadeOut so; so.want_shadow = false; so.shaded = false;
             if (active) {
@@ -236,9 +227,7 @@ TRG_DEV V3 path_radiance(const trg::RenderParams &p, const SceneView &sc, STK st
         for (uint32_t b = 0; b < p.bounces; ++b) {
             if (__ballot(active) == 0ull) break;
             const bool last = (b + 1u == p.bounces);
-#if TRG_UNIFORMS_AT_USE
             asm volatile("" : "+s"(up));
-#endif
             ShadeOut so; so.want_shadow = false; so.want_next = false; so.shaded = false; so.sdir = mk(0.0f, 0.0f, 1.0f); so.scol = mk(0.0f, 0.0f, 0.0f); so.smax = -1.0f;
             if (active) {
                 uint32_t rmask = TRG_RMASK;
@@ -305,7 +294,7 @@ __global__ __launch_bounds__(trg::kBlock, LDS_SCENE ? TRG_EXP_WAVES : TRG_EXP_WA
     // one (its traversal needs the registers, and its LDS holds only the stacks): [component][thread], conflict-free.
     constexpr bool PARK = !LDS_SCENE;
     lds_float_t *park = (lds_float_t *)(reinterpret_cast<float *>(smem + p.acc_off) + threadIdx.x);
-    lds_float_t *path_park = (PARK && TRG_PARK_PATH) ? park + 3 * trg::kBlock : nullptr;
+    lds_float_t *path_park = PARK ? park + 3 * trg::kBlock : nullptr;
     V3 acc = mk(0.0f, 0.0f, 0.0f);
     {
         const uint32_t lane = lane_id();
@@ -315,7 +304,7 @@ __global__ __launch_bounds__(trg::kBlock, LDS_SCENE ? TRG_EXP_WAVES : TRG_EXP_WA
         if (valid) offset = p.offsets[yi * p.u.width + x];
         if (valid && p.frame_begin > 0) { const v4f a = accum[pix]; acc = mk(a.x, a.y, a.z); }
         if (PARK) { park[0] = acc.x; park[trg::kBlock] = acc.y; park[2 * trg::kBlock] = acc.z; }
-        if (TRG_PARK_OFFSET && path_park) { path_park[6 * trg::kBlock] = __int_as_float((int)offset); offset = 0u; }
+        if (path_park) { path_park[6 * trg::kBlock] = __int_as_float((int)offset); offset = 0u; }
     }
 
     PathCounters pc; pc.primary = 0; pc.bounce = 0; pc.shadow = 0; pc.shaded = 0;
@@ -411,7 +400,7 @@ __global__ __launch_bounds__(trg::kBlock, LDS_SCENE ? TRG_EXP_WAVES_FP : TRG_EXP
     V3 acc = mk(0.0f, 0.0f, 0.0f);
     // an HBM-resident scene parks throughput, radiance and the pixel's Halton offset in LDS while rays are traced (path_radiance), as
     // render_kernel does: seven words per thread behind the parked radiances
-    constexpr bool PARK = !LDS_SCENE && TRG_PARK_PATH && TRG_PARK_OFFSET;
+    constexpr bool PARK = !LDS_SCENE;
     lds_float_t *path_park = PARK ? (lds_float_t *)(reinterpret_cast<float *>(smem + p.acc_off) + threadIdx.x) : nullptr;
     {
         const uint32_t lane = lane_id();

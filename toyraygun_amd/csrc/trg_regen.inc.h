@@ -63,8 +63,8 @@ TRG_DEV void regen_count(lds_int_t *wred, int k, bool pred) {
     if (n != 0u && lane_id() == 0u) wred[k] = wred[k] + (int)n;
 }
 
-static_assert(TRG_PARK_PATH && TRG_PARK_OFFSET, "render_regen_kernel uses all ten words per thread of the LDS render_kernel parks its path and its Halton offset in "
-                                               "(plan_lds_as: 40 bytes per thread): nine of path state, and waves 2 and 3 stage their log records in word [9]");
+// render_regen_kernel uses all ten words per thread of the LDS render_kernel parks its path and its Halton offset in (plan_lds_as: 40 bytes
+// per thread): nine of path state, and waves 2 and 3 stage their log records in word [9]
 template <bool COUNT, bool PERSIST = false>
 __global__ __launch_bounds__(trg::kBlock, TRG_EXP_WAVES_HBM) void render_regen_kernel(const trg::RenderParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -153,14 +153,8 @@ __global__ __launch_bounds__(trg::kBlock, TRG_EXP_WAVES_HBM) void render_regen_k
     trav_begin(sc, tv, mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 1.0f), 0.0f, 0u, stk.first());
     tv.node = kNodeDone;
     uint32_t rot = 0, it = 0;
-#ifdef TRG_REGEN_GUARD
-    uint32_t guard = 0;
-#endif
 
     for (;;) {
-#ifdef TRG_REGEN_GUARD
-        if (++guard > (1u << 24)) break;   // bring-up only
-#endif
         const bool waiting = running && !in_shadow && !in_next;
         const uint64_t wmask = __ballot(waiting);
         const uint64_t tmask = __ballot(in_shadow || in_next);

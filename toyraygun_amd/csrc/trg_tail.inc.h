@@ -18,7 +18,7 @@
 template <bool COUNT, typename STK>
 TRG_DEV void path_segment_lds(const trg::RenderParams &p, const SceneView &sc, STK stk, uint32_t offset, uint32_t frame, uint32_t b0, uint32_t b1,
                               V3 &o, V3 &d, V3 &thr, V3 &rad, bool &active, bool &primary_ray, V3 light_color, PathCounters &pc, Counters &cnt) {
-    constexpr bool TAB = !TRG_STRICT && TRG_HALTON_TABLES;
+    constexpr bool TAB = !TRG_STRICT;
     typedef const __attribute__((address_space(4))) trg_uniforms cu_t;
     cu_t *up = (cu_t *)__builtin_amdgcn_kernarg_segment_ptr();   // RenderParams::u is the first member (see path_radiance)
     for (uint32_t b = b0; b < b1; ++b) {
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(trg::kBlock, TRG_EXP_WAVES) void render_head_kernel
     PathCounters pc; pc.primary = 0; pc.bounce = 0; pc.shadow = 0; pc.shaded = 0;
     Counters cnt; cnt.nodes = 0; cnt.tris = 0; cnt.wnodes = 0; cnt.wtris = 0;
     const V3 light_color = mk(p.u.light_color[0], p.u.light_color[1], p.u.light_color[2]);
-    constexpr bool TAB = !TRG_STRICT && TRG_HALTON_TABLES;
+    constexpr bool TAB = !TRG_STRICT;
     typedef const __attribute__((address_space(4))) trg_uniforms cu_t;
     cu_t *up = (cu_t *)__builtin_amdgcn_kernarg_segment_ptr();
     v4f *queue = reinterpret_cast<v4f *>(p.tail_queue) + (size_t)(blockIdx.x * (uint32_t)trg::kWaves + wave) * p.tail_cap * 3u;
