@@ -483,7 +483,7 @@ def test_box_flavour_of_the_wide_tree_under_sanitizers():
     """The second 4-wide collapse (shipped build, scenes traversed from HBM): every box -- and every lone quad, dressed as a box of no thickness --
     is a leaf addressed like a record behind the records.  tests/helpers/box_tree_check.cpp builds 1 ... 9,000 cubes + a lone triangle + two lone
     quads (threaded above 65,536 triangles), and once a handful of hostile cubes, under -fsanitize=address,undefined and checks that every child code is in range and every leaf
-    record is reached exactly once through exactly one leaf."""
+    record is reached exactly once through exactly one leaf; and that the traversal stack the host allots holds the worst case of BOTH collapses."""
     import tempfile
     csrc = os.path.join(ROOT, "toyraygun_amd", "csrc")
     with tempfile.TemporaryDirectory() as td:
@@ -495,6 +495,10 @@ def test_box_flavour_of_the_wide_tree_under_sanitizers():
     assert r.stdout.count("every record once: yes") == 5 and "ERROR" not in r.stderr and "runtime error" not in r.stderr
     # (cubes of no size, of no thickness, at 1e30, with a NaN or an infinite corner, of two materials, with a corner off by 1e-3: not boxes, no crash)
     assert "hostile cubes: none taken for a box" in r.stdout
+    # the traversal stack: both collapses of every scene -- cubes nested in cubes, rows of touching cubes, random clouds besides -- walked for the highest
+    # level a traversal can write, against the levels the host allots for the deeper of the two (bvh_build.h wide_stack_levels)
+    assert "stack: 180 scenes of nested, touching and random cubes fit the levels allotted" in r.stdout and "stack: every scene fits" in r.stdout
+    assert "levels would not hold it" not in r.stdout
 
 
 def test_threaded_host_build_is_identical_to_the_single_threaded_one(built):

@@ -85,3 +85,169 @@ def box_zoo(O):
     almost[(almost == corner).all(1)] += np.float32(1e-2)                 # one corner of the unit cube off by 1e-2 (1e-3 once scaled)
     s.add_geometry(almost, idx, mtx((0.1, 0.1, 0.1), 0.9, (-0.1, 0.9, 1.2)), (0.5, 0.2, 0.7), 1)
     return s, 2 + 6
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# Directed rays PARALLEL to faces (tests/test_gpu_parallel_rays.py).  The random ray sets of the suite draw directions from a normal distribution
+# or aim at a point, so no component of a direction -- in the world's frame or in a box's own -- is ever exactly zero; these generators plant
+# exact zeros, -0.0, +-1e-30, +-1e-38 and a denormal (+-1e-42) there, for every box leaf, lone quad and lone triangle of a scene.
+RAY_KINDS = ("axis_outside", "axis_inside", "frame_axis", "frame_pair", "slab_edge", "tiny", "plane_in", "plane_off")
+# what the zero of an axis-parallel direction is written as in the "tiny" rays
+TINY_ZEROS = (-0.0, 1e-30, -1e-30, 1e-38, -1e-38, 1e-42, -1e-42)
+
+
+def box_frames(boxes):
+    """(centre[3], A[3,3], H[3,3]) per row of trg_debug_boxes, in float64: l = A (P - centre), inside <=> |l_k| <= 1; the columns of H = inv(A) are
+    the box's half axes."""
+    out = []
+    for row in np.asarray(boxes):
+        c, A = row[2:5].astype(np.float64), row[5:14].reshape(3, 3).astype(np.float64)
+        out.append((c, A, np.linalg.inv(A)))
+    return out
+
+
+def box_triangles(positions, frames, tol=1e-4):
+    """box[t] = the frame whose corners are the three vertices of triangle t (|l_k| = 1 on every axis), or -1: the triangle is not part of a box."""
+    T = np.asarray(positions, np.float64).reshape(-1, 3, 3)
+    box = np.full(T.shape[0], -1, np.int32)
+    for i, (c, A, _) in enumerate(frames):
+        l = np.abs((T - c) @ A.T)
+        box[(np.abs(l - 1.0) < tol).all((1, 2)) & (box < 0)] = i
+    return box
+
+
+def _slabs(lo, ld):
+    """The forward ray lo + t ld, t >= 0, against the solid |l_k| <= 1, float64, one row per ray.  A direction component that is exactly zero is
+    PARALLEL: outside that slab a miss, inside no constraint."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t1, t2 = (-1.0 - lo) / ld, (1.0 - lo) / ld
+    par = ld == 0.0
+    near = np.where(par, np.where(np.abs(lo) <= 1.0, -np.inf, np.inf), np.minimum(t1, t2))
+    far = np.where(par, np.inf, np.maximum(t1, t2))
+    return np.maximum(near.max(1), 0.0) <= far.min(1)
+
+
+def ray_box_f64(frames, which, rays):
+    """Float64 geometry of ray r against box which[r] (-1: none), on the forward ray [0, inf): (passes the box's AABB, meets the box)."""
+    o, d = rays["origin"].astype(np.float64), rays["direction"].astype(np.float64)
+
+    in_aabb, in_box = np.zeros(len(rays), bool), np.zeros(len(rays), bool)
+    for i, (c, A, H) in enumerate(frames):
+        m = which == i
+        if not m.any():
+            continue
+        half = np.abs(H).sum(1)                                           # half extent of the AABB of c + H [-1, 1]^3
+        in_aabb[m] = _slabs((o[m] - c) / half, d[m] / half)
+        in_box[m] = _slabs((o[m] - c) @ A.T, d[m] @ A.T)
+    return in_aabb, in_box
+
+
+def _finish_rays(O, rng, org, dirn, kind, which):
+    n = len(org)
+    rays = np.zeros(n, O.RAY_DTYPE)
+    rays["origin"], rays["direction"] = np.asarray(org, np.float32), np.asarray(dirn, np.float32)
+    rays["mask"] = rng.choice([1, 2, 3], n, p=[0.2, 0.1, 0.7]).astype(np.uint32)
+    rays["maxDistance"] = np.where(rng.random(n) < 0.25, rng.uniform(0.05, 2.0, n), np.inf).astype(np.float32)
+    rays["maxDistance"][rng.random(n) < 0.01] = -1.0
+    return rays, np.asarray(kind, np.int8), np.asarray(which, np.int32)
+
+
+def parallel_box_rays(O, frames, seed, per_box=1.0, only=None):
+    """Rays parallel to the faces of every box of `frames` (or of the boxes `only`).  Returns (rays, kind, which): kind indexes RAY_KINDS, which
+    names the box a ray was built for.  About 1,300 x per_box rays per box:
+      axis_outside / axis_inside   +-x, +-y, +-z, origins uniform over 1.3 x the footprint of the box's AABB, starting just outside the AABB along
+                                   the ray / somewhere inside the AABB along the ray (inside the box or not);
+      frame_axis / frame_pair      direction = one half axis of the box / a combination of two, rounded to fp32: two / one of the direction's
+                                   components in the box's frame are zero or a few ulps from it; origins inside and outside each slab;
+      slab_edge                    the same with |l_k| = 1 +- a few ulps on a parallel axis (mostly undecidable: kept few);
+      tiny                         axis-parallel directions whose zeros are written as one of TINY_ZEROS."""
+    rng = np.random.default_rng(seed)
+    org, dirn, kind, which = [], [], [], []
+
+    def emit(o, d, k, i):
+        o, d = np.atleast_2d(o), np.atleast_2d(d)
+        d = np.broadcast_to(d, o.shape)
+        org.append(o); dirn.append(d); kind.append(np.full(len(o), RAY_KINDS.index(k))); which.append(np.full(len(o), i))
+
+    n_ax, n_fr, n_tiny, n_edge = (max(lo, int(round(v * per_box))) for v, lo in ((40, 2), (30, 2), (12, 2), (2, 1)))
+    ulps = np.array([-4, -1, 0, 1, 4]) * 2.0 ** -23
+    for i, (c, A, H) in enumerate(frames):
+        if only is not None and i not in only:
+            continue
+        half = np.abs(H).sum(1)
+        for ax in range(3):
+            for sgn in (1.0, -1.0):
+                d = np.zeros(3); d[ax] = sgn
+                def foot(n):
+                    # half of the origins uniform over 1.3 x the footprint; the other half -- where the box leaves room for it -- uniform over the
+                    # part of the AABB's footprint from which this direction passes the box by
+                    o = c + rng.uniform(-1.3, 1.3, (n, 3)) * half
+                    cand = c + rng.uniform(-1.0, 1.0, (8 * n, 3)) * half
+                    cand[:, ax] = c[ax] - sgn * half[ax] * 1.5
+                    cand = cand[~_slabs((cand - c) @ A.T, np.broadcast_to(A @ d, (8 * n, 3)))][: n // 2]
+                    o[: len(cand)] = cand
+                    return o
+                o = foot(n_ax); o[:, ax] = c[ax] - sgn * half[ax] * rng.uniform(1.02, 1.5, n_ax)
+                emit(o, d, "axis_outside", i)
+                o = foot(n_ax); o[:, ax] = c[ax] + half[ax] * rng.uniform(-1.0, 1.0, n_ax)
+                emit(o, d, "axis_inside", i)
+                for z in TINY_ZEROS:
+                    dz = np.full(3, z); dz[ax] = sgn
+                    if rng.random() < 0.5:
+                        dz[(ax + 1) % 3] = 0.0                             # (one tiny component beside an exact zero)
+                    o = foot(n_tiny); o[:, ax] = c[ax] - sgn * half[ax] * (rng.uniform(1.02, 1.5, n_tiny) if z > 0 else rng.uniform(-1.0, 1.0, n_tiny))
+                    emit(o, dz, "tiny", i)
+        # in the box's own frame: l = the origin there, the direction a half axis (or two) of the box
+        for axes, k, n in [((j,), "frame_axis", n_fr) for j in range(3)] + [((j, (j + 1) % 3), "frame_pair", n_fr) for j in range(3)]:
+            par = [a for a in range(3) if a not in axes]
+            for sgn in (1.0, -1.0):
+                w = np.zeros(3); w[list(axes)] = sgn * (1.0 if len(axes) == 1 else rng.uniform(0.3, 1.0, 2) * rng.choice([-1.0, 1.0], 2))
+                d = H @ w
+                d = (d / np.linalg.norm(d)).astype(np.float32)
+                l = rng.uniform(-1.45, 1.45, (n, 3))
+                l[: n // 2, axes[0]] = -np.sign(w[axes[0]]) * rng.uniform(1.05, 1.6, n // 2)     # half of them start outside, on the side the ray comes from
+                emit(c + l @ H.T, d, k, i)
+                l = rng.uniform(-0.9, 0.9, (n_edge * len(par), 3))
+                l[:, axes[0]] = -np.sign(w[axes[0]]) * 1.3
+                for q, a in enumerate(par):
+                    l[q * n_edge:(q + 1) * n_edge, a] = rng.choice([-1.0, 1.0], n_edge) * (1.0 + rng.choice(ulps, n_edge))
+                emit(c + l @ H.T, d, "slab_edge", i)
+    return _finish_rays(O, rng, np.concatenate(org), np.concatenate(dirn), np.concatenate(kind), np.concatenate(which))
+
+
+def parallel_plane_rays(O, positions, tris, extent, seed, per_tri=1.0):
+    """Rays parallel to the supporting plane of every triangle of `tris` (indices into the flat positions): along both edges from vertex 0 and
+    along their sum -- of a parallelogram's first triangle that is the quad's diagonal --, starting inside and outside the footprint,
+      plane_in    exactly IN the plane: only where fp32 can say so (the float64 normal, the direction and the origin's offset are exact, i.e. the
+                  primitive is axis-aligned); of an oblique plane the fp32 ray nearest to "in the plane" is decided by its own rounding;
+      plane_off   at 1e-6 ... 1e-2 of `extent` off the plane, either side: inside the child box an 8-bit quantised node gives a flat primitive.
+    Returns (rays, kind, which) with which = the triangle."""
+    rng = np.random.default_rng(seed)
+    T = np.asarray(positions, np.float64).reshape(-1, 3, 3)
+    org, dirn, kind, which = [], [], [], []
+    n = max(2, int(round(6 * per_tri)))
+    for t in tris:
+        v0, e1, e2 = T[t, 0], T[t, 1] - T[t, 0], T[t, 2] - T[t, 0]
+        nrm = np.cross(e1, e2)
+        if not np.linalg.norm(nrm) > 0:
+            continue
+        nrm /= np.linalg.norm(nrm)
+        for e in (e1, e2, e1 + e2, -e1, -e2):
+            d = (e / np.linalg.norm(e)).astype(np.float32)
+            exact = float(np.dot(nrm, d.astype(np.float64))) == 0.0 and np.count_nonzero(nrm) == 1
+            for off in (0.0, 1e-6, -1e-5, 1e-4, -1e-4, 1e-3, -1e-3, 1e-2, -1e-2):
+                if off == 0.0 and not exact:
+                    continue
+                uv = rng.uniform(0.05, 0.95, (n, 2))
+                start = rng.uniform(-0.6, 0.4, n)                           # along the ray, in units of |e|: before the footprint, or inside it
+                o = v0 + uv[:, :1] * e1 + uv[:, 1:] * e2 + nrm * (off * extent)
+                along = d.astype(np.float64) * np.linalg.norm(e)
+                far = np.where(rng.random(n) < 0.5, 1.2, 0.0)               # half of them start clear of the footprint, the others wherever `start` says
+                o = o + along * np.where(far > 0, -far, start)[:, None]
+                o32 = o.astype(np.float32)
+                if off == 0.0:                                               # keep the origin's plane coordinate exactly the vertices'
+                    a = int(np.flatnonzero(nrm)[0])
+                    o32[:, a] = np.float32(T[t, 0, a])
+                org.append(o32); dirn.append(np.broadcast_to(d, o32.shape))
+                kind.append(np.full(n, RAY_KINDS.index("plane_in" if off == 0.0 else "plane_off"))); which.append(np.full(n, t))
+    return _finish_rays(O, rng, np.concatenate(org), np.concatenate(dirn), np.concatenate(kind), np.concatenate(which))

@@ -76,6 +76,14 @@ struct Bvh {
     bool wide8_ok = false;          // false: not built, or a leaf of more than two records (TRG_BVH_MAXLEAF > 2)
 };
 
+// Levels of the traversal stack a 4-wide tree of `depth4` levels of inner nodes needs and gets (trg_capi.cpp allots them, tests/helpers/
+// box_tree_check.cpp walks the trees against it): the sentinel at level 0; an inner node `k` levels below the root is entered with at most 3 k
+// entries pending (each ancestor kept at most three) and stores its three candidates in the three slots above them whether it keeps them or
+// not (trg_device.h wide_select) -- levels up to 3 (depth4 - 1) + 3 are written, 3 depth4 + 1 levels; two are spare.  The depth is that of the
+// tree the kernels WALK: the shipped build's box flavour (nodes4q_box) is another greedy collapse than the plain one, so the host carries the
+// larger of depth4 and depth4_box.
+inline uint32_t wide_stack_levels(uint32_t depth4) { return 3u * depth4 + 3u; }
+
 // the pairing rule by itself (the device builders use it too): are triangles k and k + 1 the two halves of a parallelogram?  x / y = which is X, which Y
 bool quad_pair(const float *positions3, const uint32_t *indices, const uint32_t *masks, uint32_t ntris, uint32_t k, uint32_t &x, uint32_t &y);
 bool quads_enabled();   // TRG_BVH_QUADS != 0 (default on), read at every call

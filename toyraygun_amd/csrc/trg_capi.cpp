@@ -230,7 +230,7 @@ static bool plan_lds_as(const trg_ctx *c, LdsPlan &p, bool lds_scene, bool pool,
     } else {
         // the sentinel at level 0; 4-wide: up to three pending entries per level.  (TRG_WIDE8: one two-word node group per level of the 8-wide tree,
         // behind two sentinel levels: LdsStackT::first)
-        levels = TRG_WIDE8 ? 2 * c->bvh_depth4 + 4 : 3 * c->bvh_depth4 + 3;
+        levels = TRG_WIDE8 ? 2 * c->bvh_depth4 + 4 : wide_stack_levels(c->bvh_depth4);
         p.klds = std::min(levels, (uint32_t)c->opt_stack_levels);
     }
     p.overflow_levels = levels - p.klds;
@@ -805,6 +805,8 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
     hs->bvh_nodes = bvh.n_nodes; hs->bvh_depth = bvh.depth; hs->bvh_leaves = bvh.n_leaves;
     hs->bvh_quads = bvh.n_quads; hs->bvh_boxes = (lds_candidate || hbm_boxes) ? bvh.n_boxes_real : 0u;
     hs->bvh_nodes4 = TRG_WIDE8 ? bvh.n_nodes8 : bvh.n_nodes4; hs->bvh_depth4 = TRG_WIDE8 ? bvh.depth8 : bvh.depth4;
+    // the stack is sized by the tree the kernels walk (plan_lds_as): with box leaves in HBM that is the box flavour, another collapse of the same BVH2
+    if (!TRG_WIDE8 && hbm_boxes) hs->bvh_depth4 = std::max(bvh.depth4, bvh.depth4_box);
     *out = hs;
     return TRG_OK;
 }

@@ -803,6 +803,31 @@ TRG_DEV bool trav_quad_planes(const SceneView &sc, const v4f *tr, uint32_t rec, 
     tv.hit.v = take ? v : tv.hit.v;
     return any && ok;
 }
+// 1 / ld for the slab test of a box in its own frame, with a ray PARALLEL to a pair of faces kept out of trouble: ld = +-0 (and a denormal, which
+// v_rcp_f32 flushes) gives +-inf, and then m_k -+ |1 / ld_k| is inf - inf = NaN on one side, which fmaxf / fminf drop -- the slab would count as
+// infinitely wide even for an origin outside it.  The reciprocal is held to +-1e30 instead (one v_med3_f32): exactly what the node tests do by
+// pushing the direction to +-1e-30 (clamp_away_from_zero), at a third of the instructions.  The slab's planes then lie at (-lo_k -+ 1) * 1e30: both
+// far behind or far ahead for an origin outside (a miss), one either side from inside (no constraint); the products stay finite or become an
+// infinity of one sign (the frame rows of a lone quad are ~1e9), never NaN.
+// Two forms, each where it measured faster.  The builtin (`fmed3f(rcp, -1e30f, 1e30f)`): the compiler keeps -1e30 in an SGPR and +1e30 in a VGPR
+// across the traversal loops (a VOP3 instruction reads one scalar) -- one VGPR more in every render kernel.  Written out, `v_med3_f32 v, v, s, -s`
+// reads one SGPR twice and costs no register, but gfx950 needs a wait state between v_rcp_f32 and an instruction that reads its result, which the
+// compiler inserts for its own instructions and NOT around an asm block (a lone `v_med3_f32` in asm right behind the compiler's v_rcp_f32 read
+// stale registers in the regeneration kernels): so the three reciprocals are inside the block, two instructions between each and its med3 --
+// and the scheduler cannot move anything in between.  LDS-resident scenes (register-bound): the block, C2 +0.6 % time against +1.6 % with the
+// builtin; scenes in HBM (latency-bound, the reciprocals want other work between them): the builtin, C4 +1.0 % against +2.5 % with the block.
+constexpr float kRcpParallel = 1e30f;
+TRG_DEV void rcp3_parallel_safe(float x, float y, float z, float &ix, float &iy, float &iz, bool block) {
+    if (kShipped && block) {
+        asm("v_rcp_f32 %0, %3\n\tv_rcp_f32 %1, %4\n\tv_rcp_f32 %2, %5\n\t"
+            "v_med3_f32 %0, %0, %6, -%6\n\tv_med3_f32 %1, %1, %6, -%6\n\tv_med3_f32 %2, %2, %6, -%6"
+            : "=&v"(ix), "=&v"(iy), "=&v"(iz) : "v"(x), "v"(y), "v"(z), "s"(kRcpParallel));
+    } else {   // (the strict build tests a box's twelve triangles and never comes here)
+        ix = __builtin_amdgcn_fmed3f(rcp_fast(x), -kRcpParallel, kRcpParallel);
+        iy = __builtin_amdgcn_fmed3f(rcp_fast(y), -kRcpParallel, kRcpParallel);
+        iz = __builtin_amdgcn_fmed3f(rcp_fast(z), -kRcpParallel, kRcpParallel);
+    }
+}
 // a BOX leaf of an LDS-resident scene (shipped build; bvh_build.h kLeafBox, trg_capi.cpp): `tr` = its twelve plane records -- six quads, X then Y
 // each.  A quad's test reads its X record only, so the Y slots are free: record 1 holds the box, rows (a_k, d_k) with l_k = a_k . o + d_k the
 // ray origin in the box's own frame (inside <=> |l_k| <= 1), record 3 one word per face f = 2 k + (l_k > 0): (X-record offset << 16) | its byte
@@ -818,7 +843,8 @@ TRG_DEV bool trav_box_planes(const SceneView &sc, const v4f *tr, uint32_t first,
     const float lox = b0.x * o.x + (b0.y * o.y + (b0.z * o.z + b0.w)), ldx = b0.x * d.x + (b0.y * d.y + b0.z * d.z);
     const float loy = b1.x * o.x + (b1.y * o.y + (b1.z * o.z + b1.w)), ldy = b1.x * d.x + (b1.y * d.y + b1.z * d.z);
     const float loz = b2.x * o.x + (b2.y * o.y + (b2.z * o.z + b2.w)), ldz = b2.x * d.x + (b2.y * d.y + b2.z * d.z);
-    const float ix = rcp_fast(ldx), iy = rcp_fast(ldy), iz = rcp_fast(ldz);
+    float ix, iy, iz;
+    rcp3_parallel_safe(ldx, ldy, ldz, ix, iy, iz, true);
     const float mx = -lox * ix, my = -loy * iy, mz = -loz * iz;              // the ray meets the planes l_k = -1, +1 at m_k -+ |1 / ld_k|
     const float ax = fabsf(ix), ay = fabsf(iy), az = fabsf(iz);
     const float tnear = fmaxf(fmaxf(mx - ax, my - ay), mz - az), tfar = fminf(fminf(mx + ax, my + ay), mz + az);
@@ -897,12 +923,16 @@ TRG_DEV bool trav_box_rec(const v4f b0, const v4f b1, const v4f b2, const v4f b3
     const float lox = b0.x * o.x + (b0.y * o.y + (b0.z * o.z + b0.w)), ldx = b0.x * d.x + (b0.y * d.y + b0.z * d.z);
     const float loy = b1.x * o.x + (b1.y * o.y + (b1.z * o.z + b1.w)), ldy = b1.x * d.x + (b1.y * d.y + b1.z * d.z);
     const float loz = b2.x * o.x + (b2.y * o.y + (b2.z * o.z + b2.w)), ldz = b2.x * d.x + (b2.y * d.y + b2.z * d.z);
-    const float ix = rcp_fast(ldx), iy = rcp_fast(ldy), iz = rcp_fast(ldz);
+    float ix, iy, iz;
+    rcp3_parallel_safe(ldx, ldy, ldz, ix, iy, iz, false);
     const float mx = -lox * ix, my = -loy * iy, mz = -loz * iz;              // the ray meets the planes l_k = -1, +1 at m_k -+ |1 / ld_k|
     const float ax = fabsf(ix), ay = fabsf(iy), az = fabsf(iz);
     const float tnear = fmaxf(fmaxf(mx - ax, my - ay), mz - az), tfar = fminf(fminf(mx + ax, my + ay), mz + az);
     const float t = tnear < 0.0f ? tfar : tnear;                             // (from inside: the triangles are two-sided, the ray meets the face it leaves by)
-    const bool ok = (tnear <= tfar) && (t >= 0.0f) && (t <= tv.best) && masked_in;
+    // a LONE QUAD dressed as a box (bit 31 of the face table's high word) is a triangle pair, not a solid: a ray parallel to its plane misses it
+    // (the intersection contract: Moeller-Trumbore's det == 0), also one that lies IN the plane -- "inside" its slab of no thickness
+    const bool flat_parallel = __float_as_int(b3.w) < 0 && az >= kRcpParallel;
+    const bool ok = (tnear <= tfar) && (t >= 0.0f) && (t <= tv.best) && masked_in && !flat_parallel;
     const bool closer = any || !tv.found || t < tv.best;
     bool take = ok && closer;
     // the distance-tie rule (lower original index), as far as it can be told before the triangle is named: by the box's first record (read only at
