@@ -52,6 +52,11 @@ public:
     static const int kFramesInFlight = 3;               // MetalRenderer.mm:33 kMaxFramesInFlight
     bool readAccumulation(float *rgbaOut);              // width*height*4 floats, row 0 = scene bottom
     bool savePNG(const char *path);                     // ACES + sRGB (PostProcessing.metal:44-57), top row first
+    // ---- denoising (include/trg_denoise.h).  0 (default): off, nothing changes.  1..6: the image handed to post-processing (savePNG) is an
+    //      edge-avoiding a-trous filtered COPY of the accumulation buffer, guided by the first hits of frame 0 under the current camera; the
+    //      accumulation itself goes on undisturbed.  One device only: a device group ignores it.
+    bool setDenoise(int iterations);
+    int getDenoise() const { return m_denoise; }
     int getFrameIndex() const { return m_frameIndex; }
     double getLastRenderMs() const;
     uint64_t getRayCount() const;                       // primary + bounce + shadow rays traced so far
@@ -73,6 +78,7 @@ protected:
     int m_pendingFirst;          // frame index of the first of them
     Uniforms m_pendingUniforms;  // their uniforms (frameIndex zeroed)
     unsigned int m_launches;
+    int m_denoise;               // a-trous iterations of the image handed to post-processing; 0 = off
 };
 
 }  // namespace toyraygun

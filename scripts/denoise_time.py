@@ -1,0 +1,53 @@
+"""Device time of trg_guides_render and trg_denoise (5 iterations) on the Cornell box, HIP events on the context's stream:
+python scripts/denoise_time.py [width height reps]   (default 1920 1080 20; one warm-up each).  Prints one JSON line with the medians in
+ms, next to the filter's compulsory traffic (per iteration 48 B read + 16 B written per pixel) at the measured time."""
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from toyraygun_amd import capi, denoise, host   # noqa: E402
+
+w, h, reps = (int(a) for a in (sys.argv[1:4] + ["1920", "1080", "20"][len(sys.argv[1:4]):]))
+b = host.Scene.cornell_box().buffers()
+c = capi.Context(w, h)
+c.load_scene(b["positions"], b["normals"], b["colors"], b["indices"], b["material_ids"])
+c.set_uniforms(host.uniforms(w, h)[0])
+c.set_pixel_offsets_seed()
+c.set_option(capi.OPT_TIMING, 0)
+stream = torch.cuda.Stream()
+c.set_stream(stream.cuda_stream)
+acc = torch.empty((h, w, 4), dtype=torch.float32, device="cuda")
+g = torch.empty((2, h, w, 4), dtype=torch.float32, device="cuda")
+out = torch.empty_like(acc)
+c.bind_accum(acc.data_ptr())
+c.render(0, 4, 3)
+
+
+def timed(fn):
+    fn()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream); fn(); e1.record(stream)
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return float(np.median(ms))
+
+
+res = {"width": w, "height": h, "reps": reps}
+res["guides_ms"] = timed(lambda: denoise.guides(c, 0, out=g))
+for it in (1, 5):
+    res["denoise_%d_ms" % it] = timed(lambda: denoise.denoise(c, acc, g, out=out, iterations=it))
+res["render_4spp_ms"] = timed(lambda: c.render(0, 4, 3))
+res["compulsory_GB_5"] = 5 * 64 * w * h / 1e9
+res["compulsory_GBps_at_denoise_5"] = res["compulsory_GB_5"] / (res["denoise_5_ms"] * 1e-3)
+print(json.dumps(res))
+c.bind_accum(None)
+c.set_stream(None)
+denoise.release(c)
+c.close()

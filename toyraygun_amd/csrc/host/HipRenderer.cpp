@@ -9,12 +9,13 @@
 
 #include "png_writer.h"
 #include "trg.h"
+#include "trg_denoise.h"
 
 namespace toyraygun {
 
 HipRenderer::HipRenderer()
     : m_ctx(nullptr), m_group(nullptr), m_deviceCount(0), m_bounces(3), m_deviceBuild(0), m_offsetSeed(0x5EED0001u), m_sceneLoaded(false), m_synchronous(false), m_pending(0), m_pendingFirst(0),
-      m_launches(0) {
+      m_launches(0), m_denoise(0) {
     memset(&m_pendingUniforms, 0, sizeof(m_pendingUniforms));
 }
 HipRenderer::~HipRenderer() { destroy(); }
@@ -67,7 +68,7 @@ bool HipRenderer::init() {
 void HipRenderer::destroy() {
     if (m_ctx) flush();
     if (m_group) trg_group_destroy(m_group);   // owns every context, m_ctx included
-    else if (m_ctx) trg_destroy(m_ctx);
+    else if (m_ctx) { trg_denoise_release(m_ctx); trg_destroy(m_ctx); }   // (the denoise scratch is not trg_destroy's)
     m_group = nullptr;
     m_ctx = nullptr;
     m_sceneLoaded = false;
@@ -221,9 +222,30 @@ bool HipRenderer::readAccumulation(float *rgbaOut) {
     if (m_group) return trg_group_read_accum(m_group, 0, rgbaOut) == TRG_OK;   // waits for the gather onto device 0 (and the unpack of interleaved bands)
     return trg_read_accum(m_ctx, rgbaOut) == TRG_OK;
 }
+bool HipRenderer::setDenoise(int iterations) {
+    if (iterations < 0 || iterations > TRG_DENOISE_MAX_ITERATIONS) return false;
+    m_denoise = iterations;
+    return true;
+}
 bool HipRenderer::savePNG(const char *path) {
     if (!m_ctx || !flush()) return false;
     std::vector<uint8_t> rgba((size_t)m_width * m_height * 4);
+    if (m_denoise > 0 && !m_group) {
+        // tone-map a denoised copy: filter the accumulation buffer into the denoise state's image, bind that image as the accumulation
+        // buffer for the post-processing pass, and bind the renderer's own buffer back (everything on the context's one stream)
+        trg_denoise_params dp;
+        trg_denoise_default_params(&dp);
+        dp.iterations = m_denoise;
+        void *denoised = nullptr;
+        if (trg_denoise_accum(m_ctx, 0u, &dp, &denoised) != TRG_OK || trg_bind_accum(m_ctx, denoised) != TRG_OK) {
+            printf("HipRenderer: %s\n", trg_last_error(m_ctx));
+            return false;
+        }
+        const int rc = trg_postprocess(m_ctx, rgba.data(), 1);
+        trg_bind_accum(m_ctx, nullptr);
+        if (rc != TRG_OK) return false;
+        return trg_host::write_png_rgba8(path, rgba.data(), m_width, m_height);
+    }
     if ((m_group ? trg_group_postprocess(m_group, 0, rgba.data(), 1) : trg_postprocess(m_ctx, rgba.data(), 1)) != TRG_OK) return false;
     return trg_host::write_png_rgba8(path, rgba.data(), m_width, m_height);
 }

@@ -1,0 +1,613 @@
+// trg_denoise.hip -- include/trg_denoise.h: first-hit guide buffers and the edge-avoiding a-trous filter.  A translation unit of its own beside
+// the render kernels: it launches the library's stage-level raygen / trace kernels (both builds) and adds a gather kernel and the filter.
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+
+#include "../../include/trg_denoise.h"
+#include "bvh_build.h"
+#include "trg_internal.h"
+#include "trg_kernels.h"
+
+// the definition in trg_denoise.h is evaluated as written in both settings: no fused multiply-adds anywhere in this file
+#pragma clang fp contract(off)
+
+using namespace trg;
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The context.  trg_capi.cpp keeps `struct trg_ctx` to itself, and the kernel-source hash that ties the committed profiler counters to the
+// render path covers that file, so this unit REPEATS the definition, token for token (the same class defined twice with the same tokens is one
+// class).  tests/test_denoise_host.py compares the two texts, and ctx_ok() below cross-checks three fields against the library's own accessors
+// before anything is touched: whoever changes the struct over there is told to change it here.
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// BEGIN trg_ctx (copy of trg_capi.cpp)
+struct trg_ctx {
+    int device = 0;
+    uint32_t w = 0, h = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t fence[8] = {};
+    bool fence_set[8] = {};
+    float *accum_own = nullptr, *accum = nullptr;
+    uint32_t *offsets = nullptr;
+    unsigned long long *counters = nullptr;
+    unsigned char *blob = nullptr;
+    unsigned char *tex_mem = nullptr;   // uv | ids | table | texels (trg_load_textures)
+    TexDesc tex{};
+    // global overflow levels of the traversal stacks (grow-only), one buffer per launch the caller keeps in flight
+    // (TRG_OPT_LAUNCHES_IN_FLIGHT): launch k uses slot k mod in_flight, so overlapping launches never share one
+    static constexpr int kScratchSlots = 16;
+    hipStream_t slot_stream[kScratchSlots] = {};   // which stream owns scratch slot k (slot 0 = the context's own stream)
+    int slots_used = 1;
+    int *stack_scratch[kScratchSlots] = {};
+    size_t stack_scratch_bytes[kScratchSlots] = {};
+    // wavefront schedule: path state + ray queues of one batch, one set per launch in flight (grow-only)
+    unsigned char *wf_mem[kScratchSlots] = {};
+    size_t wf_bytes[kScratchSlots] = {};
+    int cu_count = 256;
+    uint32_t *xq = nullptr;   // kScratchSlots x 8 job-queue heads of the persistent regeneration launches (TRG_OPT_TILE_ORDER 64 + n), one set per stream
+    uint32_t bvh_depth4 = 0, bvh_nodes4 = 0;
+    SceneDesc sc{};
+    bool scene_loaded = false, have_uniforms = false, have_offsets = false;
+    trg_uniforms u{};
+    bool opt_strict = false, opt_counters = false, opt_force_global = false, opt_timing = true;
+    int opt_kernel = TRG_KERNEL_AUTO;
+    uint32_t last_kernel = TRG_KERNEL_DIRECT;
+    uint32_t last_tail_k = 0;
+    int opt_gpu_build = 0;   // TRG_OPT_GPU_BUILD: 0 host SAH, 1 device binned SAH, 2 device LBVH (Karras), 3 device PLOC
+    int opt_fsplit = 0;  // 0 = auto
+    int opt_tail = -1;   // TRG_OPT_TAIL_BOUNCE: -1 auto, 0 off, K
+    int opt_regen = -1;        // TRG_OPT_REGEN: 1 = path regeneration for HBM-resident scenes (direct kernel, frame-serial), -1 = from 32,768 triangles on, 0 = the lock-step kernel
+    uint32_t last_regen = 0;
+    int opt_tail_levels = 0;   // TRG_OPT_TAIL_LEVELS: 0 = re-compact every second bounce after K, 1 = once at K only
+    int opt_in_flight = 1;  // launches of this context the caller keeps in flight (TRG_OPT_LAUNCHES_IN_FLIGHT)
+    int opt_stack_levels = (int)TRG_STACK_LDS_LEVELS;   // TRG_OPT_STACK_LDS_LEVELS
+    int opt_tail_sort = 0;     // TRG_OPT_TAIL_SORT: 0 off, 1 direction octant, 2 / 3 octant + origin cell of a 2^3 / 4^3 grid
+    int opt_tail_refill = -1;  // TRG_OPT_TAIL_REFILL: 1 = the tail launches run ONE bounce each with in-wave refill (render_rtail_kernel); -1 = the library's choice
+    float scene_lo[3] = { 0.f, 0.f, 0.f }, scene_hi[3] = { 1.f, 1.f, 1.f };   // bounds of the loaded scene (tail sort: the origin grid)
+    int opt_tile_order = -1;   // TRG_OPT_TILE_ORDER: -1 auto, 0 image columns centre-out, 1 / 2 / 4 / 8 XCD regions with that many column strips
+    uint32_t last_xcd_cols = 0;
+    double last_build_ms = 0.0;
+    bool gpu_built = false;
+    uint32_t bvh_nodes = 0, bvh_depth = 0, bvh_leaves = 0, bvh_quads = 0, bvh_boxes = 0;
+    double last_ms = 0.0, total_ms = 0.0;
+    uint32_t renders = 0;
+    uint32_t last_fsplit = 1;
+    uint32_t launches = 0;   // trg_render launches since create (never reset: picks the scratch slot)
+    std::string err;
+};
+// END trg_ctx
+
+namespace {
+
+int fail(trg_ctx *c, int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    if (c) c->err = buf;
+    return code;
+}
+#define DN_HIPCHK(c, expr)                                                                                      \
+    do {                                                                                                        \
+        hipError_t e_ = (expr);                                                                                 \
+        if (e_ != hipSuccess) return fail((c), TRG_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// the copy of the struct above against what the library itself says about the context
+bool ctx_ok(trg_ctx *c) {
+    void *acc = nullptr;
+    return c && ctx_device(c) == c->device && ctx_current_stream(c) == (void *)c->stream && trg_accum_device_ptr(c, &acc) == TRG_OK && acc == (void *)c->accum &&
+           c->w != 0 && c->h != 0;
+}
+
+// ---- per-context state (grow-only device scratch); trg_ctx has no room for it, so it is kept beside the contexts ----
+struct DenoiseState {
+    int device = 0;
+    size_t pixels = 0;             // what rays / isect / ping / pong / guides are sized for
+    trg_ray *rays = nullptr;
+    trg_isect *isect = nullptr;
+    float4 *ping = nullptr, *pong = nullptr, *guides = nullptr;   // guides: the two planes trg_render_denoised fills
+    float4 *result = nullptr;      // trg_denoise_accum's output image (allocated on its first call)
+    float4 *fguide = nullptr;      // the filter's copy of G0: distance -1 where the first hit is an emitter (dn_exclude_emitters_kernel)
+    uint32_t *rec_of_prim = nullptr;   // original primitive index -> leaf record of the HBM part of the scene blob
+    size_t prims = 0;
+    int *overflow = nullptr;       // traversal-stack levels beyond those kept in LDS (scenes traversed from HBM)
+    size_t overflow_bytes = 0;
+};
+std::mutex g_mutex;
+std::unordered_map<trg_ctx *, DenoiseState> g_states;
+
+void free_state(DenoiseState &s) {
+    (void)hipFree(s.rays); (void)hipFree(s.isect); (void)hipFree(s.ping); (void)hipFree(s.pong); (void)hipFree(s.guides);
+    (void)hipFree(s.rec_of_prim); (void)hipFree(s.overflow); (void)hipFree(s.result); (void)hipFree(s.fguide);
+    s = DenoiseState{};
+}
+
+template <typename T>
+int grow(trg_ctx *c, T *&mem, size_t &have, size_t need, size_t elem, const char *what) {
+    if (need <= have && mem) return TRG_OK;
+    if (mem) { (void)hipDeviceSynchronize(); (void)hipFree(mem); mem = nullptr; have = 0; }
+    hipError_t e = hipMalloc((void **)&mem, need * elem);
+    if (e != hipSuccess) return fail(c, TRG_ERR_NOMEM, "denoise: %s hipMalloc(%zu) failed: %s", what, need * elem, hipGetErrorString(e));
+    have = need;
+    return TRG_OK;
+}
+
+// the state of a context, with the image-sized buffers allocated (a context is used by one host thread: trg.h)
+int state_of(trg_ctx *c, DenoiseState *&out) {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    DenoiseState &s = g_states[c];
+    const size_t n = (size_t)c->w * c->h;
+    if (s.device != c->device || s.pixels != n) {   // a new context at the address of one that was destroyed without a release
+        if (s.pixels) { (void)hipDeviceSynchronize(); free_state(s); }
+        s.device = c->device;
+        hipError_t e = hipMalloc((void **)&s.rays, n * sizeof(trg_ray));
+        if (e == hipSuccess) e = hipMalloc((void **)&s.isect, n * sizeof(trg_isect));
+        if (e == hipSuccess) e = hipMalloc((void **)&s.ping, n * sizeof(float4));
+        if (e == hipSuccess) e = hipMalloc((void **)&s.pong, n * sizeof(float4));
+        if (e == hipSuccess) e = hipMalloc((void **)&s.guides, 2 * n * sizeof(float4));
+        if (e == hipSuccess) e = hipMalloc((void **)&s.fguide, n * sizeof(float4));
+        if (e != hipSuccess) {
+            free_state(s);
+            g_states.erase(c);
+            return fail(c, TRG_ERR_NOMEM, "denoise: hipMalloc of the scratch images failed: %s", hipGetErrorString(e));
+        }
+        s.pixels = n;
+    }
+    out = &s;
+    return TRG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// Guides
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// Every scene has, in its blob, one 128-byte record per triangle in LEAF order (trg_kernels.h SceneDesc::off_fat: rows 0..2 = v0 | original
+// index, e1 | material id, e2 | -; floats 12..20 the nine normal floats, 21..29 the nine colour floats) -- the one place where a scene too
+// large for LDS keeps its attributes.  The tracer reports ORIGINAL indices, so: which record holds primitive k?
+__global__ void dn_record_map_kernel(const float4 *recs, uint32_t n_rec, uint32_t n_prims, uint32_t *rec_of_prim) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rec) return;
+    const uint32_t prim = (uint32_t)__float_as_int(recs[(size_t)r * 8u].w);
+    if (prim < n_prims) rec_of_prim[prim] = r;
+}
+
+__global__ void dn_gather_kernel(const trg_isect *isect, const uint32_t *rec_of_prim, const float4 *recs, uint32_t n_prims, const TexDesc tex,
+                                 float4 *g0, float4 *g1, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 is = reinterpret_cast<const float4 *>(isect)[i];   // distance, primitiveIndex, coordinates[2]
+    const int prim = __float_as_int(is.y);
+    if (!(is.x >= 0.0f) || prim < 0 || (uint32_t)prim >= n_prims) {
+        g0[i] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        g1[i] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+        return;
+    }
+    const float4 *rec = recs + (size_t)rec_of_prim[prim] * 8u;
+    const uint32_t mat = (uint32_t)__float_as_int(rec[1].w);
+    const float4 r3 = rec[3], r4 = rec[4], r5 = rec[5], r6 = rec[6], r7 = rec[7];
+    const float c0 = is.z, c1 = is.w, c2 = 1.0f - c0 - c1;
+    float4 n4, a4;
+    n4.x = c0 * r3.x + c1 * r3.w + c2 * r4.z;
+    n4.y = c0 * r3.y + c1 * r4.x + c2 * r4.w;
+    n4.z = c0 * r3.z + c1 * r4.y + c2 * r5.x;
+    n4.w = is.x;
+    a4.x = c0 * r5.y + c1 * r6.x + c2 * r6.w;
+    a4.y = c0 * r5.z + c1 * r6.y + c2 * r7.x;
+    a4.z = c0 * r5.w + c1 * r6.z + c2 * r7.y;
+    a4.w = __int_as_float(prim);
+    if (mat == TRG_MATERIAL_EMISSIVE) {
+        a4.x = 1.0f; a4.y = 1.0f; a4.z = 1.0f;
+    } else if (tex.uv) {
+        // trg_load_textures' lookup (trg.h): nearest texel, repeat
+        const uint32_t id = tex.ids[prim];
+        if (id != 0u) {
+            const float *p = tex.uv + (size_t)prim * 6u;
+            const float u = c0 * p[0] + c1 * p[2] + c2 * p[4], v = c0 * p[1] + c1 * p[3] + c2 * p[5];
+            const uint32_t *t = tex.table + (id - 1u) * 4u;
+            const uint32_t w = t[1], h = t[2];
+            const float fu = u - floorf(u), fv = v - floorf(v);
+            uint32_t x = (uint32_t)(fu * (float)w), y = (uint32_t)(fv * (float)h);
+            x = x < w ? x : w - 1u; y = y < h ? y : h - 1u;
+            const uint32_t texel = tex.texels[t[0] + y * w + x];
+            a4.x = a4.x * ((float)(texel & 255u) / 255.0f);
+            a4.y = a4.y * ((float)((texel >> 8) & 255u) / 255.0f);
+            a4.z = a4.z * ((float)((texel >> 16) & 255u) / 255.0f);
+        }
+    }
+    g0[i] = n4;
+    g1[i] = a4;
+}
+
+inline uint32_t align16(uint32_t v) { return (v + 15u) & ~15u; }
+
+// LDS layout of the stage-level tracer for this context's scene: what trg_trace plans (trg_capi.cpp plan_lds: the frame-serial plan)
+struct TracePlan { bool lds_scene; uint32_t stack_off, total, klds, overflow_levels; };
+bool plan_trace_as(const trg_ctx *c, TracePlan &p, bool lds_scene) {
+    p.lds_scene = lds_scene;
+    uint32_t levels;
+    if (lds_scene) {
+        levels = c->bvh_depth + 2;
+        p.klds = levels;
+    } else {
+        levels = TRG_WIDE8 ? 2 * c->bvh_depth4 + 4 : wide_stack_levels(c->bvh_depth4);
+        p.klds = levels < (uint32_t)c->opt_stack_levels ? levels : (uint32_t)c->opt_stack_levels;
+    }
+    p.overflow_levels = levels - p.klds;
+    p.stack_off = lds_scene ? align16(c->sc.lds_stage_bytes) : 0u;
+    const uint32_t red_off = p.stack_off + p.klds * (uint32_t)kBlock * 4u;
+    p.total = align16(red_off + 4u * 8u * 4u);
+    if (!lds_scene) p.total += (uint32_t)kBlock * 40u;
+    return p.total <= 64u * 1024u;
+}
+int plan_trace(trg_ctx *c, TracePlan &p) {
+    const bool want_lds = !c->opt_force_global && c->sc.lds_stage_bytes != 0 && c->sc.lds_stage_bytes <= kMaxLdsScene;
+    if (want_lds && plan_trace_as(c, p, true)) return TRG_OK;
+    if (plan_trace_as(c, p, false)) return TRG_OK;
+    return fail(c, TRG_ERR_RANGE, "denoise: BVH depth %u needs %u B of LDS per workgroup", c->bvh_depth, p.total);
+}
+
+// enqueues the map original primitive index -> leaf record of the loaded scene.  Rebuilt per call (one 4-byte read per record): a scene may
+// have been reloaded into the same allocation since
+int record_map(trg_ctx *c, DenoiseState &s) {
+    const SceneDesc &sc = c->sc;
+    if (int rc = grow(c, s.rec_of_prim, s.prims, (size_t)sc.n_tris, sizeof(uint32_t), "record map")) return rc;
+    DN_HIPCHK(c, hipMemsetAsync(s.rec_of_prim, 0, (size_t)sc.n_tris * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(dn_record_map_kernel, dim3((sc.n_fat + 255u) / 256u), dim3(256), 0, c->stream, reinterpret_cast<const float4 *>(c->blob + sc.off_fat),
+                       sc.n_fat, sc.n_tris, s.rec_of_prim);
+    DN_HIPCHK(c, hipGetLastError());
+    return TRG_OK;
+}
+
+int guides_render(trg_ctx *c, DenoiseState &s, uint32_t frameIndex, float4 *guides) {
+    if (!c->scene_loaded) return fail(c, TRG_ERR_INVALID, "trg_guides_render: no scene loaded");
+    if (!c->have_uniforms || !c->have_offsets) return fail(c, TRG_ERR_INVALID, "trg_guides_render: uniforms / pixel offsets not set");
+    const size_t n = (size_t)c->w * c->h;
+    if (n > 0x7FFFFFFFull) return fail(c, TRG_ERR_RANGE, "trg_guides_render: image too large");
+    const SceneDesc &sc = c->sc;
+    if (sc.n_tris == 0 || sc.n_fat == 0) return fail(c, TRG_ERR_INVALID, "trg_guides_render: empty scene");
+    TracePlan plan;
+    if (int rc = plan_trace(c, plan)) return rc;
+    TraceParams tp{};
+    tp.sc = sc; tp.rays = s.rays; tp.out = s.isect; tp.n = (uint32_t)n; tp.stack_off = plan.stack_off;
+    tp.stack.klds = plan.klds; tp.stack.overflow = nullptr;
+    if (plan.overflow_levels) {
+        const size_t grid_threads = ((n + kBlock - 1) / kBlock) * kBlock;
+        if (int rc = grow(c, s.overflow, s.overflow_bytes, (size_t)plan.overflow_levels * grid_threads * sizeof(int), 1, "stack scratch")) return rc;
+        tp.stack.overflow = s.overflow;
+    }
+    hipStream_t st = c->stream;
+    trg_uniforms u = c->u;
+    u.frameIndex = frameIndex;
+    hipError_t e = c->opt_strict ? launch_raygen_strict(u, c->offsets, s.rays, st) : launch_raygen_fast(u, c->offsets, s.rays, st);
+    if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_guides_render: raygen launch failed: %s", hipGetErrorString(e));
+    e = c->opt_strict ? launch_trace_strict(tp, plan.lds_scene, false, plan.total, st) : launch_trace_fast(tp, plan.lds_scene, false, plan.total, st);
+    if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_guides_render: trace launch failed: %s", hipGetErrorString(e));
+    const float4 *recs = reinterpret_cast<const float4 *>(c->blob + sc.off_fat);
+    if (int rc = record_map(c, s)) return rc;
+    hipLaunchKernelGGL(dn_gather_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, s.isect, s.rec_of_prim, recs, sc.n_tris, c->tex, guides,
+                       guides + n, (uint32_t)n);
+    DN_HIPCHK(c, hipGetLastError());
+    return TRG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The filter (trg_denoise.h has the definition)
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The filter's own copy of G0: a pixel whose first hit is an EMITTER of the loaded scene (G1.w names a primitive of material
+// TRG_MATERIAL_EMISSIVE) gets distance -1, i.e. the filter treats it exactly like a miss -- it copies its input and is nobody's tap.
+// n_prims == 0 (no scene): a plain copy.
+__global__ void dn_exclude_emitters_kernel(const float4 *g0, const float4 *g1, const uint32_t *rec_of_prim, const float4 *recs, uint32_t n_prims,
+                                           float4 *fguide, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float4 g = g0[i];
+    const int prim = __float_as_int(g1[i].w);
+    if (g.w >= 0.0f && prim >= 0 && (uint32_t)prim < n_prims &&
+        (uint32_t)__float_as_int(recs[(size_t)rec_of_prim[prim] * 8u + 1u].w) == TRG_MATERIAL_EMISSIVE)
+        g.w = -1.0f;
+    fguide[i] = g;
+}
+
+struct AtrousParams {
+    const float4 *in, *g0, *g1;
+    float4 *out;
+    int w, h, spacing;
+    int demod_in, remod_out;   // first / last launch of a demodulated run
+    float sigma_color, sigma_normal, sigma_depth;
+};
+constexpr int kDnTile = 16;                      // = trg::kTileW x kTileH of the render kernels at 256 threads
+constexpr int kDnLdsMaxSpacing = 2;              // spacings 1, 2: tile + halo of 2 * spacing pixels in LDS
+constexpr int kDnLdsSide = kDnTile + 4 * kDnLdsMaxSpacing;   // 24
+static_assert(kTileW == kDnTile && kTileH == kDnTile && kBlock == 256, "the filter's tiles are the render kernels' 16 x 16 tiles");
+
+template <bool STRICT> __device__ __forceinline__ float dn_exp(float x) { return STRICT ? expf(x) : __expf(x); }
+template <bool STRICT> __device__ __forceinline__ float dn_pow(float x, float y) { return STRICT ? powf(x, y) : __powf(x, y); }
+__device__ __forceinline__ float dn_lum(const float4 c) { return 0.2126f * c.x + 0.7152f * c.y + 0.0722f * c.z; }
+
+// LDS = true: colour (already demodulated) and G0 of the tile + halo sit in LDS as [row][x] float4 -- a wavefront's four rows of 16 lanes read
+// 16 consecutive float4 each; false: every tap is a global_load_dwordx4 per plane (neighbouring lanes' taps fall on the same 128-byte lines).
+template <bool STRICT, bool LDS>
+__global__ __launch_bounds__(256) void dn_atrous_kernel(const AtrousParams p) {
+    __shared__ float4 s_col[LDS ? kDnLdsSide * kDnLdsSide : 1];
+    __shared__ float4 s_g0[LDS ? kDnLdsSide * kDnLdsSide : 1];
+    const int s = p.spacing, halo = 2 * s, side = kDnTile + 2 * halo;   // side <= kDnLdsSide when LDS
+    const int x0 = (int)blockIdx.x * kDnTile, y0 = (int)blockIdx.y * kDnTile;
+    if (LDS) {
+        for (int k = (int)threadIdx.x; k < side * side; k += 256) {
+            const int ly = k / side, lx = k - ly * side;
+            const int gx = x0 - halo + lx, gy = y0 - halo + ly;
+            float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+            if (gx >= 0 && gx < p.w && gy >= 0 && gy < p.h) {
+                const size_t q = (size_t)gy * (size_t)p.w + (size_t)gx;
+                c = p.in[q];
+                g = p.g0[q];
+                if (p.demod_in && g.w >= 0.0f) {
+                    const float4 a = p.g1[q];
+                    c.x = c.x / fmaxf(a.x, 1e-3f); c.y = c.y / fmaxf(a.y, 1e-3f); c.z = c.z / fmaxf(a.z, 1e-3f);
+                }
+            }
+            s_col[k] = c;
+            s_g0[k] = g;
+        }
+        __syncthreads();
+    }
+    const int x = x0 + ((int)threadIdx.x & 15), y = y0 + ((int)threadIdx.x >> 4);
+    if (x >= p.w || y >= p.h) return;
+    // (callers pass coordinates inside the image only)
+    auto colour = [&](int qx, int qy) -> float4 { return LDS ? s_col[(qy - y0 + halo) * side + (qx - x0 + halo)] : p.in[(size_t)qy * (size_t)p.w + (size_t)qx]; };
+    auto guide = [&](int qx, int qy) -> float4 { return LDS ? s_g0[(qy - y0 + halo) * side + (qx - x0 + halo)] : p.g0[(size_t)qy * (size_t)p.w + (size_t)qx]; };
+    const size_t pix = (size_t)y * (size_t)p.w + (size_t)x;
+    const float4 cp = colour(x, y), gp = guide(x, y);
+    if (gp.w < 0.0f) {   // a miss copies its input
+        p.out[pix] = cp;
+        return;
+    }
+    // variance of luminance over the 3 x 3 window (two passes: mean, then squared deviations)
+    float lum[9];
+    int m = 0;
+    float mean = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int qx = x + k % 3 - 1, qy = y + k / 3 - 1;
+        const bool in = qx >= 0 && qx < p.w && qy >= 0 && qy < p.h;
+        lum[k] = in ? dn_lum(colour(qx, qy)) : 0.0f;
+        mean += lum[k];
+        m += in ? 1 : 0;
+    }
+    mean = mean / (float)m;
+    float var = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int qx = x + k % 3 - 1, qy = y + k / 3 - 1;
+        const bool in = qx >= 0 && qx < p.w && qy >= 0 && qy < p.h;
+        const float d = lum[k] - mean;
+        var += in ? d * d : 0.0f;
+    }
+    var = var / (float)m;
+    // depth gradient: forward differences, backward where the forward neighbour is outside the image or a miss
+    float gx = 0.0f, gy = 0.0f;
+    {
+        float z1 = -1.0f;
+        if (x + 1 < p.w) z1 = guide(x + 1, y).w;
+        if (z1 >= 0.0f) gx = z1 - gp.w;
+        else if (x >= 1) { z1 = guide(x - 1, y).w; if (z1 >= 0.0f) gx = gp.w - z1; }
+        z1 = -1.0f;
+        if (y + 1 < p.h) z1 = guide(x, y + 1).w;
+        if (z1 >= 0.0f) gy = z1 - gp.w;
+        else if (y >= 1) { z1 = guide(x, y - 1).w; if (z1 >= 0.0f) gy = gp.w - z1; }
+    }
+    const float grad = sqrtf(gx * gx + gy * gy);
+    const float cden = p.sigma_color * p.sigma_color * (var + 1e-4f);
+    const float hk[5] = { 1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f };
+    float ar = 0.0f, ag = 0.0f, ab = 0.0f, wsum = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = x + dx * s, qy = y + dy * s;
+            if (qx < 0 || qx >= p.w || qy < 0 || qy >= p.h) continue;
+            const float4 gq = guide(qx, qy);
+            if (gq.w < 0.0f) continue;
+            const float dn = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
+            if (!(dn > 0.0f)) continue;
+            const float4 cq = colour(qx, qy);
+            const float wn = dn_pow<STRICT>(dn, p.sigma_normal);
+            const float dist = sqrtf((float)(dx * dx + dy * dy));
+            const float wz = dn_exp<STRICT>(-(fabsf(gp.w - gq.w) / (p.sigma_depth * (grad * (float)s * dist + 1e-6f))));
+            const float dr = cp.x - cq.x, dg = cp.y - cq.y, db = cp.z - cq.z;
+            const float wc = dn_exp<STRICT>(-((dr * dr + dg * dg + db * db) / cden));
+            const float wgt = hk[dx + 2] * hk[dy + 2] * wn * wz * wc;
+            ar += wgt * cq.x; ag += wgt * cq.y; ab += wgt * cq.z;
+            wsum += wgt;
+        }
+    }
+    float4 o = cp;
+    if (wsum > 0.0f) { o.x = ar / wsum; o.y = ag / wsum; o.z = ab / wsum; }
+    if (p.remod_out) {
+        const float4 a = p.g1[pix];
+        o.x = o.x * fmaxf(a.x, 1e-3f); o.y = o.y * fmaxf(a.y, 1e-3f); o.z = o.z * fmaxf(a.z, 1e-3f);
+    }
+    p.out[pix] = o;
+}
+
+template <bool STRICT>
+hipError_t launch_atrous(const AtrousParams &p, hipStream_t st) {
+    const dim3 grid((uint32_t)(p.w + kDnTile - 1) / kDnTile, (uint32_t)(p.h + kDnTile - 1) / kDnTile);
+    if (p.spacing <= kDnLdsMaxSpacing) hipLaunchKernelGGL((dn_atrous_kernel<STRICT, true>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((dn_atrous_kernel<STRICT, false>), grid, dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+bool valid_params(const trg_denoise_params &q) {
+    return q.iterations >= 0 && q.iterations <= TRG_DENOISE_MAX_ITERATIONS && q.sigma_color > 0.0f && q.sigma_normal >= 0.0f && q.sigma_depth > 0.0f;
+}
+
+int denoise(trg_ctx *c, DenoiseState &s, const float4 *in, const float4 *guides, float4 *out, const trg_denoise_params *pp) {
+    trg_denoise_params q;
+    trg_denoise_default_params(&q);
+    if (pp) q = *pp;
+    if (!valid_params(q)) return fail(c, TRG_ERR_INVALID, "trg_denoise: iterations must be 0..%d and the sigmas positive", TRG_DENOISE_MAX_ITERATIONS);
+    const size_t n = (size_t)c->w * c->h, bytes = n * sizeof(float4);
+    if ((const char *)in < (const char *)out + bytes && (const char *)out < (const char *)in + bytes)
+        return fail(c, TRG_ERR_INVALID, "trg_denoise: out_device overlaps color_in_device");
+    hipStream_t st = c->stream;
+    if (q.iterations == 0) {
+        DN_HIPCHK(c, hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, st));
+        return TRG_OK;
+    }
+    {
+        const bool scene = c->scene_loaded && c->sc.n_tris != 0 && c->sc.n_fat != 0;
+        if (scene)
+            if (int rc = record_map(c, s)) return rc;
+        hipLaunchKernelGGL(dn_exclude_emitters_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, guides, guides + n, s.rec_of_prim,
+                           scene ? reinterpret_cast<const float4 *>(c->blob + c->sc.off_fat) : nullptr, scene ? c->sc.n_tris : 0u, s.fguide, (uint32_t)n);
+        DN_HIPCHK(c, hipGetLastError());
+    }
+    AtrousParams p{};
+    p.g0 = s.fguide; p.g1 = guides + n;
+    p.w = (int)c->w; p.h = (int)c->h;
+    p.sigma_color = q.sigma_color; p.sigma_normal = q.sigma_normal; p.sigma_depth = q.sigma_depth;
+    const float4 *src = in;
+    for (int i = 0; i < q.iterations; ++i) {
+        const bool last = i + 1 == q.iterations;
+        p.in = src;
+        p.out = last ? out : ((i & 1) ? s.pong : s.ping);
+        p.spacing = 1 << i;
+        p.demod_in = (q.demodulate && i == 0) ? 1 : 0;
+        p.remod_out = (q.demodulate && last) ? 1 : 0;
+        const hipError_t e = c->opt_strict ? launch_atrous<true>(p, st) : launch_atrous<false>(p, st);
+        if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_denoise: launch failed: %s", hipGetErrorString(e));
+        src = p.out;
+    }
+    return TRG_OK;
+}
+
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
+};
+
+int enter(trg_ctx *c, DenoiseState *&s, const char *who) {
+    if (!c) return TRG_ERR_INVALID;
+    if (!ctx_ok(c)) return fail(c, TRG_ERR_INVALID, "%s: the denoiser's view of the context does not match the library's", who);
+    DN_HIPCHK(c, hipSetDevice(c->device));
+    return state_of(c, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+void trg_denoise_default_params(trg_denoise_params *p) {
+    if (!p) return;
+    p->iterations = 5; p->sigma_color = 4.0f; p->sigma_normal = 128.0f; p->sigma_depth = 1.0f; p->demodulate = 1;
+}
+
+int trg_guides_render(trg_ctx *c, uint32_t frameIndex, void *guides_device) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_guides_render")) return rc;
+    if (!guides_device) return fail(c, TRG_ERR_INVALID, "trg_guides_render: guides_device is NULL");
+    return guides_render(c, *s, frameIndex, static_cast<float4 *>(guides_device));
+}
+
+int trg_denoise(trg_ctx *c, const void *color_in_device, const void *guides_device, void *out_device, const trg_denoise_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_denoise")) return rc;
+    if (!color_in_device || !guides_device || !out_device) return fail(c, TRG_ERR_INVALID, "trg_denoise: NULL buffer");
+    return denoise(c, *s, static_cast<const float4 *>(color_in_device), static_cast<const float4 *>(guides_device), static_cast<float4 *>(out_device), p);
+}
+
+int trg_render_denoised(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, void *out_device, const trg_denoise_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_render_denoised")) return rc;
+    if (!out_device) return fail(c, TRG_ERR_INVALID, "trg_render_denoised: out_device is NULL");
+    if (p && !valid_params(*p)) return fail(c, TRG_ERR_INVALID, "trg_render_denoised: bad parameters");
+    if (int rc = trg_render(c, frameIndexBegin, spp, bounces, 0, c->h)) return rc;
+    if (int rc = guides_render(c, *s, frameIndexBegin, s->guides)) return rc;
+    return denoise(c, *s, reinterpret_cast<const float4 *>(c->accum), s->guides, static_cast<float4 *>(out_device), p);
+}
+
+int trg_denoise_accum(trg_ctx *c, uint32_t frameIndex, const trg_denoise_params *p, void **out_device) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_denoise_accum")) return rc;
+    if (!out_device) return fail(c, TRG_ERR_INVALID, "trg_denoise_accum: out_device is NULL");
+    if (!s->result) {
+        const hipError_t e = hipMalloc((void **)&s->result, s->pixels * sizeof(float4));
+        if (e != hipSuccess) return fail(c, TRG_ERR_NOMEM, "trg_denoise_accum: hipMalloc failed: %s", hipGetErrorString(e));
+    }
+    if (c->accum == reinterpret_cast<float *>(s->result)) return fail(c, TRG_ERR_INVALID, "trg_denoise_accum: the state's image is bound as the accumulation buffer");
+    if (int rc = guides_render(c, *s, frameIndex, s->guides)) return rc;
+    if (int rc = denoise(c, *s, reinterpret_cast<const float4 *>(c->accum), s->guides, s->result, p)) return rc;
+    *out_device = s->result;
+    return TRG_OK;
+}
+
+int trg_denoise_release(trg_ctx *c) {
+    if (!c) return TRG_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(g_mutex);
+    auto it = g_states.find(c);
+    if (it == g_states.end()) return TRG_OK;
+    (void)hipSetDevice(it->second.device);
+    (void)hipDeviceSynchronize();
+    free_state(it->second);
+    g_states.erase(it);
+    return TRG_OK;
+}
+
+int trg_guides_read(trg_ctx *c, uint32_t frameIndex, float *guides_host) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_guides_read")) return rc;
+    if (!guides_host) return fail(c, TRG_ERR_INVALID, "trg_guides_read: guides_host is NULL");
+    const size_t bytes = 2 * (size_t)c->w * c->h * sizeof(float4);
+    DevBuf g;
+    DN_HIPCHK(c, g.alloc(bytes));
+    if (int rc = guides_render(c, *s, frameIndex, static_cast<float4 *>(g.p))) return rc;
+    DN_HIPCHK(c, hipMemcpyAsync(guides_host, g.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    DN_HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TRG_OK;
+}
+
+int trg_denoise_host(trg_ctx *c, const float *color_in_host, const float *guides_host, float *out_host, const trg_denoise_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_denoise_host")) return rc;
+    if (!color_in_host || !guides_host || !out_host) return fail(c, TRG_ERR_INVALID, "trg_denoise_host: NULL buffer");
+    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
+    DevBuf in, g, out;
+    DN_HIPCHK(c, in.alloc(bytes)); DN_HIPCHK(c, g.alloc(2 * bytes)); DN_HIPCHK(c, out.alloc(bytes));
+    DN_HIPCHK(c, hipMemcpyAsync(in.p, color_in_host, bytes, hipMemcpyHostToDevice, c->stream));
+    DN_HIPCHK(c, hipMemcpyAsync(g.p, guides_host, 2 * bytes, hipMemcpyHostToDevice, c->stream));
+    int rc = denoise(c, *s, static_cast<const float4 *>(in.p), static_cast<const float4 *>(g.p), static_cast<float4 *>(out.p), p);
+    if (rc == TRG_OK) {
+        hipError_t e = hipMemcpyAsync(out_host, out.p, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_denoise_host: copy failed: %s", hipGetErrorString(e));
+    }
+    const hipError_t e = hipStreamSynchronize(c->stream);   // also on an error: the temporaries are freed on return
+    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_denoise_host: %s", hipGetErrorString(e));
+    return rc;
+}
+
+int trg_render_denoised_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_denoise_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_render_denoised_read")) return rc;
+    if (!out_host) return fail(c, TRG_ERR_INVALID, "trg_render_denoised_read: out_host is NULL");
+    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
+    DevBuf out;
+    DN_HIPCHK(c, out.alloc(bytes));
+    int rc = trg_render_denoised(c, frameIndexBegin, spp, bounces, out.p, p);
+    if (rc == TRG_OK) {
+        hipError_t e = hipMemcpyAsync(out_host, out.p, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_denoised_read: copy failed: %s", hipGetErrorString(e));
+    }
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_denoised_read: %s", hipGetErrorString(e));
+    return rc;
+}
+
+}  // extern "C"

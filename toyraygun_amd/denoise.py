@@ -1,0 +1,263 @@
+"""First-hit guide buffers and the edge-avoiding a-trous denoiser of include/trg_denoise.h.
+
+    g = guides(ctx, frame_index)                 # [2, h, w, 4]: G0 = normal xyz | hit distance, G1 = albedo rgb | primitive index bits
+    out = denoise(ctx, color, g, iterations=5)   # [h, w, 4]
+    out = render_denoised(ctx, 0, 4, 3)          # trg_render + guides + filter on one stream; the accumulation buffer is only read
+
+numpy arrays go through temporary device copies and the call waits for the result; torch ROCm tensors (float32, contiguous) are used in place
+through data_ptr() -- like trg_bind_accum -- and the call only enqueues on the context's current stream.  `reference_denoise` is the float64
+numpy evaluation of the definition in the header: what the GPU tests compare the kernels with.
+
+The context's denoise scratch lives until release(ctx); call it before ctx.close() (trg_destroy does not know about it).
+"""
+import ctypes as C
+import re
+
+import numpy as np
+
+from . import capi
+
+MAX_ITERATIONS = 6
+LUMA = (0.2126, 0.7152, 0.0722)
+B3 = (1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0)
+
+
+class Params(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("demodulate", C.c_int32)]
+
+
+_P = C.c_void_p
+_PP = C.POINTER(Params)
+_SYMBOLS = [
+    ("trg_denoise_default_params", None, [_PP]),
+    ("trg_guides_render", C.c_int, [_P, C.c_uint32, _P]),
+    ("trg_denoise", C.c_int, [_P, _P, _P, _P, _PP]),
+    ("trg_render_denoised", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _PP]),
+    ("trg_denoise_accum", C.c_int, [_P, C.c_uint32, _PP, C.POINTER(_P)]),
+    ("trg_denoise_release", C.c_int, [_P]),
+    ("trg_guides_read", C.c_int, [_P, C.c_uint32, _P]),
+    ("trg_denoise_host", C.c_int, [_P, _P, _P, _P, _PP]),
+    ("trg_render_denoised_read", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _PP]),
+]
+SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
+
+_bound = None
+
+
+def load():
+    """The library handle of capi.load() with the symbols of include/trg_denoise.h bound.  No fallback: a library without them is an error."""
+    global _bound
+    L = capi.load()
+    if _bound is not L:
+        for name, res, args in _SYMBOLS:
+            fn = getattr(L, name)   # AttributeError if the .so lacks a declared symbol
+            fn.restype = res
+            fn.argtypes = args
+        _bound = L
+    return L
+
+
+def header_symbols(path):
+    """The trg_* functions a C header declares with TRG_API."""
+    with open(path) as f:
+        return re.findall(r"TRG_API\s+[\w\s\*]*?\b(trg_\w+)\s*\(", f.read())
+
+
+def default_params():
+    p = Params()
+    load().trg_denoise_default_params(C.byref(p))
+    return p
+
+
+def make_params(params=None, **kw):
+    """Params from the library's defaults, a Params / dict, and keyword overrides (iterations, sigma_color, sigma_normal, sigma_depth, demodulate)."""
+    p = default_params()
+    src = {}
+    if isinstance(params, Params):
+        src = {f: getattr(params, f) for f, _ in Params._fields_}
+    elif params:
+        src = dict(params)
+    src.update(kw)
+    for k, v in src.items():
+        if k not in dict(Params._fields_):
+            raise TypeError("unknown denoise parameter %r" % k)
+        setattr(p, k, int(v) if k in ("iterations", "demodulate") else float(v))
+    return p
+
+
+def _is_tensor(a):
+    return hasattr(a, "data_ptr")
+
+
+def _tensor_ptr(t, shape, what):
+    import torch
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda" or tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must be a contiguous float32 ROCm tensor of shape %s" % (what, (tuple(shape),)))
+    return C.c_void_p(t.data_ptr())
+
+
+def _chk(ctx, rc):
+    if rc != capi.OK:
+        raise capi.TrgError(rc, (ctx.L.trg_last_error(ctx.h_ctx) or b"").decode())
+
+
+def guides(ctx, frame_index, out=None):
+    """trg_guides_render.  out = a [2, h, w, 4] float32 ROCm tensor: filled in place on the context's stream (and returned); None: a numpy array."""
+    L = load()
+    shape = (2, ctx.h, ctx.w, 4)
+    if out is not None and _is_tensor(out):
+        _chk(ctx, L.trg_guides_render(ctx.h_ctx, frame_index, _tensor_ptr(out, shape, "guides")))
+        return out
+    g = np.empty(shape, np.float32)
+    _chk(ctx, L.trg_guides_read(ctx.h_ctx, frame_index, g.ctypes.data))
+    return g
+
+
+def denoise(ctx, color, guides, out=None, params=None, **kw):
+    """trg_denoise.  All tensors (then `out` is a tensor too, or is allocated like `color`; enqueued only) or all numpy (waits)."""
+    L = load()
+    p = make_params(params, **kw)
+    cs, gs = (ctx.h, ctx.w, 4), (2, ctx.h, ctx.w, 4)
+    if _is_tensor(color):
+        import torch
+        if out is None:
+            out = torch.empty_like(color)
+        _chk(ctx, L.trg_denoise(ctx.h_ctx, _tensor_ptr(color, cs, "color"), _tensor_ptr(guides, gs, "guides"), _tensor_ptr(out, cs, "out"), C.byref(p)))
+        return out
+    c = np.ascontiguousarray(color, np.float32)
+    g = np.ascontiguousarray(guides, np.float32)
+    if c.shape != cs or g.shape != gs:
+        raise ValueError("color must be %s and guides %s" % (cs, gs))
+    o = np.empty(cs, np.float32)
+    _chk(ctx, L.trg_denoise_host(ctx.h_ctx, c.ctypes.data, g.ctypes.data, o.ctypes.data, C.byref(p)))
+    return o
+
+
+def render_denoised(ctx, frame_begin, spp, bounces, out=None, params=None, **kw):
+    """trg_render_denoised: frames [frame_begin, frame_begin + spp) into the context's accumulation buffer, guides of frame_begin, the filter."""
+    L = load()
+    p = make_params(params, **kw)
+    if out is not None and _is_tensor(out):
+        _chk(ctx, L.trg_render_denoised(ctx.h_ctx, frame_begin, spp, bounces, _tensor_ptr(out, (ctx.h, ctx.w, 4), "out"), C.byref(p)))
+        return out
+    o = np.empty((ctx.h, ctx.w, 4), np.float32)
+    _chk(ctx, L.trg_render_denoised_read(ctx.h_ctx, frame_begin, spp, bounces, o.ctypes.data, C.byref(p)))
+    return o
+
+
+def release(ctx):
+    if getattr(ctx, "h_ctx", None):
+        _chk(ctx, load().trg_denoise_release(ctx.h_ctx))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# float64 reference, written from the definition in include/trg_denoise.h
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+def _shift(a, dx, dy, fill=0.0):
+    """b[y, x] = a[y + dy, x + dx] where that lies inside, else fill; and the inside mask."""
+    h, w = a.shape[:2]
+    b = np.full_like(a, fill)
+    inside = np.zeros((h, w), bool)
+    ys, ye = max(0, -dy), min(h, h - dy)
+    xs, xe = max(0, -dx), min(w, w - dx)
+    if ys < ye and xs < xe:
+        b[ys:ye, xs:xe] = a[ys + dy:ye + dy, xs + dx:xe + dx]
+        inside[ys:ye, xs:xe] = True
+    return b, inside
+
+
+def _depth_gradient(z):
+    def along(dx, dy):
+        fwd, fin = _shift(z, dx, dy, -1.0)
+        bwd, bin_ = _shift(z, -dx, -dy, -1.0)
+        f_ok, b_ok = fin & (fwd >= 0), bin_ & (bwd >= 0)
+        return np.where(f_ok, fwd - z, np.where(b_ok, z - bwd, 0.0))
+    return np.sqrt(along(1, 0) ** 2 + along(0, 1) ** 2)
+
+
+def atrous_weights(I, g0, spacing, sigma_color, sigma_normal, sigma_depth):
+    """w[dy + 2, dx + 2, y, x] of one iteration on input I [h, w, 3] (float64); zero for skipped taps; rows of miss pixels are meaningless."""
+    h, w = I.shape[:2]
+    n, z = g0[..., :3], g0[..., 3]
+    lum = I @ np.array(LUMA)
+    cnt = np.zeros((h, w))
+    s1 = np.zeros((h, w))
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            l, ins = _shift(lum, dx, dy)
+            s1 += np.where(ins, l, 0.0); cnt += ins
+    mean = s1 / cnt
+    s2 = np.zeros((h, w))
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            l, ins = _shift(lum, dx, dy)
+            s2 += np.where(ins, (l - mean) ** 2, 0.0)
+    var = s2 / cnt
+    grad = _depth_gradient(z)
+    W = np.zeros((5, 5, h, w))
+    for dy in range(-2, 3):
+        for dx in range(-2, 3):
+            Iq, ins = _shift(I, dx * spacing, dy * spacing)
+            gq, _ = _shift(g0, dx * spacing, dy * spacing, -1.0)
+            nq, zq = gq[..., :3], gq[..., 3]
+            dn = (n * nq).sum(-1)
+            ok = ins & (zq >= 0) & (dn > 0)
+            with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+                wn = np.where(dn > 0, np.abs(dn), 1.0) ** sigma_normal
+                wz = np.exp(-np.abs(z - zq) / (sigma_depth * (grad * spacing * np.sqrt(dx * dx + dy * dy) + 1e-6)))
+                wc = np.exp(-((I - Iq) ** 2).sum(-1) / (sigma_color ** 2 * (var + 1e-4)))
+            W[dy + 2, dx + 2] = np.where(ok, B3[dx + 2] * B3[dy + 2] * wn * wz * wc, 0.0)
+    return W
+
+
+def emitter_mask(g1, material_ids):
+    """[h, w] bool: pixels whose first hit (G1.w, int32 bits) is a primitive of material 2 (TRG_MATERIAL_EMISSIVE) of a scene with these ids."""
+    prim = np.ascontiguousarray(np.asarray(g1, np.float32)[..., 3]).view(np.int32)
+    mats = np.asarray(material_ids).reshape(-1)
+    inside = (prim >= 0) & (prim < mats.shape[0])
+    return inside & (mats[np.where(inside, prim, 0)] == 2)
+
+
+def reference_denoise(color, g0, g1, params=None, material_ids=None, **kw):
+    """float64 evaluation of trg_denoise's definition.  color [h, w, 4], g0 / g1 [h, w, 4] (float32 as the device sees them); params: a Params,
+    a dict or keywords; the defaults are the header's (no library needed); material_ids: those of the context's scene (None: no scene, no
+    emitters).  Returns [h, w, 4] float64."""
+    q = dict(iterations=5, sigma_color=4.0, sigma_normal=128.0, sigma_depth=1.0, demodulate=1)
+    if isinstance(params, Params):
+        params = {f: getattr(params, f) for f, _ in Params._fields_}
+    q.update(params or {}); q.update(kw)
+    it = int(q["iterations"])
+    if not 0 <= it <= MAX_ITERATIONS:
+        raise ValueError("iterations must be 0..%d" % MAX_ITERATIONS)
+    color = np.asarray(color)
+    out = color.astype(np.float64)
+    if it == 0:
+        return out
+    # the parameters as the device holds them: fp32
+    sc, sn, sd = (float(np.float32(q[k])) for k in ("sigma_color", "sigma_normal", "sigma_depth"))
+    g0 = np.asarray(g0, np.float32).astype(np.float64)
+    if material_ids is not None:                       # a directly seen emitter is kept out of the filter like a miss
+        g0[emitter_mask(g1, material_ids), 3] = -1.0
+    alb = np.maximum(np.asarray(g1, np.float32)[..., :3].astype(np.float64), float(np.float32(1e-3)))
+    miss = g0[..., 3] < 0
+    I = out[..., :3].copy()
+    demod = bool(q["demodulate"])
+    if demod:
+        I = np.where(miss[..., None], I, I / alb)
+    for i in range(it):
+        s = 1 << i
+        W = atrous_weights(I, g0, s, sc, sn, sd)
+        acc = np.zeros_like(I)
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                Iq, _ = _shift(I, dx * s, dy * s)
+                acc += W[dy + 2, dx + 2][..., None] * Iq
+        wsum = W.sum((0, 1))
+        keep = miss | ~(wsum > 0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            I = np.where(keep[..., None], I, acc / wsum[..., None])
+    if demod:
+        I = np.where(miss[..., None], I, I * alb)
+    out[..., :3] = I
+    return out
