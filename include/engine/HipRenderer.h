@@ -55,8 +55,12 @@ public:
     // ---- denoising (include/trg_denoise.h).  0 (default): off, nothing changes.  1..6: the image handed to post-processing (savePNG) is an
     //      edge-avoiding a-trous filtered COPY of the accumulation buffer, guided by the first hits of frame 0 under the current camera; the
     //      accumulation itself goes on undisturbed.  One device only: a device group ignores it.
-    bool setDenoise(int iterations);
+    //      varianceGuided: savePNG instead renders the frames so far AGAIN as two independent halves (trg_render_denoised_variance; one more
+    //      frame when their number is odd, and it says so) and filters their mean, guided by the halves' difference; the accumulation buffer is
+    //      not touched, the ray count includes the second rendering.
+    bool setDenoise(int iterations, bool varianceGuided = false);
     int getDenoise() const { return m_denoise; }
+    bool getDenoiseVarianceGuided() const { return m_denoiseVar; }
     int getFrameIndex() const { return m_frameIndex; }
     double getLastRenderMs() const;
     uint64_t getRayCount() const;                       // primary + bounce + shadow rays traced so far
@@ -79,6 +83,7 @@ protected:
     Uniforms m_pendingUniforms;  // their uniforms (frameIndex zeroed)
     unsigned int m_launches;
     int m_denoise;               // a-trous iterations of the image handed to post-processing; 0 = off
+    bool m_denoiseVar;           // ... by the variance-guided filter from two half-sample buffers
 };
 
 }  // namespace toyraygun

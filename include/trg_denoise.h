@@ -6,8 +6,8 @@
  * accumulation buffer.  `*_device` pointers are device memory of the context's device; everything is enqueued on the context's CURRENT
  * stream (trg_set_stream) and nothing waits for the device, unless a function says so.
  *
- * STATE.  The first call allocates per-context scratch (primary rays and hit records of the guide pass, two ping-pong images of the filter);
- * it is grow-only and lives until trg_denoise_release(ctx).  trg_destroy does NOT know about it: call trg_denoise_release BEFORE trg_destroy.
+ * STATE.  The first call allocates per-context scratch (primary rays and hit records of the guide pass, two ping-pong images of the filter;
+ * the half-sample images of the variance-guided path on its first use); it is grow-only and lives until trg_denoise_release(ctx).  trg_destroy does NOT know about it: call trg_denoise_release BEFORE trg_destroy.
  */
 #ifndef TRG_DENOISE_H
 #define TRG_DENOISE_H
@@ -92,6 +92,78 @@ TRG_API int trg_denoise_release(trg_ctx *ctx);
 TRG_API int trg_guides_read(trg_ctx *ctx, uint32_t frameIndex, float *guides_host);
 TRG_API int trg_denoise_host(trg_ctx *ctx, const float *color_in_host, const float *guides_host, float *out_host, const trg_denoise_params *p);
 TRG_API int trg_render_denoised_read(trg_ctx *ctx, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_denoise_params *p);
+
+/* =============================================================================================================================================
+ * VARIANCE-GUIDED FILTERING FROM TWO HALF-SAMPLE BUFFERS (after SVGF: Schied et al., "Spatiotemporal Variance-Guided Filtering", HPG 2017).
+ * The colour weight of trg_denoise is scaled by a SPATIAL variance, which cannot tell a shadow boundary from noise.  Here the frames of one
+ * batch are rendered as two independent halves; their difference is an unbiased estimate of the variance of their mean, and the filter carries
+ * that variance through its iterations, so it narrows as the noise goes down.
+ * ============================================================================================================================================= */
+
+/* --- HALVES.  n = spp must be even and >= 2 (and frameIndexBegin + n <= 2^32 - 1), else TRG_ERR_INVALID.  halves_device: TWO planes of
+ *     width*height float4, H1 then H2; it must not overlap the bound accumulation buffer.  With b = frameIndexBegin:
+ *       a zeroed image A of the state is bound (trg_bind_accum) and trg_render(b, n/2, bounces) runs over the whole image,
+ *       a second zeroed image B is bound and trg_render(b + n/2, n/2, bounces) runs,
+ *       the caller's binding is restored: the caller's accumulation buffer is never written.
+ *     From a zeroed buffer the running average leaves (sum of the samples) / (b + n/2) in A and / (b + n) in B; one streaming kernel scales
+ *       H1.rgb = A.rgb * f1,  f1 = fl((b + n/2) / (n/2))        H2.rgb = B.rgb * f2,  f2 = fl((b + n) / (n/2))
+ *     (the quotient formed in double precision and rounded to fp32; ONE fp32 multiply per channel; for b = 0 the factors are 1 and 2 and the
+ *     scaling is exact), alpha copied: H1, H2 = the means of the two halves' samples.
+ *     Both renders are REAL renders on the context's current stream: trg_get_stats counts their rays (n frames in all), `renders` goes up by
+ *     two, and with TRG_OPT_TIMING on each waits for its kernels as trg_render always does. */
+TRG_API int trg_render_halves(trg_ctx *ctx, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, void *halves_device);
+
+typedef struct trg_denoise_var_params {
+    int32_t iterations;  /* 0 .. TRG_DENOISE_MAX_ITERATIONS; default 5 */
+    float sigma_lum;     /* default 4.0 */
+    float sigma_normal;  /* default 128 */
+    float sigma_depth;   /* default 1.0 */
+    int32_t demodulate;  /* default 1 */
+    int32_t prefilter;   /* default 1 */
+} trg_denoise_var_params;
+TRG_API void trg_denoise_var_default_params(trg_denoise_var_params *p);
+
+/* --- THE VARIANCE-GUIDED FILTER.  halves_device: H1, H2 as above; guides_device as for trg_denoise; out_device: width*height float4, must not
+ *     overlap the halves.  Notation, misses and emitters, the taps and h, w_n, w_z, w_id: exactly as for trg_denoise above.
+ *
+ *   Start.  D(X)(p) = X(p).rgb / max(a_p, 1e-3) per channel when `demodulate` and p is not a miss, else X(p).rgb.
+ *          I_0(p) = 0.5 * (D(H1)(p) + D(H2)(p))
+ *          V_0(p) = 0.25 * (L(D(H1)(p)) - L(D(H2)(p)))^2           a miss pixel has V_0 = 0
+ *   Prefilter (when `prefilter`; one degree of freedom is too noisy an estimate on its own).  For p not a miss, V_0(p) is replaced by
+ *          sum_q g(p,q) V_0(q) / sum_q g(p,q)                      (if the sum of g is not > 0: V_0(p) stays)
+ *      over the 49 pixels q = p + (dx, dy), dx, dy in {-3 .. 3}, inside the image, with g = w_n * w_z * w_id at s = 1 (no B3 factor, no colour
+ *      term; the V_0 on the right are all the un-prefiltered ones).
+ *   Iteration i = 0 .. N-1, spacing s = 2^i.  A miss pixel copies I and V.  Any other pixel, over the 25 taps inside the image:
+ *          w(p,q) = h(dx) h(dy) * w_n * w_z * w_l * w_id
+ *          w_l = exp(-|L(I_i(p)) - L(I_i(q))| / (sigma_lum * sqrt(max(0, GV_i(p))) + 1e-3))
+ *                GV_i(p) = sum_r b(r) V_i(r) / sum_r b(r) over the pixels r of the 3 x 3 window around p (spacing 1) that lie inside the image and
+ *                are not misses, b = (1/4, 1/2, 1/4) along each axis
+ *          I_{i+1}(p) = sum_q w I_i(q) / sum_q w          V_{i+1}(p) = sum_q w^2 V_i(q) / (sum_q w)^2      (sum of w not > 0: both copy)
+ *   End.   out(p).rgb = I_N(p) * max(a_p, 1e-3) when `demodulate` and p is not a miss, else I_N(p);  out(p).a = H1(p).a.
+ *          iterations == 0: out.rgb = 0.5 * (H1 + H2), one fp32 add and one multiply per channel.
+ *
+ *  Arithmetic: fp32 without contraction; TRG_OPT_STRICT 1 uses expf / powf / sqrtf, 0 the hardware's exp2 / log2 / sqrt.  The float64
+ *  reference: toyraygun_amd/denoise.py reference_denoise_variance.
+ *
+ *  On the device: V travels in the .w of the filter's ping-pong colour planes, so the LDS forms (spacings 1, 2) stage no extra bytes and a
+ *  tap of the L2 form is still one global_load_dwordx4 per plane; GV is read from the staged tile in the LDS forms.  One streaming launch
+ *  marks the emitters (as for trg_denoise), one combines H1, H2 into (I_0, V_0), the prefilter is one launch over 16 x 16 tiles with a
+ *  22 x 22 halo of G0 and V in LDS, then one launch per iteration; remodulation and alpha are part of the last. */
+TRG_API int trg_denoise_variance(trg_ctx *ctx, const void *halves_device, const void *guides_device, void *out_device, const trg_denoise_var_params *p /* NULL: defaults */);
+
+/* --- trg_render_halves(frameIndexBegin, spp, bounces) into the state's own half planes, trg_guides_render(frameIndexBegin) into the state's own
+ *     guide planes, trg_denoise_variance into out_device.  One stream.  The bound accumulation buffer is neither read nor written. */
+TRG_API int trg_render_denoised_variance(trg_ctx *ctx, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, void *out_device, const trg_denoise_var_params *p);
+
+/* --- the same for callers without device memory of their own (the engine plugin): the result goes to the image the STATE owns (the one of
+ *     trg_denoise_accum; valid until the next call of either function or trg_denoise_release).  Only enqueues (but see TRG_OPT_TIMING). */
+TRG_API int trg_render_denoised_variance_own(trg_ctx *ctx, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, const trg_denoise_var_params *p, void **out_device);
+
+/* --- with HOST buffers; they WAIT for the result.  halves_host: 2 * width*height*4 floats.  var_host (may be NULL): width*height floats, V_N of
+ *     the definition above -- the variance the filter carried to its end (V_0, prefiltered or not, when iterations == 0). */
+TRG_API int trg_render_halves_read(trg_ctx *ctx, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *halves_host);
+TRG_API int trg_denoise_variance_host(trg_ctx *ctx, const float *halves_host, const float *guides_host, float *out_host, float *var_host, const trg_denoise_var_params *p);
+TRG_API int trg_render_denoised_variance_read(trg_ctx *ctx, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_denoise_var_params *p);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,8 @@
-"""Device time of trg_guides_render and trg_denoise (5 iterations) on the Cornell box, HIP events on the context's stream:
-python scripts/denoise_time.py [width height reps]   (default 1920 1080 20; one warm-up each).  Prints one JSON line with the medians in
-ms, next to the filter's compulsory traffic (per iteration 48 B read + 16 B written per pixel) at the measured time."""
+"""Device time of trg_guides_render, trg_denoise and the variance-guided path (trg_render_halves, trg_denoise_variance) on the Cornell box, HIP
+events on the context's stream:
+python scripts/denoise_time.py [width height reps spp]   (default 1920 1080 20 16; one warm-up each).  Prints one JSON line with the medians in
+ms, next to the filter's compulsory traffic (per iteration 48 B read + 16 B written per pixel) at the measured time.  The launches of the
+variance-guided filter are taken as differences of runs that differ by one launch (prefilter on / off, N and N - 1 iterations)."""
 import json
 import os
 import sys
@@ -12,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from toyraygun_amd import capi, denoise, host   # noqa: E402
 
-w, h, reps = (int(a) for a in (sys.argv[1:4] + ["1920", "1080", "20"][len(sys.argv[1:4]):]))
+w, h, reps, spp = (int(a) for a in (sys.argv[1:5] + ["1920", "1080", "20", "16"][len(sys.argv[1:5]):]))
 b = host.Scene.cornell_box().buffers()
 c = capi.Context(w, h)
 c.load_scene(b["positions"], b["normals"], b["colors"], b["indices"], b["material_ids"])
@@ -44,6 +46,22 @@ res["guides_ms"] = timed(lambda: denoise.guides(c, 0, out=g))
 for it in (1, 5):
     res["denoise_%d_ms" % it] = timed(lambda: denoise.denoise(c, acc, g, out=out, iterations=it))
 res["render_4spp_ms"] = timed(lambda: c.render(0, 4, 3))
+# the variance-guided path: the price of the estimate (two half launches + the scaling against one launch of the same samples) ...
+hv = torch.empty((2, h, w, 4), dtype=torch.float32, device="cuda")
+res["spp"] = spp
+res["render_%dspp_ms" % spp] = timed(lambda: c.render(0, spp, 3))
+res["render_halves_%dspp_ms" % spp] = timed(lambda: denoise.render_halves(c, 0, spp, 3, out=hv))
+res["render_half_%dspp_ms" % (spp // 2)] = timed(lambda: c.render(0, spp // 2, 3))
+# ... and the filter: whole runs, then single launches as differences
+var = lambda **kw: timed(lambda: denoise.denoise_variance(c, hv, g, out=out, **kw))
+t = {(it, pre): var(iterations=it, prefilter=pre) for it in range(0, 6) for pre in (0, 1) if pre == 0 or it in (1, 5)}
+res["denoise_variance_5_ms"] = t[(5, 1)]
+res["denoise_variance_1_ms"] = t[(1, 1)]
+res["variance_prefilter_ms"] = t[(5, 1)] - t[(5, 0)]
+res["variance_combine_ms"] = t[(0, 0)]
+res["variance_iteration_ms"] = [t[(1, 0)] - t[(0, 0)]] + [t[(it, 0)] - t[(it - 1, 0)] for it in range(2, 6)]
+old = {it: timed(lambda: denoise.denoise(c, acc, g, out=out, iterations=it)) for it in range(1, 6)}
+res["denoise_iteration_ms"] = [old[1]] + [old[it] - old[it - 1] for it in range(2, 6)]
 res["compulsory_GB_5"] = 5 * 64 * w * h / 1e9
 res["compulsory_GBps_at_denoise_5"] = res["compulsory_GB_5"] / (res["denoise_5_ms"] * 1e-3)
 print(json.dumps(res))

@@ -15,7 +15,7 @@ namespace toyraygun {
 
 HipRenderer::HipRenderer()
     : m_ctx(nullptr), m_group(nullptr), m_deviceCount(0), m_bounces(3), m_deviceBuild(0), m_offsetSeed(0x5EED0001u), m_sceneLoaded(false), m_synchronous(false), m_pending(0), m_pendingFirst(0),
-      m_launches(0), m_denoise(0) {
+      m_launches(0), m_denoise(0), m_denoiseVar(false) {
     memset(&m_pendingUniforms, 0, sizeof(m_pendingUniforms));
 }
 HipRenderer::~HipRenderer() { destroy(); }
@@ -222,9 +222,10 @@ bool HipRenderer::readAccumulation(float *rgbaOut) {
     if (m_group) return trg_group_read_accum(m_group, 0, rgbaOut) == TRG_OK;   // waits for the gather onto device 0 (and the unpack of interleaved bands)
     return trg_read_accum(m_ctx, rgbaOut) == TRG_OK;
 }
-bool HipRenderer::setDenoise(int iterations) {
+bool HipRenderer::setDenoise(int iterations, bool varianceGuided) {
     if (iterations < 0 || iterations > TRG_DENOISE_MAX_ITERATIONS) return false;
     m_denoise = iterations;
+    m_denoiseVar = varianceGuided && iterations > 0;
     return true;
 }
 bool HipRenderer::savePNG(const char *path) {
@@ -237,7 +238,22 @@ bool HipRenderer::savePNG(const char *path) {
         trg_denoise_default_params(&dp);
         dp.iterations = m_denoise;
         void *denoised = nullptr;
-        if (trg_denoise_accum(m_ctx, 0u, &dp, &denoised) != TRG_OK || trg_bind_accum(m_ctx, denoised) != TRG_OK) {
+        int drc;
+        if (m_denoiseVar) {
+            // the frames so far once more, as two independent halves whose difference guides the filter (the uniforms are those of the last launch)
+            unsigned int n = m_frameIndex > 0 ? (unsigned int)m_frameIndex : 2u;
+            if (n & 1u) {
+                printf("HipRenderer: the variance-guided denoiser needs an even sample count: rendering %u samples, not %u\n", n + 1u, n);
+                ++n;
+            }
+            trg_denoise_var_params vp;
+            trg_denoise_var_default_params(&vp);
+            vp.iterations = m_denoise;
+            drc = trg_render_denoised_variance_own(m_ctx, 0u, n, m_bounces, &vp, &denoised);
+        } else {
+            drc = trg_denoise_accum(m_ctx, 0u, &dp, &denoised);
+        }
+        if (drc != TRG_OK || trg_bind_accum(m_ctx, denoised) != TRG_OK) {
             printf("HipRenderer: %s\n", trg_last_error(m_ctx));
             return false;
         }

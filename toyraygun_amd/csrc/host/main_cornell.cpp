@@ -1,6 +1,7 @@
 // main_cornell.cpp -- headless demo following the reference app's call order (reference src/main.cpp:16-98):
 // engine init -> three shaders -> renderer init -> camera -> Cornell box -> frame loop; then writes a PNG.
-//   toyraygun_cornell [width height frames bounces out.png [denoise=N]]     N = a-trous iterations of the written image, 0 = off (default)
+//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var]]]   N = a-trous iterations of the written image, 0 = off (default);
+//                                                                               ,var = the variance-guided filter from two half-sample buffers
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -28,9 +29,15 @@ int main(int argc, char **argv) {
     const int frames = argc > 3 ? atoi(argv[3]) : 64, bounces = argc > 4 ? atoi(argv[4]) : 3;
     const char *out = argc > 5 ? argv[5] : "cornell.png";
     int denoise = 0;
+    bool denoiseVar = false;
     if (argc > 6) {
-        if (strncmp(argv[6], "denoise=", 8) != 0) { std::cout << "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N]]" << std::endl; return -1; }
+        if (strncmp(argv[6], "denoise=", 8) != 0) { std::cout << "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var]]]" << std::endl; return -1; }
         denoise = atoi(argv[6] + 8);
+        const char *comma = strchr(argv[6] + 8, ',');
+        if (comma) {
+            if (strcmp(comma, ",var") != 0) { std::cout << "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var]]]" << std::endl; return -1; }
+            denoiseVar = true;
+        }
     }
 
     Engine *engine = Engine::instance();
@@ -62,7 +69,7 @@ int main(int argc, char **argv) {
 
     HipRenderer *hip = static_cast<HipRenderer *>(renderer);
     hip->setBounces((unsigned int)bounces);
-    if (!hip->setDenoise(denoise)) { std::cout << "denoise must be 0.." << 6 << std::endl; return -1; }
+    if (!hip->setDenoise(denoise, denoiseVar)) { std::cout << "denoise must be 0.." << 6 << std::endl; return -1; }
     while (!engine->hasQuit()) {
         engine->pollEvents();
         if (engine->hasQuit()) break;

@@ -119,6 +119,9 @@ struct DenoiseState {
     size_t prims = 0;
     int *overflow = nullptr;       // traversal-stack levels beyond those kept in LDS (scenes traversed from HBM)
     size_t overflow_bytes = 0;
+    // variance-guided path (allocated on its first use): the two zeroed images trg_render_halves renders into, and the half planes
+    // trg_render_denoised_variance fills
+    float4 *half_acc = nullptr, *halves = nullptr;
 };
 std::mutex g_mutex;
 std::unordered_map<trg_ctx *, DenoiseState> g_states;
@@ -126,6 +129,7 @@ std::unordered_map<trg_ctx *, DenoiseState> g_states;
 void free_state(DenoiseState &s) {
     (void)hipFree(s.rays); (void)hipFree(s.isect); (void)hipFree(s.ping); (void)hipFree(s.pong); (void)hipFree(s.guides);
     (void)hipFree(s.rec_of_prim); (void)hipFree(s.overflow); (void)hipFree(s.result); (void)hipFree(s.fguide);
+    (void)hipFree(s.half_acc); (void)hipFree(s.halves);
     s = DenoiseState{};
 }
 
@@ -161,6 +165,14 @@ int state_of(trg_ctx *c, DenoiseState *&out) {
         s.pixels = n;
     }
     out = &s;
+    return TRG_OK;
+}
+
+// an image-sized buffer of the state that only some entry points need: `planes` x width*height float4, allocated on first use
+int lazy_planes(trg_ctx *c, DenoiseState &s, float4 *&mem, size_t planes, const char *what) {
+    if (mem) return TRG_OK;
+    const hipError_t e = hipMalloc((void **)&mem, planes * s.pixels * sizeof(float4));
+    if (e != hipSuccess) { mem = nullptr; return fail(c, TRG_ERR_NOMEM, "denoise: hipMalloc of %s failed: %s", what, hipGetErrorString(e)); }
     return TRG_OK;
 }
 
@@ -319,7 +331,11 @@ struct AtrousParams {
     float4 *out;
     int w, h, spacing;
     int demod_in, remod_out;   // first / last launch of a demodulated run
-    float sigma_color, sigma_normal, sigma_depth;
+    float sigma_color, sigma_normal, sigma_depth;   // (variance-guided form: sigma_color holds sigma_lum)
+    // variance-guided form only: the last launch takes alpha from H1 and, when asked, writes the variance it carried to a plane of floats
+    int last;
+    const float4 *alpha;
+    float *var_out;
 };
 constexpr int kDnTile = 16;                      // = trg::kTileW x kTileH of the render kernels at 256 threads
 constexpr int kDnLdsMaxSpacing = 2;              // spacings 1, 2: tile + halo of 2 * spacing pixels in LDS
@@ -328,11 +344,29 @@ static_assert(kTileW == kDnTile && kTileH == kDnTile && kBlock == 256, "the filt
 
 template <bool STRICT> __device__ __forceinline__ float dn_exp(float x) { return STRICT ? expf(x) : __expf(x); }
 template <bool STRICT> __device__ __forceinline__ float dn_pow(float x, float y) { return STRICT ? powf(x, y) : __powf(x, y); }
+template <bool STRICT> __device__ __forceinline__ float dn_sqrt(float x) { return STRICT ? sqrtf(x) : __builtin_amdgcn_sqrtf(x); }
 __device__ __forceinline__ float dn_lum(const float4 c) { return 0.2126f * c.x + 0.7152f * c.y + 0.0722f * c.z; }
 
+// g_p of the header: forward differences of the depth, backward where the forward neighbour is outside the image or a miss
+template <typename Guide>
+__device__ __forceinline__ float dn_depth_gradient(const Guide &guide, int x, int y, int w, int h, float zp) {
+    float gx = 0.0f, gy = 0.0f;
+    float z1 = -1.0f;
+    if (x + 1 < w) z1 = guide(x + 1, y).w;
+    if (z1 >= 0.0f) gx = z1 - zp;
+    else if (x >= 1) { z1 = guide(x - 1, y).w; if (z1 >= 0.0f) gx = zp - z1; }
+    z1 = -1.0f;
+    if (y + 1 < h) z1 = guide(x, y + 1).w;
+    if (z1 >= 0.0f) gy = z1 - zp;
+    else if (y >= 1) { z1 = guide(x, y - 1).w; if (z1 >= 0.0f) gy = zp - z1; }
+    return sqrtf(gx * gx + gy * gy);
+}
+
+// VAR = true: the variance-guided form (trg_denoise_variance): the .w of the colour plane is V_i, the colour weight is w_l, scaled by the 3 x 3
+// binomial of V around p, and V_{i+1} is written beside I_{i+1}.
 // LDS = true: colour (already demodulated) and G0 of the tile + halo sit in LDS as [row][x] float4 -- a wavefront's four rows of 16 lanes read
 // 16 consecutive float4 each; false: every tap is a global_load_dwordx4 per plane (neighbouring lanes' taps fall on the same 128-byte lines).
-template <bool STRICT, bool LDS>
+template <bool STRICT, bool LDS, bool VAR>
 __global__ __launch_bounds__(256) void dn_atrous_kernel(const AtrousParams p) {
     __shared__ float4 s_col[LDS ? kDnLdsSide * kDnLdsSide : 1];
     __shared__ float4 s_g0[LDS ? kDnLdsSide * kDnLdsSide : 1];
@@ -365,47 +399,58 @@ __global__ __launch_bounds__(256) void dn_atrous_kernel(const AtrousParams p) {
     const size_t pix = (size_t)y * (size_t)p.w + (size_t)x;
     const float4 cp = colour(x, y), gp = guide(x, y);
     if (gp.w < 0.0f) {   // a miss copies its input
-        p.out[pix] = cp;
+        float4 o = cp;
+        if (VAR && p.last) {
+            if (p.var_out) p.var_out[pix] = cp.w;
+            o.w = p.alpha[pix].w;
+        }
+        p.out[pix] = o;
         return;
     }
-    // variance of luminance over the 3 x 3 window (two passes: mean, then squared deviations)
-    float lum[9];
-    int m = 0;
-    float mean = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        const int qx = x + k % 3 - 1, qy = y + k / 3 - 1;
-        const bool in = qx >= 0 && qx < p.w && qy >= 0 && qy < p.h;
-        lum[k] = in ? dn_lum(colour(qx, qy)) : 0.0f;
-        mean += lum[k];
-        m += in ? 1 : 0;
-    }
-    mean = mean / (float)m;
     float var = 0.0f;
+    if (VAR) {
+        // GV(p): the 3 x 3 binomial of V over the pixels inside the image that are not misses, renormalised (p itself is one of them)
+        const float bk[3] = { 0.25f, 0.5f, 0.25f };
+        float vs = 0.0f, bs = 0.0f;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        const int qx = x + k % 3 - 1, qy = y + k / 3 - 1;
-        const bool in = qx >= 0 && qx < p.w && qy >= 0 && qy < p.h;
-        const float d = lum[k] - mean;
-        var += in ? d * d : 0.0f;
+        for (int k = 0; k < 9; ++k) {
+            const int qx = x + k % 3 - 1, qy = y + k / 3 - 1;
+            if (qx < 0 || qx >= p.w || qy < 0 || qy >= p.h) continue;
+            if (guide(qx, qy).w < 0.0f) continue;
+            const float b = bk[k % 3] * bk[k / 3];
+            vs += b * colour(qx, qy).w;
+            bs += b;
+        }
+        var = vs / bs;
+    } else {
+        // variance of luminance over the 3 x 3 window (two passes: mean, then squared deviations)
+        float lum[9];
+        int m = 0;
+        float mean = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int qx = x + k % 3 - 1, qy = y + k / 3 - 1;
+            const bool in = qx >= 0 && qx < p.w && qy >= 0 && qy < p.h;
+            lum[k] = in ? dn_lum(colour(qx, qy)) : 0.0f;
+            mean += lum[k];
+            m += in ? 1 : 0;
+        }
+        mean = mean / (float)m;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int qx = x + k % 3 - 1, qy = y + k / 3 - 1;
+            const bool in = qx >= 0 && qx < p.w && qy >= 0 && qy < p.h;
+            const float d = lum[k] - mean;
+            var += in ? d * d : 0.0f;
+        }
+        var = var / (float)m;
     }
-    var = var / (float)m;
-    // depth gradient: forward differences, backward where the forward neighbour is outside the image or a miss
-    float gx = 0.0f, gy = 0.0f;
-    {
-        float z1 = -1.0f;
-        if (x + 1 < p.w) z1 = guide(x + 1, y).w;
-        if (z1 >= 0.0f) gx = z1 - gp.w;
-        else if (x >= 1) { z1 = guide(x - 1, y).w; if (z1 >= 0.0f) gx = gp.w - z1; }
-        z1 = -1.0f;
-        if (y + 1 < p.h) z1 = guide(x, y + 1).w;
-        if (z1 >= 0.0f) gy = z1 - gp.w;
-        else if (y >= 1) { z1 = guide(x, y - 1).w; if (z1 >= 0.0f) gy = gp.w - z1; }
-    }
-    const float grad = sqrtf(gx * gx + gy * gy);
-    const float cden = p.sigma_color * p.sigma_color * (var + 1e-4f);
+    const float grad = dn_depth_gradient(guide, x, y, p.w, p.h, gp.w);
+    // the denominator of the colour term: w_c's sigma_color^2 (var + 1e-4), w_l's sigma_lum sqrt(max(0, GV)) + 1e-3
+    const float cden = VAR ? p.sigma_color * dn_sqrt<STRICT>(fmaxf(0.0f, var)) + 1e-3f : p.sigma_color * p.sigma_color * (var + 1e-4f);
+    const float lp = VAR ? dn_lum(cp) : 0.0f;
     const float hk[5] = { 1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f };
-    float ar = 0.0f, ag = 0.0f, ab = 0.0f, wsum = 0.0f;
+    float ar = 0.0f, ag = 0.0f, ab = 0.0f, av = 0.0f, wsum = 0.0f;
 #pragma unroll
     for (int dy = -2; dy <= 2; ++dy) {
 #pragma unroll
@@ -420,15 +465,28 @@ __global__ __launch_bounds__(256) void dn_atrous_kernel(const AtrousParams p) {
             const float wn = dn_pow<STRICT>(dn, p.sigma_normal);
             const float dist = sqrtf((float)(dx * dx + dy * dy));
             const float wz = dn_exp<STRICT>(-(fabsf(gp.w - gq.w) / (p.sigma_depth * (grad * (float)s * dist + 1e-6f))));
-            const float dr = cp.x - cq.x, dg = cp.y - cq.y, db = cp.z - cq.z;
-            const float wc = dn_exp<STRICT>(-((dr * dr + dg * dg + db * db) / cden));
+            float wc;
+            if (VAR) {
+                wc = dn_exp<STRICT>(-(fabsf(lp - dn_lum(cq)) / cden));
+            } else {
+                const float dr = cp.x - cq.x, dg = cp.y - cq.y, db = cp.z - cq.z;
+                wc = dn_exp<STRICT>(-((dr * dr + dg * dg + db * db) / cden));
+            }
             const float wgt = hk[dx + 2] * hk[dy + 2] * wn * wz * wc;
             ar += wgt * cq.x; ag += wgt * cq.y; ab += wgt * cq.z;
+            if (VAR) av += wgt * wgt * cq.w;
             wsum += wgt;
         }
     }
     float4 o = cp;
-    if (wsum > 0.0f) { o.x = ar / wsum; o.y = ag / wsum; o.z = ab / wsum; }
+    if (wsum > 0.0f) {
+        o.x = ar / wsum; o.y = ag / wsum; o.z = ab / wsum;
+        if (VAR) o.w = av / (wsum * wsum);
+    }
+    if (VAR && p.last) {
+        if (p.var_out) p.var_out[pix] = o.w;
+        o.w = p.alpha[pix].w;
+    }
     if (p.remod_out) {
         const float4 a = p.g1[pix];
         o.x = o.x * fmaxf(a.x, 1e-3f); o.y = o.y * fmaxf(a.y, 1e-3f); o.z = o.z * fmaxf(a.z, 1e-3f);
@@ -436,16 +494,28 @@ __global__ __launch_bounds__(256) void dn_atrous_kernel(const AtrousParams p) {
     p.out[pix] = o;
 }
 
-template <bool STRICT>
+template <bool STRICT, bool VAR>
 hipError_t launch_atrous(const AtrousParams &p, hipStream_t st) {
     const dim3 grid((uint32_t)(p.w + kDnTile - 1) / kDnTile, (uint32_t)(p.h + kDnTile - 1) / kDnTile);
-    if (p.spacing <= kDnLdsMaxSpacing) hipLaunchKernelGGL((dn_atrous_kernel<STRICT, true>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((dn_atrous_kernel<STRICT, false>), grid, dim3(256), 0, st, p);
+    if (p.spacing <= kDnLdsMaxSpacing) hipLaunchKernelGGL((dn_atrous_kernel<STRICT, true, VAR>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((dn_atrous_kernel<STRICT, false, VAR>), grid, dim3(256), 0, st, p);
     return hipGetLastError();
 }
 
 bool valid_params(const trg_denoise_params &q) {
     return q.iterations >= 0 && q.iterations <= TRG_DENOISE_MAX_ITERATIONS && q.sigma_color > 0.0f && q.sigma_normal >= 0.0f && q.sigma_depth > 0.0f;
+}
+
+// enqueues the filter's copy of G0 (s.fguide) with the emitters of the loaded scene marked as misses
+int exclude_emitters(trg_ctx *c, DenoiseState &s, const float4 *guides) {
+    const size_t n = (size_t)c->w * c->h;
+    const bool scene = c->scene_loaded && c->sc.n_tris != 0 && c->sc.n_fat != 0;
+    if (scene)
+        if (int rc = record_map(c, s)) return rc;
+    hipLaunchKernelGGL(dn_exclude_emitters_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, guides, guides + n, s.rec_of_prim,
+                       scene ? reinterpret_cast<const float4 *>(c->blob + c->sc.off_fat) : nullptr, scene ? c->sc.n_tris : 0u, s.fguide, (uint32_t)n);
+    DN_HIPCHK(c, hipGetLastError());
+    return TRG_OK;
 }
 
 int denoise(trg_ctx *c, DenoiseState &s, const float4 *in, const float4 *guides, float4 *out, const trg_denoise_params *pp) {
@@ -461,14 +531,7 @@ int denoise(trg_ctx *c, DenoiseState &s, const float4 *in, const float4 *guides,
         DN_HIPCHK(c, hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, st));
         return TRG_OK;
     }
-    {
-        const bool scene = c->scene_loaded && c->sc.n_tris != 0 && c->sc.n_fat != 0;
-        if (scene)
-            if (int rc = record_map(c, s)) return rc;
-        hipLaunchKernelGGL(dn_exclude_emitters_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, guides, guides + n, s.rec_of_prim,
-                           scene ? reinterpret_cast<const float4 *>(c->blob + c->sc.off_fat) : nullptr, scene ? c->sc.n_tris : 0u, s.fguide, (uint32_t)n);
-        DN_HIPCHK(c, hipGetLastError());
-    }
+    if (int rc = exclude_emitters(c, s, guides)) return rc;
     AtrousParams p{};
     p.g0 = s.fguide; p.g1 = guides + n;
     p.w = (int)c->w; p.h = (int)c->h;
@@ -481,11 +544,205 @@ int denoise(trg_ctx *c, DenoiseState &s, const float4 *in, const float4 *guides,
         p.spacing = 1 << i;
         p.demod_in = (q.demodulate && i == 0) ? 1 : 0;
         p.remod_out = (q.demodulate && last) ? 1 : 0;
-        const hipError_t e = c->opt_strict ? launch_atrous<true>(p, st) : launch_atrous<false>(p, st);
+        const hipError_t e = c->opt_strict ? launch_atrous<true, false>(p, st) : launch_atrous<false, false>(p, st);
         if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_denoise: launch failed: %s", hipGetErrorString(e));
         src = p.out;
     }
     return TRG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The variance-guided filter from two half-sample buffers (trg_denoise.h has the definition)
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// H1.rgb = A.rgb * f1, H2.rgb = B.rgb * f2, alpha copied: the running averages trg_render left in two zeroed images, as means of their halves
+__global__ void dn_scale_halves_kernel(const float4 *a, const float4 *b, float4 *h1, float4 *h2, float f1, float f2, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float4 u = a[i], v = b[i];
+    u.x = u.x * f1; u.y = u.y * f1; u.z = u.z * f1;
+    v.x = v.x * f2; v.y = v.y * f2; v.z = v.z * f2;
+    h1[i] = u;
+    h2[i] = v;
+}
+
+// (I_0, V_0) of the header into one float4 plane.  plain: iterations == 0, out = (0.5 (H1 + H2), H1.a)
+__global__ void dn_var_combine_kernel(const float4 *h1, const float4 *h2, const float4 *fguide, const float4 *g1, float4 *out, int demod, int plain,
+                                      uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float4 a = h1[i], b = h2[i];
+    if (plain) {
+        out[i] = make_float4(0.5f * (a.x + b.x), 0.5f * (a.y + b.y), 0.5f * (a.z + b.z), a.w);
+        return;
+    }
+    const bool miss = fguide[i].w < 0.0f;
+    if (demod && !miss) {
+        const float4 al = g1[i];
+        const float dx = fmaxf(al.x, 1e-3f), dy = fmaxf(al.y, 1e-3f), dz = fmaxf(al.z, 1e-3f);
+        a.x = a.x / dx; a.y = a.y / dy; a.z = a.z / dz;
+        b.x = b.x / dx; b.y = b.y / dy; b.z = b.z / dz;
+    }
+    const float d = dn_lum(a) - dn_lum(b);
+    out[i] = make_float4(0.5f * (a.x + b.x), 0.5f * (a.y + b.y), 0.5f * (a.z + b.z), miss ? 0.0f : 0.25f * (d * d));
+}
+
+__global__ void dn_var_extract_kernel(const float4 *in, float *var, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) var[i] = in[i].w;
+}
+
+// The prefilter of V_0: 7 x 7 window at spacing 1, g = w_n w_z w_id.  G0 and V of the tile + 3 pixels of halo in LDS ([row][x]: a wavefront's four
+// rows of 16 lanes read 16 consecutive float4 / float each); the colour passes through.
+constexpr int kDnPreR = 3;
+constexpr int kDnPreSide = kDnTile + 2 * kDnPreR;   // 22
+template <bool STRICT>
+__global__ __launch_bounds__(256) void dn_var_prefilter_kernel(const float4 *in, const float4 *g0, float4 *out, int w, int h, float sigma_normal,
+                                                               float sigma_depth) {
+    __shared__ float4 s_g0[kDnPreSide * kDnPreSide];
+    __shared__ float s_v[kDnPreSide * kDnPreSide];
+    const int x0 = (int)blockIdx.x * kDnTile, y0 = (int)blockIdx.y * kDnTile;
+    for (int k = (int)threadIdx.x; k < kDnPreSide * kDnPreSide; k += 256) {
+        const int ly = k / kDnPreSide, lx = k - ly * kDnPreSide;
+        const int gx = x0 - kDnPreR + lx, gy = y0 - kDnPreR + ly;
+        float4 g = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        float v = 0.0f;
+        if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
+            const size_t q = (size_t)gy * (size_t)w + (size_t)gx;
+            g = g0[q];
+            v = in[q].w;
+        }
+        s_g0[k] = g;
+        s_v[k] = v;
+    }
+    __syncthreads();
+    const int x = x0 + ((int)threadIdx.x & 15), y = y0 + ((int)threadIdx.x >> 4);
+    if (x >= w || y >= h) return;
+    auto guide = [&](int qx, int qy) -> float4 { return s_g0[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)]; };
+    const size_t pix = (size_t)y * (size_t)w + (size_t)x;
+    float4 o = in[pix];
+    const float4 gp = guide(x, y);
+    if (gp.w < 0.0f) {   // a miss keeps V_0 = 0
+        out[pix] = o;
+        return;
+    }
+    const float grad = dn_depth_gradient(guide, x, y, w, h, gp.w);
+    float vs = 0.0f, gs = 0.0f;
+#pragma unroll
+    for (int dy = -kDnPreR; dy <= kDnPreR; ++dy) {
+#pragma unroll
+        for (int dx = -kDnPreR; dx <= kDnPreR; ++dx) {
+            const int qx = x + dx, qy = y + dy;
+            if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+            const float4 gq = guide(qx, qy);
+            if (gq.w < 0.0f) continue;
+            const float dn = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
+            if (!(dn > 0.0f)) continue;
+            const float wn = dn_pow<STRICT>(dn, sigma_normal);
+            const float dist = sqrtf((float)(dx * dx + dy * dy));
+            const float wz = dn_exp<STRICT>(-(fabsf(gp.w - gq.w) / (sigma_depth * (grad * 1.0f * dist + 1e-6f))));
+            const float g = wn * wz;
+            vs += g * s_v[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)];
+            gs += g;
+        }
+    }
+    if (gs > 0.0f) o.w = vs / gs;
+    out[pix] = o;
+}
+
+bool valid_var_params(const trg_denoise_var_params &q) {
+    return q.iterations >= 0 && q.iterations <= TRG_DENOISE_MAX_ITERATIONS && q.sigma_lum > 0.0f && q.sigma_normal >= 0.0f && q.sigma_depth > 0.0f;
+}
+
+bool overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    return (const char *)a < (const char *)b + b_bytes && (const char *)b < (const char *)a + a_bytes;
+}
+
+// var_out (may be null): a plane of width*height floats for V_N
+int denoise_variance(trg_ctx *c, DenoiseState &s, const float4 *halves, const float4 *guides, float4 *out, float *var_out, const trg_denoise_var_params *pp) {
+    trg_denoise_var_params q;
+    trg_denoise_var_default_params(&q);
+    if (pp) q = *pp;
+    if (!valid_var_params(q)) return fail(c, TRG_ERR_INVALID, "trg_denoise_variance: iterations must be 0..%d and the sigmas positive", TRG_DENOISE_MAX_ITERATIONS);
+    const size_t n = (size_t)c->w * c->h, bytes = n * sizeof(float4);
+    if (overlap(out, bytes, halves, 2 * bytes)) return fail(c, TRG_ERR_INVALID, "trg_denoise_variance: out_device overlaps halves_device");
+    hipStream_t st = c->stream;
+    const dim3 sgrid((uint32_t)((n + 255) / 256));
+    const float4 *h1 = halves, *h2 = halves + n;
+    if (q.iterations == 0 && !var_out) {
+        hipLaunchKernelGGL(dn_var_combine_kernel, sgrid, dim3(256), 0, st, h1, h2, (const float4 *)nullptr, (const float4 *)nullptr, out, 0, 1, (uint32_t)n);
+        DN_HIPCHK(c, hipGetLastError());
+        return TRG_OK;
+    }
+    if (int rc = exclude_emitters(c, s, guides)) return rc;
+    hipLaunchKernelGGL(dn_var_combine_kernel, sgrid, dim3(256), 0, st, h1, h2, (const float4 *)s.fguide, guides + n, s.ping, q.demodulate ? 1 : 0, 0, (uint32_t)n);
+    DN_HIPCHK(c, hipGetLastError());
+    const float4 *src = s.ping;
+    const dim3 grid((c->w + kDnTile - 1) / kDnTile, (c->h + kDnTile - 1) / kDnTile);
+    if (q.prefilter) {
+        if (c->opt_strict)
+            hipLaunchKernelGGL((dn_var_prefilter_kernel<true>), grid, dim3(256), 0, st, src, (const float4 *)s.fguide, s.pong, (int)c->w, (int)c->h, q.sigma_normal, q.sigma_depth);
+        else
+            hipLaunchKernelGGL((dn_var_prefilter_kernel<false>), grid, dim3(256), 0, st, src, (const float4 *)s.fguide, s.pong, (int)c->w, (int)c->h, q.sigma_normal, q.sigma_depth);
+        DN_HIPCHK(c, hipGetLastError());
+        src = s.pong;
+    }
+    if (q.iterations == 0) {   // only the variance was asked for beside the plain mean
+        hipLaunchKernelGGL(dn_var_extract_kernel, sgrid, dim3(256), 0, st, src, var_out, (uint32_t)n);
+        DN_HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(dn_var_combine_kernel, sgrid, dim3(256), 0, st, h1, h2, (const float4 *)nullptr, (const float4 *)nullptr, out, 0, 1, (uint32_t)n);
+        DN_HIPCHK(c, hipGetLastError());
+        return TRG_OK;
+    }
+    AtrousParams p{};
+    p.g0 = s.fguide; p.g1 = guides + n;
+    p.w = (int)c->w; p.h = (int)c->h;
+    p.sigma_color = q.sigma_lum; p.sigma_normal = q.sigma_normal; p.sigma_depth = q.sigma_depth;
+    p.alpha = h1; p.var_out = var_out;
+    for (int i = 0; i < q.iterations; ++i) {
+        const bool last = i + 1 == q.iterations;
+        p.in = src;
+        p.out = last ? out : (src == s.ping ? s.pong : s.ping);
+        p.spacing = 1 << i;
+        p.demod_in = 0;   // the combine kernel demodulated
+        p.remod_out = (q.demodulate && last) ? 1 : 0;
+        p.last = last ? 1 : 0;
+        const hipError_t e = c->opt_strict ? launch_atrous<true, true>(p, st) : launch_atrous<false, true>(p, st);
+        if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_denoise_variance: launch failed: %s", hipGetErrorString(e));
+        src = p.out;
+    }
+    return TRG_OK;
+}
+
+int render_halves(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n, uint32_t bounces, float4 *halves, const char *who) {
+    if (n < 2u || (n & 1u)) return fail(c, TRG_ERR_INVALID, "%s: spp must be even and at least 2 (got %u): the samples are rendered as two equal halves", who, n);
+    if ((uint64_t)b + n > 0xFFFFFFFFull) return fail(c, TRG_ERR_INVALID, "%s: frame range [%u, %u + %u) exceeds 32 bits", who, b, b, n);
+    const size_t npix = (size_t)c->w * c->h, bytes = npix * sizeof(float4);
+    if (overlap(halves, 2 * bytes, c->accum, bytes)) return fail(c, TRG_ERR_INVALID, "%s: halves_device overlaps the bound accumulation buffer", who);
+    if (int rc = lazy_planes(c, s, s.half_acc, 2, "the half-sample images")) return rc;
+    hipStream_t st = c->stream;
+    DN_HIPCHK(c, hipMemsetAsync(s.half_acc, 0, 2 * bytes, st));
+    float *const bound = c->accum;
+    const bool own = bound == c->accum_own;
+    const uint32_t half = n / 2u;
+    int rc = trg_bind_accum(c, s.half_acc);
+    if (rc == TRG_OK) rc = trg_render(c, b, half, bounces, 0, c->h);
+    if (rc == TRG_OK) rc = trg_bind_accum(c, s.half_acc + npix);
+    if (rc == TRG_OK) rc = trg_render(c, b + half, half, bounces, 0, c->h);
+    (void)trg_bind_accum(c, own ? nullptr : bound);   // (cannot fail: the pointer was bound before)
+    if (rc != TRG_OK) return rc;
+    const float f1 = (float)((double)((uint64_t)b + half) / (double)half), f2 = (float)((double)((uint64_t)b + n) / (double)half);
+    hipLaunchKernelGGL(dn_scale_halves_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, st, (const float4 *)s.half_acc, (const float4 *)(s.half_acc + npix),
+                       halves, halves + npix, f1, f2, (uint32_t)npix);
+    DN_HIPCHK(c, hipGetLastError());
+    return TRG_OK;
+}
+
+int render_denoised_variance(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n, uint32_t bounces, float4 *out, const trg_denoise_var_params *p, const char *who) {
+    if (p && !valid_var_params(*p)) return fail(c, TRG_ERR_INVALID, "%s: bad parameters", who);
+    if (int rc = lazy_planes(c, s, s.halves, 2, "the half planes")) return rc;
+    if (int rc = render_halves(c, s, b, n, bounces, s.halves, who)) return rc;
+    if (int rc = guides_render(c, s, b, s.guides)) return rc;
+    return denoise_variance(c, s, s.halves, s.guides, out, nullptr, p);
 }
 
 struct DevBuf {
@@ -607,6 +864,98 @@ int trg_render_denoised_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp,
     }
     const hipError_t e = hipStreamSynchronize(c->stream);
     if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_denoised_read: %s", hipGetErrorString(e));
+    return rc;
+}
+
+void trg_denoise_var_default_params(trg_denoise_var_params *p) {
+    if (!p) return;
+    p->iterations = 5; p->sigma_lum = 4.0f; p->sigma_normal = 128.0f; p->sigma_depth = 1.0f; p->demodulate = 1; p->prefilter = 1;
+}
+
+int trg_render_halves(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, void *halves_device) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_render_halves")) return rc;
+    if (!halves_device) return fail(c, TRG_ERR_INVALID, "trg_render_halves: halves_device is NULL");
+    return render_halves(c, *s, frameIndexBegin, spp, bounces, static_cast<float4 *>(halves_device), "trg_render_halves");
+}
+
+int trg_denoise_variance(trg_ctx *c, const void *halves_device, const void *guides_device, void *out_device, const trg_denoise_var_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_denoise_variance")) return rc;
+    if (!halves_device || !guides_device || !out_device) return fail(c, TRG_ERR_INVALID, "trg_denoise_variance: NULL buffer");
+    return denoise_variance(c, *s, static_cast<const float4 *>(halves_device), static_cast<const float4 *>(guides_device), static_cast<float4 *>(out_device), nullptr, p);
+}
+
+int trg_render_denoised_variance(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, void *out_device, const trg_denoise_var_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_render_denoised_variance")) return rc;
+    if (!out_device) return fail(c, TRG_ERR_INVALID, "trg_render_denoised_variance: out_device is NULL");
+    return render_denoised_variance(c, *s, frameIndexBegin, spp, bounces, static_cast<float4 *>(out_device), p, "trg_render_denoised_variance");
+}
+
+int trg_render_denoised_variance_own(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, const trg_denoise_var_params *p, void **out_device) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_render_denoised_variance_own")) return rc;
+    if (!out_device) return fail(c, TRG_ERR_INVALID, "trg_render_denoised_variance_own: out_device is NULL");
+    if (int rc = lazy_planes(c, *s, s->result, 1, "the result image")) return rc;
+    if (c->accum == reinterpret_cast<float *>(s->result)) return fail(c, TRG_ERR_INVALID, "trg_render_denoised_variance_own: the state's image is bound as the accumulation buffer");
+    if (int rc = render_denoised_variance(c, *s, frameIndexBegin, spp, bounces, s->result, p, "trg_render_denoised_variance_own")) return rc;
+    *out_device = s->result;
+    return TRG_OK;
+}
+
+int trg_render_halves_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *halves_host) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_render_halves_read")) return rc;
+    if (!halves_host) return fail(c, TRG_ERR_INVALID, "trg_render_halves_read: halves_host is NULL");
+    const size_t bytes = 2 * (size_t)c->w * c->h * sizeof(float4);
+    DevBuf hv;
+    DN_HIPCHK(c, hv.alloc(bytes));
+    int rc = render_halves(c, *s, frameIndexBegin, spp, bounces, static_cast<float4 *>(hv.p), "trg_render_halves_read");
+    if (rc == TRG_OK) {
+        hipError_t e = hipMemcpyAsync(halves_host, hv.p, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_halves_read: copy failed: %s", hipGetErrorString(e));
+    }
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_halves_read: %s", hipGetErrorString(e));
+    return rc;
+}
+
+int trg_denoise_variance_host(trg_ctx *c, const float *halves_host, const float *guides_host, float *out_host, float *var_host, const trg_denoise_var_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_denoise_variance_host")) return rc;
+    if (!halves_host || !guides_host || !out_host) return fail(c, TRG_ERR_INVALID, "trg_denoise_variance_host: NULL buffer");
+    const size_t npix = (size_t)c->w * c->h, bytes = npix * sizeof(float4);
+    DevBuf in, g, out, var;
+    DN_HIPCHK(c, in.alloc(2 * bytes)); DN_HIPCHK(c, g.alloc(2 * bytes)); DN_HIPCHK(c, out.alloc(bytes));
+    if (var_host) DN_HIPCHK(c, var.alloc(npix * sizeof(float)));
+    DN_HIPCHK(c, hipMemcpyAsync(in.p, halves_host, 2 * bytes, hipMemcpyHostToDevice, c->stream));
+    DN_HIPCHK(c, hipMemcpyAsync(g.p, guides_host, 2 * bytes, hipMemcpyHostToDevice, c->stream));
+    int rc = denoise_variance(c, *s, static_cast<const float4 *>(in.p), static_cast<const float4 *>(g.p), static_cast<float4 *>(out.p), static_cast<float *>(var.p), p);
+    if (rc == TRG_OK) {
+        hipError_t e = hipMemcpyAsync(out_host, out.p, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && var_host) e = hipMemcpyAsync(var_host, var.p, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_denoise_variance_host: copy failed: %s", hipGetErrorString(e));
+    }
+    const hipError_t e = hipStreamSynchronize(c->stream);   // also on an error: the temporaries are freed on return
+    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_denoise_variance_host: %s", hipGetErrorString(e));
+    return rc;
+}
+
+int trg_render_denoised_variance_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_denoise_var_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_render_denoised_variance_read")) return rc;
+    if (!out_host) return fail(c, TRG_ERR_INVALID, "trg_render_denoised_variance_read: out_host is NULL");
+    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
+    DevBuf out;
+    DN_HIPCHK(c, out.alloc(bytes));
+    int rc = render_denoised_variance(c, *s, frameIndexBegin, spp, bounces, static_cast<float4 *>(out.p), p, "trg_render_denoised_variance_read");
+    if (rc == TRG_OK) {
+        hipError_t e = hipMemcpyAsync(out_host, out.p, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_denoised_variance_read: copy failed: %s", hipGetErrorString(e));
+    }
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_denoised_variance_read: %s", hipGetErrorString(e));
     return rc;
 }
 

@@ -4,9 +4,13 @@
     out = denoise(ctx, color, g, iterations=5)   # [h, w, 4]
     out = render_denoised(ctx, 0, 4, 3)          # trg_render + guides + filter on one stream; the accumulation buffer is only read
 
+    h = render_halves(ctx, 0, 4, 3)              # [2, h, w, 4]: the means of frames [0, 2) and [2, 4), rendered independently
+    out = denoise_variance(ctx, h, g)            # the variance-guided filter (SVGF's weights, variance from the two halves)
+    out = render_denoised_variance(ctx, 0, 4, 3) # halves + guides + that filter; the accumulation buffer is not touched
+
 numpy arrays go through temporary device copies and the call waits for the result; torch ROCm tensors (float32, contiguous) are used in place
-through data_ptr() -- like trg_bind_accum -- and the call only enqueues on the context's current stream.  `reference_denoise` is the float64
-numpy evaluation of the definition in the header: what the GPU tests compare the kernels with.
+through data_ptr() -- like trg_bind_accum -- and the call only enqueues on the context's current stream.  `reference_denoise` and
+`reference_denoise_variance` are the float64 numpy evaluations of the definitions in the header: what the GPU tests compare the kernels with.
 
 The context's denoise scratch lives until release(ctx); call it before ctx.close() (trg_destroy does not know about it).
 """
@@ -27,8 +31,15 @@ class Params(C.Structure):
                 ("demodulate", C.c_int32)]
 
 
+class VarParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("demodulate", C.c_int32), ("prefilter", C.c_int32)]
+
+
 _P = C.c_void_p
 _PP = C.POINTER(Params)
+_VP = C.POINTER(VarParams)
+_U = C.c_uint32
 _SYMBOLS = [
     ("trg_denoise_default_params", None, [_PP]),
     ("trg_guides_render", C.c_int, [_P, C.c_uint32, _P]),
@@ -39,6 +50,14 @@ _SYMBOLS = [
     ("trg_guides_read", C.c_int, [_P, C.c_uint32, _P]),
     ("trg_denoise_host", C.c_int, [_P, _P, _P, _P, _PP]),
     ("trg_render_denoised_read", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _PP]),
+    ("trg_denoise_var_default_params", None, [_VP]),
+    ("trg_render_halves", C.c_int, [_P, _U, _U, _U, _P]),
+    ("trg_denoise_variance", C.c_int, [_P, _P, _P, _P, _VP]),
+    ("trg_render_denoised_variance", C.c_int, [_P, _U, _U, _U, _P, _VP]),
+    ("trg_render_denoised_variance_own", C.c_int, [_P, _U, _U, _U, _VP, C.POINTER(_P)]),
+    ("trg_render_halves_read", C.c_int, [_P, _U, _U, _U, _P]),
+    ("trg_denoise_variance_host", C.c_int, [_P, _P, _P, _P, _P, _VP]),
+    ("trg_render_denoised_variance_read", C.c_int, [_P, _U, _U, _U, _P, _VP]),
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 
@@ -83,6 +102,26 @@ def make_params(params=None, **kw):
         if k not in dict(Params._fields_):
             raise TypeError("unknown denoise parameter %r" % k)
         setattr(p, k, int(v) if k in ("iterations", "demodulate") else float(v))
+    return p
+
+
+_VAR_DEFAULTS = dict(iterations=5, sigma_lum=4.0, sigma_normal=128.0, sigma_depth=1.0, demodulate=1, prefilter=1)   # the header's
+
+
+def make_var_params(params=None, **kw):
+    """VarParams from the library's defaults, a VarParams / dict, and keyword overrides."""
+    p = VarParams()
+    load().trg_denoise_var_default_params(C.byref(p))
+    src = {}
+    if isinstance(params, VarParams):
+        src = {f: getattr(params, f) for f, _ in VarParams._fields_}
+    elif params:
+        src = dict(params)
+    src.update(kw)
+    for k, v in src.items():
+        if k not in dict(VarParams._fields_):
+            raise TypeError("unknown variance-guided denoise parameter %r" % k)
+        setattr(p, k, int(v) if k in ("iterations", "demodulate", "prefilter") else float(v))
     return p
 
 
@@ -146,6 +185,55 @@ def render_denoised(ctx, frame_begin, spp, bounces, out=None, params=None, **kw)
     return o
 
 
+def render_halves(ctx, frame_begin, spp, bounces, out=None):
+    """trg_render_halves: frames [frame_begin, frame_begin + spp/2) and [frame_begin + spp/2, frame_begin + spp) rendered from zeroed images of the
+    state and scaled to the means of their samples -> [2, h, w, 4].  spp even, >= 2.  The bound accumulation buffer is not written; the rays count."""
+    L = load()
+    shape = (2, ctx.h, ctx.w, 4)
+    if out is not None and _is_tensor(out):
+        _chk(ctx, L.trg_render_halves(ctx.h_ctx, frame_begin, spp, bounces, _tensor_ptr(out, shape, "halves")))
+        return out
+    hv = np.empty(shape, np.float32)
+    _chk(ctx, L.trg_render_halves_read(ctx.h_ctx, frame_begin, spp, bounces, hv.ctypes.data))
+    return hv
+
+
+def denoise_variance(ctx, halves, guides, out=None, params=None, return_variance=False, **kw):
+    """trg_denoise_variance.  All tensors (enqueued only) or all numpy (waits).  return_variance (numpy only): also V_N [h, w], the variance the
+    filter carried to its end."""
+    L = load()
+    p = make_var_params(params, **kw)
+    cs, gs = (ctx.h, ctx.w, 4), (2, ctx.h, ctx.w, 4)
+    if _is_tensor(halves):
+        import torch
+        if return_variance:
+            raise ValueError("return_variance needs numpy arrays (trg_denoise_variance_host)")
+        if out is None:
+            out = torch.empty(cs, dtype=torch.float32, device=halves.device)
+        _chk(ctx, L.trg_denoise_variance(ctx.h_ctx, _tensor_ptr(halves, gs, "halves"), _tensor_ptr(guides, gs, "guides"), _tensor_ptr(out, cs, "out"), C.byref(p)))
+        return out
+    hv = np.ascontiguousarray(halves, np.float32)
+    g = np.ascontiguousarray(guides, np.float32)
+    if hv.shape != gs or g.shape != gs:
+        raise ValueError("halves and guides must be %s" % (gs,))
+    o = np.empty(cs, np.float32)
+    v = np.empty((ctx.h, ctx.w), np.float32) if return_variance else None
+    _chk(ctx, L.trg_denoise_variance_host(ctx.h_ctx, hv.ctypes.data, g.ctypes.data, o.ctypes.data, v.ctypes.data if return_variance else None, C.byref(p)))
+    return (o, v) if return_variance else o
+
+
+def render_denoised_variance(ctx, frame_begin, spp, bounces, out=None, params=None, **kw):
+    """trg_render_denoised_variance: render_halves, guides of frame_begin, denoise_variance, on one stream."""
+    L = load()
+    p = make_var_params(params, **kw)
+    if out is not None and _is_tensor(out):
+        _chk(ctx, L.trg_render_denoised_variance(ctx.h_ctx, frame_begin, spp, bounces, _tensor_ptr(out, (ctx.h, ctx.w, 4), "out"), C.byref(p)))
+        return out
+    o = np.empty((ctx.h, ctx.w, 4), np.float32)
+    _chk(ctx, L.trg_render_denoised_variance_read(ctx.h_ctx, frame_begin, spp, bounces, o.ctypes.data, C.byref(p)))
+    return o
+
+
 def release(ctx):
     if getattr(ctx, "h_ctx", None):
         _chk(ctx, load().trg_denoise_release(ctx.h_ctx))
@@ -194,20 +282,34 @@ def atrous_weights(I, g0, spacing, sigma_color, sigma_normal, sigma_depth):
             l, ins = _shift(lum, dx, dy)
             s2 += np.where(ins, (l - mean) ** 2, 0.0)
     var = s2 / cnt
-    grad = _depth_gradient(z)
-    W = np.zeros((5, 5, h, w))
+    W = geometry_weights(g0, spacing, sigma_normal, sigma_depth)
     for dy in range(-2, 3):
         for dx in range(-2, 3):
-            Iq, ins = _shift(I, dx * spacing, dy * spacing)
-            gq, _ = _shift(g0, dx * spacing, dy * spacing, -1.0)
+            Iq, _ = _shift(I, dx * spacing, dy * spacing)
+            with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+                wc = np.exp(-((I - Iq) ** 2).sum(-1) / (sigma_color ** 2 * (var + 1e-4)))
+            W[dy + 2, dx + 2] = np.where(W[dy + 2, dx + 2] > 0, W[dy + 2, dx + 2] * wc, 0.0)
+    return W
+
+
+def geometry_weights(g0, spacing, sigma_normal, sigma_depth, kernel=B3):
+    """k(dx) k(dy) * w_n * w_z * w_id of the header for the (2r+1)^2 taps at `spacing`, r = len(kernel) // 2: [dy + r, dx + r, y, x]; zero for
+    skipped taps (outside the image, a miss, n_p . n_q <= 0); rows of miss pixels are meaningless."""
+    h, w = g0.shape[:2]
+    n, z = g0[..., :3], g0[..., 3]
+    r = len(kernel) // 2
+    grad = _depth_gradient(z)
+    W = np.zeros((2 * r + 1, 2 * r + 1, h, w))
+    for dy in range(-r, r + 1):
+        for dx in range(-r, r + 1):
+            gq, ins = _shift(g0, dx * spacing, dy * spacing, -1.0)
             nq, zq = gq[..., :3], gq[..., 3]
             dn = (n * nq).sum(-1)
             ok = ins & (zq >= 0) & (dn > 0)
             with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
                 wn = np.where(dn > 0, np.abs(dn), 1.0) ** sigma_normal
                 wz = np.exp(-np.abs(z - zq) / (sigma_depth * (grad * spacing * np.sqrt(dx * dx + dy * dy) + 1e-6)))
-                wc = np.exp(-((I - Iq) ** 2).sum(-1) / (sigma_color ** 2 * (var + 1e-4)))
-            W[dy + 2, dx + 2] = np.where(ok, B3[dx + 2] * B3[dy + 2] * wn * wz * wc, 0.0)
+            W[dy + r, dx + r] = np.where(ok, kernel[dx + r] * kernel[dy + r] * wn * wz, 0.0)
     return W
 
 
@@ -261,3 +363,78 @@ def reference_denoise(color, g0, g1, params=None, material_ids=None, **kw):
         I = np.where(miss[..., None], I, I * alb)
     out[..., :3] = I
     return out
+
+
+def reference_denoise_variance(h1, h2, g0, g1, params=None, material_ids=None, return_variance=False, **kw):
+    """float64 evaluation of trg_denoise_variance's definition.  h1, h2 [h, w, 4] the half buffers, g0 / g1 [h, w, 4] (float32 as the device sees
+    them); params: a VarParams, a dict or keywords over the header's defaults (no library needed); material_ids: those of the context's scene
+    (None: no scene, no emitters).  Returns [h, w, 4] float64 (and V_N [h, w] with return_variance)."""
+    q = dict(_VAR_DEFAULTS)
+    if isinstance(params, VarParams):
+        params = {f: getattr(params, f) for f, _ in VarParams._fields_}
+    q.update(params or {}); q.update(kw)
+    it = int(q["iterations"])
+    if not 0 <= it <= MAX_ITERATIONS:
+        raise ValueError("iterations must be 0..%d" % MAX_ITERATIONS)
+    h1, h2 = np.asarray(h1).astype(np.float64), np.asarray(h2).astype(np.float64)
+    out = np.empty_like(h1)
+    out[..., 3] = h1[..., 3]
+    sl, sn, sd = (float(np.float32(q[k])) for k in ("sigma_lum", "sigma_normal", "sigma_depth"))
+    g0 = np.asarray(g0, np.float32).astype(np.float64)
+    if material_ids is not None:
+        g0[emitter_mask(g1, material_ids), 3] = -1.0
+    alb = np.maximum(np.asarray(g1, np.float32)[..., :3].astype(np.float64), float(np.float32(1e-3)))
+    miss = g0[..., 3] < 0
+    demod = bool(q["demodulate"])
+    luma = np.array(LUMA)
+    d1 = np.where(miss[..., None], h1[..., :3], h1[..., :3] / alb) if demod else h1[..., :3]
+    d2 = np.where(miss[..., None], h2[..., :3], h2[..., :3] / alb) if demod else h2[..., :3]
+    I = 0.5 * (d1 + d2)
+    V = np.where(miss, 0.0, 0.25 * (d1 @ luma - d2 @ luma) ** 2)
+
+    def gather(W, a, spacing):
+        r = W.shape[0] // 2
+        acc = np.zeros_like(a)
+        for dy in range(-r, r + 1):
+            for dx in range(-r, r + 1):
+                aq, _ = _shift(a, dx * spacing, dy * spacing)
+                acc += (W[dy + r, dx + r][..., None] if a.ndim == 3 else W[dy + r, dx + r]) * aq
+        return acc
+
+    if q["prefilter"]:
+        G = geometry_weights(g0, 1, sn, sd, kernel=(1.0,) * 7)
+        gs = G.sum((0, 1))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            V = np.where(miss | ~(gs > 0), V, gather(G, V, 1) / gs)
+    if it == 0:
+        out[..., :3] = 0.5 * (h1[..., :3] + h2[..., :3])
+        return (out, V) if return_variance else out
+    binom = np.array([0.25, 0.5, 0.25])
+    valid = (~miss).astype(np.float64)
+    for i in range(it):
+        s = 1 << i
+        bs, vs = np.zeros_like(V), np.zeros_like(V)
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                vq, _ = _shift(V * valid, dx, dy)
+                mq, _ = _shift(valid, dx, dy)
+                vs += binom[dx + 1] * binom[dy + 1] * vq
+                bs += binom[dx + 1] * binom[dy + 1] * mq
+        with np.errstate(invalid="ignore", divide="ignore"):
+            gv = np.where(bs > 0, vs / bs, 0.0)
+        den = sl * np.sqrt(np.maximum(0.0, gv)) + float(np.float32(1e-3))
+        lum = I @ luma
+        W = geometry_weights(g0, s, sn, sd)
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                lq, _ = _shift(lum, dx * s, dy * s)
+                W[dy + 2, dx + 2] = W[dy + 2, dx + 2] * np.exp(-np.abs(lum - lq) / den)
+        wsum = W.sum((0, 1))
+        keep = miss | ~(wsum > 0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            I = np.where(keep[..., None], I, gather(W, I, s) / wsum[..., None])
+            V = np.where(keep, V, gather(W * W, V, s) / wsum ** 2)
+    if demod:
+        I = np.where(miss[..., None], I, I * alb)
+    out[..., :3] = I
+    return (out, V) if return_variance else out
