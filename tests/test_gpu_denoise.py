@@ -66,7 +66,41 @@ def _reference_guides(O, scene, b, w, h, frame, uniforms=None, offsets=None, tex
     return rays, prim.reshape(h, w), dist.reshape(h, w), nrm.reshape(h, w, 3), alb.reshape(h, w, 3)
 
 
-def _check_guides(g, ref, strict, undecidable=None):
+GRAZING_COS = 0.02
+
+
+def _grazing(b, ref):
+    """[h, w]: first hits that meet their triangle at under GRAZING_COS of cosine (|n . d| < 0.02: within 1.15 degrees of its plane).
+    Any fp32 ray / plane distance divides by n . d, which carries at least its own rounding, 1 u = 2^-24 for unit vectors: u / cos of t.
+    test_intersector's distance rule is 3e-6 = 50 u, so under cos = 1 / 50 ONE rounding of the denominator is more than the whole bar, for
+    the shipped plane form and for the oracle's fp32 Moeller-Trumbore alike (measured: NOTEBOOK.md, "grazing hits").  Such a pixel is one
+    that fp32 cannot decide, like a margin below 1e-5: the guide tests count it among the undecidable ones, under the same cap."""
+    rays, prim = ref[0], ref[1]
+    hit = (prim >= 0).reshape(-1)
+    pos = np.asarray(b["positions"], np.float64).reshape(-1, 3)
+    T = pos[np.asarray(b["indices"]).reshape(-1)].reshape(-1, 3, 3)[np.where(hit, prim.reshape(-1), 0)]
+    n = np.cross(T[:, 1] - T[:, 0], T[:, 2] - T[:, 0])
+    d = rays["direction"].astype(np.float64)
+    cos = np.abs((n * d).sum(1)) / np.maximum(np.linalg.norm(n, axis=1) * np.linalg.norm(d, axis=1), 1e-300)
+    return (hit & (cos < GRAZING_COS)).reshape(prim.shape)
+
+
+def _shipped_attr_bars(b, prim):
+    """Per pixel and channel, what the SHIPPED build's interpolated normal and albedo may differ from the oracle's by where the primitive agrees:
+    its barycentrics are allowed 2e-5 each by test_intersector, and value = A2 + c0 (A0 - A2) + c1 (A1 - A2), so
+    1e-6 + 2e-5 (|A0 - A2| + |A1 - A2|) of that primitive's corner values; 1e-6 alone for the albedo of an emitter, which is (1, 1, 1)."""
+    p = np.where(prim >= 0, prim, 0)
+
+    def bar(attr):
+        a = np.asarray(attr, np.float64).reshape(-1, 3, 3)[p]
+        return 1e-6 + 2e-5 * (np.abs(a[..., 0, :] - a[..., 2, :]) + np.abs(a[..., 1, :] - a[..., 2, :]))
+    nb, ab = bar(b["normals"]), bar(b["colors"])
+    ab[np.asarray(b["material_ids"])[p] == 2] = 1e-6
+    return nb, ab
+
+
+def _check_guides(g, ref, strict, undecidable=None, attr_bars=None):
+    """attr_bars: (normal, albedo) bars [h, w, 3] in place of the flat 1e-6 -- for the shipped setting on triangles whose corners differ."""
     _, prim, dist, nrm, alb = ref
     got_prim = np.ascontiguousarray(g[1, ..., 3]).view(np.int32)
     ok = np.ones(prim.shape, bool) if strict else ~undecidable.reshape(prim.shape)
@@ -79,8 +113,13 @@ def _check_guides(g, ref, strict, undecidable=None):
         np.testing.assert_allclose(g[0, ..., 3][same], dist[same], rtol=3e-6, atol=3e-6)
     miss = got_prim < 0
     assert np.array_equal(miss[ok], (prim < 0)[ok]) and (g[0, ..., 3][miss] < 0).all()
-    assert np.abs(g[0, ..., :3][same] - nrm[same]).max() <= 1e-6
-    assert np.abs(g[1, ..., :3][same] - alb[same]).max() <= 1e-6
+    if attr_bars is None:
+        assert np.abs(g[0, ..., :3][same] - nrm[same]).max() <= 1e-6, "guide normals differ"
+        assert np.abs(g[1, ..., :3][same] - alb[same]).max() <= 1e-6, "guide albedo differs"
+    else:
+        assert not strict
+        assert (np.abs(g[0, ..., :3][same] - nrm[same]) <= attr_bars[0][same]).all(), "guide normals differ"
+        assert (np.abs(g[1, ..., :3][same] - alb[same]) <= attr_bars[1][same]).all(), "guide albedo differs"
     return miss
 
 
@@ -192,6 +231,51 @@ def _synthetic(w, h, seed):
     ids[miss] = -1
     g1[..., 3] = ids.view(f32)
     return color, g0, g1
+
+
+def _smooth(w, h, seed, blocks=True):
+    """What _synthetic leaves out: a slowly turning normal field whose per-pixel length is in [0.97, 1] (interpolated normals are shorter than 1:
+    n_p . n_q is near 1 and hardly ever equal to it; |n|^256 >= 4e-4 keeps the weight of the centre tap, and with it every weight sum, far from
+    fp32 underflow); a curved depth with one step; a flat region facing the camera whose depth gradient is exactly 0; albedo uniform in [0, 1]
+    with about 10 % of the pixels at exactly 0, so that the 1e-3 clamp of demodulation and remodulation acts; colour = noise in [0, 4] x the
+    clamped albedo; a block of misses and a block of first-hit emitters like _synthetic's, shrunk with the image so that small images keep
+    pixels to filter.  At 1 x 1 that one pixel is still a miss (in _synthetic too, which at 5 x 3 leaves only column 0 as hits);
+    blocks=False leaves both blocks out: every pixel is a hit that the filter works on (_smooth_hits: the 1 x 1 image whose pixel is one)."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w]
+    a = 0.25 + 0.011 * xx + 0.004 * yy                                      # polar angle: about 0.6 rad across 48 pixels
+    b = 0.5 + 0.013 * yy - 0.006 * xx
+    n = np.stack([np.sin(a) * np.cos(b), np.sin(a) * np.sin(b), np.cos(a)], -1)
+    z = 2.0 + 0.02 * xx + 0.0015 * (yy - 0.5 * h) ** 2 + np.where(xx >= 0.6 * w, 0.4, 0.0)
+    flat = (xx < 0.4 * w) & (yy >= 0.65 * h)
+    n[flat] = (0.0, 0.0, 1.0)
+    z[flat] = 3.0
+    g0 = np.zeros((h, w, 4), f32)
+    g1 = np.zeros((h, w, 4), f32)
+    g0[..., :3] = (n * rng.uniform(0.97, 1.0, (h, w, 1))).astype(f32)
+    g0[..., 3] = z.astype(f32)
+    alb = rng.uniform(0.0, 1.0, (h, w, 3))
+    alb[rng.uniform(0.0, 1.0, (h, w)) < 0.1] = 0.0
+    g1[..., :3] = alb.astype(f32)
+    color = np.empty((h, w, 4), f32)
+    color[..., :3] = (rng.uniform(0.0, 4.0, (h, w, 3)).astype(f32) * np.maximum(g1[..., :3], f32(1e-3))).astype(f32)
+    color[..., 3] = rng.uniform(0.0, 1.0, (h, w)).astype(f32)
+    ids = np.where(xx < 0.5 * w, 3, 100000).astype(np.int32)                  # a primitive of the Cornell box, and one beyond it
+    ids[(xx >= w - min(9, w // 3)) & (yy >= h - min(6, h // 3))] = 35         # first hit = the box's light
+    miss = (xx >= w // 3) & (xx < w // 3 + min(7, (w + 1) // 2)) & (yy >= h // 4) & (yy < h // 4 + min(6, (h + 1) // 2))
+    if not blocks:
+        ids = np.where(xx < 0.5 * w, 3, 100000).astype(np.int32)
+        miss[:] = False
+    g0[miss] = (0.0, 0.0, 0.0, -1.0)
+    g1[miss, :3] = 0.0
+    ids[miss] = -1
+    g1[..., 3] = ids.view(f32)
+    return color, g0, g1
+
+
+def _smooth_hits(w, h, seed):
+    """_smooth without its blocks of misses and emitters."""
+    return _smooth(w, h, seed, blocks=False)
 
 
 _filter_refs = {}

@@ -130,14 +130,18 @@ def test_halves_leave_the_callers_accumulation_and_binding_alone(capi, dn, O, co
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- 2. filter
-def _synthetic_halves(w, h, seed=11):
-    """_synthetic's colour, guides, misses and emitter block; the halves are that colour with independent relative noise of up to 30 %, their
-    own alphas, and one pixel column where H1 == H2."""
-    color, g0, g1 = _synthetic(w, h, seed)
+def _synthetic_halves(w, h, seed=11, gen=_synthetic):
+    """_synthetic's (or another generator's) colour, guides, misses and emitter block; the halves are that colour with independent relative
+    noise of up to 30 %, their own alphas, and one pixel column where H1 == H2 (images narrower than six pixels: their last column; one
+    pixel wide: their last row instead; 1 x 1: none, its pixel keeps two different halves)."""
+    color, g0, g1 = gen(w, h, seed)
     rng = np.random.default_rng(seed + 1)
     h1 = (color * (1.0 + 0.3 * rng.uniform(-1.0, 1.0, (h, w, 4)))).astype(f32)
     h2 = (color * (1.0 + 0.3 * rng.uniform(-1.0, 1.0, (h, w, 4)))).astype(f32)
-    h2[:, 5] = h1[:, 5]
+    if w > 1:
+        h2[:, min(5, w - 1)] = h1[:, min(5, w - 1)]
+    elif h > 1:
+        h2[h - 1] = h1[h - 1]
     return np.stack([h1, h2]), g0, g1
 
 

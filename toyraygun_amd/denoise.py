@@ -242,6 +242,33 @@ def release(ctx):
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # float64 reference, written from the definition in include/trg_denoise.h
 # ---------------------------------------------------------------------------------------------------------------------------------------------
+# Every function below takes the working precision `dtype`: np.float64 (the default: THE reference) or np.float32, where every intermediate is
+# fp32, x ** sigma_normal is exp2(sigma_normal * log2 x) and exp(x) is exp2(x * log2 e) as the shipped build evaluates them -- a yardstick for
+# how far fp32 arithmetic alone moves a result (the bars of tests/test_gpu_denoise_shapes.py), never a test subject.
+_LOG2E = 1.4426950408889634
+
+
+def _exp(x, dtype):
+    return np.exp(x) if dtype is np.float64 else np.exp2(x * dtype(_LOG2E))
+
+
+def _pow(x, y, dtype):
+    return x ** y if dtype is np.float64 else np.exp2(dtype(y) * np.log2(x))
+
+
+def _lum(I, dtype):
+    if dtype is np.float64:
+        return I @ np.array(LUMA)
+    return (dtype(LUMA[0]) * I[..., 0] + dtype(LUMA[1]) * I[..., 1]) + dtype(LUMA[2]) * I[..., 2]
+
+
+def _dtype(dtype):
+    dtype = np.dtype(dtype).type
+    if dtype not in (np.float64, np.float32):
+        raise ValueError("dtype must be np.float64 or np.float32")
+    return dtype
+
+
 def _shift(a, dx, dy, fill=0.0):
     """b[y, x] = a[y + dy, x + dx] where that lies inside, else fill; and the inside mask."""
     h, w = a.shape[:2]
@@ -264,51 +291,54 @@ def _depth_gradient(z):
     return np.sqrt(along(1, 0) ** 2 + along(0, 1) ** 2)
 
 
-def atrous_weights(I, g0, spacing, sigma_color, sigma_normal, sigma_depth):
-    """w[dy + 2, dx + 2, y, x] of one iteration on input I [h, w, 3] (float64); zero for skipped taps; rows of miss pixels are meaningless."""
+def atrous_weights(I, g0, spacing, sigma_color, sigma_normal, sigma_depth, dtype=np.float64):
+    """w[dy + 2, dx + 2, y, x] of one iteration on input I [h, w, 3] (of `dtype`); zero for skipped taps; rows of miss pixels are meaningless."""
+    dtype = _dtype(dtype)
     h, w = I.shape[:2]
-    n, z = g0[..., :3], g0[..., 3]
-    lum = I @ np.array(LUMA)
-    cnt = np.zeros((h, w))
-    s1 = np.zeros((h, w))
+    lum = _lum(I, dtype)
+    cnt = np.zeros((h, w), dtype)
+    s1 = np.zeros((h, w), dtype)
     for dy in (-1, 0, 1):
         for dx in (-1, 0, 1):
             l, ins = _shift(lum, dx, dy)
             s1 += np.where(ins, l, 0.0); cnt += ins
     mean = s1 / cnt
-    s2 = np.zeros((h, w))
+    s2 = np.zeros((h, w), dtype)
     for dy in (-1, 0, 1):
         for dx in (-1, 0, 1):
             l, ins = _shift(lum, dx, dy)
             s2 += np.where(ins, (l - mean) ** 2, 0.0)
     var = s2 / cnt
-    W = geometry_weights(g0, spacing, sigma_normal, sigma_depth)
+    sc2 = sigma_color ** 2 if dtype is np.float64 else dtype(sigma_color) * dtype(sigma_color)
+    W = geometry_weights(g0, spacing, sigma_normal, sigma_depth, dtype=dtype)
     for dy in range(-2, 3):
         for dx in range(-2, 3):
             Iq, _ = _shift(I, dx * spacing, dy * spacing)
             with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-                wc = np.exp(-((I - Iq) ** 2).sum(-1) / (sigma_color ** 2 * (var + 1e-4)))
+                wc = _exp(-((I - Iq) ** 2).sum(-1) / (sc2 * (var + 1e-4)), dtype)
             W[dy + 2, dx + 2] = np.where(W[dy + 2, dx + 2] > 0, W[dy + 2, dx + 2] * wc, 0.0)
     return W
 
 
-def geometry_weights(g0, spacing, sigma_normal, sigma_depth, kernel=B3):
+def geometry_weights(g0, spacing, sigma_normal, sigma_depth, kernel=B3, dtype=np.float64):
     """k(dx) k(dy) * w_n * w_z * w_id of the header for the (2r+1)^2 taps at `spacing`, r = len(kernel) // 2: [dy + r, dx + r, y, x]; zero for
     skipped taps (outside the image, a miss, n_p . n_q <= 0); rows of miss pixels are meaningless."""
+    dtype = _dtype(dtype)
     h, w = g0.shape[:2]
     n, z = g0[..., :3], g0[..., 3]
     r = len(kernel) // 2
     grad = _depth_gradient(z)
-    W = np.zeros((2 * r + 1, 2 * r + 1, h, w))
+    W = np.zeros((2 * r + 1, 2 * r + 1, h, w), dtype)
     for dy in range(-r, r + 1):
         for dx in range(-r, r + 1):
             gq, ins = _shift(g0, dx * spacing, dy * spacing, -1.0)
             nq, zq = gq[..., :3], gq[..., 3]
             dn = (n * nq).sum(-1)
             ok = ins & (zq >= 0) & (dn > 0)
+            dist = dtype(np.sqrt(dtype(dx * dx + dy * dy)))
             with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-                wn = np.where(dn > 0, np.abs(dn), 1.0) ** sigma_normal
-                wz = np.exp(-np.abs(z - zq) / (sigma_depth * (grad * spacing * np.sqrt(dx * dx + dy * dy) + 1e-6)))
+                wn = _pow(np.where(dn > 0, np.abs(dn), 1.0), sigma_normal, dtype)
+                wz = _exp(-np.abs(z - zq) / (sigma_depth * (grad * spacing * dist + 1e-6)), dtype)
             W[dy + r, dx + r] = np.where(ok, kernel[dx + r] * kernel[dy + r] * wn * wz, 0.0)
     return W
 
@@ -321,10 +351,11 @@ def emitter_mask(g1, material_ids):
     return inside & (mats[np.where(inside, prim, 0)] == 2)
 
 
-def reference_denoise(color, g0, g1, params=None, material_ids=None, **kw):
+def reference_denoise(color, g0, g1, params=None, material_ids=None, dtype=np.float64, **kw):
     """float64 evaluation of trg_denoise's definition.  color [h, w, 4], g0 / g1 [h, w, 4] (float32 as the device sees them); params: a Params,
     a dict or keywords; the defaults are the header's (no library needed); material_ids: those of the context's scene (None: no scene, no
-    emitters).  Returns [h, w, 4] float64."""
+    emitters); dtype: the working precision (see above).  Returns [h, w, 4] of `dtype`."""
+    dtype = _dtype(dtype)
     q = dict(iterations=5, sigma_color=4.0, sigma_normal=128.0, sigma_depth=1.0, demodulate=1)
     if isinstance(params, Params):
         params = {f: getattr(params, f) for f, _ in Params._fields_}
@@ -333,15 +364,15 @@ def reference_denoise(color, g0, g1, params=None, material_ids=None, **kw):
     if not 0 <= it <= MAX_ITERATIONS:
         raise ValueError("iterations must be 0..%d" % MAX_ITERATIONS)
     color = np.asarray(color)
-    out = color.astype(np.float64)
+    out = color.astype(dtype)
     if it == 0:
         return out
     # the parameters as the device holds them: fp32
     sc, sn, sd = (float(np.float32(q[k])) for k in ("sigma_color", "sigma_normal", "sigma_depth"))
-    g0 = np.asarray(g0, np.float32).astype(np.float64)
+    g0 = np.asarray(g0, np.float32).astype(dtype)
     if material_ids is not None:                       # a directly seen emitter is kept out of the filter like a miss
         g0[emitter_mask(g1, material_ids), 3] = -1.0
-    alb = np.maximum(np.asarray(g1, np.float32)[..., :3].astype(np.float64), float(np.float32(1e-3)))
+    alb = np.maximum(np.asarray(g1, np.float32)[..., :3].astype(dtype), float(np.float32(1e-3)))
     miss = g0[..., 3] < 0
     I = out[..., :3].copy()
     demod = bool(q["demodulate"])
@@ -349,7 +380,7 @@ def reference_denoise(color, g0, g1, params=None, material_ids=None, **kw):
         I = np.where(miss[..., None], I, I / alb)
     for i in range(it):
         s = 1 << i
-        W = atrous_weights(I, g0, s, sc, sn, sd)
+        W = atrous_weights(I, g0, s, sc, sn, sd, dtype=dtype)
         acc = np.zeros_like(I)
         for dy in range(-2, 3):
             for dx in range(-2, 3):
@@ -365,10 +396,11 @@ def reference_denoise(color, g0, g1, params=None, material_ids=None, **kw):
     return out
 
 
-def reference_denoise_variance(h1, h2, g0, g1, params=None, material_ids=None, return_variance=False, **kw):
+def reference_denoise_variance(h1, h2, g0, g1, params=None, material_ids=None, return_variance=False, dtype=np.float64, **kw):
     """float64 evaluation of trg_denoise_variance's definition.  h1, h2 [h, w, 4] the half buffers, g0 / g1 [h, w, 4] (float32 as the device sees
     them); params: a VarParams, a dict or keywords over the header's defaults (no library needed); material_ids: those of the context's scene
-    (None: no scene, no emitters).  Returns [h, w, 4] float64 (and V_N [h, w] with return_variance)."""
+    (None: no scene, no emitters); dtype: the working precision (see above).  Returns [h, w, 4] of `dtype` (and V_N [h, w] with return_variance)."""
+    dtype = _dtype(dtype)
     q = dict(_VAR_DEFAULTS)
     if isinstance(params, VarParams):
         params = {f: getattr(params, f) for f, _ in VarParams._fields_}
@@ -376,21 +408,20 @@ def reference_denoise_variance(h1, h2, g0, g1, params=None, material_ids=None, r
     it = int(q["iterations"])
     if not 0 <= it <= MAX_ITERATIONS:
         raise ValueError("iterations must be 0..%d" % MAX_ITERATIONS)
-    h1, h2 = np.asarray(h1).astype(np.float64), np.asarray(h2).astype(np.float64)
+    h1, h2 = np.asarray(h1).astype(dtype), np.asarray(h2).astype(dtype)
     out = np.empty_like(h1)
     out[..., 3] = h1[..., 3]
     sl, sn, sd = (float(np.float32(q[k])) for k in ("sigma_lum", "sigma_normal", "sigma_depth"))
-    g0 = np.asarray(g0, np.float32).astype(np.float64)
+    g0 = np.asarray(g0, np.float32).astype(dtype)
     if material_ids is not None:
         g0[emitter_mask(g1, material_ids), 3] = -1.0
-    alb = np.maximum(np.asarray(g1, np.float32)[..., :3].astype(np.float64), float(np.float32(1e-3)))
+    alb = np.maximum(np.asarray(g1, np.float32)[..., :3].astype(dtype), float(np.float32(1e-3)))
     miss = g0[..., 3] < 0
     demod = bool(q["demodulate"])
-    luma = np.array(LUMA)
     d1 = np.where(miss[..., None], h1[..., :3], h1[..., :3] / alb) if demod else h1[..., :3]
     d2 = np.where(miss[..., None], h2[..., :3], h2[..., :3] / alb) if demod else h2[..., :3]
     I = 0.5 * (d1 + d2)
-    V = np.where(miss, 0.0, 0.25 * (d1 @ luma - d2 @ luma) ** 2)
+    V = np.where(miss, 0.0, 0.25 * (_lum(d1, dtype) - _lum(d2, dtype)) ** 2)
 
     def gather(W, a, spacing):
         r = W.shape[0] // 2
@@ -402,15 +433,15 @@ def reference_denoise_variance(h1, h2, g0, g1, params=None, material_ids=None, r
         return acc
 
     if q["prefilter"]:
-        G = geometry_weights(g0, 1, sn, sd, kernel=(1.0,) * 7)
+        G = geometry_weights(g0, 1, sn, sd, kernel=(1.0,) * 7, dtype=dtype)
         gs = G.sum((0, 1))
         with np.errstate(invalid="ignore", divide="ignore"):
             V = np.where(miss | ~(gs > 0), V, gather(G, V, 1) / gs)
     if it == 0:
         out[..., :3] = 0.5 * (h1[..., :3] + h2[..., :3])
         return (out, V) if return_variance else out
-    binom = np.array([0.25, 0.5, 0.25])
-    valid = (~miss).astype(np.float64)
+    binom = (0.25, 0.5, 0.25)
+    valid = (~miss).astype(dtype)
     for i in range(it):
         s = 1 << i
         bs, vs = np.zeros_like(V), np.zeros_like(V)
@@ -423,12 +454,12 @@ def reference_denoise_variance(h1, h2, g0, g1, params=None, material_ids=None, r
         with np.errstate(invalid="ignore", divide="ignore"):
             gv = np.where(bs > 0, vs / bs, 0.0)
         den = sl * np.sqrt(np.maximum(0.0, gv)) + float(np.float32(1e-3))
-        lum = I @ luma
-        W = geometry_weights(g0, s, sn, sd)
+        lum = _lum(I, dtype)
+        W = geometry_weights(g0, s, sn, sd, dtype=dtype)
         for dy in range(-2, 3):
             for dx in range(-2, 3):
                 lq, _ = _shift(lum, dx * s, dy * s)
-                W[dy + 2, dx + 2] = W[dy + 2, dx + 2] * np.exp(-np.abs(lum - lq) / den)
+                W[dy + 2, dx + 2] = W[dy + 2, dx + 2] * _exp(-np.abs(lum - lq) / den, dtype)
         wsum = W.sum((0, 1))
         keep = miss | ~(wsum > 0)
         with np.errstate(invalid="ignore", divide="ignore"):
