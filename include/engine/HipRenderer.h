@@ -58,9 +58,14 @@ public:
     //      varianceGuided: savePNG instead renders the frames so far AGAIN as two independent halves (trg_render_denoised_variance; one more
     //      frame when their number is odd, and it says so) and filters their mean, guided by the halves' difference; the accumulation buffer is
     //      not touched, the ray count includes the second rendering.
-    bool setDenoise(int iterations, bool varianceGuided = false);
+    //      temporal (not together with varianceGuided; one device only -- false with a device group or after setDevices()): every renderFrame() / renderFrames() batch is a step of
+    //      trg_render_temporal_own -- rendered into an image of the denoise state, blended with the history reprojected from the previous
+    //      batches' camera, filtered with the temporal variance -- and savePNG writes the last step's output.  The accumulation buffer is not
+    //      written in this mode (readAccumulation returns what it held before), batches are never coalesced, and loadScene() forgets the history.
+    bool setDenoise(int iterations, bool varianceGuided = false, bool temporal = false);
     int getDenoise() const { return m_denoise; }
     bool getDenoiseVarianceGuided() const { return m_denoiseVar; }
+    bool getDenoiseTemporal() const { return m_denoiseTemporal; }
     int getFrameIndex() const { return m_frameIndex; }
     double getLastRenderMs() const;
     uint64_t getRayCount() const;                       // primary + bounce + shadow rays traced so far
@@ -84,6 +89,8 @@ protected:
     unsigned int m_launches;
     int m_denoise;               // a-trous iterations of the image handed to post-processing; 0 = off
     bool m_denoiseVar;           // ... by the variance-guided filter from two half-sample buffers
+    bool m_denoiseTemporal;      // ... or every batch a temporal step (trg_render_temporal_own)
+    void *m_temporalOut;         // the last temporal step's output image (owned by the denoise state); null before the first
 };
 
 }  // namespace toyraygun

@@ -7,7 +7,7 @@
  * stream (trg_set_stream) and nothing waits for the device, unless a function says so.
  *
  * STATE.  The first call allocates per-context scratch (primary rays and hit records of the guide pass, two ping-pong images of the filter;
- * the half-sample images of the variance-guided path on its first use); it is grow-only and lives until trg_denoise_release(ctx).  trg_destroy does NOT know about it: call trg_denoise_release BEFORE trg_destroy.
+ * the half-sample images of the variance-guided path and the history planes of the temporal path on their first use); it is grow-only and lives until trg_denoise_release(ctx).  trg_destroy does NOT know about it: call trg_denoise_release BEFORE trg_destroy.
  */
 #ifndef TRG_DENOISE_H
 #define TRG_DENOISE_H
@@ -164,6 +164,118 @@ TRG_API int trg_render_denoised_variance_own(trg_ctx *ctx, uint32_t frameIndexBe
 TRG_API int trg_render_halves_read(trg_ctx *ctx, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *halves_host);
 TRG_API int trg_denoise_variance_host(trg_ctx *ctx, const float *halves_host, const float *guides_host, float *out_host, float *var_host, const trg_denoise_var_params *p);
 TRG_API int trg_render_denoised_variance_read(trg_ctx *ctx, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_denoise_var_params *p);
+
+/* =============================================================================================================================================
+ * TEMPORAL REPROJECTION AND ACCUMULATION (the other half of SVGF).  The result of the previous calls is reprojected through the guides into the
+ * current frame, colour and the first two moments of luminance are accumulated over time, and the variance-guided iterations above are handed a
+ * TEMPORAL variance: no second render, and a moving camera no longer starts from one sample per pixel.
+ * ============================================================================================================================================= */
+
+/* --- WORLD POSITIONS.  What trg_guides_render does (the same G0, G1, bit for bit), and one more plane X of width*height float4:
+ *       X(p) = (o + z * d, 0)    o, d = origin and direction of the pixel's primary ray of that frame index (trg_raygen), z = G0(p).w;
+ *                                per component one fp32 multiply and one fp32 add, not contracted
+ *       X(p) = (0, 0, 0, 0)      on a miss */
+TRG_API int trg_guides_render_pos(trg_ctx *ctx, uint32_t frameIndex, void *guides_device, void *pos_device);
+
+/* --- THE CAMERA OF A FRAME, for the call that comes after it.  Host only; touches no context.  u->inv_view_proj is read as the matrix A with
+ *     A[j][k] = m[j*4 + k] -- the way trg_raygen multiplies it: world_j = sum_k A[j][k] ndc_k.  vp16 = the inverse of A in the same layout,
+ *     inverted in double precision and rounded to fp32; TRG_ERR_INVALID when A is singular or not finite (or a pointer is NULL).
+ *     With clip_j = sum_k vp16[j*4 + k] (X, 1)_k a world point X lands at
+ *       sx = (clip.x / clip.w * 0.5 + 0.5) * width,  sy = (clip.y / clip.w * 0.5 + 0.5) * height
+ *     where pixel (x, y) has its centre at (x + 0.5, y + 0.5); row 0 is the bottom, nothing flips. */
+TRG_API int trg_temporal_view_proj(const trg_uniforms *u, float vp16[16]);
+
+typedef struct trg_temporal_params {
+    int32_t iterations;   /* 0 .. TRG_DENOISE_MAX_ITERATIONS; default 5 */
+    float sigma_lum;      /* default 4.0 */
+    float sigma_normal;   /* default 128 */
+    float sigma_depth;    /* default 1.0 */
+    int32_t demodulate;   /* default 1 */
+    float alpha;          /* in (0, 1]; default 0.2: the least weight of the new colour sample */
+    float alpha_moments;  /* in (0, 1]; default 0.2: the same for the two moments */
+    float plane_tol;      /* > 0; default 0.02: a tap's distance from the pixel's tangent plane, as a fraction of the hit distance */
+    float normal_tol;     /* in [-1, 1]; default 0.9: the least cosine between the pixel's and a tap's normal */
+    int32_t max_history;  /* >= 1; default 32: where the history length N stops growing */
+} trg_temporal_params;
+TRG_API void trg_temporal_default_params(trg_temporal_params *p);
+
+/* --- HISTORY.  Four planes of width*height float4 per pixel, owned by the state (allocated on the first call, double-buffered, freed by
+ *     trg_denoise_release):
+ *       Hc = (I.rgb, N)      the accumulated (demodulated) colour and the history length
+ *       Hm = (m1, m2, 0, 0)  the accumulated first and second moment of L(D)
+ *       F  = the filter's G0 of that frame (normal | z), emitters marked as misses (z = -1)
+ *       X  = the world positions of that frame
+ *     A new state has no history, and trg_temporal_reset forgets it (and the view-projection trg_render_temporal remembered;
+ *     it allocates nothing: harmless for a context that never denoised).
+ *     THE LIBRARY DOES NOT NOTICE A CHANGED SCENE: after trg_load_scene or trg_load_textures the caller calls trg_temporal_reset.
+ *     trg_temporal_history_read: Hc then Hm of the last call into 2 * width*height*4 floats; it WAITS for the result (TRG_ERR_INVALID while
+ *     there is no history). */
+TRG_API int trg_temporal_reset(trg_ctx *ctx);
+TRG_API int trg_temporal_history_read(trg_ctx *ctx, float *hist_host);
+
+/* --- ONE TEMPORAL STEP.  color_in_device, out_device: width*height float4; guides_device, pos_device: as trg_guides_render_pos writes them for
+ *     THIS frame; prev_view_proj: trg_temporal_view_proj of the uniforms the PREVIOUS call's frame was rendered with (read during the call).  No two
+ *     of the buffers may overlap and none may be NULL, else TRG_ERR_INVALID; so are parameters outside the ranges above -- refused before
+ *     anything is enqueued or the history changes.
+ *
+ *  Notation, misses and emitters: as for trg_denoise ("miss" means both).  A prime marks the previous call's history planes.  For a vector n,
+ *  nn(n) = n / sqrt(n.x^2 + n.y^2 + n.z^2); when that length is not > 0 every test n takes part in fails.  Sums of three products are formed
+ *  left to right.  D(p) = C(p).rgb / max(a_p, 1e-3) per channel when `demodulate` and p is not a miss, else C(p).rgb;  l = L(D(p)).
+ *
+ *   Miss.  out(p) = color_in(p) bit for bit; history I = C(p).rgb, N = 0, m1 = m2 = 0; V_0 = 0.
+ *   Reproject (p not a miss).  clip_j = vp[j*4] X(p).x + vp[j*4+1] X(p).y + vp[j*4+2] X(p).z + vp[j*4+3], left to right.
+ *          NO HISTORY when there is none in the state, or clip.w is not > 0, or with
+ *              fx = (clip.x / clip.w * 0.5 + 0.5) * width - 0.5,   fy = (clip.y / clip.w * 0.5 + 0.5) * height - 0.5
+ *          not (-1 <= fx < width and -1 <= fy < height) (all four taps would lie outside).  Otherwise x0 = floor(fx), y0 = floor(fy),
+ *          tx = fx - x0, ty = fy - y0, and the four taps q = (x0 + i, y0 + j), in the order (i, j) = (0,0), (1,0), (0,1), (1,1), have
+ *              b = (i ? tx : 1 - tx) * (j ? ty : 1 - ty)
+ *          A tap is VALID iff q is inside the image, F'(q).w >= 0,
+ *              | nn(n_p) . (X'(q) - X(p)) | <= plane_tol * z_p      and      nn(n_p) . nn(F'(q).xyz) >= normal_tol
+ *          W = sum of b over the valid taps.  W > 0: Ih, m1h, m2h, Nh = (sum of b * Hc'.rgb, Hm'.x, Hm'.y, Hc'.w over the valid taps) / W.
+ *          W not > 0: no history.
+ *   Accumulate.  No history: N = 1, I = D, m1 = l, m2 = l * l exactly.  Otherwise
+ *              N = min(Nh + 1, max_history),  a = max(alpha, 1 / N),  am = max(alpha_moments, 1 / N)
+ *              I = Ih + a (D - Ih),  m1 = m1h + am (l - m1h),  m2 = m2h + am (l * l - m2h)
+ *          (I, N) and (m1, m2) become the history together with this frame's F and X.  The history holds UNFILTERED values: SVGF's feedback of
+ *          the first filtered iteration is deliberately left out.
+ *   Variance.  N >= 4: V_0 = max(0, m2 - m1 * m1).
+ *          N < 4: with M1 = sum_q g m1(q) / sum_q g, M2 likewise with m2, over the 49 pixels q = p + (dx, dy), dx, dy in {-3 .. 3}, inside the
+ *          image (rows outer, columns inner), g = w_n * w_z * w_id at s = 1 exactly as in the prefilter of trg_denoise_variance, m1, m2 THIS
+ *          call's accumulated moments:  V_0 = max(0, M2 - M1 * M1) * 4 / N;  V_0 = 0 when the sum of g is not > 0.
+ *   Filter.  (I, V_0) goes through iterations i = 0 .. iterations-1 of trg_denoise_variance exactly as defined there (no prefilter).
+ *          out(p).rgb = I_N(p) * max(a_p, 1e-3) when `demodulate` and p is not a miss, else I_N(p);  out(p).a = color_in(p).a.
+ *          iterations == 0: out.rgb = I remodulated in that way.
+ *
+ *  Arithmetic: fp32 without contraction; TRG_OPT_STRICT 1 uses expf / powf / sqrtf, 0 the hardware's exp2 / log2 / sqrt; the divisions are
+ *  IEEE divisions in both.  The float64 reference: toyraygun_amd/denoise.py reference_temporal (+ reference_atrous_variance).
+ *
+ *  On the device: the emitter-marking launch of trg_denoise; ONE reprojection launch over 16 x 16 tiles of 256 threads, a pixel per thread: it
+ *  reads the four current planes coalesced as float4, gathers 4 taps x 4 history planes through L2 (the target is arbitrary: nothing to stage)
+ *  and writes the four new history planes and (I, V_0); ONE launch for the spatial estimate with a 22 x 22 halo of F and the moments in LDS,
+ *  which a tile without a pixel of N < 4 leaves after one ballot per wave, before staging anything; then the launches of the
+ *  variance-guided filter, unchanged. */
+TRG_API int trg_temporal_denoise(trg_ctx *ctx, const void *color_in_device, const void *guides_device, const void *pos_device, const float prev_view_proj[16],
+                                 void *out_device, const trg_temporal_params *p /* NULL: defaults */);
+
+/* --- RENDER + TEMPORAL STEP on one stream.  spp >= 1 and frameIndexBegin + spp <= 2^32 - 1.  With b = frameIndexBegin, n = spp:
+ *       1. a zeroed image of the state is bound, trg_render(b, n, bounces) runs over the whole image, the caller's binding is restored (the
+ *          bound accumulation buffer is neither read nor written, as in trg_render_halves); a real render: its rays count, `renders` goes up by one;
+ *       2. its rgb is multiplied by fl((b + n) / n) (the quotient in double precision, rounded to fp32): the mean of the samples;
+ *       3. trg_guides_render_pos(b) with the context's current uniforms into planes of the state;
+ *       4. trg_temporal_denoise against the view-projection the state remembered from its previous trg_render_temporal call; after a reset (or in
+ *          a new state) there is none and the step runs without history;
+ *       5. trg_temporal_view_proj of the current uniforms is remembered.
+ *     out_device must not overlap the bound accumulation buffer (TRG_ERR_INVALID).
+ *     _own: the result goes to the image the STATE owns (the one of trg_denoise_accum), for callers without device memory. */
+TRG_API int trg_render_temporal(trg_ctx *ctx, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, void *out_device, const trg_temporal_params *p);
+TRG_API int trg_render_temporal_own(trg_ctx *ctx, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, const trg_temporal_params *p, void **out_device);
+
+/* --- with HOST buffers; they WAIT for the result.  pos_host: width*height*4 floats.  iv_host (may be NULL): width*height*4 floats, (I.rgb, V_0);
+ *     var_host (may be NULL): width*height floats, V_N (V_0 when iterations == 0). */
+TRG_API int trg_guides_pos_read(trg_ctx *ctx, uint32_t frameIndex, float *guides_host, float *pos_host);
+TRG_API int trg_temporal_denoise_host(trg_ctx *ctx, const float *color_in_host, const float *guides_host, const float *pos_host, const float prev_view_proj[16],
+                                      float *out_host, float *iv_host, float *var_host, const trg_temporal_params *p);
+TRG_API int trg_render_temporal_read(trg_ctx *ctx, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_temporal_params *p);
 
 #ifdef __cplusplus
 }

@@ -1,8 +1,11 @@
-"""Device time of trg_guides_render, trg_denoise and the variance-guided path (trg_render_halves, trg_denoise_variance) on the Cornell box, HIP
-events on the context's stream:
+"""Device time of trg_guides_render, trg_denoise, the variance-guided path (trg_render_halves, trg_denoise_variance) and the temporal step
+(trg_guides_render_pos, trg_temporal_denoise) on the Cornell box, HIP events on the context's stream:
 python scripts/denoise_time.py [width height reps spp]   (default 1920 1080 20 16; one warm-up each).  Prints one JSON line with the medians in
 ms, next to the filter's compulsory traffic (per iteration 48 B read + 16 B written per pixel) at the measured time.  The launches of the
-variance-guided filter are taken as differences of runs that differ by one launch (prefilter on / off, N and N - 1 iterations)."""
+variance-guided filter are taken as differences of runs that differ by one launch (prefilter on / off, N and N - 1 iterations).  The temporal
+leg runs at rest (every tile of the spatial estimate leaves early once the history is four frames old) and with the eye turning 1 degree per
+call; `temporal_front_ms` = the emitter marking, the reprojection and the spatial-estimate launch (a step of 0 iterations minus its final
+copy is not separable here, so it is a step of 1 iteration minus one variance iteration of spacing 1)."""
 import json
 import os
 import sys
@@ -64,6 +67,51 @@ old = {it: timed(lambda: denoise.denoise(c, acc, g, out=out, iterations=it)) for
 res["denoise_iteration_ms"] = [old[1]] + [old[it] - old[it - 1] for it in range(2, 6)]
 res["compulsory_GB_5"] = 5 * 64 * w * h / 1e9
 res["compulsory_GBps_at_denoise_5"] = res["compulsory_GB_5"] / (res["denoise_5_ms"] * 1e-3)
+# the temporal step: guides with the position plane, then whole steps at rest and with a turning eye
+from oracle import pyoracle as O   # noqa: E402  (the uniforms of another eye; host.uniforms has the default camera only)
+x = torch.empty((h, w, 4), dtype=torch.float32, device="cuda")
+res["guides_pos_ms"] = timed(lambda: denoise.guides_pos(c, 0, out=g, pos=x))
+u_rest = O.make_uniforms(w, h)
+vp_rest = denoise.temporal_view_proj(u_rest)
+c.set_uniforms(O.uniforms_bytes(u_rest))
+denoise.guides_pos(c, 0, out=g, pos=x)
+denoise.temporal_reset(c)
+step = lambda vp, **kw: denoise.temporal_denoise(c, acc, g, x, vp, out=out, **kw)
+for _ in range(6):
+    step(vp_rest)
+res["temporal_5_rest_ms"] = timed(lambda: step(vp_rest))
+res["temporal_1_rest_ms"] = timed(lambda: step(vp_rest, iterations=1))
+res["temporal_front_rest_ms"] = res["temporal_1_rest_ms"] - res["variance_iteration_ms"][0]
+# moving: the history planes of the eye one degree back (one untimed step there), then steps at this eye against that camera
+t = np.deg2rad(1.0)
+u_back = O.make_uniforms(w, h, eye=(4.38 * np.sin(-t), 1.0, -1.0 + 4.38 * np.cos(-t)))
+vp_back = denoise.temporal_view_proj(u_back)
+
+
+def moving(**kw):
+    c.set_uniforms(O.uniforms_bytes(u_back))
+    g2, x2 = torch.empty_like(g), torch.empty_like(x)
+    denoise.guides_pos(c, 0, out=g2, pos=x2)
+    denoise.temporal_reset(c)
+    denoise.temporal_denoise(c, acc, g2, x2, None, out=out, **kw)     # N = 1 everywhere at the other eye
+    c.set_uniforms(O.uniforms_bytes(u_rest))
+    ms = []
+    for _ in range(reps):
+        # every timed step needs that history again: re-seed it untimed
+        if ms:
+            denoise.temporal_reset(c)
+            denoise.temporal_denoise(c, acc, g2, x2, None, out=out, **kw)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream); step(vp_back, **kw); e1.record(stream)
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return float(np.median(ms))
+
+
+res["temporal_5_moving_ms"] = moving()
+res["temporal_1_moving_ms"] = moving(iterations=1)
+res["temporal_front_moving_ms"] = res["temporal_1_moving_ms"] - res["variance_iteration_ms"][0]
+res["l2_iteration_ms"] = res["variance_iteration_ms"][2]
 print(json.dumps(res))
 c.bind_accum(None)
 c.set_stream(None)

@@ -15,7 +15,7 @@ namespace toyraygun {
 
 HipRenderer::HipRenderer()
     : m_ctx(nullptr), m_group(nullptr), m_deviceCount(0), m_bounces(3), m_deviceBuild(0), m_offsetSeed(0x5EED0001u), m_sceneLoaded(false), m_synchronous(false), m_pending(0), m_pendingFirst(0),
-      m_launches(0), m_denoise(0), m_denoiseVar(false) {
+      m_launches(0), m_denoise(0), m_denoiseVar(false), m_denoiseTemporal(false), m_temporalOut(nullptr) {
     memset(&m_pendingUniforms, 0, sizeof(m_pendingUniforms));
 }
 HipRenderer::~HipRenderer() { destroy(); }
@@ -72,6 +72,7 @@ void HipRenderer::destroy() {
     m_group = nullptr;
     m_ctx = nullptr;
     m_sceneLoaded = false;
+    m_temporalOut = nullptr;   // (it pointed into the denoise state)
 }
 
 void HipRenderer::loadScene(Scene *scene) {
@@ -97,6 +98,11 @@ void HipRenderer::loadScene(Scene *scene) {
         return;
     }
     m_sceneLoaded = true;
+    // the temporal history belongs to the old scene (the library does not notice a changed one)
+    if (m_denoiseTemporal) {
+        if (trg_temporal_reset(m_ctx) != TRG_OK) printf("HipRenderer: %s\n", trg_last_error(m_ctx));
+        m_temporalOut = nullptr;
+    }
     // albedo textures of the scene (Scene::addMesh with a Texture): expanded to RGBA8 and uploaded with the texture coordinates
     if (!scene->m_textures.empty() && nTris) {
         std::vector<float> uv(scene->m_uvBuffer);
@@ -167,6 +173,22 @@ bool HipRenderer::flush() {
         ++m_launches;
         return true;
     }
+    if (m_denoiseTemporal) {
+        // the batch as one temporal step: rendered into an image of the denoise state, reprojected history blended in, filtered; the
+        // accumulation buffer is not touched
+        trg_temporal_params tp;
+        trg_temporal_default_params(&tp);
+        tp.iterations = m_denoise;
+        if (trg_fence_wait(m_ctx, slot) != TRG_OK ||
+            trg_set_uniforms(m_ctx, reinterpret_cast<const trg_uniforms *>(&m_pendingUniforms)) != TRG_OK ||
+            trg_render_temporal_own(m_ctx, (uint32_t)m_pendingFirst, frames, m_bounces, &tp, &m_temporalOut) != TRG_OK ||
+            trg_fence_record(m_ctx, slot) != TRG_OK) {
+            printf("HipRenderer: %s\n", trg_last_error(m_ctx));
+            return false;
+        }
+        ++m_launches;
+        return true;
+    }
     if (trg_fence_wait(m_ctx, slot) != TRG_OK ||
         trg_set_uniforms(m_ctx, reinterpret_cast<const trg_uniforms *>(&m_pendingUniforms)) != TRG_OK ||
         trg_render(m_ctx, (uint32_t)m_pendingFirst, frames, m_bounces, 0, (uint32_t)m_height) != TRG_OK ||
@@ -191,7 +213,8 @@ bool HipRenderer::renderFrames(unsigned int frames) {
     m_frameIndex += (int)frames;
     // launch now if the device has nothing to do (or we are asked to be synchronous, or a lot has piled up); otherwise the
     // frames wait for the next call and share its launch
-    if (m_synchronous || frames > 1 || m_pending >= 64u || trg_stream_idle(m_ctx) != 0) return flush();
+    // (temporal mode: every call is a step of its own, whatever the device is doing -- how the frames are batched decides the picture)
+    if (m_synchronous || m_denoiseTemporal || frames > 1 || m_pending >= 64u || trg_stream_idle(m_ctx) != 0) return flush();
     return true;
 }
 
@@ -222,10 +245,18 @@ bool HipRenderer::readAccumulation(float *rgbaOut) {
     if (m_group) return trg_group_read_accum(m_group, 0, rgbaOut) == TRG_OK;   // waits for the gather onto device 0 (and the unpack of interleaved bands)
     return trg_read_accum(m_ctx, rgbaOut) == TRG_OK;
 }
-bool HipRenderer::setDenoise(int iterations, bool varianceGuided) {
-    if (iterations < 0 || iterations > TRG_DENOISE_MAX_ITERATIONS) return false;
+bool HipRenderer::setDenoise(int iterations, bool varianceGuided, bool temporal) {
+    if (iterations < 0 || iterations > TRG_DENOISE_MAX_ITERATIONS || (varianceGuided && temporal)) return false;
+    const bool on = temporal && iterations > 0;
+    if (on && (m_group || m_deviceCount >= 1)) return false;   // one device only: a device group (created, or asked for by setDevices) has no temporal mode
+    if (on != m_denoiseTemporal) {
+        flush();   // frames queued so far keep the mode they were queued in
+        if (m_ctx && trg_temporal_reset(m_ctx) != TRG_OK) printf("HipRenderer: %s\n", trg_last_error(m_ctx));
+        m_temporalOut = nullptr;
+    }
     m_denoise = iterations;
     m_denoiseVar = varianceGuided && iterations > 0;
+    m_denoiseTemporal = on;
     return true;
 }
 bool HipRenderer::savePNG(const char *path) {
@@ -239,7 +270,12 @@ bool HipRenderer::savePNG(const char *path) {
         dp.iterations = m_denoise;
         void *denoised = nullptr;
         int drc;
-        if (m_denoiseVar) {
+        if (m_denoiseTemporal) {
+            // the last temporal step's output is the picture
+            denoised = m_temporalOut;
+            drc = denoised ? TRG_OK : TRG_ERR_INVALID;
+            if (!denoised) { printf("HipRenderer: temporal denoising is on and no frame has been rendered\n"); return false; }
+        } else if (m_denoiseVar) {
             // the frames so far once more, as two independent halves whose difference guides the filter (the uniforms are those of the last launch)
             unsigned int n = m_frameIndex > 0 ? (unsigned int)m_frameIndex : 2u;
             if (n & 1u) {

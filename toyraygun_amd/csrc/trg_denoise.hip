@@ -1,5 +1,6 @@
 // trg_denoise.hip -- include/trg_denoise.h: first-hit guide buffers and the edge-avoiding a-trous filter.  A translation unit of its own beside
 // the render kernels: it launches the library's stage-level raygen / trace kernels (both builds) and adds a gather kernel and the filter.
+// Behind them the variance-guided form of the filter and the temporal reprojection / accumulation that feeds it.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -122,6 +123,14 @@ struct DenoiseState {
     // variance-guided path (allocated on its first use): the two zeroed images trg_render_halves renders into, and the half planes
     // trg_render_denoised_variance fills
     float4 *half_acc = nullptr, *halves = nullptr;
+    // temporal path (allocated on its first use): two sets of the four history planes Hc, Hm, F, X -- hist[hist_cur] is what the last call
+    // wrote, the next call writes the other --; the zeroed image, the position plane and the remembered view-projection of trg_render_temporal
+    float4 *hist[2] = { nullptr, nullptr };
+    int hist_cur = 0;
+    bool hist_valid = false;
+    float4 *timg = nullptr, *tpos = nullptr;
+    float prev_vp[16] = {};
+    bool have_prev_vp = false;
 };
 std::mutex g_mutex;
 std::unordered_map<trg_ctx *, DenoiseState> g_states;
@@ -130,6 +139,7 @@ void free_state(DenoiseState &s) {
     (void)hipFree(s.rays); (void)hipFree(s.isect); (void)hipFree(s.ping); (void)hipFree(s.pong); (void)hipFree(s.guides);
     (void)hipFree(s.rec_of_prim); (void)hipFree(s.overflow); (void)hipFree(s.result); (void)hipFree(s.fguide);
     (void)hipFree(s.half_acc); (void)hipFree(s.halves);
+    (void)hipFree(s.hist[0]); (void)hipFree(s.hist[1]); (void)hipFree(s.timg); (void)hipFree(s.tpos);
     s = DenoiseState{};
 }
 
@@ -189,8 +199,10 @@ __global__ void dn_record_map_kernel(const float4 *recs, uint32_t n_rec, uint32_
     if (prim < n_prims) rec_of_prim[prim] = r;
 }
 
+// POS: also the world-position plane X = (o + z d, 0) of trg_guides_render_pos, from the primary rays the hit records belong to (zero on a miss)
+template <bool POS>
 __global__ void dn_gather_kernel(const trg_isect *isect, const uint32_t *rec_of_prim, const float4 *recs, uint32_t n_prims, const TexDesc tex,
-                                 float4 *g0, float4 *g1, uint32_t n) {
+                                 float4 *g0, float4 *g1, uint32_t n, const trg_ray *rays, float4 *pos) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float4 is = reinterpret_cast<const float4 *>(isect)[i];   // distance, primitiveIndex, coordinates[2]
@@ -198,7 +210,13 @@ __global__ void dn_gather_kernel(const trg_isect *isect, const uint32_t *rec_of_
     if (!(is.x >= 0.0f) || prim < 0 || (uint32_t)prim >= n_prims) {
         g0[i] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
         g1[i] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+        if (POS) pos[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
+    }
+    if (POS) {
+        const float4 *r = reinterpret_cast<const float4 *>(rays) + (size_t)i * 3u;   // origin | mask, direction | maxDistance, colour
+        const float4 o = r[0], d = r[1];
+        pos[i] = make_float4(o.x + is.x * d.x, o.y + is.x * d.y, o.z + is.x * d.z, 0.0f);
     }
     const float4 *rec = recs + (size_t)rec_of_prim[prim] * 8u;
     const uint32_t mat = (uint32_t)__float_as_int(rec[1].w);
@@ -276,7 +294,8 @@ int record_map(trg_ctx *c, DenoiseState &s) {
     return TRG_OK;
 }
 
-int guides_render(trg_ctx *c, DenoiseState &s, uint32_t frameIndex, float4 *guides) {
+// pos (may be null): the world-position plane of trg_guides_render_pos
+int guides_render(trg_ctx *c, DenoiseState &s, uint32_t frameIndex, float4 *guides, float4 *pos = nullptr) {
     if (!c->scene_loaded) return fail(c, TRG_ERR_INVALID, "trg_guides_render: no scene loaded");
     if (!c->have_uniforms || !c->have_offsets) return fail(c, TRG_ERR_INVALID, "trg_guides_render: uniforms / pixel offsets not set");
     const size_t n = (size_t)c->w * c->h;
@@ -302,8 +321,12 @@ int guides_render(trg_ctx *c, DenoiseState &s, uint32_t frameIndex, float4 *guid
     if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_guides_render: trace launch failed: %s", hipGetErrorString(e));
     const float4 *recs = reinterpret_cast<const float4 *>(c->blob + sc.off_fat);
     if (int rc = record_map(c, s)) return rc;
-    hipLaunchKernelGGL(dn_gather_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, s.isect, s.rec_of_prim, recs, sc.n_tris, c->tex, guides,
-                       guides + n, (uint32_t)n);
+    if (pos)
+        hipLaunchKernelGGL(dn_gather_kernel<true>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, s.isect, s.rec_of_prim, recs, sc.n_tris, c->tex, guides,
+                           guides + n, (uint32_t)n, (const trg_ray *)s.rays, pos);
+    else
+        hipLaunchKernelGGL(dn_gather_kernel<false>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, s.isect, s.rec_of_prim, recs, sc.n_tris, c->tex, guides,
+                           guides + n, (uint32_t)n, (const trg_ray *)nullptr, (float4 *)nullptr);
     DN_HIPCHK(c, hipGetLastError());
     return TRG_OK;
 }
@@ -745,6 +768,344 @@ int render_denoised_variance(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n
     return denoise_variance(c, s, s.halves, s.guides, out, nullptr, p);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// Temporal reprojection and accumulation (trg_denoise.h has the definition)
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+bool valid_temporal_params(const trg_temporal_params &q) {
+    return q.iterations >= 0 && q.iterations <= TRG_DENOISE_MAX_ITERATIONS && q.sigma_lum > 0.0f && q.sigma_normal >= 0.0f && q.sigma_depth > 0.0f &&
+           q.alpha > 0.0f && q.alpha <= 1.0f && q.alpha_moments > 0.0f && q.alpha_moments <= 1.0f && q.plane_tol > 0.0f && q.normal_tol >= -1.0f &&
+           q.normal_tol <= 1.0f && q.max_history >= 1;
+}
+
+struct ReprojectParams {
+    const float4 *color, *fguide, *g1, *pos;          // this frame: C, F, G1, X
+    const float4 *hc, *hm, *hf, *hx;                  // the previous call's history planes (null: no history)
+    float4 *oc, *om, *of, *ox, *iv;                   // the new history planes and (I, V_0)
+    int w, h, demod;
+    float vp[16];
+    float alpha, alpha_moments, plane_tol, normal_tol, max_history;
+};
+
+// n / |n| into (x, y, z); false when the length is not > 0
+template <bool STRICT>
+__device__ __forceinline__ bool dn_unit(float &x, float &y, float &z) {
+    const float len = dn_sqrt<STRICT>(x * x + y * y + z * z);
+    if (!(len > 0.0f)) return false;
+    x = x / len; y = y / len; z = z / len;
+    return true;
+}
+
+// One pixel per thread over 16 x 16 tiles.  The four planes of this frame are read coalesced (a wavefront = four rows of 16 consecutive float4);
+// the four taps of the four history planes land wherever the camera moved the surface to, neighbouring lanes mostly on the same 128-byte lines
+// of L2.
+template <bool STRICT>
+__global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const ReprojectParams p) {
+    const int x = (int)blockIdx.x * kDnTile + ((int)threadIdx.x & 15), y = (int)blockIdx.y * kDnTile + ((int)threadIdx.x >> 4);
+    if (x >= p.w || y >= p.h) return;
+    const size_t pix = (size_t)y * (size_t)p.w + (size_t)x;
+    const float4 c = p.color[pix], f = p.fguide[pix], X = p.pos[pix];
+    p.of[pix] = f;
+    p.ox[pix] = X;
+    if (f.w < 0.0f) {   // a miss: nothing to accumulate
+        p.oc[pix] = make_float4(c.x, c.y, c.z, 0.0f);
+        p.om[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        p.iv[pix] = make_float4(c.x, c.y, c.z, 0.0f);
+        return;
+    }
+    float dr = c.x, dg = c.y, db = c.z;
+    if (p.demod) {
+        const float4 a = p.g1[pix];
+        dr = dr / fmaxf(a.x, 1e-3f); dg = dg / fmaxf(a.y, 1e-3f); db = db / fmaxf(a.z, 1e-3f);
+    }
+    const float l = dn_lum(make_float4(dr, dg, db, 0.0f));
+    float ir = 0.0f, ig = 0.0f, ib = 0.0f, m1 = 0.0f, m2 = 0.0f, nh = 0.0f, W = 0.0f;
+    float nx = f.x, ny = f.y, nz = f.z;
+    if (p.hc && dn_unit<STRICT>(nx, ny, nz)) {
+        const float *m = p.vp;
+        const float cx = m[0] * X.x + m[1] * X.y + m[2] * X.z + m[3];
+        const float cy = m[4] * X.x + m[5] * X.y + m[6] * X.z + m[7];
+        const float cw = m[12] * X.x + m[13] * X.y + m[14] * X.z + m[15];
+        if (cw > 0.0f) {
+            const float fx = (cx / cw * 0.5f + 0.5f) * (float)p.w - 0.5f, fy = (cy / cw * 0.5f + 0.5f) * (float)p.h - 0.5f;
+            if (fx >= -1.0f && fx < (float)p.w && fy >= -1.0f && fy < (float)p.h) {   // (false for NaN)
+                const float flx = floorf(fx), fly = floorf(fy);
+                const int x0 = (int)flx, y0 = (int)fly;
+                const float tx = fx - flx, ty = fy - fly;
+                const float tol = p.plane_tol * f.w;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int i = k & 1, j = k >> 1;
+                    const int qx = x0 + i, qy = y0 + j;
+                    if (qx < 0 || qx >= p.w || qy < 0 || qy >= p.h) continue;
+                    const size_t q = (size_t)qy * (size_t)p.w + (size_t)qx;
+                    const float4 fq = p.hf[q];
+                    if (!(fq.w >= 0.0f)) continue;
+                    const float4 xq = p.hx[q];
+                    const float dist = nx * (xq.x - X.x) + ny * (xq.y - X.y) + nz * (xq.z - X.z);
+                    if (!(fabsf(dist) <= tol)) continue;
+                    float qnx = fq.x, qny = fq.y, qnz = fq.z;
+                    if (!dn_unit<STRICT>(qnx, qny, qnz)) continue;
+                    if (!(nx * qnx + ny * qny + nz * qnz >= p.normal_tol)) continue;
+                    const float b = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
+                    const float4 hc = p.hc[q], hm = p.hm[q];
+                    ir += b * hc.x; ig += b * hc.y; ib += b * hc.z; nh += b * hc.w;
+                    m1 += b * hm.x; m2 += b * hm.y;
+                    W += b;
+                }
+            }
+        }
+    }
+    float N = 1.0f, v0;
+    if (W > 0.0f) {
+        ir = ir / W; ig = ig / W; ib = ib / W; nh = nh / W; m1 = m1 / W; m2 = m2 / W;
+        N = fminf(nh + 1.0f, p.max_history);
+        const float a = fmaxf(p.alpha, 1.0f / N), am = fmaxf(p.alpha_moments, 1.0f / N);
+        ir = ir + a * (dr - ir); ig = ig + a * (dg - ig); ib = ib + a * (db - ib);
+        m1 = m1 + am * (l - m1);
+        m2 = m2 + am * (l * l - m2);
+    } else {
+        ir = dr; ig = dg; ib = db; m1 = l; m2 = l * l;
+    }
+    v0 = fmaxf(0.0f, m2 - m1 * m1);   // (N < 4: replaced by the spatial estimate of the next launch)
+    p.oc[pix] = make_float4(ir, ig, ib, N);
+    p.om[pix] = make_float4(m1, m2, 0.0f, 0.0f);
+    p.iv[pix] = make_float4(ir, ig, ib, v0);
+}
+
+// V_0 of the pixels whose history is shorter than four frames: the variance of the moments over the 7 x 7 window, with the prefilter's weights.
+// F and the moments of the tile + 3 pixels of halo in LDS ([row][x], as dn_var_prefilter_kernel).  A tile in which no pixel needs it -- the usual
+// case once the camera has stood still for four frames -- leaves before staging anything: one ballot per wave, four flags in LDS.
+template <bool STRICT>
+__global__ __launch_bounds__(256) void dn_temporal_spatial_kernel(const float4 *hc, const float4 *hm, const float4 *g0, float4 *iv, int w, int h,
+                                                                  float sigma_normal, float sigma_depth) {
+    __shared__ float4 s_g0[kDnPreSide * kDnPreSide];
+    __shared__ float2 s_m[kDnPreSide * kDnPreSide];
+    __shared__ int s_need[4];
+    const int x0 = (int)blockIdx.x * kDnTile, y0 = (int)blockIdx.y * kDnTile;
+    const int x = x0 + ((int)threadIdx.x & 15), y = y0 + ((int)threadIdx.x >> 4);
+    const bool inside = x < w && y < h;
+    const size_t pix = inside ? (size_t)y * (size_t)w + (size_t)x : 0;
+    float N = 0.0f;
+    bool need = false;
+    if (inside) {
+        N = hc[pix].w;
+        need = g0[pix].w >= 0.0f && N < 4.0f;
+    }
+    const unsigned long long any = __ballot(need);
+    if ((threadIdx.x & 63u) == 0u) s_need[threadIdx.x >> 6] = any != 0ull ? 1 : 0;
+    __syncthreads();
+    if (!(s_need[0] | s_need[1] | s_need[2] | s_need[3])) return;   // (uniform over the workgroup)
+    for (int k = (int)threadIdx.x; k < kDnPreSide * kDnPreSide; k += 256) {
+        const int ly = k / kDnPreSide, lx = k - ly * kDnPreSide;
+        const int gx = x0 - kDnPreR + lx, gy = y0 - kDnPreR + ly;
+        float4 g = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        float2 m = make_float2(0.0f, 0.0f);
+        if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
+            const size_t q = (size_t)gy * (size_t)w + (size_t)gx;
+            g = g0[q];
+            const float4 mm = hm[q];
+            m = make_float2(mm.x, mm.y);
+        }
+        s_g0[k] = g;
+        s_m[k] = m;
+    }
+    __syncthreads();
+    if (!need) return;
+    auto guide = [&](int qx, int qy) -> float4 { return s_g0[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)]; };
+    const float4 gp = guide(x, y);
+    const float grad = dn_depth_gradient(guide, x, y, w, h, gp.w);
+    float s1 = 0.0f, s2 = 0.0f, gs = 0.0f;
+#pragma unroll
+    for (int dy = -kDnPreR; dy <= kDnPreR; ++dy) {
+#pragma unroll
+        for (int dx = -kDnPreR; dx <= kDnPreR; ++dx) {
+            const int qx = x + dx, qy = y + dy;
+            if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+            const float4 gq = guide(qx, qy);
+            if (gq.w < 0.0f) continue;
+            const float dn = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
+            if (!(dn > 0.0f)) continue;
+            const float wn = dn_pow<STRICT>(dn, sigma_normal);
+            const float dist = sqrtf((float)(dx * dx + dy * dy));
+            const float wz = dn_exp<STRICT>(-(fabsf(gp.w - gq.w) / (sigma_depth * (grad * 1.0f * dist + 1e-6f))));
+            const float g = wn * wz;
+            const float2 m = s_m[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)];
+            s1 += g * m.x; s2 += g * m.y;
+            gs += g;
+        }
+    }
+    float v0 = 0.0f;
+    if (gs > 0.0f) {
+        const float M1 = s1 / gs, M2 = s2 / gs;
+        v0 = fmaxf(0.0f, M2 - M1 * M1) * 4.0f / N;
+    }
+    iv[pix].w = v0;
+}
+
+// iterations == 0: out.rgb = I remodulated, out.a = the input's alpha; var (may be null) = V_0
+__global__ void dn_temporal_finish_kernel(const float4 *iv, const float4 *color, const float4 *fguide, const float4 *g1, float4 *out, float *var, int demod,
+                                          uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float4 o = iv[i];
+    if (var) var[i] = o.w;
+    if (demod && !(fguide[i].w < 0.0f)) {
+        const float4 a = g1[i];
+        o.x = o.x * fmaxf(a.x, 1e-3f); o.y = o.y * fmaxf(a.y, 1e-3f); o.z = o.z * fmaxf(a.z, 1e-3f);
+    }
+    o.w = color[i].w;
+    out[i] = o;
+}
+
+// rgb *= f in place: the running average trg_render left in a zeroed image, as the mean of its samples
+__global__ void dn_scale_kernel(float4 *a, float f, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float4 u = a[i];
+    u.x = u.x * f; u.y = u.y * f; u.z = u.z * f;
+    a[i] = u;
+}
+
+// inverse of the 4 x 4 matrix a (row-major) in double precision, Gauss-Jordan with partial pivoting; false when a is singular or not finite
+bool invert4(const float *a, float *out) {
+    double m[4][8];
+    double big = 0.0;
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            const double v = (double)a[i * 4 + j];
+            if (!(v - v == 0.0)) return false;   // inf or NaN
+            m[i][j] = v;
+            m[i][4 + j] = i == j ? 1.0 : 0.0;
+            if (fabs(v) > big) big = fabs(v);
+        }
+    if (!(big > 0.0)) return false;
+    for (int col = 0; col < 4; ++col) {
+        int piv = col;
+        for (int r = col + 1; r < 4; ++r)
+            if (fabs(m[r][col]) > fabs(m[piv][col])) piv = r;
+        // entries are fp32 values: a pivot this far under the largest of them is the rounding residue of a singular matrix
+        if (!(fabs(m[piv][col]) > 1e-13 * big)) return false;
+        if (piv != col)
+            for (int j = 0; j < 8; ++j) { const double t = m[piv][j]; m[piv][j] = m[col][j]; m[col][j] = t; }
+        const double d = m[col][col];
+        for (int j = 0; j < 8; ++j) m[col][j] /= d;
+        for (int r = 0; r < 4; ++r) {
+            if (r == col) continue;
+            const double f = m[r][col];
+            if (f == 0.0) continue;
+            for (int j = 0; j < 8; ++j) m[r][j] -= f * m[col][j];
+        }
+    }
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            const float v = (float)m[i][4 + j];
+            if (!(v - v == 0.0f)) return false;
+            out[i * 4 + j] = v;
+        }
+    return true;
+}
+
+// use_history = false: the step runs as after a reset (trg_render_temporal without a remembered view-projection).  iv_out (may be null): a plane
+// of width*height float4 for (I, V_0); var_out (may be null): a plane of floats for V_N
+int temporal_denoise(trg_ctx *c, DenoiseState &s, const float4 *color, const float4 *guides, const float4 *pos, const float *vp, bool use_history,
+                     float4 *out, float4 *iv_out, float *var_out, const trg_temporal_params *pp, const char *who) {
+    trg_temporal_params q;
+    trg_temporal_default_params(&q);
+    if (pp) q = *pp;
+    if (!valid_temporal_params(q))
+        return fail(c, TRG_ERR_INVALID, "%s: iterations must be 0..%d, the sigmas and plane_tol positive, alpha and alpha_moments in (0, 1], normal_tol in [-1, 1], max_history >= 1",
+                    who, TRG_DENOISE_MAX_ITERATIONS);
+    const size_t n = (size_t)c->w * c->h, bytes = n * sizeof(float4);
+    if (overlap(out, bytes, color, bytes) || overlap(out, bytes, guides, 2 * bytes) || overlap(out, bytes, pos, bytes) || overlap(color, bytes, guides, 2 * bytes) ||
+        overlap(color, bytes, pos, bytes) || overlap(pos, bytes, guides, 2 * bytes))
+        return fail(c, TRG_ERR_INVALID, "%s: the buffers overlap", who);
+    for (int k = 0; k < 16; ++k)
+        if (!(vp[k] - vp[k] == 0.0f)) return fail(c, TRG_ERR_INVALID, "%s: prev_view_proj is not finite", who);
+    if (int rc = lazy_planes(c, s, s.hist[0], 4, "the history planes")) return rc;
+    if (int rc = lazy_planes(c, s, s.hist[1], 4, "the history planes")) return rc;
+    hipStream_t st = c->stream;
+    if (int rc = exclude_emitters(c, s, guides)) return rc;
+    const float4 *prev = s.hist[s.hist_cur];
+    float4 *next = s.hist[s.hist_cur ^ 1];
+    ReprojectParams r{};
+    r.color = color; r.fguide = s.fguide; r.g1 = guides + n; r.pos = pos;
+    if (s.hist_valid && use_history) { r.hc = prev; r.hm = prev + n; r.hf = prev + 2 * n; r.hx = prev + 3 * n; }
+    r.oc = next; r.om = next + n; r.of = next + 2 * n; r.ox = next + 3 * n; r.iv = s.ping;
+    r.w = (int)c->w; r.h = (int)c->h; r.demod = q.demodulate ? 1 : 0;
+    for (int k = 0; k < 16; ++k) r.vp[k] = vp[k];
+    r.alpha = q.alpha; r.alpha_moments = q.alpha_moments; r.plane_tol = q.plane_tol; r.normal_tol = q.normal_tol; r.max_history = (float)q.max_history;
+    const dim3 grid((c->w + kDnTile - 1) / kDnTile, (c->h + kDnTile - 1) / kDnTile);
+    if (c->opt_strict) hipLaunchKernelGGL((dn_temporal_reproject_kernel<true>), grid, dim3(256), 0, st, r);
+    else hipLaunchKernelGGL((dn_temporal_reproject_kernel<false>), grid, dim3(256), 0, st, r);
+    DN_HIPCHK(c, hipGetLastError());
+    s.hist_cur ^= 1;          // (enqueued: from here on the new planes are the history, also if a later launch fails)
+    s.hist_valid = true;
+    if (c->opt_strict)
+        hipLaunchKernelGGL((dn_temporal_spatial_kernel<true>), grid, dim3(256), 0, st, (const float4 *)r.oc, (const float4 *)r.om, (const float4 *)s.fguide, s.ping,
+                           (int)c->w, (int)c->h, q.sigma_normal, q.sigma_depth);
+    else
+        hipLaunchKernelGGL((dn_temporal_spatial_kernel<false>), grid, dim3(256), 0, st, (const float4 *)r.oc, (const float4 *)r.om, (const float4 *)s.fguide, s.ping,
+                           (int)c->w, (int)c->h, q.sigma_normal, q.sigma_depth);
+    DN_HIPCHK(c, hipGetLastError());
+    if (iv_out) DN_HIPCHK(c, hipMemcpyAsync(iv_out, s.ping, bytes, hipMemcpyDeviceToDevice, st));
+    if (q.iterations == 0) {
+        hipLaunchKernelGGL(dn_temporal_finish_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)s.ping, color, (const float4 *)s.fguide,
+                           guides + n, out, var_out, q.demodulate ? 1 : 0, (uint32_t)n);
+        DN_HIPCHK(c, hipGetLastError());
+        return TRG_OK;
+    }
+    AtrousParams p{};
+    p.g0 = s.fguide; p.g1 = guides + n;
+    p.w = (int)c->w; p.h = (int)c->h;
+    p.sigma_color = q.sigma_lum; p.sigma_normal = q.sigma_normal; p.sigma_depth = q.sigma_depth;
+    p.alpha = color; p.var_out = var_out;
+    const float4 *src = s.ping;
+    for (int i = 0; i < q.iterations; ++i) {
+        const bool last = i + 1 == q.iterations;
+        p.in = src;
+        p.out = last ? out : (src == s.ping ? s.pong : s.ping);
+        p.spacing = 1 << i;
+        p.demod_in = 0;   // the reprojection kernel demodulated
+        p.remod_out = (q.demodulate && last) ? 1 : 0;
+        p.last = last ? 1 : 0;
+        const hipError_t e = c->opt_strict ? launch_atrous<true, true>(p, st) : launch_atrous<false, true>(p, st);
+        if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "%s: launch failed: %s", who, hipGetErrorString(e));
+        src = p.out;
+    }
+    return TRG_OK;
+}
+
+int render_temporal(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n, uint32_t bounces, float4 *out, const trg_temporal_params *p, const char *who) {
+    if (p && !valid_temporal_params(*p)) return fail(c, TRG_ERR_INVALID, "%s: bad parameters", who);
+    if (n < 1u) return fail(c, TRG_ERR_INVALID, "%s: spp must be at least 1", who);
+    if ((uint64_t)b + n > 0xFFFFFFFFull) return fail(c, TRG_ERR_INVALID, "%s: frame range [%u, %u + %u) exceeds 32 bits", who, b, b, n);
+    if (!c->have_uniforms) return fail(c, TRG_ERR_INVALID, "%s: uniforms not set", who);
+    float vp_now[16];
+    if (!invert4(c->u.inv_view_proj, vp_now)) return fail(c, TRG_ERR_INVALID, "%s: the uniforms' inverse view-projection is singular or not finite", who);
+    const size_t npix = (size_t)c->w * c->h, bytes = npix * sizeof(float4);
+    if (overlap(out, bytes, c->accum, bytes)) return fail(c, TRG_ERR_INVALID, "%s: out_device overlaps the bound accumulation buffer", who);
+    if (int rc = lazy_planes(c, s, s.timg, 1, "the temporal path's image")) return rc;
+    if (int rc = lazy_planes(c, s, s.tpos, 1, "the position plane")) return rc;
+    hipStream_t st = c->stream;
+    DN_HIPCHK(c, hipMemsetAsync(s.timg, 0, bytes, st));
+    float *const bound = c->accum;
+    const bool own = bound == c->accum_own;
+    int rc = trg_bind_accum(c, s.timg);
+    if (rc == TRG_OK) rc = trg_render(c, b, n, bounces, 0, c->h);
+    (void)trg_bind_accum(c, own ? nullptr : bound);   // (cannot fail: the pointer was bound before)
+    if (rc != TRG_OK) return rc;
+    const float f = (float)((double)((uint64_t)b + n) / (double)n);
+    hipLaunchKernelGGL(dn_scale_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, st, s.timg, f, (uint32_t)npix);
+    DN_HIPCHK(c, hipGetLastError());
+    if (int rc2 = guides_render(c, s, b, s.guides, s.tpos)) return rc2;
+    const float zero[16] = {};
+    rc = temporal_denoise(c, s, s.timg, s.guides, s.tpos, s.have_prev_vp ? s.prev_vp : zero, s.have_prev_vp, out, nullptr, nullptr, p, who);
+    if (rc != TRG_OK) return rc;
+    for (int k = 0; k < 16; ++k) s.prev_vp[k] = vp_now[k];
+    s.have_prev_vp = true;
+    return TRG_OK;
+}
+
 struct DevBuf {
     void *p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
@@ -956,6 +1317,132 @@ int trg_render_denoised_variance_read(trg_ctx *c, uint32_t frameIndexBegin, uint
     }
     const hipError_t e = hipStreamSynchronize(c->stream);
     if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_denoised_variance_read: %s", hipGetErrorString(e));
+    return rc;
+}
+
+void trg_temporal_default_params(trg_temporal_params *p) {
+    if (!p) return;
+    p->iterations = 5; p->sigma_lum = 4.0f; p->sigma_normal = 128.0f; p->sigma_depth = 1.0f; p->demodulate = 1;
+    p->alpha = 0.2f; p->alpha_moments = 0.2f; p->plane_tol = 0.02f; p->normal_tol = 0.9f; p->max_history = 32;
+}
+
+int trg_temporal_view_proj(const trg_uniforms *u, float vp16[16]) {
+    if (!u || !vp16) return TRG_ERR_INVALID;
+    return invert4(u->inv_view_proj, vp16) ? TRG_OK : TRG_ERR_INVALID;
+}
+
+int trg_guides_render_pos(trg_ctx *c, uint32_t frameIndex, void *guides_device, void *pos_device) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_guides_render_pos")) return rc;
+    if (!guides_device || !pos_device) return fail(c, TRG_ERR_INVALID, "trg_guides_render_pos: NULL buffer");
+    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
+    if (overlap(guides_device, 2 * bytes, pos_device, bytes)) return fail(c, TRG_ERR_INVALID, "trg_guides_render_pos: pos_device overlaps guides_device");
+    return guides_render(c, *s, frameIndex, static_cast<float4 *>(guides_device), static_cast<float4 *>(pos_device));
+}
+
+int trg_temporal_reset(trg_ctx *c) {
+    if (!c) return TRG_ERR_INVALID;
+    // allocates nothing: a context that never denoised has no state, and a new state starts without history anyway
+    std::lock_guard<std::mutex> lock(g_mutex);
+    auto it = g_states.find(c);
+    if (it == g_states.end()) return TRG_OK;
+    it->second.hist_valid = false;
+    it->second.have_prev_vp = false;
+    return TRG_OK;
+}
+
+int trg_temporal_history_read(trg_ctx *c, float *hist_host) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_temporal_history_read")) return rc;
+    if (!hist_host) return fail(c, TRG_ERR_INVALID, "trg_temporal_history_read: hist_host is NULL");
+    if (!s->hist_valid) return fail(c, TRG_ERR_INVALID, "trg_temporal_history_read: there is no history");
+    DN_HIPCHK(c, hipMemcpyAsync(hist_host, s->hist[s->hist_cur], 2 * s->pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    DN_HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TRG_OK;
+}
+
+int trg_temporal_denoise(trg_ctx *c, const void *color_in_device, const void *guides_device, const void *pos_device, const float prev_view_proj[16], void *out_device,
+                         const trg_temporal_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_temporal_denoise")) return rc;
+    if (!color_in_device || !guides_device || !pos_device || !prev_view_proj || !out_device) return fail(c, TRG_ERR_INVALID, "trg_temporal_denoise: NULL buffer");
+    return temporal_denoise(c, *s, static_cast<const float4 *>(color_in_device), static_cast<const float4 *>(guides_device), static_cast<const float4 *>(pos_device),
+                            prev_view_proj, true, static_cast<float4 *>(out_device), nullptr, nullptr, p, "trg_temporal_denoise");
+}
+
+int trg_render_temporal(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, void *out_device, const trg_temporal_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_render_temporal")) return rc;
+    if (!out_device) return fail(c, TRG_ERR_INVALID, "trg_render_temporal: out_device is NULL");
+    return render_temporal(c, *s, frameIndexBegin, spp, bounces, static_cast<float4 *>(out_device), p, "trg_render_temporal");
+}
+
+int trg_render_temporal_own(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, const trg_temporal_params *p, void **out_device) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_render_temporal_own")) return rc;
+    if (!out_device) return fail(c, TRG_ERR_INVALID, "trg_render_temporal_own: out_device is NULL");
+    if (int rc = lazy_planes(c, *s, s->result, 1, "the result image")) return rc;
+    if (c->accum == reinterpret_cast<float *>(s->result)) return fail(c, TRG_ERR_INVALID, "trg_render_temporal_own: the state's image is bound as the accumulation buffer");
+    if (int rc = render_temporal(c, *s, frameIndexBegin, spp, bounces, s->result, p, "trg_render_temporal_own")) return rc;
+    *out_device = s->result;
+    return TRG_OK;
+}
+
+int trg_guides_pos_read(trg_ctx *c, uint32_t frameIndex, float *guides_host, float *pos_host) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_guides_pos_read")) return rc;
+    if (!guides_host || !pos_host) return fail(c, TRG_ERR_INVALID, "trg_guides_pos_read: NULL buffer");
+    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
+    DevBuf g;
+    DN_HIPCHK(c, g.alloc(3 * bytes));
+    float4 *gd = static_cast<float4 *>(g.p);
+    if (int rc = guides_render(c, *s, frameIndex, gd, gd + 2 * (size_t)c->w * c->h)) return rc;
+    DN_HIPCHK(c, hipMemcpyAsync(guides_host, g.p, 2 * bytes, hipMemcpyDeviceToHost, c->stream));
+    DN_HIPCHK(c, hipMemcpyAsync(pos_host, static_cast<char *>(g.p) + 2 * bytes, bytes, hipMemcpyDeviceToHost, c->stream));
+    DN_HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TRG_OK;
+}
+
+int trg_temporal_denoise_host(trg_ctx *c, const float *color_in_host, const float *guides_host, const float *pos_host, const float prev_view_proj[16], float *out_host,
+                              float *iv_host, float *var_host, const trg_temporal_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_temporal_denoise_host")) return rc;
+    if (!color_in_host || !guides_host || !pos_host || !prev_view_proj || !out_host) return fail(c, TRG_ERR_INVALID, "trg_temporal_denoise_host: NULL buffer");
+    const size_t npix = (size_t)c->w * c->h, bytes = npix * sizeof(float4);
+    DevBuf in, g, x, out, iv, var;
+    DN_HIPCHK(c, in.alloc(bytes)); DN_HIPCHK(c, g.alloc(2 * bytes)); DN_HIPCHK(c, x.alloc(bytes)); DN_HIPCHK(c, out.alloc(bytes));
+    if (iv_host) DN_HIPCHK(c, iv.alloc(bytes));
+    if (var_host) DN_HIPCHK(c, var.alloc(npix * sizeof(float)));
+    DN_HIPCHK(c, hipMemcpyAsync(in.p, color_in_host, bytes, hipMemcpyHostToDevice, c->stream));
+    DN_HIPCHK(c, hipMemcpyAsync(g.p, guides_host, 2 * bytes, hipMemcpyHostToDevice, c->stream));
+    DN_HIPCHK(c, hipMemcpyAsync(x.p, pos_host, bytes, hipMemcpyHostToDevice, c->stream));
+    int rc = temporal_denoise(c, *s, static_cast<const float4 *>(in.p), static_cast<const float4 *>(g.p), static_cast<const float4 *>(x.p), prev_view_proj, true,
+                              static_cast<float4 *>(out.p), static_cast<float4 *>(iv.p), static_cast<float *>(var.p), p, "trg_temporal_denoise_host");
+    if (rc == TRG_OK) {
+        hipError_t e = hipMemcpyAsync(out_host, out.p, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && iv_host) e = hipMemcpyAsync(iv_host, iv.p, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && var_host) e = hipMemcpyAsync(var_host, var.p, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_temporal_denoise_host: copy failed: %s", hipGetErrorString(e));
+    }
+    const hipError_t e = hipStreamSynchronize(c->stream);   // also on an error: the temporaries are freed on return
+    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_temporal_denoise_host: %s", hipGetErrorString(e));
+    return rc;
+}
+
+int trg_render_temporal_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_temporal_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_render_temporal_read")) return rc;
+    if (!out_host) return fail(c, TRG_ERR_INVALID, "trg_render_temporal_read: out_host is NULL");
+    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
+    DevBuf out;
+    DN_HIPCHK(c, out.alloc(bytes));
+    int rc = render_temporal(c, *s, frameIndexBegin, spp, bounces, static_cast<float4 *>(out.p), p, "trg_render_temporal_read");
+    if (rc == TRG_OK) {
+        hipError_t e = hipMemcpyAsync(out_host, out.p, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_temporal_read: copy failed: %s", hipGetErrorString(e));
+    }
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_temporal_read: %s", hipGetErrorString(e));
     return rc;
 }
 

@@ -8,9 +8,15 @@
     out = denoise_variance(ctx, h, g)            # the variance-guided filter (SVGF's weights, variance from the two halves)
     out = render_denoised_variance(ctx, 0, 4, 3) # halves + guides + that filter; the accumulation buffer is not touched
 
+    g, x = guides_pos(ctx, frame_index)          # the guides and the world positions of the first hits [h, w, 4]
+    vp = temporal_view_proj(uniforms)            # world -> clip of a frame's camera, for the call that comes after it
+    out = temporal_denoise(ctx, color, g, x, vp) # one temporal step: reproject the state's history, accumulate, filter with the temporal variance
+    out = render_temporal(ctx, k, 1, 3)          # render + guides + that step; the state remembers the camera; temporal_reset(ctx) forgets
+
 numpy arrays go through temporary device copies and the call waits for the result; torch ROCm tensors (float32, contiguous) are used in place
-through data_ptr() -- like trg_bind_accum -- and the call only enqueues on the context's current stream.  `reference_denoise` and
-`reference_denoise_variance` are the float64 numpy evaluations of the definitions in the header: what the GPU tests compare the kernels with.
+through data_ptr() -- like trg_bind_accum -- and the call only enqueues on the context's current stream.  `reference_denoise`,
+`reference_denoise_variance` (its iteration loop alone: `reference_atrous_variance`) and `reference_temporal` are the float64 numpy evaluations
+of the definitions in the header: what the GPU tests compare the kernels with.
 
 The context's denoise scratch lives until release(ctx); call it before ctx.close() (trg_destroy does not know about it).
 """
@@ -36,9 +42,17 @@ class VarParams(C.Structure):
                 ("demodulate", C.c_int32), ("prefilter", C.c_int32)]
 
 
+class TemporalParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("demodulate", C.c_int32), ("alpha", C.c_float), ("alpha_moments", C.c_float), ("plane_tol", C.c_float),
+                ("normal_tol", C.c_float), ("max_history", C.c_int32)]
+
+
 _P = C.c_void_p
 _PP = C.POINTER(Params)
 _VP = C.POINTER(VarParams)
+_TP = C.POINTER(TemporalParams)
+_F16 = C.POINTER(C.c_float)
 _U = C.c_uint32
 _SYMBOLS = [
     ("trg_denoise_default_params", None, [_PP]),
@@ -58,6 +72,17 @@ _SYMBOLS = [
     ("trg_render_halves_read", C.c_int, [_P, _U, _U, _U, _P]),
     ("trg_denoise_variance_host", C.c_int, [_P, _P, _P, _P, _P, _VP]),
     ("trg_render_denoised_variance_read", C.c_int, [_P, _U, _U, _U, _P, _VP]),
+    ("trg_guides_render_pos", C.c_int, [_P, _U, _P, _P]),
+    ("trg_temporal_view_proj", C.c_int, [_P, _F16]),
+    ("trg_temporal_default_params", None, [_TP]),
+    ("trg_temporal_reset", C.c_int, [_P]),
+    ("trg_temporal_history_read", C.c_int, [_P, _P]),
+    ("trg_temporal_denoise", C.c_int, [_P, _P, _P, _P, _F16, _P, _TP]),
+    ("trg_render_temporal", C.c_int, [_P, _U, _U, _U, _P, _TP]),
+    ("trg_render_temporal_own", C.c_int, [_P, _U, _U, _U, _TP, C.POINTER(_P)]),
+    ("trg_guides_pos_read", C.c_int, [_P, _U, _P, _P]),
+    ("trg_temporal_denoise_host", C.c_int, [_P, _P, _P, _P, _F16, _P, _P, _P, _TP]),
+    ("trg_render_temporal_read", C.c_int, [_P, _U, _U, _U, _P, _TP]),
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 
@@ -234,6 +259,112 @@ def render_denoised_variance(ctx, frame_begin, spp, bounces, out=None, params=No
     return o
 
 
+_TEMPORAL_DEFAULTS = dict(iterations=5, sigma_lum=4.0, sigma_normal=128.0, sigma_depth=1.0, demodulate=1, alpha=0.2, alpha_moments=0.2,
+                          plane_tol=0.02, normal_tol=0.9, max_history=32)   # the header's
+_TEMPORAL_INTS = ("iterations", "demodulate", "max_history")
+
+
+def make_temporal_params(params=None, **kw):
+    """TemporalParams from the library's defaults, a TemporalParams / dict, and keyword overrides."""
+    p = TemporalParams()
+    load().trg_temporal_default_params(C.byref(p))
+    src = {}
+    if isinstance(params, TemporalParams):
+        src = {f: getattr(params, f) for f, _ in TemporalParams._fields_}
+    elif params:
+        src = dict(params)
+    src.update(kw)
+    for k, v in src.items():
+        if k not in dict(TemporalParams._fields_):
+            raise TypeError("unknown temporal denoise parameter %r" % k)
+        setattr(p, k, int(v) if k in _TEMPORAL_INTS else float(v))
+    return p
+
+
+def guides_pos(ctx, frame_index, out=None, pos=None):
+    """trg_guides_render_pos -> (guides [2, h, w, 4], X [h, w, 4]).  out, pos = float32 ROCm tensors: filled in place on the context's stream
+    (and returned); None: numpy arrays."""
+    L = load()
+    gs, xs = (2, ctx.h, ctx.w, 4), (ctx.h, ctx.w, 4)
+    if out is not None and _is_tensor(out):
+        _chk(ctx, L.trg_guides_render_pos(ctx.h_ctx, frame_index, _tensor_ptr(out, gs, "guides"), _tensor_ptr(pos, xs, "pos")))
+        return out, pos
+    g, x = np.empty(gs, np.float32), np.empty(xs, np.float32)
+    _chk(ctx, L.trg_guides_pos_read(ctx.h_ctx, frame_index, g.ctypes.data, x.ctypes.data))
+    return g, x
+
+
+def temporal_view_proj(uniforms):
+    """trg_temporal_view_proj: the world -> clip matrix [16] float32 of a frame's uniforms (a capi.Uniforms, any ctypes structure of that layout,
+    or its 176 bytes).  ValueError when the inverse view-projection is singular or not finite."""
+    buf = C.create_string_buffer(bytes(uniforms) if isinstance(uniforms, (bytes, bytearray)) else bytes(memoryview(uniforms)), C.sizeof(capi.Uniforms))
+    vp = np.empty(16, np.float32)
+    if load().trg_temporal_view_proj(C.cast(buf, C.c_void_p), vp.ctypes.data_as(_F16)) != capi.OK:
+        raise ValueError("the uniforms' inverse view-projection is singular or not finite")
+    return vp
+
+
+def temporal_reset(ctx):
+    _chk(ctx, load().trg_temporal_reset(ctx.h_ctx))
+
+
+def temporal_history(ctx):
+    """trg_temporal_history_read -> [2, h, w, 4]: Hc = (I.rgb, N), Hm = (m1, m2, 0, 0) of the last step.  Waits."""
+    hist = np.empty((2, ctx.h, ctx.w, 4), np.float32)
+    _chk(ctx, load().trg_temporal_history_read(ctx.h_ctx, hist.ctypes.data))
+    return hist
+
+
+def _vp_arg(prev_vp):
+    vp = np.ascontiguousarray(np.zeros(16, np.float32) if prev_vp is None else prev_vp, np.float32).reshape(-1)
+    if vp.shape != (16,):
+        raise ValueError("prev_vp must hold 16 floats")
+    return vp
+
+
+def temporal_denoise(ctx, color, guides, pos, prev_vp, out=None, params=None, return_iv=False, return_variance=False, **kw):
+    """trg_temporal_denoise.  All tensors (enqueued only) or all numpy (waits).  prev_vp: temporal_view_proj of the previous call's uniforms (host
+    memory; None: zeros, for the first call after a reset).  numpy only: return_iv also gives (I.rgb, V_0) [h, w, 4], return_variance V_N [h, w]."""
+    L = load()
+    p = make_temporal_params(params, **kw)
+    vp = _vp_arg(prev_vp)
+    cs, gs = (ctx.h, ctx.w, 4), (2, ctx.h, ctx.w, 4)
+    if _is_tensor(color):
+        import torch
+        if return_iv or return_variance:
+            raise ValueError("return_iv / return_variance need numpy arrays (trg_temporal_denoise_host)")
+        if out is None:
+            out = torch.empty_like(color)
+        _chk(ctx, L.trg_temporal_denoise(ctx.h_ctx, _tensor_ptr(color, cs, "color"), _tensor_ptr(guides, gs, "guides"), _tensor_ptr(pos, cs, "pos"),
+                                         vp.ctypes.data_as(_F16), _tensor_ptr(out, cs, "out"), C.byref(p)))
+        return out
+    c = np.ascontiguousarray(color, np.float32)
+    g = np.ascontiguousarray(guides, np.float32)
+    x = np.ascontiguousarray(pos, np.float32)
+    if c.shape != cs or g.shape != gs or x.shape != cs:
+        raise ValueError("color and pos must be %s and guides %s" % (cs, gs))
+    o = np.empty(cs, np.float32)
+    iv = np.empty(cs, np.float32) if return_iv else None
+    v = np.empty((ctx.h, ctx.w), np.float32) if return_variance else None
+    _chk(ctx, L.trg_temporal_denoise_host(ctx.h_ctx, c.ctypes.data, g.ctypes.data, x.ctypes.data, vp.ctypes.data_as(_F16), o.ctypes.data,
+                                          iv.ctypes.data if return_iv else None, v.ctypes.data if return_variance else None, C.byref(p)))
+    res = (o,) + ((iv,) if return_iv else ()) + ((v,) if return_variance else ())
+    return res if len(res) > 1 else o
+
+
+def render_temporal(ctx, frame_begin, spp, bounces, out=None, params=None, **kw):
+    """trg_render_temporal: frames [frame_begin, frame_begin + spp) from a zeroed image of the state, guides and positions of frame_begin, one
+    temporal step against the camera of the previous call.  The bound accumulation buffer is not touched; the rays count."""
+    L = load()
+    p = make_temporal_params(params, **kw)
+    if out is not None and _is_tensor(out):
+        _chk(ctx, L.trg_render_temporal(ctx.h_ctx, frame_begin, spp, bounces, _tensor_ptr(out, (ctx.h, ctx.w, 4), "out"), C.byref(p)))
+        return out
+    o = np.empty((ctx.h, ctx.w, 4), np.float32)
+    _chk(ctx, L.trg_render_temporal_read(ctx.h_ctx, frame_begin, spp, bounces, o.ctypes.data, C.byref(p)))
+    return o
+
+
 def release(ctx):
     if getattr(ctx, "h_ctx", None):
         _chk(ctx, load().trg_denoise_release(ctx.h_ctx))
@@ -396,50 +527,19 @@ def reference_denoise(color, g0, g1, params=None, material_ids=None, dtype=np.fl
     return out
 
 
-def reference_denoise_variance(h1, h2, g0, g1, params=None, material_ids=None, return_variance=False, dtype=np.float64, **kw):
-    """float64 evaluation of trg_denoise_variance's definition.  h1, h2 [h, w, 4] the half buffers, g0 / g1 [h, w, 4] (float32 as the device sees
-    them); params: a VarParams, a dict or keywords over the header's defaults (no library needed); material_ids: those of the context's scene
-    (None: no scene, no emitters); dtype: the working precision (see above).  Returns [h, w, 4] of `dtype` (and V_N [h, w] with return_variance)."""
-    dtype = _dtype(dtype)
-    q = dict(_VAR_DEFAULTS)
-    if isinstance(params, VarParams):
-        params = {f: getattr(params, f) for f, _ in VarParams._fields_}
-    q.update(params or {}); q.update(kw)
-    it = int(q["iterations"])
-    if not 0 <= it <= MAX_ITERATIONS:
-        raise ValueError("iterations must be 0..%d" % MAX_ITERATIONS)
-    h1, h2 = np.asarray(h1).astype(dtype), np.asarray(h2).astype(dtype)
-    out = np.empty_like(h1)
-    out[..., 3] = h1[..., 3]
-    sl, sn, sd = (float(np.float32(q[k])) for k in ("sigma_lum", "sigma_normal", "sigma_depth"))
-    g0 = np.asarray(g0, np.float32).astype(dtype)
-    if material_ids is not None:
-        g0[emitter_mask(g1, material_ids), 3] = -1.0
-    alb = np.maximum(np.asarray(g1, np.float32)[..., :3].astype(dtype), float(np.float32(1e-3)))
-    miss = g0[..., 3] < 0
-    demod = bool(q["demodulate"])
-    d1 = np.where(miss[..., None], h1[..., :3], h1[..., :3] / alb) if demod else h1[..., :3]
-    d2 = np.where(miss[..., None], h2[..., :3], h2[..., :3] / alb) if demod else h2[..., :3]
-    I = 0.5 * (d1 + d2)
-    V = np.where(miss, 0.0, 0.25 * (_lum(d1, dtype) - _lum(d2, dtype)) ** 2)
+def _gather(W, a, spacing):
+    r = W.shape[0] // 2
+    acc = np.zeros_like(a)
+    for dy in range(-r, r + 1):
+        for dx in range(-r, r + 1):
+            aq, _ = _shift(a, dx * spacing, dy * spacing)
+            acc += (W[dy + r, dx + r][..., None] if a.ndim == 3 else W[dy + r, dx + r]) * aq
+    return acc
 
-    def gather(W, a, spacing):
-        r = W.shape[0] // 2
-        acc = np.zeros_like(a)
-        for dy in range(-r, r + 1):
-            for dx in range(-r, r + 1):
-                aq, _ = _shift(a, dx * spacing, dy * spacing)
-                acc += (W[dy + r, dx + r][..., None] if a.ndim == 3 else W[dy + r, dx + r]) * aq
-        return acc
 
-    if q["prefilter"]:
-        G = geometry_weights(g0, 1, sn, sd, kernel=(1.0,) * 7, dtype=dtype)
-        gs = G.sum((0, 1))
-        with np.errstate(invalid="ignore", divide="ignore"):
-            V = np.where(miss | ~(gs > 0), V, gather(G, V, 1) / gs)
-    if it == 0:
-        out[..., :3] = 0.5 * (h1[..., :3] + h2[..., :3])
-        return (out, V) if return_variance else out
+def _atrous_variance_loop(I, V, g0, miss, alb, it, sl, sn, sd, demod, dtype):
+    """Iterations 0 .. it-1 of the variance-guided filter and the remodulation, on arrays of `dtype` (g0 with the emitters already marked)."""
+    gather = _gather
     binom = (0.25, 0.5, 0.25)
     valid = (~miss).astype(dtype)
     for i in range(it):
@@ -467,5 +567,192 @@ def reference_denoise_variance(h1, h2, g0, g1, params=None, material_ids=None, r
             V = np.where(keep, V, gather(W * W, V, s) / wsum ** 2)
     if demod:
         I = np.where(miss[..., None], I, I * alb)
+    return I, V
+
+
+def _filter_inputs(g0, g1, material_ids, dtype):
+    """(the filter's G0 with the emitters marked as misses, the clamped albedo, the miss mask) in `dtype`."""
+    g0 = np.asarray(g0, np.float32).astype(dtype)
+    if material_ids is not None:
+        g0[emitter_mask(g1, material_ids), 3] = -1.0
+    alb = np.maximum(np.asarray(g1, np.float32)[..., :3].astype(dtype), float(np.float32(1e-3)))
+    return g0, alb, g0[..., 3] < 0
+
+
+def reference_atrous_variance(I0, V0, g0, g1, params=None, material_ids=None, dtype=np.float64, **kw):
+    """The iteration loop of trg_denoise_variance's definition on its own: (I_0 [h, w, 3], V_0 [h, w]) -- DEMODULATED when `demodulate` -- through
+    iterations 0 .. N-1 and the remodulation.  params: a VarParams / TemporalParams, a dict or keywords; only iterations, sigma_lum,
+    sigma_normal, sigma_depth and demodulate are read (defaults: the header's).  Returns (rgb [h, w, 3], V_N [h, w]) of `dtype`.
+    reference_denoise_variance is its start, this loop, and the alpha channel; reference_temporal supplies another start."""
+    dtype = _dtype(dtype)
+    q = dict(_VAR_DEFAULTS)
+    if isinstance(params, C.Structure):
+        params = {f: getattr(params, f) for f, _ in params._fields_}
+    q.update(params or {}); q.update(kw)
+    it = int(q["iterations"])
+    if not 0 <= it <= MAX_ITERATIONS:
+        raise ValueError("iterations must be 0..%d" % MAX_ITERATIONS)
+    sl, sn, sd = (float(np.float32(q[k])) for k in ("sigma_lum", "sigma_normal", "sigma_depth"))
+    g0, alb, miss = _filter_inputs(g0, g1, material_ids, dtype)
+    I = np.asarray(I0)[..., :3].astype(dtype)
+    V = np.asarray(V0).astype(dtype)
+    return _atrous_variance_loop(I, V, g0, miss, alb, it, sl, sn, sd, bool(q["demodulate"]), dtype)
+
+
+def reference_denoise_variance(h1, h2, g0, g1, params=None, material_ids=None, return_variance=False, dtype=np.float64, **kw):
+    """float64 evaluation of trg_denoise_variance's definition.  h1, h2 [h, w, 4] the half buffers, g0 / g1 [h, w, 4] (float32 as the device sees
+    them); params: a VarParams, a dict or keywords over the header's defaults (no library needed); material_ids: those of the context's scene
+    (None: no scene, no emitters); dtype: the working precision (see above).  Returns [h, w, 4] of `dtype` (and V_N [h, w] with return_variance)."""
+    dtype = _dtype(dtype)
+    q = dict(_VAR_DEFAULTS)
+    if isinstance(params, VarParams):
+        params = {f: getattr(params, f) for f, _ in VarParams._fields_}
+    q.update(params or {}); q.update(kw)
+    it = int(q["iterations"])
+    if not 0 <= it <= MAX_ITERATIONS:
+        raise ValueError("iterations must be 0..%d" % MAX_ITERATIONS)
+    h1, h2 = np.asarray(h1).astype(dtype), np.asarray(h2).astype(dtype)
+    out = np.empty_like(h1)
+    out[..., 3] = h1[..., 3]
+    sl, sn, sd = (float(np.float32(q[k])) for k in ("sigma_lum", "sigma_normal", "sigma_depth"))
+    g0 = np.asarray(g0, np.float32).astype(dtype)
+    if material_ids is not None:
+        g0[emitter_mask(g1, material_ids), 3] = -1.0
+    alb = np.maximum(np.asarray(g1, np.float32)[..., :3].astype(dtype), float(np.float32(1e-3)))
+    miss = g0[..., 3] < 0
+    demod = bool(q["demodulate"])
+    d1 = np.where(miss[..., None], h1[..., :3], h1[..., :3] / alb) if demod else h1[..., :3]
+    d2 = np.where(miss[..., None], h2[..., :3], h2[..., :3] / alb) if demod else h2[..., :3]
+    I = 0.5 * (d1 + d2)
+    V = np.where(miss, 0.0, 0.25 * (_lum(d1, dtype) - _lum(d2, dtype)) ** 2)
+
+    if q["prefilter"]:
+        G = geometry_weights(g0, 1, sn, sd, kernel=(1.0,) * 7, dtype=dtype)
+        gs = G.sum((0, 1))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            V = np.where(miss | ~(gs > 0), V, _gather(G, V, 1) / gs)
+    if it == 0:
+        out[..., :3] = 0.5 * (h1[..., :3] + h2[..., :3])
+        return (out, V) if return_variance else out
+    I, V = _atrous_variance_loop(I, V, g0, miss, alb, it, sl, sn, sd, demod, dtype)
     out[..., :3] = I
     return (out, V) if return_variance else out
+
+
+NEAR = 1e-4   # reference_temporal: how close (relative) to its threshold a discrete decision counts as undecidable in fp32
+
+
+def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, material_ids=None, dtype=np.float64, near_parts=False, **kw):
+    """float64 evaluation of ONE step of trg_temporal_denoise's definition up to the filter: reprojection, accumulation, V_0.
+    color, g0, g1, pos [h, w, 4] (float32 as the device sees them); history: the previous call's four planes (Hc, Hm, F, X), each [h, w, 4], or
+    None; prev_vp: 16 floats; params: a TemporalParams, a dict or keywords over the header's defaults (no library needed); material_ids: those
+    of the context's scene; dtype: the working precision (np.float32: the yardstick mode of the other references).
+    Returns (new history [4, h, w, 4], iv [h, w, 4] = (I.rgb, V_0), near [h, w] bool) -- near marks the pixels where a discrete decision lies
+    within NEAR of flipping: clip.w against 0, a relevant tap's plane distance against plane_tol z_p (relative to that bound) or its normal
+    cosine against normal_tol (cosines of unit vectors: absolute), W against 0 (W is a sum of bilinear weights that add up to 1: absolute; the
+    window test -1 <= f < size is the same decision, every tap it removes has a weight near 0), and N against 4 (relative).  The result then
+    goes through reference_atrous_variance.  near_parts: the third result is the pair (near without the last decision, near of N against 4 alone)
+    instead -- N against 4 chooses between the two forms of V_0 and nothing else, so colour, N and the moments of such a pixel are still decided."""
+    dtype = _dtype(dtype)
+    q = dict(_TEMPORAL_DEFAULTS)
+    if isinstance(params, TemporalParams):
+        params = {f: getattr(params, f) for f, _ in TemporalParams._fields_}
+    q.update(params or {}); q.update(kw)
+    alpha, alpha_m, plane_tol, normal_tol = (dtype(np.float32(q[k])) for k in ("alpha", "alpha_moments", "plane_tol", "normal_tol"))
+    max_hist = dtype(int(q["max_history"]))
+    sn, sd = float(np.float32(q["sigma_normal"])), float(np.float32(q["sigma_depth"]))
+    demod = bool(q["demodulate"])
+    C3 = np.asarray(color, np.float32)[..., :3].astype(dtype)
+    F, alb, miss = _filter_inputs(g0, g1, material_ids, dtype)
+    X = np.asarray(pos, np.float32)[..., :3].astype(dtype)
+    h, w = miss.shape
+    D = np.where(miss[..., None], C3, C3 / alb) if demod else C3
+    l = _lum(D, dtype)
+    near = np.zeros((h, w), bool)
+
+    def unit(v):
+        ln = np.sqrt((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2])
+        ok = ln > 0
+        return v / np.where(ok, ln, 1.0)[..., None], ok
+
+    def dot3(a, b):
+        return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+    W = np.zeros((h, w), dtype)
+    acc = np.zeros((h, w, 6), dtype)                       # I.rgb, N, m1, m2
+    if history is not None:
+        Hc, Hm, Hf, Hx = (np.asarray(p, np.float32).astype(dtype) for p in history)
+        vp = np.asarray(prev_vp, np.float32).reshape(16).astype(dtype)
+        n, n_ok = unit(F[..., :3])
+        clip = [((vp[j * 4] * X[..., 0] + vp[j * 4 + 1] * X[..., 1]) + vp[j * 4 + 2] * X[..., 2]) + vp[j * 4 + 3] for j in (0, 1, 3)]
+        cw = clip[2]
+        cand = ~miss & n_ok                                 # pixels that look for history at all
+        scale = np.abs(vp[12] * X[..., 0]) + np.abs(vp[13] * X[..., 1]) + np.abs(vp[14] * X[..., 2]) + np.abs(vp[15])
+        near |= cand & (np.abs(cw) <= NEAR * scale)
+        front = cand & (cw > 0)
+        cws = np.where(front, cw, 1.0)
+        fx = (clip[0] / cws * dtype(0.5) + dtype(0.5)) * dtype(w) - dtype(0.5)
+        fy = (clip[1] / cws * dtype(0.5) + dtype(0.5)) * dtype(h) - dtype(0.5)
+        # (the definition's window -1 <= f < size says "some tap is inside"; taps outside are skipped below anyway, so a window one pixel wider
+        #  gives the same sums and only keeps the integer conversion safe)
+        with np.errstate(invalid="ignore"):
+            window = front & (fx >= -2) & (fx < w + 1) & (fy >= -2) & (fy < h + 1)
+        fxs, fys = np.where(window, fx, 0.0), np.where(window, fy, 0.0)
+        flx, fly = np.floor(fxs), np.floor(fys)
+        x0, y0 = flx.astype(np.int64), fly.astype(np.int64)
+        tx, ty = fxs - flx, fys - fly
+        tol = plane_tol * F[..., 3]
+        for j in (0, 1):
+            for i in (0, 1):
+                qx, qy = x0 + i, y0 + j
+                inside = window & (qx >= 0) & (qx < w) & (qy >= 0) & (qy < h)
+                cx, cy = np.clip(qx, 0, w - 1), np.clip(qy, 0, h - 1)
+                fq, xq = Hf[cy, cx], Hx[cy, cx][..., :3]
+                live = inside & (fq[..., 3] >= 0)
+                dist = np.abs(dot3(n, xq - X))
+                nq, nq_ok = unit(fq[..., :3])
+                cosn = dot3(n, nq)
+                with np.errstate(invalid="ignore"):
+                    valid = live & (dist <= tol) & nq_ok & (cosn >= normal_tol)
+                    near |= live & ((np.abs(dist - tol) <= NEAR * tol) | (nq_ok & (np.abs(cosn - normal_tol) <= NEAR)))
+                b = (tx if i else 1 - tx) * (ty if j else 1 - ty)
+                b = np.where(valid, b, 0.0)
+                hc, hm = Hc[cy, cx], Hm[cy, cx]
+                acc[..., :4] += b[..., None] * hc
+                acc[..., 4] += b * hm[..., 0]
+                acc[..., 5] += b * hm[..., 1]
+                W += b
+        # W > 0: a sum of weights near 0 with a valid tap in it; or none in it while the sample sits within NEAR of a pixel centre's row or
+        # column, where one rounding brings another tap pair into play with a weight near 0
+        on_grid = (tx <= NEAR) | (tx >= 1 - NEAR) | (ty <= NEAR) | (ty >= 1 - NEAR)
+        near |= window & (W <= NEAR) & ((W > 0) | on_grid)
+    have = W > 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        hist = acc / np.where(have, W, 1.0)[..., None]
+    Nh = hist[..., 3]
+    N = np.where(have, np.minimum(Nh + 1, max_hist), 1.0).astype(dtype)
+    one = dtype(1.0)
+    a = np.maximum(alpha, one / N)[..., None]
+    am = np.maximum(alpha_m, one / N)
+    I = np.where(have[..., None], hist[..., :3] + a * (D - hist[..., :3]), D)
+    m1 = np.where(have, hist[..., 4] + am * (l - hist[..., 4]), l)
+    m2 = np.where(have, hist[..., 5] + am * (l * l - hist[..., 5]), l * l)
+    I = np.where(miss[..., None], C3, I)
+    N = np.where(miss, 0.0, N).astype(dtype)
+    m1, m2 = np.where(miss, 0.0, m1).astype(dtype), np.where(miss, 0.0, m2).astype(dtype)
+    near_n = ~miss & (np.abs(N - 4) <= NEAR * 4)
+    # V_0: temporal from four frames on, else the spatial estimate over this call's moments with the prefilter's weights
+    G = geometry_weights(F, 1, sn, sd, kernel=(1.0,) * 7, dtype=dtype)
+    gs = G.sum((0, 1))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        M1, M2 = _gather(G, m1, 1) / gs, _gather(G, m2, 1) / gs
+        spatial = np.where(gs > 0, np.maximum(0.0, M2 - M1 * M1) * dtype(4.0) / np.where(miss, 1.0, N), 0.0)
+    V0 = np.where(miss, 0.0, np.where(N >= 4, np.maximum(0.0, m2 - m1 * m1), spatial)).astype(dtype)
+    new = np.zeros((4, h, w, 4), dtype)
+    new[0, ..., :3], new[0, ..., 3] = I, N
+    new[1, ..., 0], new[1, ..., 1] = m1, m2
+    new[2] = F
+    new[3, ..., :3] = X
+    new[3, ..., 3] = np.asarray(pos, np.float32)[..., 3].astype(dtype)
+    iv = np.concatenate([I, V0[..., None]], -1).astype(dtype)
+    return new, iv, ((near, near_n) if near_parts else near | near_n)
