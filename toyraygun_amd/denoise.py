@@ -470,7 +470,7 @@ def geometry_weights(g0, spacing, sigma_normal, sigma_depth, kernel=B3, dtype=np
             with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
                 wn = _pow(np.where(dn > 0, np.abs(dn), 1.0), sigma_normal, dtype)
                 wz = _exp(-np.abs(z - zq) / (sigma_depth * (grad * spacing * dist + 1e-6)), dtype)
-            W[dy + r, dx + r] = np.where(ok, kernel[dx + r] * kernel[dy + r] * wn * wz, 0.0)
+                W[dy + r, dx + r] = np.where(ok, kernel[dx + r] * kernel[dy + r] * wn * wz, 0.0)
     return W
 
 
