@@ -100,6 +100,28 @@ int fail(trg_ctx *c, int code, const char *fmt, ...) {
         if (e_ != hipSuccess) return fail((c), TRG_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// ---- the two launch shapes of this unit, on the context's stream; `who` names the entry point in the error text.  The arguments are converted to
+// the kernel's parameter types here, so a call site writes nullptr and size_t as they come ----
+template <typename... Params, typename... Args>
+int launch(trg_ctx *c, const char *who, void (*kernel)(Params...), dim3 grid, Args... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, static_cast<Params>(args)...);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRG_OK : fail(c, TRG_ERR_DEVICE, "%s: launch failed: %s", who, hipGetErrorString(e));
+}
+// one thread per element (pixel, leaf record) in blocks of 256
+template <typename Kernel, typename... Args>
+int launch_each(trg_ctx *c, const char *who, Kernel kernel, size_t n, Args... args) {
+    return launch(c, who, kernel, dim3((uint32_t)((n + 255) / 256)), args...);
+}
+// one 16 x 16 tile of the image per block of 256
+constexpr int kDnTile = 16;                      // = trg::kTileW x kTileH of the render kernels at 256 threads
+template <typename Kernel, typename... Args>
+int launch_tiles(trg_ctx *c, const char *who, Kernel kernel, Args... args) {
+    return launch(c, who, kernel, dim3((c->w + kDnTile - 1) / kDnTile, (c->h + kDnTile - 1) / kDnTile), args...);
+}
+// the instantiation of a kernel template for the context's build setting (STRICT is its first parameter): the arguments are written once
+#define DN_FOR_SETTING(c, kernel, ...) ((c)->opt_strict ? kernel<true, ##__VA_ARGS__> : kernel<false, ##__VA_ARGS__>)
+
 // the copy of the struct above against what the library itself says about the context
 bool ctx_ok(trg_ctx *c) {
     void *acc = nullptr;
@@ -284,14 +306,11 @@ int plan_trace(trg_ctx *c, TracePlan &p) {
 
 // enqueues the map original primitive index -> leaf record of the loaded scene.  Rebuilt per call (one 4-byte read per record): a scene may
 // have been reloaded into the same allocation since
-int record_map(trg_ctx *c, DenoiseState &s) {
+int record_map(trg_ctx *c, DenoiseState &s, const char *who) {
     const SceneDesc &sc = c->sc;
     if (int rc = grow(c, s.rec_of_prim, s.prims, (size_t)sc.n_tris, sizeof(uint32_t), "record map")) return rc;
     DN_HIPCHK(c, hipMemsetAsync(s.rec_of_prim, 0, (size_t)sc.n_tris * sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(dn_record_map_kernel, dim3((sc.n_fat + 255u) / 256u), dim3(256), 0, c->stream, reinterpret_cast<const float4 *>(c->blob + sc.off_fat),
-                       sc.n_fat, sc.n_tris, s.rec_of_prim);
-    DN_HIPCHK(c, hipGetLastError());
-    return TRG_OK;
+    return launch_each(c, who, dn_record_map_kernel, sc.n_fat, reinterpret_cast<const float4 *>(c->blob + sc.off_fat), sc.n_fat, sc.n_tris, s.rec_of_prim);
 }
 
 // pos (may be null): the world-position plane of trg_guides_render_pos
@@ -315,20 +334,13 @@ int guides_render(trg_ctx *c, DenoiseState &s, uint32_t frameIndex, float4 *guid
     hipStream_t st = c->stream;
     trg_uniforms u = c->u;
     u.frameIndex = frameIndex;
-    hipError_t e = c->opt_strict ? launch_raygen_strict(u, c->offsets, s.rays, st) : launch_raygen_fast(u, c->offsets, s.rays, st);
+    hipError_t e = (c->opt_strict ? launch_raygen_strict : launch_raygen_fast)(u, c->offsets, s.rays, st);
     if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_guides_render: raygen launch failed: %s", hipGetErrorString(e));
-    e = c->opt_strict ? launch_trace_strict(tp, plan.lds_scene, false, plan.total, st) : launch_trace_fast(tp, plan.lds_scene, false, plan.total, st);
+    e = (c->opt_strict ? launch_trace_strict : launch_trace_fast)(tp, plan.lds_scene, false, plan.total, st);
     if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_guides_render: trace launch failed: %s", hipGetErrorString(e));
-    const float4 *recs = reinterpret_cast<const float4 *>(c->blob + sc.off_fat);
-    if (int rc = record_map(c, s)) return rc;
-    if (pos)
-        hipLaunchKernelGGL(dn_gather_kernel<true>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, s.isect, s.rec_of_prim, recs, sc.n_tris, c->tex, guides,
-                           guides + n, (uint32_t)n, (const trg_ray *)s.rays, pos);
-    else
-        hipLaunchKernelGGL(dn_gather_kernel<false>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, s.isect, s.rec_of_prim, recs, sc.n_tris, c->tex, guides,
-                           guides + n, (uint32_t)n, (const trg_ray *)nullptr, (float4 *)nullptr);
-    DN_HIPCHK(c, hipGetLastError());
-    return TRG_OK;
+    if (int rc = record_map(c, s, "trg_guides_render")) return rc;
+    return launch_each(c, "trg_guides_render", pos ? dn_gather_kernel<true> : dn_gather_kernel<false>, n, s.isect, s.rec_of_prim,
+                       reinterpret_cast<const float4 *>(c->blob + sc.off_fat), sc.n_tris, c->tex, guides, guides + n, n, pos ? s.rays : nullptr, pos);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -360,7 +372,6 @@ struct AtrousParams {
     const float4 *alpha;
     float *var_out;
 };
-constexpr int kDnTile = 16;                      // = trg::kTileW x kTileH of the render kernels at 256 threads
 constexpr int kDnLdsMaxSpacing = 2;              // spacings 1, 2: tile + halo of 2 * spacing pixels in LDS
 constexpr int kDnLdsSide = kDnTile + 4 * kDnLdsMaxSpacing;   // 24
 static_assert(kTileW == kDnTile && kTileH == kDnTile && kBlock == 256, "the filter's tiles are the render kernels' 16 x 16 tiles");
@@ -369,6 +380,9 @@ template <bool STRICT> __device__ __forceinline__ float dn_exp(float x) { return
 template <bool STRICT> __device__ __forceinline__ float dn_pow(float x, float y) { return STRICT ? powf(x, y) : __powf(x, y); }
 template <bool STRICT> __device__ __forceinline__ float dn_sqrt(float x) { return STRICT ? sqrtf(x) : __builtin_amdgcn_sqrtf(x); }
 __device__ __forceinline__ float dn_lum(const float4 c) { return 0.2126f * c.x + 0.7152f * c.y + 0.0722f * c.z; }
+// c.rgb / max(albedo, 1e-3) and c.rgb * max(albedo, 1e-3) of the header
+__device__ __forceinline__ float4 dn_demodulate(const float4 c, const float4 a) { return make_float4(c.x / fmaxf(a.x, 1e-3f), c.y / fmaxf(a.y, 1e-3f), c.z / fmaxf(a.z, 1e-3f), c.w); }
+__device__ __forceinline__ float4 dn_remodulate(const float4 c, const float4 a) { return make_float4(c.x * fmaxf(a.x, 1e-3f), c.y * fmaxf(a.y, 1e-3f), c.z * fmaxf(a.z, 1e-3f), c.w); }
 
 // g_p of the header: forward differences of the depth, backward where the forward neighbour is outside the image or a miss
 template <typename Guide>
@@ -383,6 +397,15 @@ __device__ __forceinline__ float dn_depth_gradient(const Guide &guide, int x, in
     if (z1 >= 0.0f) gy = z1 - zp;
     else if (y >= 1) { z1 = guide(x, y - 1).w; if (z1 >= 0.0f) gy = zp - z1; }
     return sqrtf(gx * gx + gy * gy);
+}
+
+// k w_n w_z of the header, multiplied in that order, for the tap q = p + s (dx, dy) with n_p . n_q = dn > 0 and the depths zp, zq
+template <bool STRICT>
+__device__ __forceinline__ float dn_geometry_weight(float k, float dn, float zp, float zq, float grad, float s, int dx, int dy, float sigma_normal, float sigma_depth) {
+    const float wn = dn_pow<STRICT>(dn, sigma_normal);
+    const float dist = sqrtf((float)(dx * dx + dy * dy));
+    const float wz = dn_exp<STRICT>(-(fabsf(zp - zq) / (sigma_depth * (grad * s * dist + 1e-6f))));
+    return k * wn * wz;
 }
 
 // VAR = true: the variance-guided form (trg_denoise_variance): the .w of the colour plane is V_i, the colour weight is w_l, scaled by the 3 x 3
@@ -404,10 +427,7 @@ __global__ __launch_bounds__(256) void dn_atrous_kernel(const AtrousParams p) {
                 const size_t q = (size_t)gy * (size_t)p.w + (size_t)gx;
                 c = p.in[q];
                 g = p.g0[q];
-                if (p.demod_in && g.w >= 0.0f) {
-                    const float4 a = p.g1[q];
-                    c.x = c.x / fmaxf(a.x, 1e-3f); c.y = c.y / fmaxf(a.y, 1e-3f); c.z = c.z / fmaxf(a.z, 1e-3f);
-                }
+                if (p.demod_in && g.w >= 0.0f) c = dn_demodulate(c, p.g1[q]);
             }
             s_col[k] = c;
             s_g0[k] = g;
@@ -485,9 +505,7 @@ __global__ __launch_bounds__(256) void dn_atrous_kernel(const AtrousParams p) {
             const float dn = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
             if (!(dn > 0.0f)) continue;
             const float4 cq = colour(qx, qy);
-            const float wn = dn_pow<STRICT>(dn, p.sigma_normal);
-            const float dist = sqrtf((float)(dx * dx + dy * dy));
-            const float wz = dn_exp<STRICT>(-(fabsf(gp.w - gq.w) / (p.sigma_depth * (grad * (float)s * dist + 1e-6f))));
+            const float wg = dn_geometry_weight<STRICT>(hk[dx + 2] * hk[dy + 2], dn, gp.w, gq.w, grad, (float)s, dx, dy, p.sigma_normal, p.sigma_depth);
             float wc;
             if (VAR) {
                 wc = dn_exp<STRICT>(-(fabsf(lp - dn_lum(cq)) / cden));
@@ -495,7 +513,7 @@ __global__ __launch_bounds__(256) void dn_atrous_kernel(const AtrousParams p) {
                 const float dr = cp.x - cq.x, dg = cp.y - cq.y, db = cp.z - cq.z;
                 wc = dn_exp<STRICT>(-((dr * dr + dg * dg + db * db) / cden));
             }
-            const float wgt = hk[dx + 2] * hk[dy + 2] * wn * wz * wc;
+            const float wgt = wg * wc;
             ar += wgt * cq.x; ag += wgt * cq.y; ab += wgt * cq.z;
             if (VAR) av += wgt * wgt * cq.w;
             wsum += wgt;
@@ -510,19 +528,12 @@ __global__ __launch_bounds__(256) void dn_atrous_kernel(const AtrousParams p) {
         if (p.var_out) p.var_out[pix] = o.w;
         o.w = p.alpha[pix].w;
     }
-    if (p.remod_out) {
-        const float4 a = p.g1[pix];
-        o.x = o.x * fmaxf(a.x, 1e-3f); o.y = o.y * fmaxf(a.y, 1e-3f); o.z = o.z * fmaxf(a.z, 1e-3f);
-    }
+    if (p.remod_out) o = dn_remodulate(o, p.g1[pix]);
     p.out[pix] = o;
 }
 
-template <bool STRICT, bool VAR>
-hipError_t launch_atrous(const AtrousParams &p, hipStream_t st) {
-    const dim3 grid((uint32_t)(p.w + kDnTile - 1) / kDnTile, (uint32_t)(p.h + kDnTile - 1) / kDnTile);
-    if (p.spacing <= kDnLdsMaxSpacing) hipLaunchKernelGGL((dn_atrous_kernel<STRICT, true, VAR>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((dn_atrous_kernel<STRICT, false, VAR>), grid, dim3(256), 0, st, p);
-    return hipGetLastError();
+bool overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    return (const char *)a < (const char *)b + b_bytes && (const char *)b < (const char *)a + a_bytes;
 }
 
 bool valid_params(const trg_denoise_params &q) {
@@ -530,14 +541,39 @@ bool valid_params(const trg_denoise_params &q) {
 }
 
 // enqueues the filter's copy of G0 (s.fguide) with the emitters of the loaded scene marked as misses
-int exclude_emitters(trg_ctx *c, DenoiseState &s, const float4 *guides) {
+int exclude_emitters(trg_ctx *c, DenoiseState &s, const float4 *guides, const char *who) {
     const size_t n = (size_t)c->w * c->h;
     const bool scene = c->scene_loaded && c->sc.n_tris != 0 && c->sc.n_fat != 0;
     if (scene)
-        if (int rc = record_map(c, s)) return rc;
-    hipLaunchKernelGGL(dn_exclude_emitters_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, guides, guides + n, s.rec_of_prim,
-                       scene ? reinterpret_cast<const float4 *>(c->blob + c->sc.off_fat) : nullptr, scene ? c->sc.n_tris : 0u, s.fguide, (uint32_t)n);
-    DN_HIPCHK(c, hipGetLastError());
+        if (int rc = record_map(c, s, who)) return rc;
+    return launch_each(c, who, dn_exclude_emitters_kernel, n, guides, guides + n, s.rec_of_prim,
+                       scene ? reinterpret_cast<const float4 *>(c->blob + c->sc.off_fat) : nullptr, scene ? c->sc.n_tris : 0u, s.fguide, n);
+}
+
+// what the launches of one run of the filter share
+AtrousParams atrous_params(const trg_ctx *c, const DenoiseState &s, const float4 *guides, float sigma_color, float sigma_normal, float sigma_depth) {
+    AtrousParams p{};
+    p.g0 = s.fguide; p.g1 = guides + (size_t)c->w * c->h;
+    p.w = (int)c->w; p.h = (int)c->h;
+    p.sigma_color = sigma_color; p.sigma_normal = sigma_normal; p.sigma_depth = sigma_depth;
+    return p;
+}
+// The filter's iterations 0 .. N-1 from `src` to `out`, spacing 2^i: every launch but the last writes whichever of the state's ping / pong is not
+// its source; the first launch demodulates and the last one remodulates when asked.  VAR: the variance-guided form, p.alpha and p.var_out set
+template <bool VAR>
+int atrous_run(trg_ctx *c, DenoiseState &s, const char *who, AtrousParams p, const float4 *src, float4 *out, int iterations, bool demod_first, bool remod_last) {
+    for (int i = 0; i < iterations; ++i) {
+        const bool last = i + 1 == iterations;
+        p.in = src;
+        p.out = last ? out : (src == s.ping ? s.pong : s.ping);
+        p.spacing = 1 << i;
+        p.demod_in = (demod_first && i == 0) ? 1 : 0;
+        p.remod_out = (remod_last && last) ? 1 : 0;
+        p.last = last ? 1 : 0;
+        const auto kernel = p.spacing <= kDnLdsMaxSpacing ? DN_FOR_SETTING(c, dn_atrous_kernel, true, VAR) : DN_FOR_SETTING(c, dn_atrous_kernel, false, VAR);
+        if (int rc = launch_tiles(c, who, kernel, p)) return rc;
+        src = p.out;
+    }
     return TRG_OK;
 }
 
@@ -547,31 +583,14 @@ int denoise(trg_ctx *c, DenoiseState &s, const float4 *in, const float4 *guides,
     if (pp) q = *pp;
     if (!valid_params(q)) return fail(c, TRG_ERR_INVALID, "trg_denoise: iterations must be 0..%d and the sigmas positive", TRG_DENOISE_MAX_ITERATIONS);
     const size_t n = (size_t)c->w * c->h, bytes = n * sizeof(float4);
-    if ((const char *)in < (const char *)out + bytes && (const char *)out < (const char *)in + bytes)
-        return fail(c, TRG_ERR_INVALID, "trg_denoise: out_device overlaps color_in_device");
-    hipStream_t st = c->stream;
+    if (overlap(out, bytes, in, bytes)) return fail(c, TRG_ERR_INVALID, "trg_denoise: out_device overlaps color_in_device");
     if (q.iterations == 0) {
-        DN_HIPCHK(c, hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, st));
+        DN_HIPCHK(c, hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, c->stream));
         return TRG_OK;
     }
-    if (int rc = exclude_emitters(c, s, guides)) return rc;
-    AtrousParams p{};
-    p.g0 = s.fguide; p.g1 = guides + n;
-    p.w = (int)c->w; p.h = (int)c->h;
-    p.sigma_color = q.sigma_color; p.sigma_normal = q.sigma_normal; p.sigma_depth = q.sigma_depth;
-    const float4 *src = in;
-    for (int i = 0; i < q.iterations; ++i) {
-        const bool last = i + 1 == q.iterations;
-        p.in = src;
-        p.out = last ? out : ((i & 1) ? s.pong : s.ping);
-        p.spacing = 1 << i;
-        p.demod_in = (q.demodulate && i == 0) ? 1 : 0;
-        p.remod_out = (q.demodulate && last) ? 1 : 0;
-        const hipError_t e = c->opt_strict ? launch_atrous<true, false>(p, st) : launch_atrous<false, false>(p, st);
-        if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_denoise: launch failed: %s", hipGetErrorString(e));
-        src = p.out;
-    }
-    return TRG_OK;
+    if (int rc = exclude_emitters(c, s, guides, "trg_denoise")) return rc;
+    return atrous_run<false>(c, s, "trg_denoise", atrous_params(c, s, guides, q.sigma_color, q.sigma_normal, q.sigma_depth), in, out, q.iterations, q.demodulate != 0,
+                             q.demodulate != 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -601,9 +620,8 @@ __global__ void dn_var_combine_kernel(const float4 *h1, const float4 *h2, const 
     const bool miss = fguide[i].w < 0.0f;
     if (demod && !miss) {
         const float4 al = g1[i];
-        const float dx = fmaxf(al.x, 1e-3f), dy = fmaxf(al.y, 1e-3f), dz = fmaxf(al.z, 1e-3f);
-        a.x = a.x / dx; a.y = a.y / dy; a.z = a.z / dz;
-        b.x = b.x / dx; b.y = b.y / dy; b.z = b.z / dz;
+        a = dn_demodulate(a, al);
+        b = dn_demodulate(b, al);
     }
     const float d = dn_lum(a) - dn_lum(b);
     out[i] = make_float4(0.5f * (a.x + b.x), 0.5f * (a.y + b.y), 0.5f * (a.z + b.z), miss ? 0.0f : 0.25f * (d * d));
@@ -614,42 +632,41 @@ __global__ void dn_var_extract_kernel(const float4 *in, float *var, uint32_t n) 
     if (i < n) var[i] = in[i].w;
 }
 
-// The prefilter of V_0: 7 x 7 window at spacing 1, g = w_n w_z w_id.  G0 and V of the tile + 3 pixels of halo in LDS ([row][x]: a wavefront's four
-// rows of 16 lanes read 16 consecutive float4 / float each); the colour passes through.
+// The 7 x 7 geometry window at spacing 1, g = w_n w_z w_id, of the prefilter of V_0 and of the temporal step's spatial estimate: G0 and NP floats
+// of payload per pixel of the tile + 3 pixels of halo are staged in LDS ([row][x]: a wavefront's four rows of 16 lanes read 16 consecutive
+// float4 / payloads each), by the whole workgroup; then a thread with `active` set (a pixel inside the image) whose pixel is no miss gets
+// sum[k] = the g-weighted sum of payload k over the window and gs = the sum of g, and true.
 constexpr int kDnPreR = 3;
 constexpr int kDnPreSide = kDnTile + 2 * kDnPreR;   // 22
-template <bool STRICT>
-__global__ __launch_bounds__(256) void dn_var_prefilter_kernel(const float4 *in, const float4 *g0, float4 *out, int w, int h, float sigma_normal,
-                                                               float sigma_depth) {
+template <int NP> struct alignas(4 * NP) DnPayload { float v[NP]; };
+template <bool STRICT, int NP, typename Load>
+__device__ __forceinline__ bool dn_window7(const float4 *g0, const Load payload, int w, int h, float sigma_normal, float sigma_depth, bool active, float (&sum)[NP],
+                                           float &gs) {
     __shared__ float4 s_g0[kDnPreSide * kDnPreSide];
-    __shared__ float s_v[kDnPreSide * kDnPreSide];
+    __shared__ DnPayload<NP> s_p[kDnPreSide * kDnPreSide];
     const int x0 = (int)blockIdx.x * kDnTile, y0 = (int)blockIdx.y * kDnTile;
     for (int k = (int)threadIdx.x; k < kDnPreSide * kDnPreSide; k += 256) {
         const int ly = k / kDnPreSide, lx = k - ly * kDnPreSide;
         const int gx = x0 - kDnPreR + lx, gy = y0 - kDnPreR + ly;
         float4 g = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
-        float v = 0.0f;
+        DnPayload<NP> v{};
         if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
             const size_t q = (size_t)gy * (size_t)w + (size_t)gx;
             g = g0[q];
-            v = in[q].w;
+            v = payload(q);
         }
         s_g0[k] = g;
-        s_v[k] = v;
+        s_p[k] = v;
     }
     __syncthreads();
+    if (!active) return false;
     const int x = x0 + ((int)threadIdx.x & 15), y = y0 + ((int)threadIdx.x >> 4);
-    if (x >= w || y >= h) return;
     auto guide = [&](int qx, int qy) -> float4 { return s_g0[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)]; };
-    const size_t pix = (size_t)y * (size_t)w + (size_t)x;
-    float4 o = in[pix];
     const float4 gp = guide(x, y);
-    if (gp.w < 0.0f) {   // a miss keeps V_0 = 0
-        out[pix] = o;
-        return;
-    }
+    if (gp.w < 0.0f) return false;
     const float grad = dn_depth_gradient(guide, x, y, w, h, gp.w);
-    float vs = 0.0f, gs = 0.0f;
+    gs = 0.0f;
+    for (int k = 0; k < NP; ++k) sum[k] = 0.0f;
 #pragma unroll
     for (int dy = -kDnPreR; dy <= kDnPreR; ++dy) {
 #pragma unroll
@@ -660,15 +677,27 @@ __global__ __launch_bounds__(256) void dn_var_prefilter_kernel(const float4 *in,
             if (gq.w < 0.0f) continue;
             const float dn = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
             if (!(dn > 0.0f)) continue;
-            const float wn = dn_pow<STRICT>(dn, sigma_normal);
-            const float dist = sqrtf((float)(dx * dx + dy * dy));
-            const float wz = dn_exp<STRICT>(-(fabsf(gp.w - gq.w) / (sigma_depth * (grad * 1.0f * dist + 1e-6f))));
-            const float g = wn * wz;
-            vs += g * s_v[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)];
+            const float g = dn_geometry_weight<STRICT>(1.0f, dn, gp.w, gq.w, grad, 1.0f, dx, dy, sigma_normal, sigma_depth);
+            const DnPayload<NP> v = s_p[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)];
+            for (int k = 0; k < NP; ++k) sum[k] += g * v.v[k];
             gs += g;
         }
     }
-    if (gs > 0.0f) o.w = vs / gs;
+    return true;
+}
+
+// The prefilter of V_0: the payload is V; the colour passes through, and a miss keeps V_0 = 0
+template <bool STRICT>
+__global__ __launch_bounds__(256) void dn_var_prefilter_kernel(const float4 *in, const float4 *g0, float4 *out, int w, int h, float sigma_normal,
+                                                               float sigma_depth) {
+    const int x = (int)blockIdx.x * kDnTile + ((int)threadIdx.x & 15), y = (int)blockIdx.y * kDnTile + ((int)threadIdx.x >> 4);
+    const bool inside = x < w && y < h;
+    float vs[1], gs;
+    const bool hit = dn_window7<STRICT, 1>(g0, [&](size_t q) { return DnPayload<1>{ { in[q].w } }; }, w, h, sigma_normal, sigma_depth, inside, vs, gs);
+    if (!inside) return;
+    const size_t pix = (size_t)y * (size_t)w + (size_t)x;
+    float4 o = in[pix];
+    if (hit && gs > 0.0f) o.w = vs[0] / gs;
     out[pix] = o;
 }
 
@@ -676,64 +705,47 @@ bool valid_var_params(const trg_denoise_var_params &q) {
     return q.iterations >= 0 && q.iterations <= TRG_DENOISE_MAX_ITERATIONS && q.sigma_lum > 0.0f && q.sigma_normal >= 0.0f && q.sigma_depth > 0.0f;
 }
 
-bool overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-    return (const char *)a < (const char *)b + b_bytes && (const char *)b < (const char *)a + a_bytes;
-}
-
 // var_out (may be null): a plane of width*height floats for V_N
 int denoise_variance(trg_ctx *c, DenoiseState &s, const float4 *halves, const float4 *guides, float4 *out, float *var_out, const trg_denoise_var_params *pp) {
+    const char *const who = "trg_denoise_variance";
     trg_denoise_var_params q;
     trg_denoise_var_default_params(&q);
     if (pp) q = *pp;
     if (!valid_var_params(q)) return fail(c, TRG_ERR_INVALID, "trg_denoise_variance: iterations must be 0..%d and the sigmas positive", TRG_DENOISE_MAX_ITERATIONS);
     const size_t n = (size_t)c->w * c->h, bytes = n * sizeof(float4);
     if (overlap(out, bytes, halves, 2 * bytes)) return fail(c, TRG_ERR_INVALID, "trg_denoise_variance: out_device overlaps halves_device");
-    hipStream_t st = c->stream;
-    const dim3 sgrid((uint32_t)((n + 255) / 256));
     const float4 *h1 = halves, *h2 = halves + n;
-    if (q.iterations == 0 && !var_out) {
-        hipLaunchKernelGGL(dn_var_combine_kernel, sgrid, dim3(256), 0, st, h1, h2, (const float4 *)nullptr, (const float4 *)nullptr, out, 0, 1, (uint32_t)n);
-        DN_HIPCHK(c, hipGetLastError());
-        return TRG_OK;
-    }
-    if (int rc = exclude_emitters(c, s, guides)) return rc;
-    hipLaunchKernelGGL(dn_var_combine_kernel, sgrid, dim3(256), 0, st, h1, h2, (const float4 *)s.fguide, guides + n, s.ping, q.demodulate ? 1 : 0, 0, (uint32_t)n);
-    DN_HIPCHK(c, hipGetLastError());
+    if (q.iterations == 0 && !var_out) return launch_each(c, who, dn_var_combine_kernel, n, h1, h2, nullptr, nullptr, out, 0, 1, n);
+    if (int rc = exclude_emitters(c, s, guides, who)) return rc;
+    if (int rc = launch_each(c, who, dn_var_combine_kernel, n, h1, h2, s.fguide, guides + n, s.ping, q.demodulate ? 1 : 0, 0, n)) return rc;
     const float4 *src = s.ping;
-    const dim3 grid((c->w + kDnTile - 1) / kDnTile, (c->h + kDnTile - 1) / kDnTile);
     if (q.prefilter) {
-        if (c->opt_strict)
-            hipLaunchKernelGGL((dn_var_prefilter_kernel<true>), grid, dim3(256), 0, st, src, (const float4 *)s.fguide, s.pong, (int)c->w, (int)c->h, q.sigma_normal, q.sigma_depth);
-        else
-            hipLaunchKernelGGL((dn_var_prefilter_kernel<false>), grid, dim3(256), 0, st, src, (const float4 *)s.fguide, s.pong, (int)c->w, (int)c->h, q.sigma_normal, q.sigma_depth);
-        DN_HIPCHK(c, hipGetLastError());
+        if (int rc = launch_tiles(c, who, DN_FOR_SETTING(c, dn_var_prefilter_kernel), src, s.fguide, s.pong, c->w, c->h, q.sigma_normal, q.sigma_depth)) return rc;
         src = s.pong;
     }
     if (q.iterations == 0) {   // only the variance was asked for beside the plain mean
-        hipLaunchKernelGGL(dn_var_extract_kernel, sgrid, dim3(256), 0, st, src, var_out, (uint32_t)n);
-        DN_HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(dn_var_combine_kernel, sgrid, dim3(256), 0, st, h1, h2, (const float4 *)nullptr, (const float4 *)nullptr, out, 0, 1, (uint32_t)n);
-        DN_HIPCHK(c, hipGetLastError());
-        return TRG_OK;
+        if (int rc = launch_each(c, who, dn_var_extract_kernel, n, src, var_out, n)) return rc;
+        return launch_each(c, who, dn_var_combine_kernel, n, h1, h2, nullptr, nullptr, out, 0, 1, n);
     }
-    AtrousParams p{};
-    p.g0 = s.fguide; p.g1 = guides + n;
-    p.w = (int)c->w; p.h = (int)c->h;
-    p.sigma_color = q.sigma_lum; p.sigma_normal = q.sigma_normal; p.sigma_depth = q.sigma_depth;
+    AtrousParams p = atrous_params(c, s, guides, q.sigma_lum, q.sigma_normal, q.sigma_depth);
     p.alpha = h1; p.var_out = var_out;
-    for (int i = 0; i < q.iterations; ++i) {
-        const bool last = i + 1 == q.iterations;
-        p.in = src;
-        p.out = last ? out : (src == s.ping ? s.pong : s.ping);
-        p.spacing = 1 << i;
-        p.demod_in = 0;   // the combine kernel demodulated
-        p.remod_out = (q.demodulate && last) ? 1 : 0;
-        p.last = last ? 1 : 0;
-        const hipError_t e = c->opt_strict ? launch_atrous<true, true>(p, st) : launch_atrous<false, true>(p, st);
-        if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_denoise_variance: launch failed: %s", hipGetErrorString(e));
-        src = p.out;
+    return atrous_run<true>(c, s, who, p, src, out, q.iterations, false, q.demodulate != 0);   // (the combine kernel demodulated)
+}
+
+// trg_render of `parts` consecutive runs of n frames from b on, run k into plane k of `img`, an image of the state that is zeroed first.  The
+// caller's accumulation buffer stays bound afterwards, also on failure
+int render_zeroed(trg_ctx *c, float4 *img, uint32_t parts, uint32_t b, uint32_t n, uint32_t bounces) {
+    const size_t npix = (size_t)c->w * c->h;
+    DN_HIPCHK(c, hipMemsetAsync(img, 0, parts * npix * sizeof(float4), c->stream));
+    float *const bound = c->accum;
+    const bool own = bound == c->accum_own;
+    int rc = TRG_OK;
+    for (uint32_t k = 0; k < parts && rc == TRG_OK; ++k) {
+        rc = trg_bind_accum(c, img + k * npix);
+        if (rc == TRG_OK) rc = trg_render(c, b + k * n, n, bounces, 0, c->h);
     }
-    return TRG_OK;
+    (void)trg_bind_accum(c, own ? nullptr : bound);   // (cannot fail: the pointer was bound before)
+    return rc;
 }
 
 int render_halves(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n, uint32_t bounces, float4 *halves, const char *who) {
@@ -742,22 +754,10 @@ int render_halves(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n, uint32_t 
     const size_t npix = (size_t)c->w * c->h, bytes = npix * sizeof(float4);
     if (overlap(halves, 2 * bytes, c->accum, bytes)) return fail(c, TRG_ERR_INVALID, "%s: halves_device overlaps the bound accumulation buffer", who);
     if (int rc = lazy_planes(c, s, s.half_acc, 2, "the half-sample images")) return rc;
-    hipStream_t st = c->stream;
-    DN_HIPCHK(c, hipMemsetAsync(s.half_acc, 0, 2 * bytes, st));
-    float *const bound = c->accum;
-    const bool own = bound == c->accum_own;
     const uint32_t half = n / 2u;
-    int rc = trg_bind_accum(c, s.half_acc);
-    if (rc == TRG_OK) rc = trg_render(c, b, half, bounces, 0, c->h);
-    if (rc == TRG_OK) rc = trg_bind_accum(c, s.half_acc + npix);
-    if (rc == TRG_OK) rc = trg_render(c, b + half, half, bounces, 0, c->h);
-    (void)trg_bind_accum(c, own ? nullptr : bound);   // (cannot fail: the pointer was bound before)
-    if (rc != TRG_OK) return rc;
+    if (int rc = render_zeroed(c, s.half_acc, 2, b, half, bounces)) return rc;
     const float f1 = (float)((double)((uint64_t)b + half) / (double)half), f2 = (float)((double)((uint64_t)b + n) / (double)half);
-    hipLaunchKernelGGL(dn_scale_halves_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, st, (const float4 *)s.half_acc, (const float4 *)(s.half_acc + npix),
-                       halves, halves + npix, f1, f2, (uint32_t)npix);
-    DN_HIPCHK(c, hipGetLastError());
-    return TRG_OK;
+    return launch_each(c, who, dn_scale_halves_kernel, npix, s.half_acc, s.half_acc + npix, halves, halves + npix, f1, f2, npix);
 }
 
 int render_denoised_variance(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n, uint32_t bounces, float4 *out, const trg_denoise_var_params *p, const char *who) {
@@ -813,10 +813,7 @@ __global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const Reproj
         return;
     }
     float dr = c.x, dg = c.y, db = c.z;
-    if (p.demod) {
-        const float4 a = p.g1[pix];
-        dr = dr / fmaxf(a.x, 1e-3f); dg = dg / fmaxf(a.y, 1e-3f); db = db / fmaxf(a.z, 1e-3f);
-    }
+    if (p.demod) { const float4 d = dn_demodulate(c, p.g1[pix]); dr = d.x; dg = d.y; db = d.z; }
     const float l = dn_lum(make_float4(dr, dg, db, 0.0f));
     float ir = 0.0f, ig = 0.0f, ib = 0.0f, m1 = 0.0f, m2 = 0.0f, nh = 0.0f, W = 0.0f;
     float nx = f.x, ny = f.y, nz = f.z;
@@ -872,17 +869,14 @@ __global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const Reproj
     p.iv[pix] = make_float4(ir, ig, ib, v0);
 }
 
-// V_0 of the pixels whose history is shorter than four frames: the variance of the moments over the 7 x 7 window, with the prefilter's weights.
-// F and the moments of the tile + 3 pixels of halo in LDS ([row][x], as dn_var_prefilter_kernel).  A tile in which no pixel needs it -- the usual
-// case once the camera has stood still for four frames -- leaves before staging anything: one ballot per wave, four flags in LDS.
+// V_0 of the pixels whose history is shorter than four frames: the variance of the moments over the 7 x 7 window, with the prefilter's weights
+// (dn_window7, the payload is the two moments).  A tile in which no pixel needs it -- the usual case once the camera has stood still for four
+// frames -- leaves before staging anything: one ballot per wave, four flags in LDS.
 template <bool STRICT>
 __global__ __launch_bounds__(256) void dn_temporal_spatial_kernel(const float4 *hc, const float4 *hm, const float4 *g0, float4 *iv, int w, int h,
                                                                   float sigma_normal, float sigma_depth) {
-    __shared__ float4 s_g0[kDnPreSide * kDnPreSide];
-    __shared__ float2 s_m[kDnPreSide * kDnPreSide];
     __shared__ int s_need[4];
-    const int x0 = (int)blockIdx.x * kDnTile, y0 = (int)blockIdx.y * kDnTile;
-    const int x = x0 + ((int)threadIdx.x & 15), y = y0 + ((int)threadIdx.x >> 4);
+    const int x = (int)blockIdx.x * kDnTile + ((int)threadIdx.x & 15), y = (int)blockIdx.y * kDnTile + ((int)threadIdx.x >> 4);
     const bool inside = x < w && y < h;
     const size_t pix = inside ? (size_t)y * (size_t)w + (size_t)x : 0;
     float N = 0.0f;
@@ -895,48 +889,12 @@ __global__ __launch_bounds__(256) void dn_temporal_spatial_kernel(const float4 *
     if ((threadIdx.x & 63u) == 0u) s_need[threadIdx.x >> 6] = any != 0ull ? 1 : 0;
     __syncthreads();
     if (!(s_need[0] | s_need[1] | s_need[2] | s_need[3])) return;   // (uniform over the workgroup)
-    for (int k = (int)threadIdx.x; k < kDnPreSide * kDnPreSide; k += 256) {
-        const int ly = k / kDnPreSide, lx = k - ly * kDnPreSide;
-        const int gx = x0 - kDnPreR + lx, gy = y0 - kDnPreR + ly;
-        float4 g = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
-        float2 m = make_float2(0.0f, 0.0f);
-        if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
-            const size_t q = (size_t)gy * (size_t)w + (size_t)gx;
-            g = g0[q];
-            const float4 mm = hm[q];
-            m = make_float2(mm.x, mm.y);
-        }
-        s_g0[k] = g;
-        s_m[k] = m;
-    }
-    __syncthreads();
-    if (!need) return;
-    auto guide = [&](int qx, int qy) -> float4 { return s_g0[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)]; };
-    const float4 gp = guide(x, y);
-    const float grad = dn_depth_gradient(guide, x, y, w, h, gp.w);
-    float s1 = 0.0f, s2 = 0.0f, gs = 0.0f;
-#pragma unroll
-    for (int dy = -kDnPreR; dy <= kDnPreR; ++dy) {
-#pragma unroll
-        for (int dx = -kDnPreR; dx <= kDnPreR; ++dx) {
-            const int qx = x + dx, qy = y + dy;
-            if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
-            const float4 gq = guide(qx, qy);
-            if (gq.w < 0.0f) continue;
-            const float dn = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
-            if (!(dn > 0.0f)) continue;
-            const float wn = dn_pow<STRICT>(dn, sigma_normal);
-            const float dist = sqrtf((float)(dx * dx + dy * dy));
-            const float wz = dn_exp<STRICT>(-(fabsf(gp.w - gq.w) / (sigma_depth * (grad * 1.0f * dist + 1e-6f))));
-            const float g = wn * wz;
-            const float2 m = s_m[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)];
-            s1 += g * m.x; s2 += g * m.y;
-            gs += g;
-        }
-    }
+    float sm[2], gs;
+    const auto moments = [&](size_t q) { const float4 mm = hm[q]; return DnPayload<2>{ { mm.x, mm.y } }; };
+    if (!dn_window7<STRICT, 2>(g0, moments, w, h, sigma_normal, sigma_depth, need, sm, gs)) return;
     float v0 = 0.0f;
     if (gs > 0.0f) {
-        const float M1 = s1 / gs, M2 = s2 / gs;
+        const float M1 = sm[0] / gs, M2 = sm[1] / gs;
         v0 = fmaxf(0.0f, M2 - M1 * M1) * 4.0f / N;
     }
     iv[pix].w = v0;
@@ -949,10 +907,7 @@ __global__ void dn_temporal_finish_kernel(const float4 *iv, const float4 *color,
     if (i >= n) return;
     float4 o = iv[i];
     if (var) var[i] = o.w;
-    if (demod && !(fguide[i].w < 0.0f)) {
-        const float4 a = g1[i];
-        o.x = o.x * fmaxf(a.x, 1e-3f); o.y = o.y * fmaxf(a.y, 1e-3f); o.z = o.z * fmaxf(a.z, 1e-3f);
-    }
+    if (demod && !(fguide[i].w < 0.0f)) o = dn_remodulate(o, g1[i]);
     o.w = color[i].w;
     out[i] = o;
 }
@@ -1023,8 +978,7 @@ int temporal_denoise(trg_ctx *c, DenoiseState &s, const float4 *color, const flo
         if (!(vp[k] - vp[k] == 0.0f)) return fail(c, TRG_ERR_INVALID, "%s: prev_view_proj is not finite", who);
     if (int rc = lazy_planes(c, s, s.hist[0], 4, "the history planes")) return rc;
     if (int rc = lazy_planes(c, s, s.hist[1], 4, "the history planes")) return rc;
-    hipStream_t st = c->stream;
-    if (int rc = exclude_emitters(c, s, guides)) return rc;
+    if (int rc = exclude_emitters(c, s, guides, who)) return rc;
     const float4 *prev = s.hist[s.hist_cur];
     float4 *next = s.hist[s.hist_cur ^ 1];
     ReprojectParams r{};
@@ -1034,45 +988,15 @@ int temporal_denoise(trg_ctx *c, DenoiseState &s, const float4 *color, const flo
     r.w = (int)c->w; r.h = (int)c->h; r.demod = q.demodulate ? 1 : 0;
     for (int k = 0; k < 16; ++k) r.vp[k] = vp[k];
     r.alpha = q.alpha; r.alpha_moments = q.alpha_moments; r.plane_tol = q.plane_tol; r.normal_tol = q.normal_tol; r.max_history = (float)q.max_history;
-    const dim3 grid((c->w + kDnTile - 1) / kDnTile, (c->h + kDnTile - 1) / kDnTile);
-    if (c->opt_strict) hipLaunchKernelGGL((dn_temporal_reproject_kernel<true>), grid, dim3(256), 0, st, r);
-    else hipLaunchKernelGGL((dn_temporal_reproject_kernel<false>), grid, dim3(256), 0, st, r);
-    DN_HIPCHK(c, hipGetLastError());
+    if (int rc = launch_tiles(c, who, DN_FOR_SETTING(c, dn_temporal_reproject_kernel), r)) return rc;
     s.hist_cur ^= 1;          // (enqueued: from here on the new planes are the history, also if a later launch fails)
     s.hist_valid = true;
-    if (c->opt_strict)
-        hipLaunchKernelGGL((dn_temporal_spatial_kernel<true>), grid, dim3(256), 0, st, (const float4 *)r.oc, (const float4 *)r.om, (const float4 *)s.fguide, s.ping,
-                           (int)c->w, (int)c->h, q.sigma_normal, q.sigma_depth);
-    else
-        hipLaunchKernelGGL((dn_temporal_spatial_kernel<false>), grid, dim3(256), 0, st, (const float4 *)r.oc, (const float4 *)r.om, (const float4 *)s.fguide, s.ping,
-                           (int)c->w, (int)c->h, q.sigma_normal, q.sigma_depth);
-    DN_HIPCHK(c, hipGetLastError());
-    if (iv_out) DN_HIPCHK(c, hipMemcpyAsync(iv_out, s.ping, bytes, hipMemcpyDeviceToDevice, st));
-    if (q.iterations == 0) {
-        hipLaunchKernelGGL(dn_temporal_finish_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)s.ping, color, (const float4 *)s.fguide,
-                           guides + n, out, var_out, q.demodulate ? 1 : 0, (uint32_t)n);
-        DN_HIPCHK(c, hipGetLastError());
-        return TRG_OK;
-    }
-    AtrousParams p{};
-    p.g0 = s.fguide; p.g1 = guides + n;
-    p.w = (int)c->w; p.h = (int)c->h;
-    p.sigma_color = q.sigma_lum; p.sigma_normal = q.sigma_normal; p.sigma_depth = q.sigma_depth;
+    if (int rc = launch_tiles(c, who, DN_FOR_SETTING(c, dn_temporal_spatial_kernel), r.oc, r.om, s.fguide, s.ping, c->w, c->h, q.sigma_normal, q.sigma_depth)) return rc;
+    if (iv_out) DN_HIPCHK(c, hipMemcpyAsync(iv_out, s.ping, bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (q.iterations == 0) return launch_each(c, who, dn_temporal_finish_kernel, n, s.ping, color, s.fguide, guides + n, out, var_out, q.demodulate ? 1 : 0, n);
+    AtrousParams p = atrous_params(c, s, guides, q.sigma_lum, q.sigma_normal, q.sigma_depth);
     p.alpha = color; p.var_out = var_out;
-    const float4 *src = s.ping;
-    for (int i = 0; i < q.iterations; ++i) {
-        const bool last = i + 1 == q.iterations;
-        p.in = src;
-        p.out = last ? out : (src == s.ping ? s.pong : s.ping);
-        p.spacing = 1 << i;
-        p.demod_in = 0;   // the reprojection kernel demodulated
-        p.remod_out = (q.demodulate && last) ? 1 : 0;
-        p.last = last ? 1 : 0;
-        const hipError_t e = c->opt_strict ? launch_atrous<true, true>(p, st) : launch_atrous<false, true>(p, st);
-        if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "%s: launch failed: %s", who, hipGetErrorString(e));
-        src = p.out;
-    }
-    return TRG_OK;
+    return atrous_run<true>(c, s, who, p, s.ping, out, q.iterations, false, q.demodulate != 0);   // (the reprojection kernel demodulated)
 }
 
 int render_temporal(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n, uint32_t bounces, float4 *out, const trg_temporal_params *p, const char *who) {
@@ -1086,31 +1010,67 @@ int render_temporal(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n, uint32_
     if (overlap(out, bytes, c->accum, bytes)) return fail(c, TRG_ERR_INVALID, "%s: out_device overlaps the bound accumulation buffer", who);
     if (int rc = lazy_planes(c, s, s.timg, 1, "the temporal path's image")) return rc;
     if (int rc = lazy_planes(c, s, s.tpos, 1, "the position plane")) return rc;
-    hipStream_t st = c->stream;
-    DN_HIPCHK(c, hipMemsetAsync(s.timg, 0, bytes, st));
-    float *const bound = c->accum;
-    const bool own = bound == c->accum_own;
-    int rc = trg_bind_accum(c, s.timg);
-    if (rc == TRG_OK) rc = trg_render(c, b, n, bounces, 0, c->h);
-    (void)trg_bind_accum(c, own ? nullptr : bound);   // (cannot fail: the pointer was bound before)
-    if (rc != TRG_OK) return rc;
+    if (int rc = render_zeroed(c, s.timg, 1, b, n, bounces)) return rc;
     const float f = (float)((double)((uint64_t)b + n) / (double)n);
-    hipLaunchKernelGGL(dn_scale_kernel, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, st, s.timg, f, (uint32_t)npix);
-    DN_HIPCHK(c, hipGetLastError());
-    if (int rc2 = guides_render(c, s, b, s.guides, s.tpos)) return rc2;
+    if (int rc = launch_each(c, who, dn_scale_kernel, npix, s.timg, f, npix)) return rc;
+    if (int rc = guides_render(c, s, b, s.guides, s.tpos)) return rc;
     const float zero[16] = {};
-    rc = temporal_denoise(c, s, s.timg, s.guides, s.tpos, s.have_prev_vp ? s.prev_vp : zero, s.have_prev_vp, out, nullptr, nullptr, p, who);
+    const int rc = temporal_denoise(c, s, s.timg, s.guides, s.tpos, s.have_prev_vp ? s.prev_vp : zero, s.have_prev_vp, out, nullptr, nullptr, p, who);
     if (rc != TRG_OK) return rc;
     for (int k = 0; k < 16; ++k) s.prev_vp[k] = vp_now[k];
     s.have_prev_vp = true;
     return TRG_OK;
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
+// The round trip of an entry point that works on host memory: device temporaries, uploads, the run (while rc is TRG_OK), downloads.  finish()
+// waits for the stream also after an error -- only then does the destructor free the temporaries -- and returns the first error.
+struct HostTrip {
+    trg_ctx *c;
+    const char *who;
+    int rc = TRG_OK;
+    struct { void *dev, *host; size_t bytes; } temp[8] = {};   // (trg_temporal_denoise_host has six)
+    int n = 0;
+    HostTrip(trg_ctx *c_, const char *who_) : c(c_), who(who_) {}
+    HostTrip(const HostTrip &) = delete;
+    ~HostTrip() { for (int k = 0; k < n; ++k) (void)hipFree(temp[k].dev); }
+    // a temporary of `bytes` that finish() copies to `host` (may be null: none); null after a failure
+    void *alloc(size_t bytes, void *host) {
+        if (rc != TRG_OK) return nullptr;
+        const hipError_t e = hipMalloc(&temp[n].dev, bytes ? bytes : 16);
+        if (e != hipSuccess) { rc = fail(c, TRG_ERR_DEVICE, "%s: hipMalloc(%zu) failed: %s", who, bytes, hipGetErrorString(e)); return nullptr; }
+        temp[n].host = host; temp[n].bytes = bytes;
+        return temp[n++].dev;
+    }
+    // a temporary with a copy of `host`
+    const float4 *upload(const float *host, size_t bytes) {
+        void *dev = alloc(bytes, nullptr);
+        if (dev) {
+            const hipError_t e = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "%s: copy failed: %s", who, hipGetErrorString(e));
+        }
+        return static_cast<const float4 *>(dev);
+    }
+    // a temporary for a result that goes to `host`; null when host is (an output nobody asked for)
+    template <typename T = float4>
+    T *result(float *host, size_t bytes) { return host ? static_cast<T *>(alloc(bytes, host)) : nullptr; }
+    int finish() {
+        for (int k = 0; k < n && rc == TRG_OK; ++k) {
+            if (!temp[k].host) continue;
+            const hipError_t e = hipMemcpyAsync(temp[k].host, temp[k].dev, temp[k].bytes, hipMemcpyDeviceToHost, c->stream);
+            if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "%s: copy failed: %s", who, hipGetErrorString(e));
+        }
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+        return rc;
+    }
 };
+
+// the state's result image of the _own entry points (allocated on first use); refused while the caller has bound it as the accumulation buffer
+int own_result(trg_ctx *c, DenoiseState &s, const char *who) {
+    if (int rc = lazy_planes(c, s, s.result, 1, "the result image")) return rc;
+    if (c->accum == reinterpret_cast<float *>(s.result)) return fail(c, TRG_ERR_INVALID, "%s: the state's image is bound as the accumulation buffer", who);
+    return TRG_OK;
+}
 
 int enter(trg_ctx *c, DenoiseState *&s, const char *who) {
     if (!c) return TRG_ERR_INVALID;
@@ -1156,11 +1116,7 @@ int trg_denoise_accum(trg_ctx *c, uint32_t frameIndex, const trg_denoise_params 
     DenoiseState *s;
     if (int rc = enter(c, s, "trg_denoise_accum")) return rc;
     if (!out_device) return fail(c, TRG_ERR_INVALID, "trg_denoise_accum: out_device is NULL");
-    if (!s->result) {
-        const hipError_t e = hipMalloc((void **)&s->result, s->pixels * sizeof(float4));
-        if (e != hipSuccess) return fail(c, TRG_ERR_NOMEM, "trg_denoise_accum: hipMalloc failed: %s", hipGetErrorString(e));
-    }
-    if (c->accum == reinterpret_cast<float *>(s->result)) return fail(c, TRG_ERR_INVALID, "trg_denoise_accum: the state's image is bound as the accumulation buffer");
+    if (int rc = own_result(c, *s, "trg_denoise_accum")) return rc;
     if (int rc = guides_render(c, *s, frameIndex, s->guides)) return rc;
     if (int rc = denoise(c, *s, reinterpret_cast<const float4 *>(c->accum), s->guides, s->result, p)) return rc;
     *out_device = s->result;
@@ -1183,49 +1139,32 @@ int trg_guides_read(trg_ctx *c, uint32_t frameIndex, float *guides_host) {
     DenoiseState *s;
     if (int rc = enter(c, s, "trg_guides_read")) return rc;
     if (!guides_host) return fail(c, TRG_ERR_INVALID, "trg_guides_read: guides_host is NULL");
-    const size_t bytes = 2 * (size_t)c->w * c->h * sizeof(float4);
-    DevBuf g;
-    DN_HIPCHK(c, g.alloc(bytes));
-    if (int rc = guides_render(c, *s, frameIndex, static_cast<float4 *>(g.p))) return rc;
-    DN_HIPCHK(c, hipMemcpyAsync(guides_host, g.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    DN_HIPCHK(c, hipStreamSynchronize(c->stream));
-    return TRG_OK;
+    HostTrip t(c, "trg_guides_read");
+    float4 *g = t.result(guides_host, 2 * s->pixels * sizeof(float4));
+    if (t.rc == TRG_OK) t.rc = guides_render(c, *s, frameIndex, g);
+    return t.finish();
 }
 
 int trg_denoise_host(trg_ctx *c, const float *color_in_host, const float *guides_host, float *out_host, const trg_denoise_params *p) {
     DenoiseState *s;
     if (int rc = enter(c, s, "trg_denoise_host")) return rc;
     if (!color_in_host || !guides_host || !out_host) return fail(c, TRG_ERR_INVALID, "trg_denoise_host: NULL buffer");
-    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
-    DevBuf in, g, out;
-    DN_HIPCHK(c, in.alloc(bytes)); DN_HIPCHK(c, g.alloc(2 * bytes)); DN_HIPCHK(c, out.alloc(bytes));
-    DN_HIPCHK(c, hipMemcpyAsync(in.p, color_in_host, bytes, hipMemcpyHostToDevice, c->stream));
-    DN_HIPCHK(c, hipMemcpyAsync(g.p, guides_host, 2 * bytes, hipMemcpyHostToDevice, c->stream));
-    int rc = denoise(c, *s, static_cast<const float4 *>(in.p), static_cast<const float4 *>(g.p), static_cast<float4 *>(out.p), p);
-    if (rc == TRG_OK) {
-        hipError_t e = hipMemcpyAsync(out_host, out.p, bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_denoise_host: copy failed: %s", hipGetErrorString(e));
-    }
-    const hipError_t e = hipStreamSynchronize(c->stream);   // also on an error: the temporaries are freed on return
-    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_denoise_host: %s", hipGetErrorString(e));
-    return rc;
+    const size_t bytes = s->pixels * sizeof(float4);
+    HostTrip t(c, "trg_denoise_host");
+    const float4 *in = t.upload(color_in_host, bytes), *g = t.upload(guides_host, 2 * bytes);
+    float4 *out = t.result(out_host, bytes);
+    if (t.rc == TRG_OK) t.rc = denoise(c, *s, in, g, out, p);
+    return t.finish();
 }
 
 int trg_render_denoised_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_denoise_params *p) {
     DenoiseState *s;
     if (int rc = enter(c, s, "trg_render_denoised_read")) return rc;
     if (!out_host) return fail(c, TRG_ERR_INVALID, "trg_render_denoised_read: out_host is NULL");
-    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
-    DevBuf out;
-    DN_HIPCHK(c, out.alloc(bytes));
-    int rc = trg_render_denoised(c, frameIndexBegin, spp, bounces, out.p, p);
-    if (rc == TRG_OK) {
-        hipError_t e = hipMemcpyAsync(out_host, out.p, bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_denoised_read: copy failed: %s", hipGetErrorString(e));
-    }
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_denoised_read: %s", hipGetErrorString(e));
-    return rc;
+    HostTrip t(c, "trg_render_denoised_read");
+    float4 *out = t.result(out_host, s->pixels * sizeof(float4));
+    if (t.rc == TRG_OK) t.rc = trg_render_denoised(c, frameIndexBegin, spp, bounces, out, p);
+    return t.finish();
 }
 
 void trg_denoise_var_default_params(trg_denoise_var_params *p) {
@@ -1258,8 +1197,7 @@ int trg_render_denoised_variance_own(trg_ctx *c, uint32_t frameIndexBegin, uint3
     DenoiseState *s;
     if (int rc = enter(c, s, "trg_render_denoised_variance_own")) return rc;
     if (!out_device) return fail(c, TRG_ERR_INVALID, "trg_render_denoised_variance_own: out_device is NULL");
-    if (int rc = lazy_planes(c, *s, s->result, 1, "the result image")) return rc;
-    if (c->accum == reinterpret_cast<float *>(s->result)) return fail(c, TRG_ERR_INVALID, "trg_render_denoised_variance_own: the state's image is bound as the accumulation buffer");
+    if (int rc = own_result(c, *s, "trg_render_denoised_variance_own")) return rc;
     if (int rc = render_denoised_variance(c, *s, frameIndexBegin, spp, bounces, s->result, p, "trg_render_denoised_variance_own")) return rc;
     *out_device = s->result;
     return TRG_OK;
@@ -1269,55 +1207,33 @@ int trg_render_halves_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, u
     DenoiseState *s;
     if (int rc = enter(c, s, "trg_render_halves_read")) return rc;
     if (!halves_host) return fail(c, TRG_ERR_INVALID, "trg_render_halves_read: halves_host is NULL");
-    const size_t bytes = 2 * (size_t)c->w * c->h * sizeof(float4);
-    DevBuf hv;
-    DN_HIPCHK(c, hv.alloc(bytes));
-    int rc = render_halves(c, *s, frameIndexBegin, spp, bounces, static_cast<float4 *>(hv.p), "trg_render_halves_read");
-    if (rc == TRG_OK) {
-        hipError_t e = hipMemcpyAsync(halves_host, hv.p, bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_halves_read: copy failed: %s", hipGetErrorString(e));
-    }
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_halves_read: %s", hipGetErrorString(e));
-    return rc;
+    HostTrip t(c, "trg_render_halves_read");
+    float4 *hv = t.result(halves_host, 2 * s->pixels * sizeof(float4));
+    if (t.rc == TRG_OK) t.rc = render_halves(c, *s, frameIndexBegin, spp, bounces, hv, "trg_render_halves_read");
+    return t.finish();
 }
 
 int trg_denoise_variance_host(trg_ctx *c, const float *halves_host, const float *guides_host, float *out_host, float *var_host, const trg_denoise_var_params *p) {
     DenoiseState *s;
     if (int rc = enter(c, s, "trg_denoise_variance_host")) return rc;
     if (!halves_host || !guides_host || !out_host) return fail(c, TRG_ERR_INVALID, "trg_denoise_variance_host: NULL buffer");
-    const size_t npix = (size_t)c->w * c->h, bytes = npix * sizeof(float4);
-    DevBuf in, g, out, var;
-    DN_HIPCHK(c, in.alloc(2 * bytes)); DN_HIPCHK(c, g.alloc(2 * bytes)); DN_HIPCHK(c, out.alloc(bytes));
-    if (var_host) DN_HIPCHK(c, var.alloc(npix * sizeof(float)));
-    DN_HIPCHK(c, hipMemcpyAsync(in.p, halves_host, 2 * bytes, hipMemcpyHostToDevice, c->stream));
-    DN_HIPCHK(c, hipMemcpyAsync(g.p, guides_host, 2 * bytes, hipMemcpyHostToDevice, c->stream));
-    int rc = denoise_variance(c, *s, static_cast<const float4 *>(in.p), static_cast<const float4 *>(g.p), static_cast<float4 *>(out.p), static_cast<float *>(var.p), p);
-    if (rc == TRG_OK) {
-        hipError_t e = hipMemcpyAsync(out_host, out.p, bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && var_host) e = hipMemcpyAsync(var_host, var.p, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_denoise_variance_host: copy failed: %s", hipGetErrorString(e));
-    }
-    const hipError_t e = hipStreamSynchronize(c->stream);   // also on an error: the temporaries are freed on return
-    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_denoise_variance_host: %s", hipGetErrorString(e));
-    return rc;
+    const size_t bytes = s->pixels * sizeof(float4);
+    HostTrip t(c, "trg_denoise_variance_host");
+    const float4 *in = t.upload(halves_host, 2 * bytes), *g = t.upload(guides_host, 2 * bytes);
+    float4 *out = t.result(out_host, bytes);
+    float *var = t.result<float>(var_host, s->pixels * sizeof(float));
+    if (t.rc == TRG_OK) t.rc = denoise_variance(c, *s, in, g, out, var, p);
+    return t.finish();
 }
 
 int trg_render_denoised_variance_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_denoise_var_params *p) {
     DenoiseState *s;
     if (int rc = enter(c, s, "trg_render_denoised_variance_read")) return rc;
     if (!out_host) return fail(c, TRG_ERR_INVALID, "trg_render_denoised_variance_read: out_host is NULL");
-    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
-    DevBuf out;
-    DN_HIPCHK(c, out.alloc(bytes));
-    int rc = render_denoised_variance(c, *s, frameIndexBegin, spp, bounces, static_cast<float4 *>(out.p), p, "trg_render_denoised_variance_read");
-    if (rc == TRG_OK) {
-        hipError_t e = hipMemcpyAsync(out_host, out.p, bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_denoised_variance_read: copy failed: %s", hipGetErrorString(e));
-    }
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_denoised_variance_read: %s", hipGetErrorString(e));
-    return rc;
+    HostTrip t(c, "trg_render_denoised_variance_read");
+    float4 *out = t.result(out_host, s->pixels * sizeof(float4));
+    if (t.rc == TRG_OK) t.rc = render_denoised_variance(c, *s, frameIndexBegin, spp, bounces, out, p, "trg_render_denoised_variance_read");
+    return t.finish();
 }
 
 void trg_temporal_default_params(trg_temporal_params *p) {
@@ -1381,8 +1297,7 @@ int trg_render_temporal_own(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, 
     DenoiseState *s;
     if (int rc = enter(c, s, "trg_render_temporal_own")) return rc;
     if (!out_device) return fail(c, TRG_ERR_INVALID, "trg_render_temporal_own: out_device is NULL");
-    if (int rc = lazy_planes(c, *s, s->result, 1, "the result image")) return rc;
-    if (c->accum == reinterpret_cast<float *>(s->result)) return fail(c, TRG_ERR_INVALID, "trg_render_temporal_own: the state's image is bound as the accumulation buffer");
+    if (int rc = own_result(c, *s, "trg_render_temporal_own")) return rc;
     if (int rc = render_temporal(c, *s, frameIndexBegin, spp, bounces, s->result, p, "trg_render_temporal_own")) return rc;
     *out_device = s->result;
     return TRG_OK;
@@ -1392,15 +1307,11 @@ int trg_guides_pos_read(trg_ctx *c, uint32_t frameIndex, float *guides_host, flo
     DenoiseState *s;
     if (int rc = enter(c, s, "trg_guides_pos_read")) return rc;
     if (!guides_host || !pos_host) return fail(c, TRG_ERR_INVALID, "trg_guides_pos_read: NULL buffer");
-    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
-    DevBuf g;
-    DN_HIPCHK(c, g.alloc(3 * bytes));
-    float4 *gd = static_cast<float4 *>(g.p);
-    if (int rc = guides_render(c, *s, frameIndex, gd, gd + 2 * (size_t)c->w * c->h)) return rc;
-    DN_HIPCHK(c, hipMemcpyAsync(guides_host, g.p, 2 * bytes, hipMemcpyDeviceToHost, c->stream));
-    DN_HIPCHK(c, hipMemcpyAsync(pos_host, static_cast<char *>(g.p) + 2 * bytes, bytes, hipMemcpyDeviceToHost, c->stream));
-    DN_HIPCHK(c, hipStreamSynchronize(c->stream));
-    return TRG_OK;
+    const size_t bytes = s->pixels * sizeof(float4);
+    HostTrip t(c, "trg_guides_pos_read");
+    float4 *g = t.result(guides_host, 2 * bytes), *x = t.result(pos_host, bytes);
+    if (t.rc == TRG_OK) t.rc = guides_render(c, *s, frameIndex, g, x);
+    return t.finish();
 }
 
 int trg_temporal_denoise_host(trg_ctx *c, const float *color_in_host, const float *guides_host, const float *pos_host, const float prev_view_proj[16], float *out_host,
@@ -1408,42 +1319,23 @@ int trg_temporal_denoise_host(trg_ctx *c, const float *color_in_host, const floa
     DenoiseState *s;
     if (int rc = enter(c, s, "trg_temporal_denoise_host")) return rc;
     if (!color_in_host || !guides_host || !pos_host || !prev_view_proj || !out_host) return fail(c, TRG_ERR_INVALID, "trg_temporal_denoise_host: NULL buffer");
-    const size_t npix = (size_t)c->w * c->h, bytes = npix * sizeof(float4);
-    DevBuf in, g, x, out, iv, var;
-    DN_HIPCHK(c, in.alloc(bytes)); DN_HIPCHK(c, g.alloc(2 * bytes)); DN_HIPCHK(c, x.alloc(bytes)); DN_HIPCHK(c, out.alloc(bytes));
-    if (iv_host) DN_HIPCHK(c, iv.alloc(bytes));
-    if (var_host) DN_HIPCHK(c, var.alloc(npix * sizeof(float)));
-    DN_HIPCHK(c, hipMemcpyAsync(in.p, color_in_host, bytes, hipMemcpyHostToDevice, c->stream));
-    DN_HIPCHK(c, hipMemcpyAsync(g.p, guides_host, 2 * bytes, hipMemcpyHostToDevice, c->stream));
-    DN_HIPCHK(c, hipMemcpyAsync(x.p, pos_host, bytes, hipMemcpyHostToDevice, c->stream));
-    int rc = temporal_denoise(c, *s, static_cast<const float4 *>(in.p), static_cast<const float4 *>(g.p), static_cast<const float4 *>(x.p), prev_view_proj, true,
-                              static_cast<float4 *>(out.p), static_cast<float4 *>(iv.p), static_cast<float *>(var.p), p, "trg_temporal_denoise_host");
-    if (rc == TRG_OK) {
-        hipError_t e = hipMemcpyAsync(out_host, out.p, bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && iv_host) e = hipMemcpyAsync(iv_host, iv.p, bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && var_host) e = hipMemcpyAsync(var_host, var.p, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_temporal_denoise_host: copy failed: %s", hipGetErrorString(e));
-    }
-    const hipError_t e = hipStreamSynchronize(c->stream);   // also on an error: the temporaries are freed on return
-    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_temporal_denoise_host: %s", hipGetErrorString(e));
-    return rc;
+    const size_t bytes = s->pixels * sizeof(float4);
+    HostTrip t(c, "trg_temporal_denoise_host");
+    const float4 *in = t.upload(color_in_host, bytes), *g = t.upload(guides_host, 2 * bytes), *x = t.upload(pos_host, bytes);
+    float4 *out = t.result(out_host, bytes), *iv = t.result(iv_host, bytes);
+    float *var = t.result<float>(var_host, s->pixels * sizeof(float));
+    if (t.rc == TRG_OK) t.rc = temporal_denoise(c, *s, in, g, x, prev_view_proj, true, out, iv, var, p, "trg_temporal_denoise_host");
+    return t.finish();
 }
 
 int trg_render_temporal_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_temporal_params *p) {
     DenoiseState *s;
     if (int rc = enter(c, s, "trg_render_temporal_read")) return rc;
     if (!out_host) return fail(c, TRG_ERR_INVALID, "trg_render_temporal_read: out_host is NULL");
-    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
-    DevBuf out;
-    DN_HIPCHK(c, out.alloc(bytes));
-    int rc = render_temporal(c, *s, frameIndexBegin, spp, bounces, static_cast<float4 *>(out.p), p, "trg_render_temporal_read");
-    if (rc == TRG_OK) {
-        hipError_t e = hipMemcpyAsync(out_host, out.p, bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_temporal_read: copy failed: %s", hipGetErrorString(e));
-    }
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    if (rc == TRG_OK && e != hipSuccess) rc = fail(c, TRG_ERR_DEVICE, "trg_render_temporal_read: %s", hipGetErrorString(e));
-    return rc;
+    HostTrip t(c, "trg_render_temporal_read");
+    float4 *out = t.result(out_host, s->pixels * sizeof(float4));
+    if (t.rc == TRG_OK) t.rc = render_temporal(c, *s, frameIndexBegin, spp, bounces, out, p, "trg_render_temporal_read");
+    return t.finish();
 }
 
 }  // extern "C"

@@ -114,40 +114,43 @@ def default_params():
     return p
 
 
-def make_params(params=None, **kw):
-    """Params from the library's defaults, a Params / dict, and keyword overrides (iterations, sigma_color, sigma_normal, sigma_depth, demodulate)."""
-    p = default_params()
-    src = {}
-    if isinstance(params, Params):
-        src = {f: getattr(params, f) for f, _ in Params._fields_}
-    elif params:
-        src = dict(params)
+def _unpack(params):
+    return {f: getattr(params, f) for f, _ in params._fields_}
+
+
+def _make(cls, defaults_symbol, ints, what, params, kw):
+    """A `cls` from the library's defaults, a `cls` / dict, and keyword overrides."""
+    p = cls()
+    getattr(load(), defaults_symbol)(C.byref(p))
+    src = _unpack(params) if isinstance(params, cls) else dict(params or {})
     src.update(kw)
     for k, v in src.items():
-        if k not in dict(Params._fields_):
-            raise TypeError("unknown denoise parameter %r" % k)
-        setattr(p, k, int(v) if k in ("iterations", "demodulate") else float(v))
+        if k not in dict(cls._fields_):
+            raise TypeError("unknown %s parameter %r" % (what, k))
+        setattr(p, k, int(v) if k in ints else float(v))
     return p
 
 
-_VAR_DEFAULTS = dict(iterations=5, sigma_lum=4.0, sigma_normal=128.0, sigma_depth=1.0, demodulate=1, prefilter=1)   # the header's
+def make_params(params=None, **kw):
+    """Params from the library's defaults, a Params / dict, and keyword overrides (iterations, sigma_color, sigma_normal, sigma_depth, demodulate)."""
+    return _make(Params, "trg_denoise_default_params", ("iterations", "demodulate"), "denoise", params, kw)
+
+
+# the header's defaults, for the references (no library needed)
+_DEFAULTS = dict(iterations=5, sigma_color=4.0, sigma_normal=128.0, sigma_depth=1.0, demodulate=1)
+_VAR_DEFAULTS = dict(iterations=5, sigma_lum=4.0, sigma_normal=128.0, sigma_depth=1.0, demodulate=1, prefilter=1)
+_TEMPORAL_DEFAULTS = dict(iterations=5, sigma_lum=4.0, sigma_normal=128.0, sigma_depth=1.0, demodulate=1, alpha=0.2, alpha_moments=0.2,
+                          plane_tol=0.02, normal_tol=0.9, max_history=32)
 
 
 def make_var_params(params=None, **kw):
     """VarParams from the library's defaults, a VarParams / dict, and keyword overrides."""
-    p = VarParams()
-    load().trg_denoise_var_default_params(C.byref(p))
-    src = {}
-    if isinstance(params, VarParams):
-        src = {f: getattr(params, f) for f, _ in VarParams._fields_}
-    elif params:
-        src = dict(params)
-    src.update(kw)
-    for k, v in src.items():
-        if k not in dict(VarParams._fields_):
-            raise TypeError("unknown variance-guided denoise parameter %r" % k)
-        setattr(p, k, int(v) if k in ("iterations", "demodulate", "prefilter") else float(v))
-    return p
+    return _make(VarParams, "trg_denoise_var_default_params", ("iterations", "demodulate", "prefilter"), "variance-guided denoise", params, kw)
+
+
+def make_temporal_params(params=None, **kw):
+    """TemporalParams from the library's defaults, a TemporalParams / dict, and keyword overrides."""
+    return _make(TemporalParams, "trg_temporal_default_params", ("iterations", "demodulate", "max_history"), "temporal denoise", params, kw)
 
 
 def _is_tensor(a):
@@ -166,16 +169,22 @@ def _chk(ctx, rc):
         raise capi.TrgError(rc, (ctx.L.trg_last_error(ctx.h_ctx) or b"").decode())
 
 
+def _fill(ctx, device_entry, read_entry, args, out, planes, what, *params):
+    """`out` a float32 ROCm tensor: filled in place through the device entry point, on the context's stream (and returned); None: a numpy array
+    through the _read entry point, which waits.  planes = 2: [2, h, w, 4], 0: [h, w, 4]."""
+    L = load()
+    shape = ((planes,) if planes else ()) + (ctx.h, ctx.w, 4)
+    if out is not None and _is_tensor(out):
+        _chk(ctx, getattr(L, device_entry)(ctx.h_ctx, *args, _tensor_ptr(out, shape, what), *params))
+        return out
+    o = np.empty(shape, np.float32)
+    _chk(ctx, getattr(L, read_entry)(ctx.h_ctx, *args, o.ctypes.data, *params))
+    return o
+
+
 def guides(ctx, frame_index, out=None):
     """trg_guides_render.  out = a [2, h, w, 4] float32 ROCm tensor: filled in place on the context's stream (and returned); None: a numpy array."""
-    L = load()
-    shape = (2, ctx.h, ctx.w, 4)
-    if out is not None and _is_tensor(out):
-        _chk(ctx, L.trg_guides_render(ctx.h_ctx, frame_index, _tensor_ptr(out, shape, "guides")))
-        return out
-    g = np.empty(shape, np.float32)
-    _chk(ctx, L.trg_guides_read(ctx.h_ctx, frame_index, g.ctypes.data))
-    return g
+    return _fill(ctx, "trg_guides_render", "trg_guides_read", (frame_index,), out, 2, "guides")
 
 
 def denoise(ctx, color, guides, out=None, params=None, **kw):
@@ -200,27 +209,13 @@ def denoise(ctx, color, guides, out=None, params=None, **kw):
 
 def render_denoised(ctx, frame_begin, spp, bounces, out=None, params=None, **kw):
     """trg_render_denoised: frames [frame_begin, frame_begin + spp) into the context's accumulation buffer, guides of frame_begin, the filter."""
-    L = load()
-    p = make_params(params, **kw)
-    if out is not None and _is_tensor(out):
-        _chk(ctx, L.trg_render_denoised(ctx.h_ctx, frame_begin, spp, bounces, _tensor_ptr(out, (ctx.h, ctx.w, 4), "out"), C.byref(p)))
-        return out
-    o = np.empty((ctx.h, ctx.w, 4), np.float32)
-    _chk(ctx, L.trg_render_denoised_read(ctx.h_ctx, frame_begin, spp, bounces, o.ctypes.data, C.byref(p)))
-    return o
+    return _fill(ctx, "trg_render_denoised", "trg_render_denoised_read", (frame_begin, spp, bounces), out, 0, "out", C.byref(make_params(params, **kw)))
 
 
 def render_halves(ctx, frame_begin, spp, bounces, out=None):
     """trg_render_halves: frames [frame_begin, frame_begin + spp/2) and [frame_begin + spp/2, frame_begin + spp) rendered from zeroed images of the
     state and scaled to the means of their samples -> [2, h, w, 4].  spp even, >= 2.  The bound accumulation buffer is not written; the rays count."""
-    L = load()
-    shape = (2, ctx.h, ctx.w, 4)
-    if out is not None and _is_tensor(out):
-        _chk(ctx, L.trg_render_halves(ctx.h_ctx, frame_begin, spp, bounces, _tensor_ptr(out, shape, "halves")))
-        return out
-    hv = np.empty(shape, np.float32)
-    _chk(ctx, L.trg_render_halves_read(ctx.h_ctx, frame_begin, spp, bounces, hv.ctypes.data))
-    return hv
+    return _fill(ctx, "trg_render_halves", "trg_render_halves_read", (frame_begin, spp, bounces), out, 2, "halves")
 
 
 def denoise_variance(ctx, halves, guides, out=None, params=None, return_variance=False, **kw):
@@ -249,36 +244,8 @@ def denoise_variance(ctx, halves, guides, out=None, params=None, return_variance
 
 def render_denoised_variance(ctx, frame_begin, spp, bounces, out=None, params=None, **kw):
     """trg_render_denoised_variance: render_halves, guides of frame_begin, denoise_variance, on one stream."""
-    L = load()
-    p = make_var_params(params, **kw)
-    if out is not None and _is_tensor(out):
-        _chk(ctx, L.trg_render_denoised_variance(ctx.h_ctx, frame_begin, spp, bounces, _tensor_ptr(out, (ctx.h, ctx.w, 4), "out"), C.byref(p)))
-        return out
-    o = np.empty((ctx.h, ctx.w, 4), np.float32)
-    _chk(ctx, L.trg_render_denoised_variance_read(ctx.h_ctx, frame_begin, spp, bounces, o.ctypes.data, C.byref(p)))
-    return o
-
-
-_TEMPORAL_DEFAULTS = dict(iterations=5, sigma_lum=4.0, sigma_normal=128.0, sigma_depth=1.0, demodulate=1, alpha=0.2, alpha_moments=0.2,
-                          plane_tol=0.02, normal_tol=0.9, max_history=32)   # the header's
-_TEMPORAL_INTS = ("iterations", "demodulate", "max_history")
-
-
-def make_temporal_params(params=None, **kw):
-    """TemporalParams from the library's defaults, a TemporalParams / dict, and keyword overrides."""
-    p = TemporalParams()
-    load().trg_temporal_default_params(C.byref(p))
-    src = {}
-    if isinstance(params, TemporalParams):
-        src = {f: getattr(params, f) for f, _ in TemporalParams._fields_}
-    elif params:
-        src = dict(params)
-    src.update(kw)
-    for k, v in src.items():
-        if k not in dict(TemporalParams._fields_):
-            raise TypeError("unknown temporal denoise parameter %r" % k)
-        setattr(p, k, int(v) if k in _TEMPORAL_INTS else float(v))
-    return p
+    return _fill(ctx, "trg_render_denoised_variance", "trg_render_denoised_variance_read", (frame_begin, spp, bounces), out, 0, "out",
+                 C.byref(make_var_params(params, **kw)))
 
 
 def guides_pos(ctx, frame_index, out=None, pos=None):
@@ -355,14 +322,7 @@ def temporal_denoise(ctx, color, guides, pos, prev_vp, out=None, params=None, re
 def render_temporal(ctx, frame_begin, spp, bounces, out=None, params=None, **kw):
     """trg_render_temporal: frames [frame_begin, frame_begin + spp) from a zeroed image of the state, guides and positions of frame_begin, one
     temporal step against the camera of the previous call.  The bound accumulation buffer is not touched; the rays count."""
-    L = load()
-    p = make_temporal_params(params, **kw)
-    if out is not None and _is_tensor(out):
-        _chk(ctx, L.trg_render_temporal(ctx.h_ctx, frame_begin, spp, bounces, _tensor_ptr(out, (ctx.h, ctx.w, 4), "out"), C.byref(p)))
-        return out
-    o = np.empty((ctx.h, ctx.w, 4), np.float32)
-    _chk(ctx, L.trg_render_temporal_read(ctx.h_ctx, frame_begin, spp, bounces, o.ctypes.data, C.byref(p)))
-    return o
+    return _fill(ctx, "trg_render_temporal", "trg_render_temporal_read", (frame_begin, spp, bounces), out, 0, "out", C.byref(make_temporal_params(params, **kw)))
 
 
 def release(ctx):
@@ -482,29 +442,30 @@ def emitter_mask(g1, material_ids):
     return inside & (mats[np.where(inside, prim, 0)] == 2)
 
 
+def _options(defaults, cls, params, kw):
+    """The header's defaults, then a `cls` structure or a dict, then keywords; the iteration count checked against the header's range."""
+    q = dict(defaults)
+    if isinstance(params, cls):
+        params = _unpack(params)
+    q.update(params or {}); q.update(kw)
+    if not 0 <= int(q["iterations"]) <= MAX_ITERATIONS:
+        raise ValueError("iterations must be 0..%d" % MAX_ITERATIONS)
+    return q
+
+
 def reference_denoise(color, g0, g1, params=None, material_ids=None, dtype=np.float64, **kw):
     """float64 evaluation of trg_denoise's definition.  color [h, w, 4], g0 / g1 [h, w, 4] (float32 as the device sees them); params: a Params,
     a dict or keywords; the defaults are the header's (no library needed); material_ids: those of the context's scene (None: no scene, no
     emitters); dtype: the working precision (see above).  Returns [h, w, 4] of `dtype`."""
     dtype = _dtype(dtype)
-    q = dict(iterations=5, sigma_color=4.0, sigma_normal=128.0, sigma_depth=1.0, demodulate=1)
-    if isinstance(params, Params):
-        params = {f: getattr(params, f) for f, _ in Params._fields_}
-    q.update(params or {}); q.update(kw)
+    q = _options(_DEFAULTS, Params, params, kw)
     it = int(q["iterations"])
-    if not 0 <= it <= MAX_ITERATIONS:
-        raise ValueError("iterations must be 0..%d" % MAX_ITERATIONS)
-    color = np.asarray(color)
-    out = color.astype(dtype)
+    out = np.asarray(color).astype(dtype)
     if it == 0:
         return out
     # the parameters as the device holds them: fp32
     sc, sn, sd = (float(np.float32(q[k])) for k in ("sigma_color", "sigma_normal", "sigma_depth"))
-    g0 = np.asarray(g0, np.float32).astype(dtype)
-    if material_ids is not None:                       # a directly seen emitter is kept out of the filter like a miss
-        g0[emitter_mask(g1, material_ids), 3] = -1.0
-    alb = np.maximum(np.asarray(g1, np.float32)[..., :3].astype(dtype), float(np.float32(1e-3)))
-    miss = g0[..., 3] < 0
+    g0, alb, miss = _filter_inputs(g0, g1, material_ids, dtype)
     I = out[..., :3].copy()
     demod = bool(q["demodulate"])
     if demod:
@@ -512,15 +473,10 @@ def reference_denoise(color, g0, g1, params=None, material_ids=None, dtype=np.fl
     for i in range(it):
         s = 1 << i
         W = atrous_weights(I, g0, s, sc, sn, sd, dtype=dtype)
-        acc = np.zeros_like(I)
-        for dy in range(-2, 3):
-            for dx in range(-2, 3):
-                Iq, _ = _shift(I, dx * s, dy * s)
-                acc += W[dy + 2, dx + 2][..., None] * Iq
         wsum = W.sum((0, 1))
         keep = miss | ~(wsum > 0)
         with np.errstate(invalid="ignore", divide="ignore"):
-            I = np.where(keep[..., None], I, acc / wsum[..., None])
+            I = np.where(keep[..., None], I, _gather(W, I, s) / wsum[..., None])
     if demod:
         I = np.where(miss[..., None], I, I * alb)
     out[..., :3] = I
@@ -539,7 +495,6 @@ def _gather(W, a, spacing):
 
 def _atrous_variance_loop(I, V, g0, miss, alb, it, sl, sn, sd, demod, dtype):
     """Iterations 0 .. it-1 of the variance-guided filter and the remodulation, on arrays of `dtype` (g0 with the emitters already marked)."""
-    gather = _gather
     binom = (0.25, 0.5, 0.25)
     valid = (~miss).astype(dtype)
     for i in range(it):
@@ -563,8 +518,8 @@ def _atrous_variance_loop(I, V, g0, miss, alb, it, sl, sn, sd, demod, dtype):
         wsum = W.sum((0, 1))
         keep = miss | ~(wsum > 0)
         with np.errstate(invalid="ignore", divide="ignore"):
-            I = np.where(keep[..., None], I, gather(W, I, s) / wsum[..., None])
-            V = np.where(keep, V, gather(W * W, V, s) / wsum ** 2)
+            I = np.where(keep[..., None], I, _gather(W, I, s) / wsum[..., None])
+            V = np.where(keep, V, _gather(W * W, V, s) / wsum ** 2)
     if demod:
         I = np.where(miss[..., None], I, I * alb)
     return I, V
@@ -573,7 +528,7 @@ def _atrous_variance_loop(I, V, g0, miss, alb, it, sl, sn, sd, demod, dtype):
 def _filter_inputs(g0, g1, material_ids, dtype):
     """(the filter's G0 with the emitters marked as misses, the clamped albedo, the miss mask) in `dtype`."""
     g0 = np.asarray(g0, np.float32).astype(dtype)
-    if material_ids is not None:
+    if material_ids is not None:                       # a directly seen emitter is kept out of the filter like a miss
         g0[emitter_mask(g1, material_ids), 3] = -1.0
     alb = np.maximum(np.asarray(g1, np.float32)[..., :3].astype(dtype), float(np.float32(1e-3)))
     return g0, alb, g0[..., 3] < 0
@@ -585,18 +540,12 @@ def reference_atrous_variance(I0, V0, g0, g1, params=None, material_ids=None, dt
     sigma_normal, sigma_depth and demodulate are read (defaults: the header's).  Returns (rgb [h, w, 3], V_N [h, w]) of `dtype`.
     reference_denoise_variance is its start, this loop, and the alpha channel; reference_temporal supplies another start."""
     dtype = _dtype(dtype)
-    q = dict(_VAR_DEFAULTS)
-    if isinstance(params, C.Structure):
-        params = {f: getattr(params, f) for f, _ in params._fields_}
-    q.update(params or {}); q.update(kw)
-    it = int(q["iterations"])
-    if not 0 <= it <= MAX_ITERATIONS:
-        raise ValueError("iterations must be 0..%d" % MAX_ITERATIONS)
+    q = _options(_VAR_DEFAULTS, C.Structure, params, kw)
     sl, sn, sd = (float(np.float32(q[k])) for k in ("sigma_lum", "sigma_normal", "sigma_depth"))
     g0, alb, miss = _filter_inputs(g0, g1, material_ids, dtype)
     I = np.asarray(I0)[..., :3].astype(dtype)
     V = np.asarray(V0).astype(dtype)
-    return _atrous_variance_loop(I, V, g0, miss, alb, it, sl, sn, sd, bool(q["demodulate"]), dtype)
+    return _atrous_variance_loop(I, V, g0, miss, alb, int(q["iterations"]), sl, sn, sd, bool(q["demodulate"]), dtype)
 
 
 def reference_denoise_variance(h1, h2, g0, g1, params=None, material_ids=None, return_variance=False, dtype=np.float64, **kw):
@@ -604,22 +553,13 @@ def reference_denoise_variance(h1, h2, g0, g1, params=None, material_ids=None, r
     them); params: a VarParams, a dict or keywords over the header's defaults (no library needed); material_ids: those of the context's scene
     (None: no scene, no emitters); dtype: the working precision (see above).  Returns [h, w, 4] of `dtype` (and V_N [h, w] with return_variance)."""
     dtype = _dtype(dtype)
-    q = dict(_VAR_DEFAULTS)
-    if isinstance(params, VarParams):
-        params = {f: getattr(params, f) for f, _ in VarParams._fields_}
-    q.update(params or {}); q.update(kw)
+    q = _options(_VAR_DEFAULTS, VarParams, params, kw)
     it = int(q["iterations"])
-    if not 0 <= it <= MAX_ITERATIONS:
-        raise ValueError("iterations must be 0..%d" % MAX_ITERATIONS)
     h1, h2 = np.asarray(h1).astype(dtype), np.asarray(h2).astype(dtype)
     out = np.empty_like(h1)
     out[..., 3] = h1[..., 3]
     sl, sn, sd = (float(np.float32(q[k])) for k in ("sigma_lum", "sigma_normal", "sigma_depth"))
-    g0 = np.asarray(g0, np.float32).astype(dtype)
-    if material_ids is not None:
-        g0[emitter_mask(g1, material_ids), 3] = -1.0
-    alb = np.maximum(np.asarray(g1, np.float32)[..., :3].astype(dtype), float(np.float32(1e-3)))
-    miss = g0[..., 3] < 0
+    g0, alb, miss = _filter_inputs(g0, g1, material_ids, dtype)
     demod = bool(q["demodulate"])
     d1 = np.where(miss[..., None], h1[..., :3], h1[..., :3] / alb) if demod else h1[..., :3]
     d2 = np.where(miss[..., None], h2[..., :3], h2[..., :3] / alb) if demod else h2[..., :3]
@@ -654,10 +594,7 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
     goes through reference_atrous_variance.  near_parts: the third result is the pair (near without the last decision, near of N against 4 alone)
     instead -- N against 4 chooses between the two forms of V_0 and nothing else, so colour, N and the moments of such a pixel are still decided."""
     dtype = _dtype(dtype)
-    q = dict(_TEMPORAL_DEFAULTS)
-    if isinstance(params, TemporalParams):
-        params = {f: getattr(params, f) for f, _ in TemporalParams._fields_}
-    q.update(params or {}); q.update(kw)
+    q = _options(_TEMPORAL_DEFAULTS, TemporalParams, params, kw)
     alpha, alpha_m, plane_tol, normal_tol = (dtype(np.float32(q[k])) for k in ("alpha", "alpha_moments", "plane_tol", "normal_tol"))
     max_hist = dtype(int(q["max_history"]))
     sn, sd = float(np.float32(q["sigma_normal"])), float(np.float32(q["sigma_depth"]))
