@@ -54,6 +54,64 @@ def make_ctx(O, scene, w, h, offsets=None, uniforms=None):
     return c
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# Cameras and lights other than the default block (tests/test_uniforms_host.py, tests/test_gpu_uniforms.py).  The default block is nearly blind
+# to a permuted light colour (white), to light_right and light_up swapped (equal lengths, nine of twelve components zero) and to a wrong
+# cam_pos.x (zero); these cases are not.  name -> (eye, at).
+CAMERAS = {
+    "default":      ((0.0, 1.0, 3.38), (0.0, 1.0, -1.0)),             # control
+    "outside_back": ((0.0, 1.0, -6.0), (0.0, 1.0, 0.0)),              # outside the room: hits and misses in one wave
+    "from_above":   ((0.0, 5.0, 0.3), (0.0, 0.0, 0.0)),               # through the back of the ceiling, the view almost along the look-at's up vector
+    "inside_low":   ((0.7, 0.15, 1.5), (-0.5, 1.6, -0.5)),            # every component non-zero, grazing the floor
+    "nearly_up":    ((0.0, 0.5, 0.5), (0.02, 2.0, 0.47)),             # one degree off the degenerate look-at
+    "in_tall_box":  ((-0.335, 0.6, -0.29), (0.5, 0.3, 1.0)),          # origin inside a box leaf: every primary hit is a back face of that cube
+    "away":         ((0.0, 1.0, 3.38), (0.0, 1.0, 8.0)),              # no ray hits anything: a black frame and not one secondary ray
+}
+# The exactly degenerate camera (`at` straight above `eye`) is NOT here and must not be added: its inverse view-projection is NaN and so is every
+# ray; tests/test_uniforms_host.py asserts finite rays for every entry.
+
+# name -> None (the block's own light) or (pos, forward, right, up, color)
+LIGHTS = {
+    "default":         None,
+    "tilted_coloured": ((0.4, 1.6, 0.3), (-0.48, -0.8, -0.36), (0.3, 0.0, -0.4), (0.1, 0.05, 0.02), (5.0, 0.5, 2.0)),    # no two components alike
+    "floor_up":        ((0.0, 0.0005, 0.5), (0.0, 1.0, 0.0), (0.6, 0.0, 0.0), (0.0, 0.0, 0.6), (0.2, 1.0, 0.4)),        # half a millimetre above the floor
+    "sideways":        ((0.0, 1.0, 0.0), (0.0, 0.0, -1.0), (0.25, 0.0, 0.0), (0.0, 0.25, 0.0), (1.0, 1.0, 1.0)),         # radiance ~67 near it; half the room dark
+    "point_dim":       ((0.3, 1.2, 0.8), (0.0, -1.0, 0.0), (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), (0.0, 0.03, 1.5)),          # zero extent, one channel exactly zero
+}
+LIGHT_FIELDS = ("light_pos", "light_forward", "light_right", "light_up", "light_color")
+UNIFORM_SHAPES = ((72, 40), (33, 17))      # 9 x 5 whole 8x8 tiles; partial tiles both ways
+FAST_RUNS = {(72, 40): (8, 5), (33, 17): (3, 15)}      # shape -> (spp, bounces) of the shipped build's runs against the libm oracle
+
+
+def uniforms_case(O, w, h, cam, light, frame=0):
+    """The oracle's uniform block for CAMERAS[cam] with the first three floats of every light field overwritten by LIGHTS[light]."""
+    eye, at = CAMERAS[cam]
+    u = O.make_uniforms(w, h, frame, eye, at)
+    if LIGHTS[light] is not None:
+        for name, v in zip(LIGHT_FIELDS, LIGHTS[light]):
+            getattr(u, name)[0:3] = [float(np.float32(x)) for x in v]
+    return u
+
+
+def fast_bar(img, ref, rays):
+    """The shipped build's bar on a small image: (passes, rmse, outlier pixels, outlier pixels allowed) -- RMSE <= TOL_RMSE and no more pixels
+    beyond 1e-4 * max(1, |ref|) than edge_flip_allowance gives `rays` rays."""
+    pixels = ref.shape[0] * ref.shape[1]
+    rmse, frac_ok, _ = image_metrics(img, ref)
+    allowed = edge_flip_allowance(pixels, rays)
+    return bool(rmse <= TOL_RMSE and frac_ok >= 1.0 - allowed / pixels), rmse, int(round((1.0 - frac_ok) * pixels)), allowed
+
+
+def uniform_pairs():
+    """All 7 x 5 (camera, light) names."""
+    return [(c, l) for c in CAMERAS for l in LIGHTS]
+
+
+# every camera and every light at least once (7 pairs)
+REDUCED_PAIRS = (("default", "tilted_coloured"), ("outside_back", "floor_up"), ("from_above", "sideways"), ("inside_low", "point_dim"),
+                 ("nearly_up", "default"), ("in_tall_box", "tilted_coloured"), ("away", "sideways"))
+
+
 def box_zoo(O):
     """A scene that fits in LDS and exercises the BOX leaves (bvh_build.h kLeafBox): the Cornell box (two cubes standing on the floor) plus cubes that
     are rotated, sheared (a parallelepiped), mirrored (negative scale: the vertex order flips), nested in another, emissive (material 2: seen by
