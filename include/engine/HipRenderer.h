@@ -4,6 +4,8 @@
 #pragma once
 #include <stdint.h>
 
+#include <vector>
+
 #include "engine/Renderer.h"
 
 struct trg_ctx;
@@ -19,6 +21,11 @@ public:
     bool init() override;                   // creates the device context; false (+message on stdout) on failure
     void destroy() override;
     void loadScene(Scene *scene) override;  // uploads the five Scene vectors, builds the BVH
+    // The same scene with its geometry MOVED: uploads like loadScene.  In temporal mode (setDenoise), when the triangle count is the one of the
+    // scene uploaded last (and neither scene has textures), the history is KEPT: the vectors uploaded last are handed to
+    // trg_temporal_set_previous_scene (include/trg_denoise.h) -- triangle k of `scene` is the surface triangle k was -- and the next step looks
+    // for every pixel's history where its surface was.  In every other case it is loadScene.
+    void updateScene(Scene *scene);
     // One more sample per pixel into the running average.  ASYNCHRONOUS like the reference's (MetalRenderer.mm:373-552: encode,
     // commit, return; three frames in flight behind a semaphore, :33,377,385-387): the call never waits for the GPU to finish
     // a frame.  It takes a snapshot of the uniforms and either launches at once (GPU idle) or -- while earlier launches are
@@ -91,6 +98,12 @@ protected:
     bool m_denoiseVar;           // ... by the variance-guided filter from two half-sample buffers
     bool m_denoiseTemporal;      // ... or every batch a temporal step (trg_render_temporal_own)
     void *m_temporalOut;         // the last temporal step's output image (owned by the denoise state); null before the first
+    // updateScene: the positions, normals and indices uploaded last (temporal mode, one device; else empty), whether they came with textures,
+    // and whether the loadScene in progress keeps the temporal history
+    std::vector<float> m_lastPositions, m_lastNormals;
+    std::vector<uint32_t> m_lastIndices;
+    bool m_lastTextured;
+    bool m_keepHistory;
 };
 
 }  // namespace toyraygun

@@ -207,7 +207,8 @@ TRG_API void trg_temporal_default_params(trg_temporal_params *p);
  *       X  = the world positions of that frame
  *     A new state has no history, and trg_temporal_reset forgets it (and the view-projection trg_render_temporal remembered;
  *     it allocates nothing: harmless for a context that never denoised).
- *     THE LIBRARY DOES NOT NOTICE A CHANGED SCENE: after trg_load_scene or trg_load_textures the caller calls trg_temporal_reset.
+ *     THE LIBRARY DOES NOT NOTICE A CHANGED SCENE: after trg_load_scene or trg_load_textures the caller calls trg_temporal_reset
+ *     -- or, for geometry that moved and kept its topology, trg_temporal_set_previous_scene (MOVING GEOMETRY below), which keeps the history.
  *     trg_temporal_history_read: Hc then Hm of the last call into 2 * width*height*4 floats; it WAITS for the result (TRG_ERR_INVALID while
  *     there is no history). */
 TRG_API int trg_temporal_reset(trg_ctx *ctx);
@@ -276,6 +277,69 @@ TRG_API int trg_guides_pos_read(trg_ctx *ctx, uint32_t frameIndex, float *guides
 TRG_API int trg_temporal_denoise_host(trg_ctx *ctx, const float *color_in_host, const float *guides_host, const float *pos_host, const float prev_view_proj[16],
                                       float *out_host, float *iv_host, float *var_host, const trg_temporal_params *p);
 TRG_API int trg_render_temporal_read(trg_ctx *ctx, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_temporal_params *p);
+
+/* =============================================================================================================================================
+ * MOVING GEOMETRY: PREVIOUS-POSITION PLANES (SVGF's motion vectors, in world space).  The step above follows a moving CAMERA: it looks for the
+ * history of a pixel where the previous camera saw the hit's CURRENT world position.  A surface that moved was somewhere else then, so the
+ * step either rejects good history (motion along the normal beyond plane_tol * z, a rotation beyond normal_tol) or accepts the history of
+ * another surface point (a slide within the plane).  Here the caller says where every triangle was, and the step looks there.
+ *
+ * NOT COVERED.  Moving or changing EMITTERS: the history then holds stale lighting, and only `alpha` forgets it.  A changed TOPOLOGY (another
+ * triangle count, or triangle k no longer the surface triangle k was): the caller calls trg_temporal_reset.  Device groups (trg_group_*).
+ * Feeding filtered colour back into the history: as above, the history holds unfiltered values.
+ * ============================================================================================================================================= */
+
+/* --- PREVIOUS GEOMETRY.  Call it AFTER trg_load_scene of the new geometry.  Triangle k here is the surface that triangle k of the loaded scene
+ *     was at the previous call.  The layouts are trg_load_scene's: triangle k has the corners positions3[3 * indices[3k + c]], c = 0, 1, 2, and
+ *     the normals normals3[3 * (3k + c)].  n_tris must be the loaded scene's triangle count, or 0: the previous scene is forgotten (no pointer
+ *     is read, the state is disarmed).  TRG_ERR_INVALID when no scene is loaded, n_tris is neither, an index is >= n_verts, or positions3 or
+ *     indices is NULL.  normals3 == NULL: the normals did not change (a pure translation); the previous normal of a hit is then its current one.
+ *     Everything is copied into a grow-only device array of the state (freed by trg_denoise_release), one record of 80 bytes per ORIGINAL
+ *     primitive index -- what the tracer reports, so no map is needed to find it -- of five float4:
+ *       (P0.x P0.y P0.z P1.x) (P1.y P1.z P2.x P2.y) (P2.z N0.x N0.y N0.z) (N1.x N1.y N1.z N2.x) (N2.y N2.z 0 0)        N = 0 without normals3
+ *     The call WAITS for the copy (the caller's arrays may be freed when it returns); a refused call changes nothing.
+ *     ARMING.  A successful call with n_tris != 0 ARMS the state: the next successful trg_render_temporal / _own / _read uses the previous scene
+ *     and disarms it.  One call describes ONE transition: a caller who stops animating sees no phantom motion.  trg_temporal_reset disarms
+ *     too (the stored geometry stays).  While armed, trg_render_temporal* compares the stored triangle count with the loaded scene's and
+ *     returns TRG_ERR_INVALID, before anything is enqueued or the history changes, when they differ (a trg_load_scene in between). */
+TRG_API int trg_temporal_set_previous_scene(trg_ctx *ctx, const float *positions3, const float *normals3 /* may be NULL */, const uint32_t *indices,
+                                            uint32_t n_verts, uint32_t n_tris);
+
+/* --- MOTION PLANES.  G0, G1 and X are written as trg_guides_render_pos writes them, bit for bit.  motion_device: TWO planes of width*height
+ *     float4, M0 then M1.  With c0, c1 = the hit's trg_isect.coordinates, c2 = 1 - c0 - c1 (as for the guides) and P0', P1', P2' / N0', N1', N2'
+ *     the previous corners / normals of the hit primitive:
+ *       M0(p) = ((c0 * P0' + c1 * P1') + c2 * P2', 1)      where the surface point under p WAS; every product and sum one fp32 operation, not
+ *       M1(p) = ((c0 * N0' + c1 * N1') + c2 * N2', 0)      contracted.  Previous scene set with normals3 == NULL: M1 = (G0(p).xyz, 0) bit for bit
+ *       M0(p) = M1(p) = (0, 0, 0, 0)                       on a miss
+ *     M0.w > 0 says "a previous position is known": a caller who writes the planes from their own data (skinning) may clear it per pixel.
+ *     TRG_ERR_INVALID without a previous scene of the loaded scene's triangle count (whether the state is armed plays no part), when a pointer
+ *     is NULL or two of the buffers overlap.
+ *     On the device: ONE launch behind the gather of the guides, a pixel per thread: it reads the pixel's hit record (one coalesced float4 of
+ *     the guide pass' scratch) and the hit primitive's record above as float4 (the position rows alone without normals3, then G0(p) instead),
+ *     and writes two coalesced float4.  No atomics, no scratch, no LDS. */
+TRG_API int trg_guides_render_motion(trg_ctx *ctx, uint32_t frameIndex, void *guides_device, void *pos_device, void *motion_device);
+
+/* --- THE STEP WITH MOTION.  trg_temporal_denoise exactly -- arguments, refusals, every formula --, with motion_device (as above; it must not be
+ *     NULL nor overlap any other buffer) and three substitutions in Reproject:
+ *       clip_j = vp[j*4] M0(p).x + vp[j*4+1] M0(p).y + vp[j*4+2] M0(p).z + vp[j*4+3]                  (M0(p).xyz in place of X(p))
+ *       a tap's plane test:   | nn(M1(p).xyz) . (X'(q) - M0(p).xyz) | <= plane_tol * z_p               (z_p is still THIS frame's depth)
+ *       a tap's normal test:  nn(M1(p).xyz) . nn(F'(q).xyz) >= normal_tol
+ *     and NO HISTORY also when M0(p).w is not > 0 or nn(M1(p).xyz) has no length (the current normal n_p takes no part any more).
+ *     Nothing else changes: the history that is written is this frame's F and X (not M), accumulation, V_0 and the filter are as above.
+ *     So with M0 = (X.xyz, 1) and M1 = (G0.xyz, 0) every result -- out, the history, (I, V_0), V_N -- is trg_temporal_denoise's BIT FOR BIT.
+ *     The float64 reference: reference_temporal(..., motion=(M0, M1)).
+ *     On the device: the same launches; the reprojection kernel reads two more coalesced float4 per pixel. */
+TRG_API int trg_temporal_denoise_motion(trg_ctx *ctx, const void *color_in_device, const void *guides_device, const void *pos_device, const void *motion_device,
+                                        const float prev_view_proj[16], void *out_device, const trg_temporal_params *p /* NULL: defaults */);
+
+/* --- trg_render_temporal / _own / _read WHILE ARMED: step 3 is trg_guides_render_motion into two more planes of the state (allocated on the first
+ *     such call), step 4 is trg_temporal_denoise_motion; the call then disarms the state.  Unarmed they do what they did, bit for bit.
+ *
+ * --- with HOST buffers; they WAIT for the result.  motion_host: 2 * width*height*4 floats; the other buffers as for trg_guides_pos_read and
+ *     trg_temporal_denoise_host. */
+TRG_API int trg_guides_motion_read(trg_ctx *ctx, uint32_t frameIndex, float *guides_host, float *pos_host, float *motion_host);
+TRG_API int trg_temporal_denoise_motion_host(trg_ctx *ctx, const float *color_in_host, const float *guides_host, const float *pos_host, const float *motion_host,
+                                             const float prev_view_proj[16], float *out_host, float *iv_host, float *var_host, const trg_temporal_params *p);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,9 @@ ms, next to the filter's compulsory traffic (per iteration 48 B read + 16 B writ
 variance-guided filter are taken as differences of runs that differ by one launch (prefilter on / off, N and N - 1 iterations).  The temporal
 leg runs at rest (every tile of the spatial estimate leaves early once the history is four frames old) and with the eye turning 1 degree per
 call; `temporal_front_ms` = the emitter marking, the reprojection and the spatial-estimate launch (a step of 0 iterations minus its final
-copy is not separable here, so it is a step of 1 iteration minus one variance iteration of spacing 1)."""
+copy is not separable here, so it is a step of 1 iteration minus one variance iteration of spacing 1).  The moving-geometry leg
+(trg_temporal_set_previous_scene, trg_guides_render_motion, trg_temporal_denoise_motion) comes last: the motion-plane launch, and the step with
+the motion planes beside the plain step at rest."""
 import json
 import os
 import sys
@@ -112,6 +114,26 @@ res["temporal_5_moving_ms"] = moving()
 res["temporal_1_moving_ms"] = moving(iterations=1)
 res["temporal_front_moving_ms"] = res["temporal_1_moving_ms"] - res["variance_iteration_ms"][0]
 res["l2_iteration_ms"] = res["variance_iteration_ms"][2]
+# moving geometry.  The motion-plane launch as guides_motion minus guides_pos.  Then steps with the motion planes, the camera at rest, after six
+# calls: first with a previous scene that IS the loaded scene (nothing moved: every pixel finds its history as in the plain leg at rest, every
+# tile of the spatial estimate leaves early, so the difference to the plain 1-iteration step is the reprojection kernel's MOTION form alone),
+# then with the short box 0.02 further left at the previous call (the pixels the box uncovers keep N < 4, so the spatial estimate runs on
+# their tiles in every call)
+mo = torch.empty((2, h, w, 4), dtype=torch.float32, device="cuda")
+moved = b["positions"].copy()
+moved[:36, 0] -= np.float32(0.02)
+for name, prev in (("still", b["positions"]), ("moved", moved)):
+    denoise.temporal_set_previous_scene(c, prev, b["normals"], b["indices"])
+    if name == "still":
+        res["guides_motion_ms"] = timed(lambda: denoise.guides_motion(c, 0, out=g, pos=x, motion=mo))
+        res["motion_planes_ms"] = res["guides_motion_ms"] - res["guides_pos_ms"]
+    denoise.guides_motion(c, 0, out=g, pos=x, motion=mo)
+    denoise.temporal_reset(c)
+    for _ in range(6):
+        step(vp_rest, motion=mo)
+    res["temporal_5_motion_%s_ms" % name] = timed(lambda: step(vp_rest, motion=mo))
+    res["temporal_1_motion_%s_ms" % name] = timed(lambda: step(vp_rest, motion=mo, iterations=1))
+res["reproject_motion_extra_ms"] = res["temporal_1_motion_still_ms"] - res["temporal_1_rest_ms"]
 print(json.dumps(res))
 c.bind_accum(None)
 c.set_stream(None)

@@ -15,7 +15,7 @@ namespace toyraygun {
 
 HipRenderer::HipRenderer()
     : m_ctx(nullptr), m_group(nullptr), m_deviceCount(0), m_bounces(3), m_deviceBuild(0), m_offsetSeed(0x5EED0001u), m_sceneLoaded(false), m_synchronous(false), m_pending(0), m_pendingFirst(0),
-      m_launches(0), m_denoise(0), m_denoiseVar(false), m_denoiseTemporal(false), m_temporalOut(nullptr) {
+      m_launches(0), m_denoise(0), m_denoiseVar(false), m_denoiseTemporal(false), m_temporalOut(nullptr), m_lastTextured(false), m_keepHistory(false) {
     memset(&m_pendingUniforms, 0, sizeof(m_pendingUniforms));
 }
 HipRenderer::~HipRenderer() { destroy(); }
@@ -98,10 +98,18 @@ void HipRenderer::loadScene(Scene *scene) {
         return;
     }
     m_sceneLoaded = true;
-    // the temporal history belongs to the old scene (the library does not notice a changed one)
-    if (m_denoiseTemporal) {
+    // the temporal history belongs to the old scene (the library does not notice a changed one) -- unless updateScene vouches for it
+    if (m_denoiseTemporal && !m_keepHistory) {
         if (trg_temporal_reset(m_ctx) != TRG_OK) printf("HipRenderer: %s\n", trg_last_error(m_ctx));
         m_temporalOut = nullptr;
+    }
+    // what updateScene hands to trg_temporal_set_previous_scene when this geometry moves
+    m_lastPositions.clear(); m_lastNormals.clear(); m_lastIndices.clear();
+    m_lastTextured = !scene->m_textures.empty();
+    if (m_denoiseTemporal && !m_group && nVerts) {
+        m_lastPositions.assign(pos, pos + (size_t)nVerts * 3);
+        m_lastNormals.assign(nrm, nrm + (size_t)nVerts * 3);
+        m_lastIndices.assign(idx, idx + (size_t)nVerts);
     }
     // albedo textures of the scene (Scene::addMesh with a Texture): expanded to RGBA8 and uploaded with the texture coordinates
     if (!scene->m_textures.empty() && nTris) {
@@ -132,6 +140,26 @@ void HipRenderer::loadScene(Scene *scene) {
             m_sceneLoaded = false;
             return;
         }
+    }
+}
+
+void HipRenderer::updateScene(Scene *scene) {
+    if (!m_ctx || !scene) return;
+    const size_t nTris = scene->m_materialIDBuffer.size();
+    const bool keep = m_denoiseTemporal && !m_group && m_sceneLoaded && nTris != 0 && m_lastIndices.size() == nTris * 3 && !m_lastTextured &&
+                      scene->m_textures.empty();
+    if (!keep) { loadScene(scene); return; }
+    std::vector<float> positions, normals;
+    std::vector<uint32_t> indices;
+    positions.swap(m_lastPositions); normals.swap(m_lastNormals); indices.swap(m_lastIndices);
+    m_keepHistory = true;
+    loadScene(scene);
+    m_keepHistory = false;
+    if (!m_sceneLoaded) return;
+    if (trg_temporal_set_previous_scene(m_ctx, positions.data(), normals.data(), indices.data(), (uint32_t)(positions.size() / 3), (uint32_t)nTris) != TRG_OK) {
+        printf("HipRenderer: %s\n", trg_last_error(m_ctx));
+        trg_temporal_reset(m_ctx);   // the history cannot be followed: start over, as loadScene does
+        m_temporalOut = nullptr;
     }
 }
 

@@ -1,11 +1,13 @@
 // main_cornell.cpp -- headless demo following the reference app's call order (reference src/main.cpp:16-98):
 // engine init -> three shaders -> renderer init -> camera -> Cornell box -> frame loop; then writes a PNG.
-//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal]] [orbit=DEG]]
+//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal]] [orbit=DEG] [slide=D]]
 //     denoise=N    a-trous iterations of the written image, 0 = off (default)
 //     ,var         the variance-guided filter from two half-sample buffers
 //     ,temporal    the frames are rendered as `frames` calls of 1 spp, each a temporal step (reprojected history, temporal variance); the
 //                  picture is the last step's
 //     orbit=DEG    the eye turns about the look-at point (about the vertical axis) by DEG degrees per call
+//     slide=D      before call k the box is rebuilt with the short box moved by k * D along x and handed to HipRenderer::updateScene: with
+//                  ,temporal the history follows the moving box (trg_temporal_set_previous_scene), otherwise it is a plain loadScene
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -21,6 +23,22 @@
 
 using namespace toyraygun;
 
+// the Cornell box (cornellBox.h) with the short box moved by dx along x
+static Scene *createSlidCornellBox(float dx) {
+    Scene *scene = new Scene();
+    int n = 0;
+    const toyraygun_scenes::Placement *p = toyraygun_scenes::cornellPlacements(&n);
+    float m[16];
+    for (int i = 0; i < n; ++i) {
+        bx::mtxSRT(m, p[i].scale[0], p[i].scale[1], p[i].scale[2], p[i].rot[0], p[i].rot[1], p[i].rot[2], p[i].pos[0] + (i == 0 ? dx : 0.0f), p[i].pos[1], p[i].pos[2]);
+        const bx::Vec3 color(p[i].color[0], p[i].color[1], p[i].color[2]);
+        if (p[i].kind == 'c') scene->addCube(color, m);
+        else if (p[i].kind == 'p') scene->addPlane(color, m);
+        else scene->addAreaLight(color, m);
+    }
+    return scene;
+}
+
 static Shader *loadShader(const char *name, ShaderType type, const char *const *fns, const ShaderFunctionType *types, int n) {
     Shader *s = Engine::createShader();
     if (!s->load(name)) { std::cout << "Failed to load " << name << " shader." << std::endl; return nullptr; }
@@ -35,9 +53,15 @@ int main(int argc, char **argv) {
     const char *out = argc > 5 ? argv[5] : "cornell.png";
     int denoise = 0;
     bool denoiseVar = false, denoiseTemporal = false;
-    double orbit = 0.0;
-    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal]] [orbit=DEG]]";
+    double orbit = 0.0, slide = 0.0;
+    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal]] [orbit=DEG] [slide=D]]";
     for (int a = 6; a < argc; ++a) {
+        if (strncmp(argv[a], "slide=", 6) == 0) {
+            char *end = nullptr;
+            slide = strtod(argv[a] + 6, &end);
+            if (end == argv[a] + 6 || *end != 0) { std::cout << usage << std::endl; return -1; }
+            continue;
+        }
         if (strncmp(argv[a], "orbit=", 6) == 0) {
             char *end = nullptr;
             orbit = strtod(argv[a] + 6, &end);
@@ -78,12 +102,12 @@ int main(int argc, char **argv) {
     renderer->setCameraPosition(bx::Vec3(0.0f, 1.0f, 3.38f));
     renderer->setCameraLookAt(bx::Vec3(0.0f, 1.0f, -1.0f));
 
+    // (the denoise mode first: in temporal mode the renderer remembers the geometry it uploads, for updateScene)
+    HipRenderer *hip = static_cast<HipRenderer *>(renderer);
+    if (!hip->setDenoise(denoise, denoiseVar, denoiseTemporal)) { std::cout << "denoise must be 0.." << 6 << std::endl; return -1; }
     Scene *scene = createCornellBoxScene();
     renderer->loadScene(scene);
-
-    HipRenderer *hip = static_cast<HipRenderer *>(renderer);
     hip->setBounces((unsigned int)bounces);
-    if (!hip->setDenoise(denoise, denoiseVar, denoiseTemporal)) { std::cout << "denoise must be 0.." << 6 << std::endl; return -1; }
     const bx::Vec3 eye0(0.0f, 1.0f, 3.38f), at(0.0f, 1.0f, -1.0f);
     int call = 0;
     while (!engine->hasQuit()) {
@@ -93,6 +117,11 @@ int main(int argc, char **argv) {
             const double t = orbit * (double)call * 3.14159265358979323846 / 180.0;
             const double dx = (double)eye0.x - (double)at.x, dz = (double)eye0.z - (double)at.z;
             renderer->setCameraPosition(bx::Vec3((float)((double)at.x + dx * cos(t) + dz * sin(t)), eye0.y, (float)((double)at.z - dx * sin(t) + dz * cos(t))));
+        }
+        if (slide != 0.0 && call > 0) {
+            Scene *moved = createSlidCornellBox((float)((double)call * slide));
+            hip->updateScene(moved);
+            delete moved;   // (the renderer borrows the scene for the call only)
         }
         renderer->renderFrame();
         ++call;

@@ -1,6 +1,7 @@
 // trg_denoise.hip -- include/trg_denoise.h: first-hit guide buffers and the edge-avoiding a-trous filter.  A translation unit of its own beside
 // the render kernels: it launches the library's stage-level raygen / trace kernels (both builds) and adds a gather kernel and the filter.
 // Behind them the variance-guided form of the filter and the temporal reprojection / accumulation that feeds it.
+// For geometry that moved: the previous scene, the motion planes and the MOTION form of the reprojection.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -8,6 +9,7 @@
 #include <mutex>
 #include <string>
 #include <unordered_map>
+#include <vector>
 
 #include "../../include/trg_denoise.h"
 #include "bvh_build.h"
@@ -153,6 +155,13 @@ struct DenoiseState {
     float4 *timg = nullptr, *tpos = nullptr;
     float prev_vp[16] = {};
     bool have_prev_vp = false;
+    // moving geometry (trg_temporal_set_previous_scene): kPrevRecord float4 per original primitive index (grow-only), how many are stored (0: no
+    // previous scene), whether they hold normals, whether the next trg_render_temporal uses them; the two motion planes of trg_render_temporal
+    float4 *prev_geo = nullptr;
+    size_t prev_cap = 0;
+    uint32_t prev_tris = 0;
+    bool prev_normals = false, armed = false;
+    float4 *tmotion = nullptr;
 };
 std::mutex g_mutex;
 std::unordered_map<trg_ctx *, DenoiseState> g_states;
@@ -162,6 +171,7 @@ void free_state(DenoiseState &s) {
     (void)hipFree(s.rec_of_prim); (void)hipFree(s.overflow); (void)hipFree(s.result); (void)hipFree(s.fguide);
     (void)hipFree(s.half_acc); (void)hipFree(s.halves);
     (void)hipFree(s.hist[0]); (void)hipFree(s.hist[1]); (void)hipFree(s.timg); (void)hipFree(s.tpos);
+    (void)hipFree(s.prev_geo); (void)hipFree(s.tmotion);
     s = DenoiseState{};
 }
 
@@ -341,6 +351,47 @@ int guides_render(trg_ctx *c, DenoiseState &s, uint32_t frameIndex, float4 *guid
     if (int rc = record_map(c, s, "trg_guides_render")) return rc;
     return launch_each(c, "trg_guides_render", pos ? dn_gather_kernel<true> : dn_gather_kernel<false>, n, s.isect, s.rec_of_prim,
                        reinterpret_cast<const float4 *>(c->blob + sc.off_fat), sc.n_tris, c->tex, guides, guides + n, n, pos ? s.rays : nullptr, pos);
+}
+
+// ---- moving geometry: the previous scene and the motion planes (trg_denoise.h, MOVING GEOMETRY) ----
+// One record per ORIGINAL primitive index, five float4: (P0.xyz P1.x) (P1.yz P2.xy) (P2.z N0.xyz) (N1.xyz N2.x) (N2.yz 0 0)
+constexpr uint32_t kPrevRecord = 5;
+
+// M0 = (the hit's barycentrics over the previous corners, 1), M1 = (the same over the previous normals, 0); zero on a miss -- the gather's test.
+// NORMALS = false: the previous scene came without normals, M1 = (G0.xyz, 0) and the two normal rows of the record are not read.
+template <bool NORMALS>
+__global__ void dn_motion_kernel(const trg_isect *isect, const float4 *prev, uint32_t n_prims, const float4 *g0, float4 *m0, float4 *m1, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 is = reinterpret_cast<const float4 *>(isect)[i];   // distance, primitiveIndex, coordinates[2]
+    const int prim = __float_as_int(is.y);
+    if (!(is.x >= 0.0f) || prim < 0 || (uint32_t)prim >= n_prims) {
+        m0[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        m1[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const float4 *rec = prev + (size_t)prim * kPrevRecord;
+    const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+    const float c0 = is.z, c1 = is.w, c2 = 1.0f - c0 - c1;
+    m0[i] = make_float4((c0 * r0.x + c1 * r0.w) + c2 * r1.z, (c0 * r0.y + c1 * r1.x) + c2 * r1.w, (c0 * r0.z + c1 * r1.y) + c2 * r2.x, 1.0f);
+    if (NORMALS) {
+        const float4 r3 = rec[3], r4 = rec[4];
+        m1[i] = make_float4((c0 * r2.y + c1 * r3.x) + c2 * r3.w, (c0 * r2.z + c1 * r3.y) + c2 * r4.x, (c0 * r2.w + c1 * r3.z) + c2 * r4.y, 0.0f);
+    } else {
+        const float4 g = g0[i];
+        m1[i] = make_float4(g.x, g.y, g.z, 0.0f);
+    }
+}
+
+// is there a previous scene for the scene that is loaded?
+bool have_previous_scene(const trg_ctx *c, const DenoiseState &s) { return c->scene_loaded && s.prev_tris != 0 && s.prev_tris == c->sc.n_tris; }
+
+// trg_guides_render_pos and, behind it, the two motion planes (the caller has checked have_previous_scene)
+int guides_render_motion(trg_ctx *c, DenoiseState &s, uint32_t frameIndex, float4 *guides, float4 *pos, float4 *motion) {
+    if (int rc = guides_render(c, s, frameIndex, guides, pos)) return rc;
+    const size_t n = (size_t)c->w * c->h;
+    return launch_each(c, "trg_guides_render_motion", s.prev_normals ? dn_motion_kernel<true> : dn_motion_kernel<false>, n, s.isect, s.prev_geo, s.prev_tris, guides,
+                       motion, motion + n, n);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -784,6 +835,7 @@ struct ReprojectParams {
     int w, h, demod;
     float vp[16];
     float alpha, alpha_moments, plane_tol, normal_tol, max_history;
+    const float4 *m0, *m1;                            // MOTION: the previous-position planes M0, M1 (last: the other fields keep their offsets)
 };
 
 // n / |n| into (x, y, z); false when the length is not > 0
@@ -798,12 +850,15 @@ __device__ __forceinline__ bool dn_unit(float &x, float &y, float &z) {
 // One pixel per thread over 16 x 16 tiles.  The four planes of this frame are read coalesced (a wavefront = four rows of 16 consecutive float4);
 // the four taps of the four history planes land wherever the camera moved the surface to, neighbouring lanes mostly on the same 128-byte lines
 // of L2.
-template <bool STRICT>
+// MOTION (trg_temporal_denoise_motion): the history is looked for where the surface WAS -- M0.xyz takes X's place in the projection and in the
+// plane test, M1.xyz the current normal's in both tests -- and only where M0.w > 0; two more coalesced float4 per pixel.
+template <bool STRICT, bool MOTION>
 __global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const ReprojectParams p) {
     const int x = (int)blockIdx.x * kDnTile + ((int)threadIdx.x & 15), y = (int)blockIdx.y * kDnTile + ((int)threadIdx.x >> 4);
     if (x >= p.w || y >= p.h) return;
     const size_t pix = (size_t)y * (size_t)p.w + (size_t)x;
     const float4 c = p.color[pix], f = p.fguide[pix], X = p.pos[pix];
+    const float4 R = MOTION ? p.m0[pix] : X;            // where the hit was when the history was written
     p.of[pix] = f;
     p.ox[pix] = X;
     if (f.w < 0.0f) {   // a miss: nothing to accumulate
@@ -817,11 +872,12 @@ __global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const Reproj
     const float l = dn_lum(make_float4(dr, dg, db, 0.0f));
     float ir = 0.0f, ig = 0.0f, ib = 0.0f, m1 = 0.0f, m2 = 0.0f, nh = 0.0f, W = 0.0f;
     float nx = f.x, ny = f.y, nz = f.z;
-    if (p.hc && dn_unit<STRICT>(nx, ny, nz)) {
+    if (MOTION) { const float4 pn = p.m1[pix]; nx = pn.x; ny = pn.y; nz = pn.z; }
+    if (p.hc && (!MOTION || R.w > 0.0f) && dn_unit<STRICT>(nx, ny, nz)) {
         const float *m = p.vp;
-        const float cx = m[0] * X.x + m[1] * X.y + m[2] * X.z + m[3];
-        const float cy = m[4] * X.x + m[5] * X.y + m[6] * X.z + m[7];
-        const float cw = m[12] * X.x + m[13] * X.y + m[14] * X.z + m[15];
+        const float cx = m[0] * R.x + m[1] * R.y + m[2] * R.z + m[3];
+        const float cy = m[4] * R.x + m[5] * R.y + m[6] * R.z + m[7];
+        const float cw = m[12] * R.x + m[13] * R.y + m[14] * R.z + m[15];
         if (cw > 0.0f) {
             const float fx = (cx / cw * 0.5f + 0.5f) * (float)p.w - 0.5f, fy = (cy / cw * 0.5f + 0.5f) * (float)p.h - 0.5f;
             if (fx >= -1.0f && fx < (float)p.w && fy >= -1.0f && fy < (float)p.h) {   // (false for NaN)
@@ -838,7 +894,7 @@ __global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const Reproj
                     const float4 fq = p.hf[q];
                     if (!(fq.w >= 0.0f)) continue;
                     const float4 xq = p.hx[q];
-                    const float dist = nx * (xq.x - X.x) + ny * (xq.y - X.y) + nz * (xq.z - X.z);
+                    const float dist = nx * (xq.x - R.x) + ny * (xq.y - R.y) + nz * (xq.z - R.z);
                     if (!(fabsf(dist) <= tol)) continue;
                     float qnx = fq.x, qny = fq.y, qnz = fq.z;
                     if (!dn_unit<STRICT>(qnx, qny, qnz)) continue;
@@ -961,9 +1017,10 @@ bool invert4(const float *a, float *out) {
 }
 
 // use_history = false: the step runs as after a reset (trg_render_temporal without a remembered view-projection).  iv_out (may be null): a plane
-// of width*height float4 for (I, V_0); var_out (may be null): a plane of floats for V_N
+// of width*height float4 for (I, V_0); var_out (may be null): a plane of floats for V_N; motion (may be null): the planes M0, M1 of
+// trg_temporal_denoise_motion
 int temporal_denoise(trg_ctx *c, DenoiseState &s, const float4 *color, const float4 *guides, const float4 *pos, const float *vp, bool use_history,
-                     float4 *out, float4 *iv_out, float *var_out, const trg_temporal_params *pp, const char *who) {
+                     float4 *out, float4 *iv_out, float *var_out, const trg_temporal_params *pp, const char *who, const float4 *motion = nullptr) {
     trg_temporal_params q;
     trg_temporal_default_params(&q);
     if (pp) q = *pp;
@@ -974,6 +1031,9 @@ int temporal_denoise(trg_ctx *c, DenoiseState &s, const float4 *color, const flo
     if (overlap(out, bytes, color, bytes) || overlap(out, bytes, guides, 2 * bytes) || overlap(out, bytes, pos, bytes) || overlap(color, bytes, guides, 2 * bytes) ||
         overlap(color, bytes, pos, bytes) || overlap(pos, bytes, guides, 2 * bytes))
         return fail(c, TRG_ERR_INVALID, "%s: the buffers overlap", who);
+    if (motion && (overlap(motion, 2 * bytes, out, bytes) || overlap(motion, 2 * bytes, color, bytes) || overlap(motion, 2 * bytes, guides, 2 * bytes) ||
+                   overlap(motion, 2 * bytes, pos, bytes)))
+        return fail(c, TRG_ERR_INVALID, "%s: motion_device overlaps another buffer", who);
     for (int k = 0; k < 16; ++k)
         if (!(vp[k] - vp[k] == 0.0f)) return fail(c, TRG_ERR_INVALID, "%s: prev_view_proj is not finite", who);
     if (int rc = lazy_planes(c, s, s.hist[0], 4, "the history planes")) return rc;
@@ -988,7 +1048,9 @@ int temporal_denoise(trg_ctx *c, DenoiseState &s, const float4 *color, const flo
     r.w = (int)c->w; r.h = (int)c->h; r.demod = q.demodulate ? 1 : 0;
     for (int k = 0; k < 16; ++k) r.vp[k] = vp[k];
     r.alpha = q.alpha; r.alpha_moments = q.alpha_moments; r.plane_tol = q.plane_tol; r.normal_tol = q.normal_tol; r.max_history = (float)q.max_history;
-    if (int rc = launch_tiles(c, who, DN_FOR_SETTING(c, dn_temporal_reproject_kernel), r)) return rc;
+    if (motion) { r.m0 = motion; r.m1 = motion + n; }
+    if (int rc = launch_tiles(c, who, motion ? DN_FOR_SETTING(c, dn_temporal_reproject_kernel, true) : DN_FOR_SETTING(c, dn_temporal_reproject_kernel, false), r))
+        return rc;
     s.hist_cur ^= 1;          // (enqueued: from here on the new planes are the history, also if a later launch fails)
     s.hist_valid = true;
     if (int rc = launch_tiles(c, who, DN_FOR_SETTING(c, dn_temporal_spatial_kernel), r.oc, r.om, s.fguide, s.ping, c->w, c->h, q.sigma_normal, q.sigma_depth)) return rc;
@@ -1008,17 +1070,26 @@ int render_temporal(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n, uint32_
     if (!invert4(c->u.inv_view_proj, vp_now)) return fail(c, TRG_ERR_INVALID, "%s: the uniforms' inverse view-projection is singular or not finite", who);
     const size_t npix = (size_t)c->w * c->h, bytes = npix * sizeof(float4);
     if (overlap(out, bytes, c->accum, bytes)) return fail(c, TRG_ERR_INVALID, "%s: out_device overlaps the bound accumulation buffer", who);
+    // armed (trg_temporal_set_previous_scene): this call looks for the history where the geometry was, and consumes the arming
+    const bool armed = s.armed;
+    if (armed && !have_previous_scene(c, s))
+        return fail(c, TRG_ERR_INVALID, "%s: the previous scene has %u triangles, the loaded scene %u: call trg_temporal_set_previous_scene again, or trg_temporal_reset",
+                    who, s.prev_tris, c->scene_loaded ? c->sc.n_tris : 0u);
     if (int rc = lazy_planes(c, s, s.timg, 1, "the temporal path's image")) return rc;
     if (int rc = lazy_planes(c, s, s.tpos, 1, "the position plane")) return rc;
+    if (armed)
+        if (int rc = lazy_planes(c, s, s.tmotion, 2, "the motion planes")) return rc;
     if (int rc = render_zeroed(c, s.timg, 1, b, n, bounces)) return rc;
     const float f = (float)((double)((uint64_t)b + n) / (double)n);
     if (int rc = launch_each(c, who, dn_scale_kernel, npix, s.timg, f, npix)) return rc;
-    if (int rc = guides_render(c, s, b, s.guides, s.tpos)) return rc;
+    if (int rc = armed ? guides_render_motion(c, s, b, s.guides, s.tpos, s.tmotion) : guides_render(c, s, b, s.guides, s.tpos)) return rc;
     const float zero[16] = {};
-    const int rc = temporal_denoise(c, s, s.timg, s.guides, s.tpos, s.have_prev_vp ? s.prev_vp : zero, s.have_prev_vp, out, nullptr, nullptr, p, who);
+    const int rc = temporal_denoise(c, s, s.timg, s.guides, s.tpos, s.have_prev_vp ? s.prev_vp : zero, s.have_prev_vp, out, nullptr, nullptr, p, who,
+                                    armed ? s.tmotion : nullptr);
     if (rc != TRG_OK) return rc;
     for (int k = 0; k < 16; ++k) s.prev_vp[k] = vp_now[k];
     s.have_prev_vp = true;
+    s.armed = false;
     return TRG_OK;
 }
 
@@ -1028,7 +1099,7 @@ struct HostTrip {
     trg_ctx *c;
     const char *who;
     int rc = TRG_OK;
-    struct { void *dev, *host; size_t bytes; } temp[8] = {};   // (trg_temporal_denoise_host has six)
+    struct { void *dev, *host; size_t bytes; } temp[8] = {};   // (trg_temporal_denoise_motion_host has seven)
     int n = 0;
     HostTrip(trg_ctx *c_, const char *who_) : c(c_), who(who_) {}
     HostTrip(const HostTrip &) = delete;
@@ -1264,6 +1335,7 @@ int trg_temporal_reset(trg_ctx *c) {
     if (it == g_states.end()) return TRG_OK;
     it->second.hist_valid = false;
     it->second.have_prev_vp = false;
+    it->second.armed = false;
     return TRG_OK;
 }
 
@@ -1335,6 +1407,93 @@ int trg_render_temporal_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp,
     HostTrip t(c, "trg_render_temporal_read");
     float4 *out = t.result(out_host, s->pixels * sizeof(float4));
     if (t.rc == TRG_OK) t.rc = render_temporal(c, *s, frameIndexBegin, spp, bounces, out, p, "trg_render_temporal_read");
+    return t.finish();
+}
+
+int trg_temporal_set_previous_scene(trg_ctx *c, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris) {
+    const char *const who = "trg_temporal_set_previous_scene";
+    if (!c) return TRG_ERR_INVALID;
+    if (n_tris != 0 && (!positions3 || !indices)) return fail(c, TRG_ERR_INVALID, "%s: positions3 / indices is NULL", who);
+    DenoiseState *s;
+    if (int rc = enter(c, s, who)) return rc;
+    if (!c->scene_loaded) return fail(c, TRG_ERR_INVALID, "%s: no scene loaded", who);
+    if (n_tris == 0) {
+        s->prev_tris = 0;
+        s->armed = false;
+        return TRG_OK;
+    }
+    if (n_tris != c->sc.n_tris) return fail(c, TRG_ERR_INVALID, "%s: %u triangles, the loaded scene has %u", who, n_tris, c->sc.n_tris);
+    for (size_t k = 0; k < (size_t)n_tris * 3u; ++k)
+        if (indices[k] >= n_verts) return fail(c, TRG_ERR_INVALID, "%s: index %u of triangle %zu is outside the %u vertices", who, indices[k], k / 3u, n_verts);
+    std::vector<float> rec((size_t)n_tris * kPrevRecord * 4u, 0.0f);
+    for (size_t t = 0; t < n_tris; ++t) {
+        float *r = rec.data() + t * kPrevRecord * 4u;
+        for (int corner = 0; corner < 3; ++corner)
+            for (int k = 0; k < 3; ++k) {
+                r[corner * 3 + k] = positions3[(size_t)indices[t * 3u + corner] * 3u + k];
+                if (normals3) r[9 + corner * 3 + k] = normals3[(t * 3u + corner) * 3u + k];
+            }
+    }
+    if (int rc = grow(c, s->prev_geo, s->prev_cap, (size_t)n_tris * kPrevRecord, sizeof(float4), "previous scene")) {
+        s->prev_tris = 0;   // (the old array is gone)
+        s->armed = false;
+        return rc;
+    }
+    // the running launches of an earlier call may still read the array: the copy is ordered behind them on the context's stream
+    DN_HIPCHK(c, hipMemcpyAsync(s->prev_geo, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    DN_HIPCHK(c, hipStreamSynchronize(c->stream));
+    s->prev_tris = n_tris;
+    s->prev_normals = normals3 != nullptr;
+    s->armed = true;
+    return TRG_OK;
+}
+
+int trg_guides_render_motion(trg_ctx *c, uint32_t frameIndex, void *guides_device, void *pos_device, void *motion_device) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_guides_render_motion")) return rc;
+    if (!guides_device || !pos_device || !motion_device) return fail(c, TRG_ERR_INVALID, "trg_guides_render_motion: NULL buffer");
+    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
+    if (overlap(guides_device, 2 * bytes, pos_device, bytes) || overlap(motion_device, 2 * bytes, guides_device, 2 * bytes) || overlap(motion_device, 2 * bytes, pos_device, bytes))
+        return fail(c, TRG_ERR_INVALID, "trg_guides_render_motion: the buffers overlap");
+    if (!have_previous_scene(c, *s)) return fail(c, TRG_ERR_INVALID, "trg_guides_render_motion: no previous scene of the loaded scene's triangle count (trg_temporal_set_previous_scene)");
+    return guides_render_motion(c, *s, frameIndex, static_cast<float4 *>(guides_device), static_cast<float4 *>(pos_device), static_cast<float4 *>(motion_device));
+}
+
+int trg_temporal_denoise_motion(trg_ctx *c, const void *color_in_device, const void *guides_device, const void *pos_device, const void *motion_device,
+                                const float prev_view_proj[16], void *out_device, const trg_temporal_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_temporal_denoise_motion")) return rc;
+    if (!color_in_device || !guides_device || !pos_device || !motion_device || !prev_view_proj || !out_device)
+        return fail(c, TRG_ERR_INVALID, "trg_temporal_denoise_motion: NULL buffer");
+    return temporal_denoise(c, *s, static_cast<const float4 *>(color_in_device), static_cast<const float4 *>(guides_device), static_cast<const float4 *>(pos_device),
+                            prev_view_proj, true, static_cast<float4 *>(out_device), nullptr, nullptr, p, "trg_temporal_denoise_motion",
+                            static_cast<const float4 *>(motion_device));
+}
+
+int trg_guides_motion_read(trg_ctx *c, uint32_t frameIndex, float *guides_host, float *pos_host, float *motion_host) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_guides_motion_read")) return rc;
+    if (!guides_host || !pos_host || !motion_host) return fail(c, TRG_ERR_INVALID, "trg_guides_motion_read: NULL buffer");
+    if (!have_previous_scene(c, *s)) return fail(c, TRG_ERR_INVALID, "trg_guides_motion_read: no previous scene of the loaded scene's triangle count (trg_temporal_set_previous_scene)");
+    const size_t bytes = s->pixels * sizeof(float4);
+    HostTrip t(c, "trg_guides_motion_read");
+    float4 *g = t.result(guides_host, 2 * bytes), *x = t.result(pos_host, bytes), *m = t.result(motion_host, 2 * bytes);
+    if (t.rc == TRG_OK) t.rc = guides_render_motion(c, *s, frameIndex, g, x, m);
+    return t.finish();
+}
+
+int trg_temporal_denoise_motion_host(trg_ctx *c, const float *color_in_host, const float *guides_host, const float *pos_host, const float *motion_host,
+                                     const float prev_view_proj[16], float *out_host, float *iv_host, float *var_host, const trg_temporal_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, "trg_temporal_denoise_motion_host")) return rc;
+    if (!color_in_host || !guides_host || !pos_host || !motion_host || !prev_view_proj || !out_host)
+        return fail(c, TRG_ERR_INVALID, "trg_temporal_denoise_motion_host: NULL buffer");
+    const size_t bytes = s->pixels * sizeof(float4);
+    HostTrip t(c, "trg_temporal_denoise_motion_host");
+    const float4 *in = t.upload(color_in_host, bytes), *g = t.upload(guides_host, 2 * bytes), *x = t.upload(pos_host, bytes), *m = t.upload(motion_host, 2 * bytes);
+    float4 *out = t.result(out_host, bytes), *iv = t.result(iv_host, bytes);
+    float *var = t.result<float>(var_host, s->pixels * sizeof(float));
+    if (t.rc == TRG_OK) t.rc = temporal_denoise(c, *s, in, g, x, prev_view_proj, true, out, iv, var, p, "trg_temporal_denoise_motion_host", m);
     return t.finish();
 }
 

@@ -13,6 +13,11 @@
     out = temporal_denoise(ctx, color, g, x, vp) # one temporal step: reproject the state's history, accumulate, filter with the temporal variance
     out = render_temporal(ctx, k, 1, 3)          # render + guides + that step; the state remembers the camera; temporal_reset(ctx) forgets
 
+    ctx.load_scene(...moved geometry...)         # moving geometry of unchanged topology keeps its history:
+    temporal_set_previous_scene(ctx, old_positions, old_normals, indices)   # where every triangle was; arms the next render_temporal
+    g, x, m = guides_motion(ctx, frame_index)    # the guides, X, and M0 / M1 [2, h, w, 4]: where each hit was and its normal then
+    out = temporal_denoise(ctx, color, g, x, vp, motion=m)                  # the step looks for the history there
+
 numpy arrays go through temporary device copies and the call waits for the result; torch ROCm tensors (float32, contiguous) are used in place
 through data_ptr() -- like trg_bind_accum -- and the call only enqueues on the context's current stream.  `reference_denoise`,
 `reference_denoise_variance` (its iteration loop alone: `reference_atrous_variance`) and `reference_temporal` are the float64 numpy evaluations
@@ -83,6 +88,11 @@ _SYMBOLS = [
     ("trg_guides_pos_read", C.c_int, [_P, _U, _P, _P]),
     ("trg_temporal_denoise_host", C.c_int, [_P, _P, _P, _P, _F16, _P, _P, _P, _TP]),
     ("trg_render_temporal_read", C.c_int, [_P, _U, _U, _U, _P, _TP]),
+    ("trg_temporal_set_previous_scene", C.c_int, [_P, _P, _P, _P, _U, _U]),
+    ("trg_guides_render_motion", C.c_int, [_P, _U, _P, _P, _P]),
+    ("trg_temporal_denoise_motion", C.c_int, [_P, _P, _P, _P, _P, _F16, _P, _TP]),
+    ("trg_guides_motion_read", C.c_int, [_P, _U, _P, _P, _P]),
+    ("trg_temporal_denoise_motion_host", C.c_int, [_P, _P, _P, _P, _P, _F16, _P, _P, _P, _TP]),
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 
@@ -289,9 +299,40 @@ def _vp_arg(prev_vp):
     return vp
 
 
-def temporal_denoise(ctx, color, guides, pos, prev_vp, out=None, params=None, return_iv=False, return_variance=False, **kw):
-    """trg_temporal_denoise.  All tensors (enqueued only) or all numpy (waits).  prev_vp: temporal_view_proj of the previous call's uniforms (host
-    memory; None: zeros, for the first call after a reset).  numpy only: return_iv also gives (I.rgb, V_0) [h, w, 4], return_variance V_N [h, w]."""
+def temporal_set_previous_scene(ctx, positions, normals, indices):
+    """trg_temporal_set_previous_scene: where the triangles of the loaded scene were at the previous call -- positions [n_verts, 3], normals
+    [3 * n_tris, 3] or None (unchanged), indices [3 * n_tris], in trg_load_scene's layouts.  Arms the state for the next render_temporal.
+    positions = None: the previous scene is forgotten."""
+    L = load()
+    if positions is None:
+        _chk(ctx, L.trg_temporal_set_previous_scene(ctx.h_ctx, None, None, None, 0, 0))
+        return
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if idx.shape[0] % 3 or (nrm is not None and nrm.shape[0] != idx.shape[0]):
+        raise ValueError("expected 3*n_tris indices and, with normals, 3*n_tris of them")
+    _chk(ctx, L.trg_temporal_set_previous_scene(ctx.h_ctx, pos.ctypes.data, None if nrm is None else nrm.ctypes.data, idx.ctypes.data, pos.shape[0], idx.shape[0] // 3))
+
+
+def guides_motion(ctx, frame_index, out=None, pos=None, motion=None):
+    """trg_guides_render_motion -> (guides [2, h, w, 4], X [h, w, 4], motion [2, h, w, 4] = M0, M1: where the hit was and its normal then, by the
+    previous scene of temporal_set_previous_scene).  out, pos, motion = float32 ROCm tensors: filled in place on the context's stream (and
+    returned); None: numpy arrays."""
+    L = load()
+    gs, xs = (2, ctx.h, ctx.w, 4), (ctx.h, ctx.w, 4)
+    if out is not None and _is_tensor(out):
+        _chk(ctx, L.trg_guides_render_motion(ctx.h_ctx, frame_index, _tensor_ptr(out, gs, "guides"), _tensor_ptr(pos, xs, "pos"), _tensor_ptr(motion, gs, "motion")))
+        return out, pos, motion
+    g, x, m = np.empty(gs, np.float32), np.empty(xs, np.float32), np.empty(gs, np.float32)
+    _chk(ctx, L.trg_guides_motion_read(ctx.h_ctx, frame_index, g.ctypes.data, x.ctypes.data, m.ctypes.data))
+    return g, x, m
+
+
+def temporal_denoise(ctx, color, guides, pos, prev_vp, out=None, params=None, return_iv=False, return_variance=False, motion=None, **kw):
+    """trg_temporal_denoise; with motion [2, h, w, 4] (M0, M1 as guides_motion gives them) trg_temporal_denoise_motion.  All tensors (enqueued
+    only) or all numpy (waits).  prev_vp: temporal_view_proj of the previous call's uniforms (host memory; None: zeros, for the first call
+    after a reset).  numpy only: return_iv also gives (I.rgb, V_0) [h, w, 4], return_variance V_N [h, w]."""
     L = load()
     p = make_temporal_params(params, **kw)
     vp = _vp_arg(prev_vp)
@@ -302,19 +343,27 @@ def temporal_denoise(ctx, color, guides, pos, prev_vp, out=None, params=None, re
             raise ValueError("return_iv / return_variance need numpy arrays (trg_temporal_denoise_host)")
         if out is None:
             out = torch.empty_like(color)
-        _chk(ctx, L.trg_temporal_denoise(ctx.h_ctx, _tensor_ptr(color, cs, "color"), _tensor_ptr(guides, gs, "guides"), _tensor_ptr(pos, cs, "pos"),
-                                         vp.ctypes.data_as(_F16), _tensor_ptr(out, cs, "out"), C.byref(p)))
+        args = (_tensor_ptr(color, cs, "color"), _tensor_ptr(guides, gs, "guides"), _tensor_ptr(pos, cs, "pos"))
+        tail = (vp.ctypes.data_as(_F16), _tensor_ptr(out, cs, "out"), C.byref(p))
+        if motion is None:
+            _chk(ctx, L.trg_temporal_denoise(ctx.h_ctx, *args, *tail))
+        else:
+            _chk(ctx, L.trg_temporal_denoise_motion(ctx.h_ctx, *args, _tensor_ptr(motion, gs, "motion"), *tail))
         return out
     c = np.ascontiguousarray(color, np.float32)
     g = np.ascontiguousarray(guides, np.float32)
     x = np.ascontiguousarray(pos, np.float32)
-    if c.shape != cs or g.shape != gs or x.shape != cs:
-        raise ValueError("color and pos must be %s and guides %s" % (cs, gs))
+    m = None if motion is None else np.ascontiguousarray(motion, np.float32)
+    if c.shape != cs or g.shape != gs or x.shape != cs or (m is not None and m.shape != gs):
+        raise ValueError("color and pos must be %s, guides and motion %s" % (cs, gs))
     o = np.empty(cs, np.float32)
     iv = np.empty(cs, np.float32) if return_iv else None
     v = np.empty((ctx.h, ctx.w), np.float32) if return_variance else None
-    _chk(ctx, L.trg_temporal_denoise_host(ctx.h_ctx, c.ctypes.data, g.ctypes.data, x.ctypes.data, vp.ctypes.data_as(_F16), o.ctypes.data,
-                                          iv.ctypes.data if return_iv else None, v.ctypes.data if return_variance else None, C.byref(p)))
+    tail = (vp.ctypes.data_as(_F16), o.ctypes.data, iv.ctypes.data if return_iv else None, v.ctypes.data if return_variance else None, C.byref(p))
+    if m is None:
+        _chk(ctx, L.trg_temporal_denoise_host(ctx.h_ctx, c.ctypes.data, g.ctypes.data, x.ctypes.data, *tail))
+    else:
+        _chk(ctx, L.trg_temporal_denoise_motion_host(ctx.h_ctx, c.ctypes.data, g.ctypes.data, x.ctypes.data, m.ctypes.data, *tail))
     res = (o,) + ((iv,) if return_iv else ()) + ((v,) if return_variance else ())
     return res if len(res) > 1 else o
 
@@ -582,7 +631,38 @@ def reference_denoise_variance(h1, h2, g0, g1, params=None, material_ids=None, r
 NEAR = 1e-4   # reference_temporal: how close (relative) to its threshold a discrete decision counts as undecidable in fp32
 
 
-def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, material_ids=None, dtype=np.float64, near_parts=False, **kw):
+def reference_motion(isect, prev_positions, prev_normals, indices, g0):
+    """The motion planes of trg_guides_render_motion, fp32-exact by construction: every product and sum below is one float32 operation in the
+    header's order.  isect: the hit records of the frame's primary rays (capi.ISECT_DTYPE, h*w of them: trg_raygen + trg_trace of the same frame
+    index); prev_positions [n_verts, 3], prev_normals [3 * n_tris, 3] or None, indices [3 * n_tris]: what trg_temporal_set_previous_scene was
+    given; g0 [h, w, 4]: the frame's G0 (M1 without previous normals).  Returns [2, h, w, 4] float32: M0, M1."""
+    f = np.float32
+    g0 = np.asarray(g0, np.float32)
+    h, w = g0.shape[:2]
+    pos = np.asarray(prev_positions, np.float32).reshape(-1, 3)
+    idx = np.asarray(indices, np.int64).reshape(-1, 3)
+    dist = np.asarray(isect["distance"], np.float32).reshape(h, w)
+    prim = np.asarray(isect["primitiveIndex"], np.int64).reshape(h, w)
+    co = np.asarray(isect["coordinates"], np.float32).reshape(h, w, 2)
+    hit = (dist >= 0) & (prim >= 0) & (prim < idx.shape[0])
+    k = np.where(hit, prim, 0)
+    c0, c1 = co[..., 0:1], co[..., 1:2]
+    c2 = (f(1.0) - c0) - c1
+
+    def blend(a):                                     # a [h, w, 3 corners, 3]
+        return ((c0 * a[..., 0, :] + c1 * a[..., 1, :]) + c2 * a[..., 2, :]).astype(np.float32)
+    m = np.zeros((2, h, w, 4), np.float32)
+    m[0, ..., :3] = blend(pos[idx[k]])
+    m[0, ..., 3] = 1.0
+    if prev_normals is None:
+        m[1, ..., :3] = g0[..., :3]
+    else:
+        m[1, ..., :3] = blend(np.asarray(prev_normals, np.float32).reshape(-1, 3, 3)[k])
+    m[:, ~hit] = 0.0
+    return m
+
+
+def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, material_ids=None, dtype=np.float64, near_parts=False, motion=None, **kw):
     """float64 evaluation of ONE step of trg_temporal_denoise's definition up to the filter: reprojection, accumulation, V_0.
     color, g0, g1, pos [h, w, 4] (float32 as the device sees them); history: the previous call's four planes (Hc, Hm, F, X), each [h, w, 4], or
     None; prev_vp: 16 floats; params: a TemporalParams, a dict or keywords over the header's defaults (no library needed); material_ids: those
@@ -592,7 +672,10 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
     cosine against normal_tol (cosines of unit vectors: absolute), W against 0 (W is a sum of bilinear weights that add up to 1: absolute; the
     window test -1 <= f < size is the same decision, every tap it removes has a weight near 0), and N against 4 (relative).  The result then
     goes through reference_atrous_variance.  near_parts: the third result is the pair (near without the last decision, near of N against 4 alone)
-    instead -- N against 4 chooses between the two forms of V_0 and nothing else, so colour, N and the moments of such a pixel are still decided."""
+    instead -- N against 4 chooses between the two forms of V_0 and nothing else, so colour, N and the moments of such a pixel are still decided.
+    motion: None, or (M0, M1) [2, h, w, 4]: trg_temporal_denoise_motion's definition -- M0.xyz in place of X(p) in the projection and the plane
+    test, M1.xyz in place of the pixel's normal in the plane and the normal test, no history where M0.w is not > 0; `near` marks the same
+    decisions, on the substituted operands."""
     dtype = _dtype(dtype)
     q = _options(_TEMPORAL_DEFAULTS, TemporalParams, params, kw)
     alpha, alpha_m, plane_tol, normal_tol = (dtype(np.float32(q[k])) for k in ("alpha", "alpha_moments", "plane_tol", "normal_tol"))
@@ -620,11 +703,16 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
     if history is not None:
         Hc, Hm, Hf, Hx = (np.asarray(p, np.float32).astype(dtype) for p in history)
         vp = np.asarray(prev_vp, np.float32).reshape(16).astype(dtype)
-        n, n_ok = unit(F[..., :3])
-        clip = [((vp[j * 4] * X[..., 0] + vp[j * 4 + 1] * X[..., 1]) + vp[j * 4 + 2] * X[..., 2]) + vp[j * 4 + 3] for j in (0, 1, 3)]
+        known = True
+        R = X                                               # where the hit was when the history was written, and its normal then
+        if motion is not None:
+            M = np.asarray(motion, np.float32).astype(dtype)
+            R, known = M[0, ..., :3], M[0, ..., 3] > 0
+        n, n_ok = unit(F[..., :3] if motion is None else M[1, ..., :3])
+        clip = [((vp[j * 4] * R[..., 0] + vp[j * 4 + 1] * R[..., 1]) + vp[j * 4 + 2] * R[..., 2]) + vp[j * 4 + 3] for j in (0, 1, 3)]
         cw = clip[2]
-        cand = ~miss & n_ok                                 # pixels that look for history at all
-        scale = np.abs(vp[12] * X[..., 0]) + np.abs(vp[13] * X[..., 1]) + np.abs(vp[14] * X[..., 2]) + np.abs(vp[15])
+        cand = ~miss & n_ok & known                         # pixels that look for history at all
+        scale = np.abs(vp[12] * R[..., 0]) + np.abs(vp[13] * R[..., 1]) + np.abs(vp[14] * R[..., 2]) + np.abs(vp[15])
         near |= cand & (np.abs(cw) <= NEAR * scale)
         front = cand & (cw > 0)
         cws = np.where(front, cw, 1.0)
@@ -646,7 +734,7 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
                 cx, cy = np.clip(qx, 0, w - 1), np.clip(qy, 0, h - 1)
                 fq, xq = Hf[cy, cx], Hx[cy, cx][..., :3]
                 live = inside & (fq[..., 3] >= 0)
-                dist = np.abs(dot3(n, xq - X))
+                dist = np.abs(dot3(n, xq - R))
                 nq, nq_ok = unit(fq[..., :3])
                 cosn = dot3(n, nq)
                 with np.errstate(invalid="ignore"):
