@@ -73,6 +73,11 @@ public:
     int getDenoise() const { return m_denoise; }
     bool getDenoiseVarianceGuided() const { return m_denoiseVar; }
     bool getDenoiseTemporal() const { return m_denoiseTemporal; }
+    // ---- changing light (trg_temporal_set_lag_correction): gate >= 0 switches the gated lag correction of the temporal steps on (3 is the
+    //      library's suggestion, TRG_TEMPORAL_LAG_GATE_DEFAULT), a negative gate off (the default).  Effective in temporal mode on one device;
+    //      it may be set before init() and survives loadScene.  False for a NaN, or when the library refuses.
+    bool setLagCorrection(float gate);
+    float getLagCorrection() const { return m_lagGate; }
     int getFrameIndex() const { return m_frameIndex; }
     double getLastRenderMs() const;
     uint64_t getRayCount() const;                       // primary + bounce + shadow rays traced so far
@@ -98,6 +103,7 @@ protected:
     bool m_denoiseVar;           // ... by the variance-guided filter from two half-sample buffers
     bool m_denoiseTemporal;      // ... or every batch a temporal step (trg_render_temporal_own)
     void *m_temporalOut;         // the last temporal step's output image (owned by the denoise state); null before the first
+    float m_lagGate;             // the gate of the lag correction of the temporal steps; < 0 = off
     // updateScene: the positions, normals and indices uploaded last (temporal mode, one device; else empty), whether they came with textures,
     // and whether the loadScene in progress keeps the temporal history
     std::vector<float> m_lastPositions, m_lastNormals;

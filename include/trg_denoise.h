@@ -284,7 +284,9 @@ TRG_API int trg_render_temporal_read(trg_ctx *ctx, uint32_t frameIndexBegin, uin
  * step either rejects good history (motion along the normal beyond plane_tol * z, a rotation beyond normal_tol) or accepts the history of
  * another surface point (a slide within the plane).  Here the caller says where every triangle was, and the step looks there.
  *
- * NOT COVERED.  Moving or changing EMITTERS: the history then holds stale lighting, and only `alpha` forgets it.  A changed TOPOLOGY (another
+ * NOT COVERED.  Moving or changing EMITTERS: the history then holds stale lighting; `alpha` forgets it, and the gated lag correction (CHANGING
+ * LIGHT below, off by default) removes what a 7 x 7 window can tell from noise -- a change of brightness almost at once, a moved shadow
+ * hardly.  A changed TOPOLOGY (another
  * triangle count, or triangle k no longer the surface triangle k was): the caller calls trg_temporal_reset.  Device groups (trg_group_*).
  * Feeding filtered colour back into the history: as above, the history holds unfiltered values.
  * ============================================================================================================================================= */
@@ -340,6 +342,56 @@ TRG_API int trg_temporal_denoise_motion(trg_ctx *ctx, const void *color_in_devic
 TRG_API int trg_guides_motion_read(trg_ctx *ctx, uint32_t frameIndex, float *guides_host, float *pos_host, float *motion_host);
 TRG_API int trg_temporal_denoise_motion_host(trg_ctx *ctx, const float *color_in_host, const float *guides_host, const float *pos_host, const float *motion_host,
                                              const float prev_view_proj[16], float *out_host, float *iv_host, float *var_host, const trg_temporal_params *p);
+
+/* =============================================================================================================================================
+ * CHANGING LIGHT: GATED LAG CORRECTION.  When the lighting changes (trg_set_uniforms: the area light lives in trg_uniforms; or a moved box
+ * whose shadow moves over a floor that did not), every surface still reprojects perfectly onto a history that is now wrong, and with
+ * alpha = 0.2 a change leaves 0.8^m of the old picture after m calls.  The new samples know better: over a 7 x 7 window their mean differs from
+ * the accumulated colour's by the LAG.  Where that difference is larger than the noise of the window mean explains, it is added to the accumulated
+ * colour.  Off by default, switched on per context; with it off every entry point enqueues what it did and gives the same bits.
+ * ============================================================================================================================================= */
+
+/* --- THE CORRECTION sits between Accumulate and Variance of ONE TEMPORAL STEP.  Notation: trg_temporal_denoise's; p a pixel that is not a miss
+ *     ("miss" includes emitters), D(q) this call's demodulated sample, I(q) the colour Accumulate produced for this call, F this call's filter G0.
+ *     The window: the 49 pixels q = p + (dx, dy), dx, dy in {-3 .. 3}, inside the image, rows outer, columns inner, the centre included;
+ *     g = w_n * w_z * w_id at s = 1 exactly as in the prefilter of trg_denoise_variance and in the spatial estimate, with the step's sigma_normal
+ *     and sigma_depth -- times 2^-k, k = floor(log2 g(p,p)) kept within [-126, 126] (g(p,p), the centre's own weight, is (n_p . n_p)^sigma_normal; a zero normal has no tap at all):
+ *     a power of two scales every sum exactly and cancels in every quotient below, so the results are those of the unscaled g bit for bit
+ *     wherever fp32 holds the unscaled sums; it is there because G2 squares a weight that w_n lets grow to 1e20 for normals longer than 1.
+ *     Per channel, every sum in window order, every product and sum one fp32 operation:
+ *       G  = sum g                    G2 = sum g * g
+ *       d  = (sum g * (D(q) - I(q))) / G
+ *       A1 = sum g * t,   A2 = sum g * (t * t),   t = D(q) - D(p)          (centred on p: no cancellation on flat regions)
+ *       se = sqrt(max(0, A2 / G - (A1 / G) * (A1 / G)) * G2) / G           the standard error of the window mean of D
+ *       m  = |d| - gate * se
+ *       Ic = max(I(p) + copysign(m, d), min(I(p), 0))   when m > 0         (soft threshold; never pushes a non-negative colour below 0)
+ *       Ic = I(p) bit for bit                           when m is not > 0, or G is not > 0, or p is a miss
+ *     Ic replaces I in the history plane Hc (N is untouched) and in (I, V_0), which is handed to the iterations and returned as iv_host.
+ *     The moments, N and V_0 are NOT corrected: after a change of lighting the temporal variance is too large for a few calls (it holds the
+ *     step between the old and the new level), and the filter is wider for as long.
+ *     Three consequences:  where D = I on the whole window (a first call without history; a second call of the same constant colour) d = 0 and
+ *     Ic = I bit for bit.  On a flat D, se = 0 and Ic = I + d: camera at rest, constant colour c0 and then c1, and every pixel whose window
+ *     holds one history length has Ic = c1 up to rounding, whatever the gate.  Every operation is continuous in its inputs (at m = 0 both forms
+ *     of Ic give I(p)); the one discrete decision, G > 0, is the spatial estimate's.
+ *     Arithmetic: fp32 without contraction; TRG_OPT_STRICT 1 uses sqrtf, 0 the hardware's sqrt; the divisions are IEEE divisions in both.
+ *     The float64 reference: toyraygun_amd/denoise.py reference_lag, reference_temporal(..., lag=gate).
+ *
+ *     On the device: ONE launch between the reprojection and the spatial estimate, and only while the correction is on: 16 x 16 tiles of 256
+ *     threads, F, (D.rgb, E.r) and (E.g, E.b), E = D - I, of the tile and 3 pixels of halo in LDS (22 x 22 x 40 B = 19 KB; D is recomputed
+ *     from the colour and G1 while staging; E(q) is the very fp32 difference the definition sums), 49 taps, eleven running sums.  It reads
+ *     (I, V_0) as the reprojection wrote it, rewrites .rgb of the new Hc plane in place and writes the corrected (I, V_0) to the filter's other
+ *     ping-pong image, so no tile reads what another one writes.  No atomics, no scratch. */
+#define TRG_TEMPORAL_LAG_GATE_DEFAULT 3.0f
+/* gate >= 0: on, for every later trg_temporal_denoise / _motion / _host and trg_render_temporal / _own / _read of this context; gate < 0: off
+ * (the state of a new context); NaN: TRG_ERR_INVALID, nothing changes.  Host only: allocates nothing on the device, harmless for a context
+ * that never denoised; survives trg_temporal_reset, ends with trg_denoise_release. */
+TRG_API int trg_temporal_set_lag_correction(trg_ctx *ctx, float gate);
+TRG_API int trg_temporal_lag_correction(trg_ctx *ctx, float *gate);   /* what is set; < 0 when off */
+/* the correction alone on host buffers (stage-level, for tests; WAITS): colour, guides as for trg_temporal_denoise_host, hc_host = a plane
+ * (I.rgb, N); out_hc_host = (Ic.rgb, N).  Emitters are marked from the context's loaded scene as everywhere.  gate must be >= 0, sigma_normal
+ * >= 0 and sigma_depth > 0, else TRG_ERR_INVALID.  The context's own setting and history are neither read nor changed. */
+TRG_API int trg_temporal_lag_correct_host(trg_ctx *ctx, const float *color_in_host, const float *guides_host, const float *hc_host, float gate,
+                                          float sigma_normal, float sigma_depth, int32_t demodulate, float *out_hc_host);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,8 @@ leg runs at rest (every tile of the spatial estimate leaves early once the histo
 call; `temporal_front_ms` = the emitter marking, the reprojection and the spatial-estimate launch (a step of 0 iterations minus its final
 copy is not separable here, so it is a step of 1 iteration minus one variance iteration of spacing 1).  The moving-geometry leg
 (trg_temporal_set_previous_scene, trg_guides_render_motion, trg_temporal_denoise_motion) comes last: the motion-plane launch, and the step with
-the motion planes beside the plain step at rest."""
+the motion planes beside the plain step at rest.  The changing-light leg (trg_temporal_set_lag_correction) is the plain step at rest with the
+lag correction on and, right beside it, off again: the two differ by the one launch of dn_temporal_lag_kernel."""
 import json
 import os
 import sys
@@ -134,6 +135,15 @@ for name, prev in (("still", b["positions"]), ("moved", moved)):
     res["temporal_5_motion_%s_ms" % name] = timed(lambda: step(vp_rest, motion=mo))
     res["temporal_1_motion_%s_ms" % name] = timed(lambda: step(vp_rest, motion=mo, iterations=1))
 res["reproject_motion_extra_ms"] = res["temporal_1_motion_still_ms"] - res["temporal_1_rest_ms"]
+# changing light: the step at rest with the lag correction on, then off, measured side by side after six calls each -- the same launches but one
+denoise.temporal_reset(c)
+for name, gate in (("lag", denoise.LAG_GATE_DEFAULT), ("lag_off", -1.0)):
+    denoise.temporal_set_lag_correction(c, gate)
+    for _ in range(6):
+        step(vp_rest)
+    res["temporal_5_%s_ms" % name] = timed(lambda: step(vp_rest))
+    res["temporal_1_%s_ms" % name] = timed(lambda: step(vp_rest, iterations=1))
+res["lag_launch_ms"] = [res["temporal_%d_lag_ms" % it] - res["temporal_%d_lag_off_ms" % it] for it in (1, 5)]
 print(json.dumps(res))
 c.bind_accum(None)
 c.set_stream(None)

@@ -1,10 +1,12 @@
 // main_cornell.cpp -- headless demo following the reference app's call order (reference src/main.cpp:16-98):
 // engine init -> three shaders -> renderer init -> camera -> Cornell box -> frame loop; then writes a PNG.
-//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal]] [orbit=DEG] [slide=D]]
+//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]]]] [orbit=DEG] [slide=D]]
 //     denoise=N    a-trous iterations of the written image, 0 = off (default)
 //     ,var         the variance-guided filter from two half-sample buffers
 //     ,temporal    the frames are rendered as `frames` calls of 1 spp, each a temporal step (reprojected history, temporal variance); the
 //                  picture is the last step's
+//     ,lag[=G]     (behind ,temporal) the gated lag correction of the accumulated colour at gate G (default 3): a moved shadow or a changed
+//                  light no longer waits for the history to fade (HipRenderer::setLagCorrection)
 //     orbit=DEG    the eye turns about the look-at point (about the vertical axis) by DEG degrees per call
 //     slide=D      before call k the box is rebuilt with the short box moved by k * D along x and handed to HipRenderer::updateScene: with
 //                  ,temporal the history follows the moving box (trg_temporal_set_previous_scene), otherwise it is a plain loadScene
@@ -20,6 +22,7 @@
 #include "engine/HipRenderer.h"
 #include "engine/Renderer.h"
 #include "engine/Shader.h"
+#include "trg_denoise.h"
 
 using namespace toyraygun;
 
@@ -53,8 +56,8 @@ int main(int argc, char **argv) {
     const char *out = argc > 5 ? argv[5] : "cornell.png";
     int denoise = 0;
     bool denoiseVar = false, denoiseTemporal = false;
-    double orbit = 0.0, slide = 0.0;
-    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal]] [orbit=DEG] [slide=D]]";
+    double orbit = 0.0, slide = 0.0, lagGate = -1.0;
+    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]]]] [orbit=DEG] [slide=D]]";
     for (int a = 6; a < argc; ++a) {
         if (strncmp(argv[a], "slide=", 6) == 0) {
             char *end = nullptr;
@@ -74,6 +77,13 @@ int main(int argc, char **argv) {
         if (comma) {
             if (strcmp(comma, ",var") == 0) denoiseVar = true;
             else if (strcmp(comma, ",temporal") == 0) denoiseTemporal = true;
+            else if (strcmp(comma, ",temporal,lag") == 0) { denoiseTemporal = true; lagGate = TRG_TEMPORAL_LAG_GATE_DEFAULT; }
+            else if (strncmp(comma, ",temporal,lag=", 14) == 0) {
+                char *end = nullptr;
+                lagGate = strtod(comma + 14, &end);
+                if (end == comma + 14 || *end != 0 || !(lagGate >= 0.0)) { std::cout << usage << std::endl; return -1; }
+                denoiseTemporal = true;
+            }
             else { std::cout << usage << std::endl; return -1; }
         }
     }
@@ -105,6 +115,7 @@ int main(int argc, char **argv) {
     // (the denoise mode first: in temporal mode the renderer remembers the geometry it uploads, for updateScene)
     HipRenderer *hip = static_cast<HipRenderer *>(renderer);
     if (!hip->setDenoise(denoise, denoiseVar, denoiseTemporal)) { std::cout << "denoise must be 0.." << 6 << std::endl; return -1; }
+    if (lagGate >= 0.0 && !hip->setLagCorrection((float)lagGate)) { std::cout << "the lag correction was refused" << std::endl; return -1; }
     Scene *scene = createCornellBoxScene();
     renderer->loadScene(scene);
     hip->setBounces((unsigned int)bounces);

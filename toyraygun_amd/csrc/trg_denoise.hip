@@ -2,6 +2,7 @@
 // the render kernels: it launches the library's stage-level raygen / trace kernels (both builds) and adds a gather kernel and the filter.
 // Behind them the variance-guided form of the filter and the temporal reprojection / accumulation that feeds it.
 // For geometry that moved: the previous scene, the motion planes and the MOTION form of the reprojection.
+// For lighting that changed: the gated lag correction of the accumulated colour.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -162,6 +163,8 @@ struct DenoiseState {
     uint32_t prev_tris = 0;
     bool prev_normals = false, armed = false;
     float4 *tmotion = nullptr;
+    // changing light (trg_temporal_set_lag_correction): the gate of the lag correction, < 0 = off.  Set on a state that may own nothing yet
+    float lag_gate = -1.0f;
 };
 std::mutex g_mutex;
 std::unordered_map<trg_ctx *, DenoiseState> g_states;
@@ -956,6 +959,111 @@ __global__ __launch_bounds__(256) void dn_temporal_spatial_kernel(const float4 *
     iv[pix].w = v0;
 }
 
+// The gated lag correction of the accumulated colour (trg_denoise.h, CHANGING LIGHT): the 7 x 7 geometry window of dn_window7, a sibling of it
+// because a tap needs the centre's D and the sums are not all linear in the payload.  Staged per pixel of the tile + 3 pixels of halo: F, and
+// 24 bytes of payload as one float4 (D.rgb, E.r) and one DnPayload<2> (E.g, E.b), E = D - I -- the rows read as dn_window7's float4 and
+// DnPayload<2> rows do, no worse on the banks.  I comes from (I, V_0) as the reprojection wrote it and is not written here: the corrected
+// colour goes to .rgb of the new Hc plane and, with V_0, to `iv_out`, another image.
+struct LagParams {
+    const float4 *color, *g0, *g1, *iv_in;   // this frame: C, F, G1; (I, V_0)
+    float4 *hc, *iv_out;
+    int w, h, demod;
+    float gate, sigma_normal, sigma_depth;
+};
+// one channel: I, the window sums of g E, g t and g t^2 (t = D(q) - D(p)), G and G2 -> Ic
+template <bool STRICT>
+__device__ __forceinline__ float dn_lag_channel(float I, float ds, float a1, float a2, float G, float G2, float gate) {
+    const float d = ds / G, m1 = a1 / G;
+    const float se = dn_sqrt<STRICT>(fmaxf(0.0f, a2 / G - m1 * m1) * G2) / G;
+    const float m = fabsf(d) - gate * se;
+    if (!(m > 0.0f)) return I;
+    return fmaxf(I + copysignf(m, d), fminf(I, 0.0f));
+}
+template <bool STRICT>
+__global__ __launch_bounds__(256) void dn_temporal_lag_kernel(const LagParams p) {
+    __shared__ float4 s_g0[kDnPreSide * kDnPreSide];
+    __shared__ float4 s_d[kDnPreSide * kDnPreSide];
+    __shared__ DnPayload<2> s_e[kDnPreSide * kDnPreSide];
+    const int x0 = (int)blockIdx.x * kDnTile, y0 = (int)blockIdx.y * kDnTile;
+    for (int k = (int)threadIdx.x; k < kDnPreSide * kDnPreSide; k += 256) {
+        const int ly = k / kDnPreSide, lx = k - ly * kDnPreSide;
+        const int gx = x0 - kDnPreR + lx, gy = y0 - kDnPreR + ly;
+        float4 g = make_float4(0.0f, 0.0f, 0.0f, -1.0f), d = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        DnPayload<2> e{};
+        if (gx >= 0 && gx < p.w && gy >= 0 && gy < p.h) {
+            const size_t q = (size_t)gy * (size_t)p.w + (size_t)gx;
+            g = p.g0[q];
+            float4 c = p.color[q];
+            const float4 i = p.iv_in[q];
+            if (p.demod && g.w >= 0.0f) c = dn_demodulate(c, p.g1[q]);
+            d = make_float4(c.x, c.y, c.z, c.x - i.x);
+            e.v[0] = c.y - i.y; e.v[1] = c.z - i.z;
+        }
+        s_g0[k] = g;
+        s_d[k] = d;
+        s_e[k] = e;
+    }
+    __syncthreads();
+    const int x = x0 + ((int)threadIdx.x & 15), y = y0 + ((int)threadIdx.x >> 4);
+    if (x >= p.w || y >= p.h) return;
+    const size_t pix = (size_t)y * (size_t)p.w + (size_t)x;
+    float4 iv = p.iv_in[pix];
+    auto guide = [&](int qx, int qy) -> float4 { return s_g0[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)]; };
+    const float4 gp = guide(x, y);
+    if (gp.w < 0.0f) {   // a miss keeps its colour (its Hc is the reprojection's)
+        p.iv_out[pix] = iv;
+        return;
+    }
+    const float4 dp = s_d[(y - y0 + kDnPreR) * kDnPreSide + (x - x0 + kDnPreR)];
+    const float grad = dn_depth_gradient(guide, x, y, p.w, p.h, gp.w);
+    // 2^-k, k = the exponent of the centre's own weight within [-126, 126]: an exact scaling that keeps g * g inside fp32 (a zero normal has no
+    // tap at all, whatever the scale)
+    const float nn = gp.x * gp.x + gp.y * gp.y + gp.z * gp.z;
+    const float gc = nn > 0.0f ? dn_geometry_weight<STRICT>(1.0f, nn, gp.w, gp.w, grad, 1.0f, 0, 0, p.sigma_normal, p.sigma_depth) : 1.0f;
+    int k2 = (int)((__float_as_uint(gc) >> 23) & 255u) - 127;
+    k2 = k2 < -126 ? -126 : (k2 > 126 ? 126 : k2);
+    const float scale = __uint_as_float((uint32_t)(127 - k2) << 23);
+    float G = 0.0f, G2 = 0.0f, er = 0.0f, eg = 0.0f, eb = 0.0f, a1r = 0.0f, a1g = 0.0f, a1b = 0.0f, a2r = 0.0f, a2g = 0.0f, a2b = 0.0f;
+#pragma unroll
+    for (int dy = -kDnPreR; dy <= kDnPreR; ++dy) {
+#pragma unroll
+        for (int dx = -kDnPreR; dx <= kDnPreR; ++dx) {
+            const int qx = x + dx, qy = y + dy;
+            if (qx < 0 || qx >= p.w || qy < 0 || qy >= p.h) continue;
+            const float4 gq = guide(qx, qy);
+            if (gq.w < 0.0f) continue;
+            const float dn = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
+            if (!(dn > 0.0f)) continue;
+            const float g = dn_geometry_weight<STRICT>(1.0f, dn, gp.w, gq.w, grad, 1.0f, dx, dy, p.sigma_normal, p.sigma_depth) * scale;
+            const int k = (qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR);
+            const float4 dq = s_d[k];
+            const DnPayload<2> eq = s_e[k];
+            const float tr = dq.x - dp.x, tg = dq.y - dp.y, tb = dq.z - dp.z;
+            G += g; G2 += g * g;
+            er += g * dq.w; eg += g * eq.v[0]; eb += g * eq.v[1];
+            a1r += g * tr; a1g += g * tg; a1b += g * tb;
+            a2r += g * (tr * tr); a2g += g * (tg * tg); a2b += g * (tb * tb);
+        }
+    }
+    if (G > 0.0f) {
+        iv.x = dn_lag_channel<STRICT>(iv.x, er, a1r, a2r, G, G2, p.gate);
+        iv.y = dn_lag_channel<STRICT>(iv.y, eg, a1g, a2g, G, G2, p.gate);
+        iv.z = dn_lag_channel<STRICT>(iv.z, eb, a1b, a2b, G, G2, p.gate);
+        p.hc[pix] = make_float4(iv.x, iv.y, iv.z, p.hc[pix].w);
+    }
+    p.iv_out[pix] = iv;
+}
+// enqueues the correction: I from `iv_in`, Ic into .rgb of `hc` and, beside iv_in's .w, into `iv_out` (neither may be iv_in)
+int lag_correct(trg_ctx *c, DenoiseState &s, const char *who, const float4 *color, const float4 *guides, const float4 *iv_in, float4 *hc, float4 *iv_out, float gate,
+                float sigma_normal, float sigma_depth, bool demod) {
+    LagParams l{};
+    l.color = color; l.g0 = s.fguide; l.g1 = guides + (size_t)c->w * c->h; l.iv_in = iv_in;
+    l.hc = hc; l.iv_out = iv_out;
+    l.w = (int)c->w; l.h = (int)c->h; l.demod = demod ? 1 : 0;
+    l.gate = gate; l.sigma_normal = sigma_normal; l.sigma_depth = sigma_depth;
+    return launch_tiles(c, who, DN_FOR_SETTING(c, dn_temporal_lag_kernel), l);
+}
+
 // iterations == 0: out.rgb = I remodulated, out.a = the input's alpha; var (may be null) = V_0
 __global__ void dn_temporal_finish_kernel(const float4 *iv, const float4 *color, const float4 *fguide, const float4 *g1, float4 *out, float *var, int demod,
                                           uint32_t n) {
@@ -1053,12 +1161,18 @@ int temporal_denoise(trg_ctx *c, DenoiseState &s, const float4 *color, const flo
         return rc;
     s.hist_cur ^= 1;          // (enqueued: from here on the new planes are the history, also if a later launch fails)
     s.hist_valid = true;
-    if (int rc = launch_tiles(c, who, DN_FOR_SETTING(c, dn_temporal_spatial_kernel), r.oc, r.om, s.fguide, s.ping, c->w, c->h, q.sigma_normal, q.sigma_depth)) return rc;
-    if (iv_out) DN_HIPCHK(c, hipMemcpyAsync(iv_out, s.ping, bytes, hipMemcpyDeviceToDevice, c->stream));
-    if (q.iterations == 0) return launch_each(c, who, dn_temporal_finish_kernel, n, s.ping, color, s.fguide, guides + n, out, var_out, q.demodulate ? 1 : 0, n);
+    // the lag correction, while it is on: (I, V_0) moves to the other ping-pong image, everything behind it starts from there
+    float4 *iv = s.ping;
+    if (s.lag_gate >= 0.0f) {
+        if (int rc = lag_correct(c, s, who, color, guides, s.ping, r.oc, s.pong, s.lag_gate, q.sigma_normal, q.sigma_depth, q.demodulate != 0)) return rc;
+        iv = s.pong;
+    }
+    if (int rc = launch_tiles(c, who, DN_FOR_SETTING(c, dn_temporal_spatial_kernel), r.oc, r.om, s.fguide, iv, c->w, c->h, q.sigma_normal, q.sigma_depth)) return rc;
+    if (iv_out) DN_HIPCHK(c, hipMemcpyAsync(iv_out, iv, bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (q.iterations == 0) return launch_each(c, who, dn_temporal_finish_kernel, n, iv, color, s.fguide, guides + n, out, var_out, q.demodulate ? 1 : 0, n);
     AtrousParams p = atrous_params(c, s, guides, q.sigma_lum, q.sigma_normal, q.sigma_depth);
     p.alpha = color; p.var_out = var_out;
-    return atrous_run<true>(c, s, who, p, s.ping, out, q.iterations, false, q.demodulate != 0);   // (the reprojection kernel demodulated)
+    return atrous_run<true>(c, s, who, p, iv, out, q.iterations, false, q.demodulate != 0);   // (the reprojection kernel demodulated)
 }
 
 int render_temporal(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n, uint32_t bounces, float4 *out, const trg_temporal_params *p, const char *who) {
@@ -1494,6 +1608,47 @@ int trg_temporal_denoise_motion_host(trg_ctx *c, const float *color_in_host, con
     float4 *out = t.result(out_host, bytes), *iv = t.result(iv_host, bytes);
     float *var = t.result<float>(var_host, s->pixels * sizeof(float));
     if (t.rc == TRG_OK) t.rc = temporal_denoise(c, *s, in, g, x, prev_view_proj, true, out, iv, var, p, "trg_temporal_denoise_motion_host", m);
+    return t.finish();
+}
+
+int trg_temporal_set_lag_correction(trg_ctx *c, float gate) {
+    if (!c) return TRG_ERR_INVALID;
+    if (!ctx_ok(c)) return fail(c, TRG_ERR_INVALID, "trg_temporal_set_lag_correction: the denoiser's view of the context does not match the library's");
+    if (gate != gate) return fail(c, TRG_ERR_INVALID, "trg_temporal_set_lag_correction: gate is NaN");
+    // allocates nothing: a state created here owns no image yet (pixels == 0), and state_of fills it in on the first call that denoises
+    std::lock_guard<std::mutex> lock(g_mutex);
+    DenoiseState &s = g_states[c];
+    if (!s.pixels) s.device = c->device;
+    s.lag_gate = gate;
+    return TRG_OK;
+}
+
+int trg_temporal_lag_correction(trg_ctx *c, float *gate) {
+    if (!c) return TRG_ERR_INVALID;
+    if (!gate) return fail(c, TRG_ERR_INVALID, "trg_temporal_lag_correction: gate is NULL");
+    std::lock_guard<std::mutex> lock(g_mutex);
+    auto it = g_states.find(c);
+    *gate = it == g_states.end() ? -1.0f : it->second.lag_gate;
+    return TRG_OK;
+}
+
+int trg_temporal_lag_correct_host(trg_ctx *c, const float *color_in_host, const float *guides_host, const float *hc_host, float gate, float sigma_normal,
+                                  float sigma_depth, int32_t demodulate, float *out_hc_host) {
+    const char *const who = "trg_temporal_lag_correct_host";
+    DenoiseState *s;
+    if (int rc = enter(c, s, who)) return rc;
+    if (!color_in_host || !guides_host || !hc_host || !out_hc_host) return fail(c, TRG_ERR_INVALID, "%s: NULL buffer", who);
+    if (!(gate >= 0.0f) || !(sigma_normal >= 0.0f) || !(sigma_depth > 0.0f)) return fail(c, TRG_ERR_INVALID, "%s: gate and sigma_normal must be >= 0 and sigma_depth > 0", who);
+    const size_t bytes = s->pixels * sizeof(float4);
+    HostTrip t(c, who);
+    const float4 *in = t.upload(color_in_host, bytes), *g = t.upload(guides_host, 2 * bytes), *hc = t.upload(hc_host, bytes);
+    float4 *res = t.result(out_hc_host, bytes);
+    if (t.rc == TRG_OK) {
+        const hipError_t e = hipMemcpyAsync(res, hc, bytes, hipMemcpyDeviceToDevice, c->stream);   // the plane whose .rgb is rewritten; N stays
+        if (e != hipSuccess) t.rc = fail(c, TRG_ERR_DEVICE, "%s: copy failed: %s", who, hipGetErrorString(e));
+    }
+    if (t.rc == TRG_OK) t.rc = exclude_emitters(c, *s, g, who);
+    if (t.rc == TRG_OK) t.rc = lag_correct(c, *s, who, in, g, hc, res, s->pong, gate, sigma_normal, sigma_depth, demodulate != 0);
     return t.finish();
 }
 

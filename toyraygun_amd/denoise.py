@@ -18,6 +18,9 @@
     g, x, m = guides_motion(ctx, frame_index)    # the guides, X, and M0 / M1 [2, h, w, 4]: where each hit was and its normal then
     out = temporal_denoise(ctx, color, g, x, vp, motion=m)                  # the step looks for the history there
 
+    temporal_set_lag_correction(ctx, 3.0)        # changing light: every later step corrects the accumulated colour by the gated lag of its
+                                                 # 7 x 7 window (off again: a negative gate); lag_correct(...) is that stage alone
+
 numpy arrays go through temporary device copies and the call waits for the result; torch ROCm tensors (float32, contiguous) are used in place
 through data_ptr() -- like trg_bind_accum -- and the call only enqueues on the context's current stream.  `reference_denoise`,
 `reference_denoise_variance` (its iteration loop alone: `reference_atrous_variance`) and `reference_temporal` are the float64 numpy evaluations
@@ -93,7 +96,11 @@ _SYMBOLS = [
     ("trg_temporal_denoise_motion", C.c_int, [_P, _P, _P, _P, _P, _F16, _P, _TP]),
     ("trg_guides_motion_read", C.c_int, [_P, _U, _P, _P, _P]),
     ("trg_temporal_denoise_motion_host", C.c_int, [_P, _P, _P, _P, _P, _F16, _P, _P, _P, _TP]),
+    ("trg_temporal_set_lag_correction", C.c_int, [_P, C.c_float]),
+    ("trg_temporal_lag_correction", C.c_int, [_P, _F16]),
+    ("trg_temporal_lag_correct_host", C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_int32, _P]),
 ]
+LAG_GATE_DEFAULT = 3.0   # TRG_TEMPORAL_LAG_GATE_DEFAULT
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 
 _bound = None
@@ -372,6 +379,34 @@ def render_temporal(ctx, frame_begin, spp, bounces, out=None, params=None, **kw)
     """trg_render_temporal: frames [frame_begin, frame_begin + spp) from a zeroed image of the state, guides and positions of frame_begin, one
     temporal step against the camera of the previous call.  The bound accumulation buffer is not touched; the rays count."""
     return _fill(ctx, "trg_render_temporal", "trg_render_temporal_read", (frame_begin, spp, bounces), out, 0, "out", C.byref(make_temporal_params(params, **kw)))
+
+
+def temporal_set_lag_correction(ctx, gate=LAG_GATE_DEFAULT):
+    """trg_temporal_set_lag_correction: gate >= 0 switches the gated lag correction of the accumulated colour on for every later temporal step of
+    this context (a lighting change no longer waits for `alpha`), gate < 0 (or None) off -- the state of a new context.  NaN is refused."""
+    _chk(ctx, load().trg_temporal_set_lag_correction(ctx.h_ctx, -1.0 if gate is None else float(gate)))
+
+
+def temporal_lag_correction(ctx):
+    """trg_temporal_lag_correction: the gate that is set; < 0 when the correction is off."""
+    gate = C.c_float(0.0)
+    _chk(ctx, load().trg_temporal_lag_correction(ctx.h_ctx, C.byref(gate)))
+    return float(gate.value)
+
+
+def lag_correct(ctx, color, guides, hc, gate, sigma_normal=128.0, sigma_depth=1.0, demodulate=1):
+    """trg_temporal_lag_correct_host: the correction alone (stage-level; numpy; waits).  color [h, w, 4], guides [2, h, w, 4], hc [h, w, 4] =
+    (I.rgb, N) -> (Ic.rgb, N) [h, w, 4].  The context's own setting and history play no part."""
+    cs, gs = (ctx.h, ctx.w, 4), (2, ctx.h, ctx.w, 4)
+    c = np.ascontiguousarray(color, np.float32)
+    g = np.ascontiguousarray(guides, np.float32)
+    hcp = np.ascontiguousarray(hc, np.float32)
+    if c.shape != cs or g.shape != gs or hcp.shape != cs:
+        raise ValueError("color and hc must be %s and guides %s" % (cs, gs))
+    o = np.empty(cs, np.float32)
+    _chk(ctx, load().trg_temporal_lag_correct_host(ctx.h_ctx, c.ctypes.data, g.ctypes.data, hcp.ctypes.data, float(gate), float(sigma_normal), float(sigma_depth),
+                                                   int(demodulate), o.ctypes.data))
+    return o
 
 
 def release(ctx):
@@ -662,7 +697,55 @@ def reference_motion(isect, prev_positions, prev_normals, indices, g0):
     return m
 
 
-def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, material_ids=None, dtype=np.float64, near_parts=False, motion=None, **kw):
+def _lag(D, I, F, miss, gate, sn, sd, dtype):
+    """The gated lag correction of the header (CHANGING LIGHT) on arrays of `dtype`: D, I [h, w, 3], F the filter's G0 with the emitters marked.
+    Returns (Ic [h, w, 3], changed [h, w] bool)."""
+    gate = dtype(np.float32(gate))
+    Wg = geometry_weights(F, 1, sn, sd, kernel=(1.0,) * 7, dtype=dtype)
+    # times 2^-k, k = the exponent of the centre's own weight within [-126, 126]: exact, and g * g stays inside fp32
+    gc = Wg[3, 3]
+    k = np.clip(np.frexp(np.where(np.isfinite(gc) & (gc > 0), gc, 1.0))[1] - 1, -126, 126)
+    Wg = np.where(miss[None, None], 0.0, np.ldexp(Wg, -k[None, None])).astype(dtype)      # (the rows of misses are meaningless: none is corrected)
+    h, w = miss.shape
+    G, G2 = np.zeros((h, w), dtype), np.zeros((h, w), dtype)
+    E, A1, A2 = (np.zeros((h, w, 3), dtype) for _ in range(3))
+    for dy in range(-3, 4):                                # rows outer, columns inner: the header's order
+        for dx in range(-3, 4):
+            g = Wg[dy + 3, dx + 3]
+            Dq, _ = _shift(D, dx, dy)
+            Iq, _ = _shift(I, dx, dy)
+            t = Dq - D
+            G += g
+            G2 += g * g
+            E += g[..., None] * (Dq - Iq)
+            A1 += g[..., None] * t
+            A2 += g[..., None] * (t * t)
+    ok = ~miss & (G > 0)
+    Gs = np.where(ok, G, 1.0).astype(dtype)[..., None]
+    d, m1 = E / Gs, A1 / Gs
+    se = np.sqrt(np.maximum(0.0, A2 / Gs - m1 * m1) * G2[..., None]) / Gs
+    m = np.abs(d) - gate * se
+    with np.errstate(invalid="ignore"):
+        on = ok[..., None] & (m > 0)
+    Ic = np.where(on, np.maximum(I + np.copysign(m, d), np.minimum(I, 0.0)), I).astype(dtype)
+    return Ic, (Ic != I).any(-1)
+
+
+def reference_lag(color, g0, g1, hc, gate, params=None, material_ids=None, dtype=np.float64, **kw):
+    """float64 evaluation of the gated lag correction (the header's CHANGING LIGHT) on its own: color, g0, g1 [h, w, 4] of this call, hc [h, w, 4]
+    = (I.rgb, N) as Accumulate left it (taken in the precision it comes in: the device's fp32 plane, or a float64 plane of reference_temporal); params: a TemporalParams, a dict or keywords -- sigma_normal, sigma_depth and demodulate are read (defaults:
+    the header's); material_ids: those of the context's scene; dtype: the working precision.  Returns (Ic [h, w, 3] of `dtype`, the [h, w] bool
+    mask of the pixels it changed)."""
+    dtype = _dtype(dtype)
+    q = _options(_TEMPORAL_DEFAULTS, TemporalParams, params, kw)
+    sn, sd = float(np.float32(q["sigma_normal"])), float(np.float32(q["sigma_depth"]))
+    C3 = np.asarray(color, np.float32)[..., :3].astype(dtype)
+    F, alb, miss = _filter_inputs(g0, g1, material_ids, dtype)
+    D = np.where(miss[..., None], C3, C3 / alb) if q["demodulate"] else C3
+    return _lag(D, np.asarray(hc)[..., :3].astype(dtype), F, miss, gate, sn, sd, dtype)
+
+
+def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, material_ids=None, dtype=np.float64, near_parts=False, motion=None, lag=None, **kw):
     """float64 evaluation of ONE step of trg_temporal_denoise's definition up to the filter: reprojection, accumulation, V_0.
     color, g0, g1, pos [h, w, 4] (float32 as the device sees them); history: the previous call's four planes (Hc, Hm, F, X), each [h, w, 4], or
     None; prev_vp: 16 floats; params: a TemporalParams, a dict or keywords over the header's defaults (no library needed); material_ids: those
@@ -675,7 +758,9 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
     instead -- N against 4 chooses between the two forms of V_0 and nothing else, so colour, N and the moments of such a pixel are still decided.
     motion: None, or (M0, M1) [2, h, w, 4]: trg_temporal_denoise_motion's definition -- M0.xyz in place of X(p) in the projection and the plane
     test, M1.xyz in place of the pixel's normal in the plane and the normal test, no history where M0.w is not > 0; `near` marks the same
-    decisions, on the substituted operands."""
+    decisions, on the substituted operands.
+    lag: None, or the gate of the lag correction (trg_temporal_set_lag_correction): Ic takes I's place in the new Hc and in iv; the moments, N
+    and V_0 are the uncorrected step's, and `near` gains nothing (the correction's one decision, G > 0, is the spatial estimate's)."""
     dtype = _dtype(dtype)
     q = _options(_TEMPORAL_DEFAULTS, TemporalParams, params, kw)
     alpha, alpha_m, plane_tol, normal_tol = (dtype(np.float32(q[k])) for k in ("alpha", "alpha_moments", "plane_tol", "normal_tol"))
@@ -773,6 +858,8 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
         M1, M2 = _gather(G, m1, 1) / gs, _gather(G, m2, 1) / gs
         spatial = np.where(gs > 0, np.maximum(0.0, M2 - M1 * M1) * dtype(4.0) / np.where(miss, 1.0, N), 0.0)
     V0 = np.where(miss, 0.0, np.where(N >= 4, np.maximum(0.0, m2 - m1 * m1), spatial)).astype(dtype)
+    if lag is not None:
+        I = _lag(D.astype(dtype), I.astype(dtype), F, miss, lag, sn, sd, dtype)[0]
     new = np.zeros((4, h, w, 4), dtype)
     new[0, ..., :3], new[0, ..., 3] = I, N
     new[1, ..., 0], new[1, ..., 1] = m1, m2
