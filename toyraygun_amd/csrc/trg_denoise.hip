@@ -7,6 +7,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -169,12 +170,17 @@ struct DenoiseState {
 std::mutex g_mutex;
 std::unordered_map<trg_ctx *, DenoiseState> g_states;
 
+// every device buffer of a state, as f(pointer, bytes per pixel that state_of allocates with the state -- 0: the buffer is allocated on first use)
+template <typename F>
+void each_buffer(DenoiseState &s, F f) {
+    f(s.rays, sizeof(trg_ray)); f(s.isect, sizeof(trg_isect)); f(s.ping, sizeof(float4)); f(s.pong, sizeof(float4)); f(s.guides, 2 * sizeof(float4));
+    f(s.fguide, sizeof(float4));
+    f(s.result, 0); f(s.rec_of_prim, 0); f(s.overflow, 0); f(s.half_acc, 0); f(s.halves, 0); f(s.hist[0], 0); f(s.hist[1], 0); f(s.timg, 0); f(s.tpos, 0);
+    f(s.prev_geo, 0); f(s.tmotion, 0);
+}
+
 void free_state(DenoiseState &s) {
-    (void)hipFree(s.rays); (void)hipFree(s.isect); (void)hipFree(s.ping); (void)hipFree(s.pong); (void)hipFree(s.guides);
-    (void)hipFree(s.rec_of_prim); (void)hipFree(s.overflow); (void)hipFree(s.result); (void)hipFree(s.fguide);
-    (void)hipFree(s.half_acc); (void)hipFree(s.halves);
-    (void)hipFree(s.hist[0]); (void)hipFree(s.hist[1]); (void)hipFree(s.timg); (void)hipFree(s.tpos);
-    (void)hipFree(s.prev_geo); (void)hipFree(s.tmotion);
+    each_buffer(s, [](auto *mem, size_t) { (void)hipFree(mem); });
     s = DenoiseState{};
 }
 
@@ -196,12 +202,10 @@ int state_of(trg_ctx *c, DenoiseState *&out) {
     if (s.device != c->device || s.pixels != n) {   // a new context at the address of one that was destroyed without a release
         if (s.pixels) { (void)hipDeviceSynchronize(); free_state(s); }
         s.device = c->device;
-        hipError_t e = hipMalloc((void **)&s.rays, n * sizeof(trg_ray));
-        if (e == hipSuccess) e = hipMalloc((void **)&s.isect, n * sizeof(trg_isect));
-        if (e == hipSuccess) e = hipMalloc((void **)&s.ping, n * sizeof(float4));
-        if (e == hipSuccess) e = hipMalloc((void **)&s.pong, n * sizeof(float4));
-        if (e == hipSuccess) e = hipMalloc((void **)&s.guides, 2 * n * sizeof(float4));
-        if (e == hipSuccess) e = hipMalloc((void **)&s.fguide, n * sizeof(float4));
+        hipError_t e = hipSuccess;
+        each_buffer(s, [&](auto *&mem, size_t per_pixel) {
+            if (per_pixel && e == hipSuccess) e = hipMalloc((void **)&mem, n * per_pixel);
+        });
         if (e != hipSuccess) {
             free_state(s);
             g_states.erase(c);
@@ -326,36 +330,6 @@ int record_map(trg_ctx *c, DenoiseState &s, const char *who) {
     return launch_each(c, who, dn_record_map_kernel, sc.n_fat, reinterpret_cast<const float4 *>(c->blob + sc.off_fat), sc.n_fat, sc.n_tris, s.rec_of_prim);
 }
 
-// pos (may be null): the world-position plane of trg_guides_render_pos
-int guides_render(trg_ctx *c, DenoiseState &s, uint32_t frameIndex, float4 *guides, float4 *pos = nullptr) {
-    if (!c->scene_loaded) return fail(c, TRG_ERR_INVALID, "trg_guides_render: no scene loaded");
-    if (!c->have_uniforms || !c->have_offsets) return fail(c, TRG_ERR_INVALID, "trg_guides_render: uniforms / pixel offsets not set");
-    const size_t n = (size_t)c->w * c->h;
-    if (n > 0x7FFFFFFFull) return fail(c, TRG_ERR_RANGE, "trg_guides_render: image too large");
-    const SceneDesc &sc = c->sc;
-    if (sc.n_tris == 0 || sc.n_fat == 0) return fail(c, TRG_ERR_INVALID, "trg_guides_render: empty scene");
-    TracePlan plan;
-    if (int rc = plan_trace(c, plan)) return rc;
-    TraceParams tp{};
-    tp.sc = sc; tp.rays = s.rays; tp.out = s.isect; tp.n = (uint32_t)n; tp.stack_off = plan.stack_off;
-    tp.stack.klds = plan.klds; tp.stack.overflow = nullptr;
-    if (plan.overflow_levels) {
-        const size_t grid_threads = ((n + kBlock - 1) / kBlock) * kBlock;
-        if (int rc = grow(c, s.overflow, s.overflow_bytes, (size_t)plan.overflow_levels * grid_threads * sizeof(int), 1, "stack scratch")) return rc;
-        tp.stack.overflow = s.overflow;
-    }
-    hipStream_t st = c->stream;
-    trg_uniforms u = c->u;
-    u.frameIndex = frameIndex;
-    hipError_t e = (c->opt_strict ? launch_raygen_strict : launch_raygen_fast)(u, c->offsets, s.rays, st);
-    if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_guides_render: raygen launch failed: %s", hipGetErrorString(e));
-    e = (c->opt_strict ? launch_trace_strict : launch_trace_fast)(tp, plan.lds_scene, false, plan.total, st);
-    if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_guides_render: trace launch failed: %s", hipGetErrorString(e));
-    if (int rc = record_map(c, s, "trg_guides_render")) return rc;
-    return launch_each(c, "trg_guides_render", pos ? dn_gather_kernel<true> : dn_gather_kernel<false>, n, s.isect, s.rec_of_prim,
-                       reinterpret_cast<const float4 *>(c->blob + sc.off_fat), sc.n_tris, c->tex, guides, guides + n, n, pos ? s.rays : nullptr, pos);
-}
-
 // ---- moving geometry: the previous scene and the motion planes (trg_denoise.h, MOVING GEOMETRY) ----
 // One record per ORIGINAL primitive index, five float4: (P0.xyz P1.x) (P1.yz P2.xy) (P2.z N0.xyz) (N1.xyz N2.x) (N2.yz 0 0)
 constexpr uint32_t kPrevRecord = 5;
@@ -389,10 +363,37 @@ __global__ void dn_motion_kernel(const trg_isect *isect, const float4 *prev, uin
 // is there a previous scene for the scene that is loaded?
 bool have_previous_scene(const trg_ctx *c, const DenoiseState &s) { return c->scene_loaded && s.prev_tris != 0 && s.prev_tris == c->sc.n_tris; }
 
-// trg_guides_render_pos and, behind it, the two motion planes (the caller has checked have_previous_scene)
-int guides_render_motion(trg_ctx *c, DenoiseState &s, uint32_t frameIndex, float4 *guides, float4 *pos, float4 *motion) {
-    if (int rc = guides_render(c, s, frameIndex, guides, pos)) return rc;
+// pos (may be null): the world-position plane of trg_guides_render_pos; motion (may be null, needs pos): behind it the two motion planes of
+// trg_guides_render_motion (the caller has checked have_previous_scene)
+int guides_render(trg_ctx *c, DenoiseState &s, uint32_t frameIndex, float4 *guides, float4 *pos = nullptr, float4 *motion = nullptr) {
+    if (!c->scene_loaded) return fail(c, TRG_ERR_INVALID, "trg_guides_render: no scene loaded");
+    if (!c->have_uniforms || !c->have_offsets) return fail(c, TRG_ERR_INVALID, "trg_guides_render: uniforms / pixel offsets not set");
     const size_t n = (size_t)c->w * c->h;
+    if (n > 0x7FFFFFFFull) return fail(c, TRG_ERR_RANGE, "trg_guides_render: image too large");
+    const SceneDesc &sc = c->sc;
+    if (sc.n_tris == 0 || sc.n_fat == 0) return fail(c, TRG_ERR_INVALID, "trg_guides_render: empty scene");
+    TracePlan plan;
+    if (int rc = plan_trace(c, plan)) return rc;
+    TraceParams tp{};
+    tp.sc = sc; tp.rays = s.rays; tp.out = s.isect; tp.n = (uint32_t)n; tp.stack_off = plan.stack_off;
+    tp.stack.klds = plan.klds; tp.stack.overflow = nullptr;
+    if (plan.overflow_levels) {
+        const size_t grid_threads = ((n + kBlock - 1) / kBlock) * kBlock;
+        if (int rc = grow(c, s.overflow, s.overflow_bytes, (size_t)plan.overflow_levels * grid_threads * sizeof(int), 1, "stack scratch")) return rc;
+        tp.stack.overflow = s.overflow;
+    }
+    hipStream_t st = c->stream;
+    trg_uniforms u = c->u;
+    u.frameIndex = frameIndex;
+    hipError_t e = (c->opt_strict ? launch_raygen_strict : launch_raygen_fast)(u, c->offsets, s.rays, st);
+    if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_guides_render: raygen launch failed: %s", hipGetErrorString(e));
+    e = (c->opt_strict ? launch_trace_strict : launch_trace_fast)(tp, plan.lds_scene, false, plan.total, st);
+    if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_guides_render: trace launch failed: %s", hipGetErrorString(e));
+    if (int rc = record_map(c, s, "trg_guides_render")) return rc;
+    if (int rc = launch_each(c, "trg_guides_render", pos ? dn_gather_kernel<true> : dn_gather_kernel<false>, n, s.isect, s.rec_of_prim,
+                             reinterpret_cast<const float4 *>(c->blob + sc.off_fat), sc.n_tris, c->tex, guides, guides + n, n, pos ? s.rays : nullptr, pos))
+        return rc;
+    if (!motion) return TRG_OK;
     return launch_each(c, "trg_guides_render_motion", s.prev_normals ? dn_motion_kernel<true> : dn_motion_kernel<false>, n, s.isect, s.prev_geo, s.prev_tris, guides,
                        motion, motion + n, n);
 }
@@ -589,10 +590,20 @@ __global__ __launch_bounds__(256) void dn_atrous_kernel(const AtrousParams p) {
 bool overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
     return (const char *)a < (const char *)b + b_bytes && (const char *)b < (const char *)a + a_bytes;
 }
-
-bool valid_params(const trg_denoise_params &q) {
-    return q.iterations >= 0 && q.iterations <= TRG_DENOISE_MAX_ITERATIONS && q.sigma_color > 0.0f && q.sigma_normal >= 0.0f && q.sigma_depth > 0.0f;
+// are these buffers pairwise disjoint?  (a null pointer is a buffer the call does not have)
+struct Span { const void *mem; size_t bytes; };
+bool disjoint(std::initializer_list<Span> spans) {
+    for (const Span *a = spans.begin(); a != spans.end(); ++a)
+        for (const Span *b = a + 1; b != spans.end(); ++b)
+            if (a->mem && b->mem && overlap(a->mem, a->bytes, b->mem, b->bytes)) return false;
+    return true;
 }
+
+// the leading fields that the three parameter structures share (sigma_color of the plain filter, sigma_lum of the other two)
+bool valid_filter(int iterations, float sigma_color, float sigma_normal, float sigma_depth) {
+    return iterations >= 0 && iterations <= TRG_DENOISE_MAX_ITERATIONS && sigma_color > 0.0f && sigma_normal >= 0.0f && sigma_depth > 0.0f;
+}
+bool valid_params(const trg_denoise_params &q) { return valid_filter(q.iterations, q.sigma_color, q.sigma_normal, q.sigma_depth); }
 
 // enqueues the filter's copy of G0 (s.fguide) with the emitters of the loaded scene marked as misses
 int exclude_emitters(trg_ctx *c, DenoiseState &s, const float4 *guides, const char *who) {
@@ -686,41 +697,50 @@ __global__ void dn_var_extract_kernel(const float4 *in, float *var, uint32_t n) 
     if (i < n) var[i] = in[i].w;
 }
 
-// The 7 x 7 geometry window at spacing 1, g = w_n w_z w_id, of the prefilter of V_0 and of the temporal step's spatial estimate: G0 and NP floats
-// of payload per pixel of the tile + 3 pixels of halo are staged in LDS ([row][x]: a wavefront's four rows of 16 lanes read 16 consecutive
-// float4 / payloads each), by the whole workgroup; then a thread with `active` set (a pixel inside the image) whose pixel is no miss gets
-// sum[k] = the g-weighted sum of payload k over the window and gs = the sum of g, and true.
+// The 7 x 7 geometry window at spacing 1, g = w_n w_z w_id, of the prefilter of V_0, of the temporal step's spatial estimate and of the lag
+// correction: the one place that stages, tests and walks it.  A user's payload is a structure `Planes` -- one array of kDnPreArea per staged plane
+// ([row][x] like s_g0 here: a wavefront's four rows of 16 lanes read 16 consecutive elements each), a `Pixel` (zeros: a pixel outside the image)
+// and put / get of a pixel at a slot -- and three pieces:
+//   load(q, g)                  the payload of pixel q, whose (filter's) G0 is g; by the whole workgroup, for the tile + 3 pixels of halo;
+//   centre(pixel, own_weight)   once, by a thread with `active` set (a pixel inside the image) whose pixel is no miss: its own payload, and
+//                               own_weight() = the weight of the centre tap (1 for a zero normal, which has no tap); returns the factor on every g;
+//   tap(pixel, g)               for each tap that counts -- inside the image, no miss, n_p . n_q > 0 --, rows outer, columns inner.
+// True for the threads that walked the window.
 constexpr int kDnPreR = 3;
 constexpr int kDnPreSide = kDnTile + 2 * kDnPreR;   // 22
+constexpr int kDnPreArea = kDnPreSide * kDnPreSide;
 template <int NP> struct alignas(4 * NP) DnPayload { float v[NP]; };
-template <bool STRICT, int NP, typename Load>
-__device__ __forceinline__ bool dn_window7(const float4 *g0, const Load payload, int w, int h, float sigma_normal, float sigma_depth, bool active, float (&sum)[NP],
-                                           float &gs) {
-    __shared__ float4 s_g0[kDnPreSide * kDnPreSide];
-    __shared__ DnPayload<NP> s_p[kDnPreSide * kDnPreSide];
+template <bool STRICT, typename Planes, typename Load, typename Centre, typename Tap>
+__device__ __forceinline__ bool dn_window7(const float4 *g0, int w, int h, float sigma_normal, float sigma_depth, bool active, const Load load, const Centre centre,
+                                           const Tap tap) {
+    __shared__ float4 s_g0[kDnPreArea];
+    __shared__ Planes s_p;
     const int x0 = (int)blockIdx.x * kDnTile, y0 = (int)blockIdx.y * kDnTile;
-    for (int k = (int)threadIdx.x; k < kDnPreSide * kDnPreSide; k += 256) {
+    for (int k = (int)threadIdx.x; k < kDnPreArea; k += 256) {
         const int ly = k / kDnPreSide, lx = k - ly * kDnPreSide;
         const int gx = x0 - kDnPreR + lx, gy = y0 - kDnPreR + ly;
         float4 g = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
-        DnPayload<NP> v{};
+        typename Planes::Pixel v{};
         if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
             const size_t q = (size_t)gy * (size_t)w + (size_t)gx;
             g = g0[q];
-            v = payload(q);
+            v = load(q, g);
         }
         s_g0[k] = g;
-        s_p[k] = v;
+        s_p.put(k, v);
     }
     __syncthreads();
     if (!active) return false;
     const int x = x0 + ((int)threadIdx.x & 15), y = y0 + ((int)threadIdx.x >> 4);
-    auto guide = [&](int qx, int qy) -> float4 { return s_g0[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)]; };
+    auto slot = [&](int qx, int qy) -> int { return (qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR); };
+    auto guide = [&](int qx, int qy) -> float4 { return s_g0[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)]; };   // (through slot() it costs the linear users three VGPRs)
     const float4 gp = guide(x, y);
     if (gp.w < 0.0f) return false;
     const float grad = dn_depth_gradient(guide, x, y, w, h, gp.w);
-    gs = 0.0f;
-    for (int k = 0; k < NP; ++k) sum[k] = 0.0f;
+    const float scale = centre(s_p.get(slot(x, y)), [&]() -> float {
+        const float nn = gp.x * gp.x + gp.y * gp.y + gp.z * gp.z;
+        return nn > 0.0f ? dn_geometry_weight<STRICT>(1.0f, nn, gp.w, gp.w, grad, 1.0f, 0, 0, sigma_normal, sigma_depth) : 1.0f;
+    });
 #pragma unroll
     for (int dy = -kDnPreR; dy <= kDnPreR; ++dy) {
 #pragma unroll
@@ -731,13 +751,34 @@ __device__ __forceinline__ bool dn_window7(const float4 *g0, const Load payload,
             if (gq.w < 0.0f) continue;
             const float dn = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
             if (!(dn > 0.0f)) continue;
-            const float g = dn_geometry_weight<STRICT>(1.0f, dn, gp.w, gq.w, grad, 1.0f, dx, dy, sigma_normal, sigma_depth);
-            const DnPayload<NP> v = s_p[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)];
-            for (int k = 0; k < NP; ++k) sum[k] += g * v.v[k];
-            gs += g;
+            const float g = dn_geometry_weight<STRICT>(1.0f, dn, gp.w, gq.w, grad, 1.0f, dx, dy, sigma_normal, sigma_depth) * scale;
+            tap(s_p.get(slot(qx, qy)), g);
         }
     }
     return true;
+}
+// The window whose sums are linear in a payload of NP floats per pixel, read by `load(q)` (an absent pixel holds zeros): sum[k] = the g-weighted
+// sum of payload k, gs = the sum of g
+template <bool STRICT, int NP, typename Load>
+__device__ __forceinline__ bool dn_window7_sums(const float4 *g0, const Load load, int w, int h, float sigma_normal, float sigma_depth, bool active, float (&sum)[NP],
+                                                float &gs) {
+    struct Planes {
+        using Pixel = DnPayload<NP>;
+        Pixel v[kDnPreArea];
+        __device__ void put(int k, const Pixel &p) { v[k] = p; }
+        __device__ Pixel get(int k) const { return v[k]; }
+    };
+    return dn_window7<STRICT, Planes>(
+        g0, w, h, sigma_normal, sigma_depth, active, [&](size_t q, const float4 &) { return load(q); },
+        [&](const DnPayload<NP> &, const auto &) {
+            gs = 0.0f;
+            for (int j = 0; j < NP; ++j) sum[j] = 0.0f;
+            return 1.0f;
+        },
+        [&](const DnPayload<NP> &v, float g) {
+            for (int j = 0; j < NP; ++j) sum[j] += g * v.v[j];
+            gs += g;
+        });
 }
 
 // The prefilter of V_0: the payload is V; the colour passes through, and a miss keeps V_0 = 0
@@ -747,7 +788,7 @@ __global__ __launch_bounds__(256) void dn_var_prefilter_kernel(const float4 *in,
     const int x = (int)blockIdx.x * kDnTile + ((int)threadIdx.x & 15), y = (int)blockIdx.y * kDnTile + ((int)threadIdx.x >> 4);
     const bool inside = x < w && y < h;
     float vs[1], gs;
-    const bool hit = dn_window7<STRICT, 1>(g0, [&](size_t q) { return DnPayload<1>{ { in[q].w } }; }, w, h, sigma_normal, sigma_depth, inside, vs, gs);
+    const bool hit = dn_window7_sums<STRICT, 1>(g0, [&](size_t q) { return DnPayload<1>{ { in[q].w } }; }, w, h, sigma_normal, sigma_depth, inside, vs, gs);
     if (!inside) return;
     const size_t pix = (size_t)y * (size_t)w + (size_t)x;
     float4 o = in[pix];
@@ -755,9 +796,7 @@ __global__ __launch_bounds__(256) void dn_var_prefilter_kernel(const float4 *in,
     out[pix] = o;
 }
 
-bool valid_var_params(const trg_denoise_var_params &q) {
-    return q.iterations >= 0 && q.iterations <= TRG_DENOISE_MAX_ITERATIONS && q.sigma_lum > 0.0f && q.sigma_normal >= 0.0f && q.sigma_depth > 0.0f;
-}
+bool valid_var_params(const trg_denoise_var_params &q) { return valid_filter(q.iterations, q.sigma_lum, q.sigma_normal, q.sigma_depth); }
 
 // var_out (may be null): a plane of width*height floats for V_N
 int denoise_variance(trg_ctx *c, DenoiseState &s, const float4 *halves, const float4 *guides, float4 *out, float *var_out, const trg_denoise_var_params *pp) {
@@ -826,9 +865,8 @@ int render_denoised_variance(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n
 // Temporal reprojection and accumulation (trg_denoise.h has the definition)
 // ---------------------------------------------------------------------------------------------------------------------------------------------
 bool valid_temporal_params(const trg_temporal_params &q) {
-    return q.iterations >= 0 && q.iterations <= TRG_DENOISE_MAX_ITERATIONS && q.sigma_lum > 0.0f && q.sigma_normal >= 0.0f && q.sigma_depth > 0.0f &&
-           q.alpha > 0.0f && q.alpha <= 1.0f && q.alpha_moments > 0.0f && q.alpha_moments <= 1.0f && q.plane_tol > 0.0f && q.normal_tol >= -1.0f &&
-           q.normal_tol <= 1.0f && q.max_history >= 1;
+    return valid_filter(q.iterations, q.sigma_lum, q.sigma_normal, q.sigma_depth) && q.alpha > 0.0f && q.alpha <= 1.0f && q.alpha_moments > 0.0f &&
+           q.alpha_moments <= 1.0f && q.plane_tol > 0.0f && q.normal_tol >= -1.0f && q.normal_tol <= 1.0f && q.max_history >= 1;
 }
 
 struct ReprojectParams {
@@ -950,7 +988,7 @@ __global__ __launch_bounds__(256) void dn_temporal_spatial_kernel(const float4 *
     if (!(s_need[0] | s_need[1] | s_need[2] | s_need[3])) return;   // (uniform over the workgroup)
     float sm[2], gs;
     const auto moments = [&](size_t q) { const float4 mm = hm[q]; return DnPayload<2>{ { mm.x, mm.y } }; };
-    if (!dn_window7<STRICT, 2>(g0, moments, w, h, sigma_normal, sigma_depth, need, sm, gs)) return;
+    if (!dn_window7_sums<STRICT, 2>(g0, moments, w, h, sigma_normal, sigma_depth, need, sm, gs)) return;
     float v0 = 0.0f;
     if (gs > 0.0f) {
         const float M1 = sm[0] / gs, M2 = sm[1] / gs;
@@ -959,11 +997,11 @@ __global__ __launch_bounds__(256) void dn_temporal_spatial_kernel(const float4 *
     iv[pix].w = v0;
 }
 
-// The gated lag correction of the accumulated colour (trg_denoise.h, CHANGING LIGHT): the 7 x 7 geometry window of dn_window7, a sibling of it
-// because a tap needs the centre's D and the sums are not all linear in the payload.  Staged per pixel of the tile + 3 pixels of halo: F, and
-// 24 bytes of payload as one float4 (D.rgb, E.r) and one DnPayload<2> (E.g, E.b), E = D - I -- the rows read as dn_window7's float4 and
-// DnPayload<2> rows do, no worse on the banks.  I comes from (I, V_0) as the reprojection wrote it and is not written here: the corrected
-// colour goes to .rgb of the new Hc plane and, with V_0, to `iv_out`, another image.
+// The gated lag correction of the accumulated colour (trg_denoise.h, CHANGING LIGHT) over the 7 x 7 geometry window of dn_window7; a tap needs
+// the centre's D and the sums are not all linear in the payload, so the tap body is its own.  Staged per pixel: 24 bytes of payload as one float4
+// (D.rgb, E.r) and one DnPayload<2> (E.g, E.b), E = D - I -- the rows read as the window's float4 and DnPayload<2> rows do, no worse on the
+// banks.  I comes from (I, V_0) as the reprojection wrote it and is not written here: the corrected colour goes to .rgb of the new Hc plane and,
+// with V_0, to `iv_out`, another image.
 struct LagParams {
     const float4 *color, *g0, *g1, *iv_in;   // this frame: C, F, G1; (I, V_0)
     float4 *hc, *iv_out;
@@ -981,71 +1019,44 @@ __device__ __forceinline__ float dn_lag_channel(float I, float ds, float a1, flo
 }
 template <bool STRICT>
 __global__ __launch_bounds__(256) void dn_temporal_lag_kernel(const LagParams p) {
-    __shared__ float4 s_g0[kDnPreSide * kDnPreSide];
-    __shared__ float4 s_d[kDnPreSide * kDnPreSide];
-    __shared__ DnPayload<2> s_e[kDnPreSide * kDnPreSide];
-    const int x0 = (int)blockIdx.x * kDnTile, y0 = (int)blockIdx.y * kDnTile;
-    for (int k = (int)threadIdx.x; k < kDnPreSide * kDnPreSide; k += 256) {
-        const int ly = k / kDnPreSide, lx = k - ly * kDnPreSide;
-        const int gx = x0 - kDnPreR + lx, gy = y0 - kDnPreR + ly;
-        float4 g = make_float4(0.0f, 0.0f, 0.0f, -1.0f), d = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        DnPayload<2> e{};
-        if (gx >= 0 && gx < p.w && gy >= 0 && gy < p.h) {
-            const size_t q = (size_t)gy * (size_t)p.w + (size_t)gx;
-            g = p.g0[q];
-            float4 c = p.color[q];
-            const float4 i = p.iv_in[q];
-            if (p.demod && g.w >= 0.0f) c = dn_demodulate(c, p.g1[q]);
-            d = make_float4(c.x, c.y, c.z, c.x - i.x);
-            e.v[0] = c.y - i.y; e.v[1] = c.z - i.z;
-        }
-        s_g0[k] = g;
-        s_d[k] = d;
-        s_e[k] = e;
-    }
-    __syncthreads();
-    const int x = x0 + ((int)threadIdx.x & 15), y = y0 + ((int)threadIdx.x >> 4);
-    if (x >= p.w || y >= p.h) return;
+    struct Planes {
+        struct Pixel { float4 d; DnPayload<2> e; };
+        float4 d[kDnPreArea];
+        DnPayload<2> e[kDnPreArea];
+        __device__ void put(int k, const Pixel &p) { d[k] = p.d; e[k] = p.e; }
+        __device__ Pixel get(int k) const { return Pixel{ d[k], e[k] }; }
+    };
+    const int x = (int)blockIdx.x * kDnTile + ((int)threadIdx.x & 15), y = (int)blockIdx.y * kDnTile + ((int)threadIdx.x >> 4);
+    const bool inside = x < p.w && y < p.h;
+    const auto load = [&](size_t q, const float4 &g) {
+        float4 c = p.color[q];
+        const float4 i = p.iv_in[q];
+        if (p.demod && g.w >= 0.0f) c = dn_demodulate(c, p.g1[q]);
+        return typename Planes::Pixel{ make_float4(c.x, c.y, c.z, c.x - i.x), { { c.y - i.y, c.z - i.z } } };
+    };
+    float4 dp;
+    const auto centre = [&](const typename Planes::Pixel &own, const auto &own_weight) -> float {
+        dp = own.d;
+        // 2^-k, k = the exponent of the centre's own weight within [-126, 126]: an exact scaling that keeps g * g inside fp32
+        int k2 = (int)((__float_as_uint(own_weight()) >> 23) & 255u) - 127;
+        k2 = k2 < -126 ? -126 : (k2 > 126 ? 126 : k2);
+        return __uint_as_float((uint32_t)(127 - k2) << 23);
+    };
+    float G = 0.0f, G2 = 0.0f, er = 0.0f, eg = 0.0f, eb = 0.0f, a1r = 0.0f, a1g = 0.0f, a1b = 0.0f, a2r = 0.0f, a2g = 0.0f, a2b = 0.0f;
+    const auto tap = [&](const typename Planes::Pixel &q, float g) {
+        const float4 dq = q.d;
+        const DnPayload<2> eq = q.e;
+        const float tr = dq.x - dp.x, tg = dq.y - dp.y, tb = dq.z - dp.z;
+        G += g; G2 += g * g;
+        er += g * dq.w; eg += g * eq.v[0]; eb += g * eq.v[1];
+        a1r += g * tr; a1g += g * tg; a1b += g * tb;
+        a2r += g * (tr * tr); a2g += g * (tg * tg); a2b += g * (tb * tb);
+    };
+    const bool hit = dn_window7<STRICT, Planes>(p.g0, p.w, p.h, p.sigma_normal, p.sigma_depth, inside, load, centre, tap);
+    if (!inside) return;
     const size_t pix = (size_t)y * (size_t)p.w + (size_t)x;
     float4 iv = p.iv_in[pix];
-    auto guide = [&](int qx, int qy) -> float4 { return s_g0[(qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR)]; };
-    const float4 gp = guide(x, y);
-    if (gp.w < 0.0f) {   // a miss keeps its colour (its Hc is the reprojection's)
-        p.iv_out[pix] = iv;
-        return;
-    }
-    const float4 dp = s_d[(y - y0 + kDnPreR) * kDnPreSide + (x - x0 + kDnPreR)];
-    const float grad = dn_depth_gradient(guide, x, y, p.w, p.h, gp.w);
-    // 2^-k, k = the exponent of the centre's own weight within [-126, 126]: an exact scaling that keeps g * g inside fp32 (a zero normal has no
-    // tap at all, whatever the scale)
-    const float nn = gp.x * gp.x + gp.y * gp.y + gp.z * gp.z;
-    const float gc = nn > 0.0f ? dn_geometry_weight<STRICT>(1.0f, nn, gp.w, gp.w, grad, 1.0f, 0, 0, p.sigma_normal, p.sigma_depth) : 1.0f;
-    int k2 = (int)((__float_as_uint(gc) >> 23) & 255u) - 127;
-    k2 = k2 < -126 ? -126 : (k2 > 126 ? 126 : k2);
-    const float scale = __uint_as_float((uint32_t)(127 - k2) << 23);
-    float G = 0.0f, G2 = 0.0f, er = 0.0f, eg = 0.0f, eb = 0.0f, a1r = 0.0f, a1g = 0.0f, a1b = 0.0f, a2r = 0.0f, a2g = 0.0f, a2b = 0.0f;
-#pragma unroll
-    for (int dy = -kDnPreR; dy <= kDnPreR; ++dy) {
-#pragma unroll
-        for (int dx = -kDnPreR; dx <= kDnPreR; ++dx) {
-            const int qx = x + dx, qy = y + dy;
-            if (qx < 0 || qx >= p.w || qy < 0 || qy >= p.h) continue;
-            const float4 gq = guide(qx, qy);
-            if (gq.w < 0.0f) continue;
-            const float dn = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
-            if (!(dn > 0.0f)) continue;
-            const float g = dn_geometry_weight<STRICT>(1.0f, dn, gp.w, gq.w, grad, 1.0f, dx, dy, p.sigma_normal, p.sigma_depth) * scale;
-            const int k = (qy - y0 + kDnPreR) * kDnPreSide + (qx - x0 + kDnPreR);
-            const float4 dq = s_d[k];
-            const DnPayload<2> eq = s_e[k];
-            const float tr = dq.x - dp.x, tg = dq.y - dp.y, tb = dq.z - dp.z;
-            G += g; G2 += g * g;
-            er += g * dq.w; eg += g * eq.v[0]; eb += g * eq.v[1];
-            a1r += g * tr; a1g += g * tg; a1b += g * tb;
-            a2r += g * (tr * tr); a2g += g * (tg * tg); a2b += g * (tb * tb);
-        }
-    }
-    if (G > 0.0f) {
+    if (hit && G > 0.0f) {   // (a miss keeps its colour: its Hc is the reprojection's)
         iv.x = dn_lag_channel<STRICT>(iv.x, er, a1r, a2r, G, G2, p.gate);
         iv.y = dn_lag_channel<STRICT>(iv.y, eg, a1g, a2g, G, G2, p.gate);
         iv.z = dn_lag_channel<STRICT>(iv.z, eb, a1b, a2b, G, G2, p.gate);
@@ -1136,11 +1147,8 @@ int temporal_denoise(trg_ctx *c, DenoiseState &s, const float4 *color, const flo
         return fail(c, TRG_ERR_INVALID, "%s: iterations must be 0..%d, the sigmas and plane_tol positive, alpha and alpha_moments in (0, 1], normal_tol in [-1, 1], max_history >= 1",
                     who, TRG_DENOISE_MAX_ITERATIONS);
     const size_t n = (size_t)c->w * c->h, bytes = n * sizeof(float4);
-    if (overlap(out, bytes, color, bytes) || overlap(out, bytes, guides, 2 * bytes) || overlap(out, bytes, pos, bytes) || overlap(color, bytes, guides, 2 * bytes) ||
-        overlap(color, bytes, pos, bytes) || overlap(pos, bytes, guides, 2 * bytes))
-        return fail(c, TRG_ERR_INVALID, "%s: the buffers overlap", who);
-    if (motion && (overlap(motion, 2 * bytes, out, bytes) || overlap(motion, 2 * bytes, color, bytes) || overlap(motion, 2 * bytes, guides, 2 * bytes) ||
-                   overlap(motion, 2 * bytes, pos, bytes)))
+    if (!disjoint({ { out, bytes }, { color, bytes }, { guides, 2 * bytes }, { pos, bytes } })) return fail(c, TRG_ERR_INVALID, "%s: the buffers overlap", who);
+    if (!disjoint({ { motion, 2 * bytes }, { out, bytes }, { color, bytes }, { guides, 2 * bytes }, { pos, bytes } }))   // (the last four are disjoint)
         return fail(c, TRG_ERR_INVALID, "%s: motion_device overlaps another buffer", who);
     for (int k = 0; k < 16; ++k)
         if (!(vp[k] - vp[k] == 0.0f)) return fail(c, TRG_ERR_INVALID, "%s: prev_view_proj is not finite", who);
@@ -1196,7 +1204,7 @@ int render_temporal(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n, uint32_
     if (int rc = render_zeroed(c, s.timg, 1, b, n, bounces)) return rc;
     const float f = (float)((double)((uint64_t)b + n) / (double)n);
     if (int rc = launch_each(c, who, dn_scale_kernel, npix, s.timg, f, npix)) return rc;
-    if (int rc = armed ? guides_render_motion(c, s, b, s.guides, s.tpos, s.tmotion) : guides_render(c, s, b, s.guides, s.tpos)) return rc;
+    if (int rc = guides_render(c, s, b, s.guides, s.tpos, armed ? s.tmotion : nullptr)) return rc;
     const float zero[16] = {};
     const int rc = temporal_denoise(c, s, s.timg, s.guides, s.tpos, s.have_prev_vp ? s.prev_vp : zero, s.have_prev_vp, out, nullptr, nullptr, p, who,
                                     armed ? s.tmotion : nullptr);
@@ -1264,6 +1272,78 @@ int enter(trg_ctx *c, DenoiseState *&s, const char *who) {
     return state_of(c, s);
 }
 
+// ---- the bodies that families of entry points share; `who` is the entry point's own name ----
+// _own: run(state, image) into the state's result image, whose address is handed out
+template <typename Run>
+int run_own(trg_ctx *c, const char *who, void **out_device, const Run run) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, who)) return rc;
+    if (!out_device) return fail(c, TRG_ERR_INVALID, "%s: out_device is NULL", who);
+    if (int rc = own_result(c, *s, who)) return rc;
+    if (int rc = run(*s, s->result)) return rc;
+    *out_device = s->result;
+    return TRG_OK;
+}
+// _read: run(state, images) into a temporary of `planes` images that goes to `host`, the argument the entry point calls `what`
+template <typename Run>
+int run_read(trg_ctx *c, const char *who, float *host, const char *what, size_t planes, const Run run) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, who)) return rc;
+    if (!host) return fail(c, TRG_ERR_INVALID, "%s: %s is NULL", who, what);
+    HostTrip t(c, who);
+    float4 *res = t.result(host, planes * s->pixels * sizeof(float4));
+    if (t.rc == TRG_OK) t.rc = run(*s, res);
+    return t.finish();
+}
+// trg_guides_render_pos and, moving, trg_guides_render_motion
+int guides_pos_device(trg_ctx *c, const char *who, uint32_t frameIndex, void *guides, void *pos, bool moving, void *motion) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, who)) return rc;
+    if (!guides || !pos || (moving && !motion)) return fail(c, TRG_ERR_INVALID, "%s: NULL buffer", who);
+    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
+    if (!disjoint({ { guides, 2 * bytes }, { pos, bytes }, { motion, 2 * bytes } }))
+        return fail(c, TRG_ERR_INVALID, moving ? "%s: the buffers overlap" : "%s: pos_device overlaps guides_device", who);
+    if (moving && !have_previous_scene(c, *s))
+        return fail(c, TRG_ERR_INVALID, "%s: no previous scene of the loaded scene's triangle count (trg_temporal_set_previous_scene)", who);
+    return guides_render(c, *s, frameIndex, static_cast<float4 *>(guides), static_cast<float4 *>(pos), static_cast<float4 *>(motion));
+}
+// trg_guides_pos_read and, moving, trg_guides_motion_read
+int guides_pos_host(trg_ctx *c, const char *who, uint32_t frameIndex, float *guides, float *pos, bool moving, float *motion) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, who)) return rc;
+    if (!guides || !pos || (moving && !motion)) return fail(c, TRG_ERR_INVALID, "%s: NULL buffer", who);
+    if (moving && !have_previous_scene(c, *s))
+        return fail(c, TRG_ERR_INVALID, "%s: no previous scene of the loaded scene's triangle count (trg_temporal_set_previous_scene)", who);
+    const size_t bytes = s->pixels * sizeof(float4);
+    HostTrip t(c, who);
+    float4 *g = t.result(guides, 2 * bytes), *x = t.result(pos, bytes), *m = t.result(motion, 2 * bytes);
+    if (t.rc == TRG_OK) t.rc = guides_render(c, *s, frameIndex, g, x, m);
+    return t.finish();
+}
+// trg_temporal_denoise and, moving, trg_temporal_denoise_motion
+int temporal_device(trg_ctx *c, const char *who, const void *color, const void *guides, const void *pos, bool moving, const void *motion, const float *prev_view_proj,
+                    void *out, const trg_temporal_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, who)) return rc;
+    if (!color || !guides || !pos || (moving && !motion) || !prev_view_proj || !out) return fail(c, TRG_ERR_INVALID, "%s: NULL buffer", who);
+    return temporal_denoise(c, *s, static_cast<const float4 *>(color), static_cast<const float4 *>(guides), static_cast<const float4 *>(pos), prev_view_proj, true,
+                            static_cast<float4 *>(out), nullptr, nullptr, p, who, static_cast<const float4 *>(motion));
+}
+// trg_temporal_denoise_host and, moving, trg_temporal_denoise_motion_host
+int temporal_host(trg_ctx *c, const char *who, const float *color, const float *guides, const float *pos, bool moving, const float *motion, const float *prev_view_proj,
+                  float *out_host, float *iv_host, float *var_host, const trg_temporal_params *p) {
+    DenoiseState *s;
+    if (int rc = enter(c, s, who)) return rc;
+    if (!color || !guides || !pos || (moving && !motion) || !prev_view_proj || !out_host) return fail(c, TRG_ERR_INVALID, "%s: NULL buffer", who);
+    const size_t bytes = s->pixels * sizeof(float4);
+    HostTrip t(c, who);
+    const float4 *in = t.upload(color, bytes), *g = t.upload(guides, 2 * bytes), *x = t.upload(pos, bytes), *m = moving ? t.upload(motion, 2 * bytes) : nullptr;
+    float4 *out = t.result(out_host, bytes), *iv = t.result(iv_host, bytes);
+    float *var = t.result<float>(var_host, s->pixels * sizeof(float));
+    if (t.rc == TRG_OK) t.rc = temporal_denoise(c, *s, in, g, x, prev_view_proj, true, out, iv, var, p, who, m);
+    return t.finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -1298,14 +1378,10 @@ int trg_render_denoised(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint
 }
 
 int trg_denoise_accum(trg_ctx *c, uint32_t frameIndex, const trg_denoise_params *p, void **out_device) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_denoise_accum")) return rc;
-    if (!out_device) return fail(c, TRG_ERR_INVALID, "trg_denoise_accum: out_device is NULL");
-    if (int rc = own_result(c, *s, "trg_denoise_accum")) return rc;
-    if (int rc = guides_render(c, *s, frameIndex, s->guides)) return rc;
-    if (int rc = denoise(c, *s, reinterpret_cast<const float4 *>(c->accum), s->guides, s->result, p)) return rc;
-    *out_device = s->result;
-    return TRG_OK;
+    return run_own(c, "trg_denoise_accum", out_device, [&](DenoiseState &s, float4 *out) {
+        if (int rc = guides_render(c, s, frameIndex, s.guides)) return rc;
+        return denoise(c, s, reinterpret_cast<const float4 *>(c->accum), s.guides, out, p);
+    });
 }
 
 int trg_denoise_release(trg_ctx *c) {
@@ -1321,13 +1397,7 @@ int trg_denoise_release(trg_ctx *c) {
 }
 
 int trg_guides_read(trg_ctx *c, uint32_t frameIndex, float *guides_host) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_guides_read")) return rc;
-    if (!guides_host) return fail(c, TRG_ERR_INVALID, "trg_guides_read: guides_host is NULL");
-    HostTrip t(c, "trg_guides_read");
-    float4 *g = t.result(guides_host, 2 * s->pixels * sizeof(float4));
-    if (t.rc == TRG_OK) t.rc = guides_render(c, *s, frameIndex, g);
-    return t.finish();
+    return run_read(c, "trg_guides_read", guides_host, "guides_host", 2, [&](DenoiseState &s, float4 *g) { return guides_render(c, s, frameIndex, g); });
 }
 
 int trg_denoise_host(trg_ctx *c, const float *color_in_host, const float *guides_host, float *out_host, const trg_denoise_params *p) {
@@ -1343,13 +1413,8 @@ int trg_denoise_host(trg_ctx *c, const float *color_in_host, const float *guides
 }
 
 int trg_render_denoised_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_denoise_params *p) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_render_denoised_read")) return rc;
-    if (!out_host) return fail(c, TRG_ERR_INVALID, "trg_render_denoised_read: out_host is NULL");
-    HostTrip t(c, "trg_render_denoised_read");
-    float4 *out = t.result(out_host, s->pixels * sizeof(float4));
-    if (t.rc == TRG_OK) t.rc = trg_render_denoised(c, frameIndexBegin, spp, bounces, out, p);
-    return t.finish();
+    return run_read(c, "trg_render_denoised_read", out_host, "out_host", 1,
+                    [&](DenoiseState &, float4 *out) { return trg_render_denoised(c, frameIndexBegin, spp, bounces, out, p); });
 }
 
 void trg_denoise_var_default_params(trg_denoise_var_params *p) {
@@ -1379,23 +1444,13 @@ int trg_render_denoised_variance(trg_ctx *c, uint32_t frameIndexBegin, uint32_t 
 }
 
 int trg_render_denoised_variance_own(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, const trg_denoise_var_params *p, void **out_device) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_render_denoised_variance_own")) return rc;
-    if (!out_device) return fail(c, TRG_ERR_INVALID, "trg_render_denoised_variance_own: out_device is NULL");
-    if (int rc = own_result(c, *s, "trg_render_denoised_variance_own")) return rc;
-    if (int rc = render_denoised_variance(c, *s, frameIndexBegin, spp, bounces, s->result, p, "trg_render_denoised_variance_own")) return rc;
-    *out_device = s->result;
-    return TRG_OK;
+    const char *const who = "trg_render_denoised_variance_own";
+    return run_own(c, who, out_device, [&](DenoiseState &s, float4 *out) { return render_denoised_variance(c, s, frameIndexBegin, spp, bounces, out, p, who); });
 }
 
 int trg_render_halves_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *halves_host) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_render_halves_read")) return rc;
-    if (!halves_host) return fail(c, TRG_ERR_INVALID, "trg_render_halves_read: halves_host is NULL");
-    HostTrip t(c, "trg_render_halves_read");
-    float4 *hv = t.result(halves_host, 2 * s->pixels * sizeof(float4));
-    if (t.rc == TRG_OK) t.rc = render_halves(c, *s, frameIndexBegin, spp, bounces, hv, "trg_render_halves_read");
-    return t.finish();
+    const char *const who = "trg_render_halves_read";
+    return run_read(c, who, halves_host, "halves_host", 2, [&](DenoiseState &s, float4 *hv) { return render_halves(c, s, frameIndexBegin, spp, bounces, hv, who); });
 }
 
 int trg_denoise_variance_host(trg_ctx *c, const float *halves_host, const float *guides_host, float *out_host, float *var_host, const trg_denoise_var_params *p) {
@@ -1412,13 +1467,8 @@ int trg_denoise_variance_host(trg_ctx *c, const float *halves_host, const float 
 }
 
 int trg_render_denoised_variance_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_denoise_var_params *p) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_render_denoised_variance_read")) return rc;
-    if (!out_host) return fail(c, TRG_ERR_INVALID, "trg_render_denoised_variance_read: out_host is NULL");
-    HostTrip t(c, "trg_render_denoised_variance_read");
-    float4 *out = t.result(out_host, s->pixels * sizeof(float4));
-    if (t.rc == TRG_OK) t.rc = render_denoised_variance(c, *s, frameIndexBegin, spp, bounces, out, p, "trg_render_denoised_variance_read");
-    return t.finish();
+    const char *const who = "trg_render_denoised_variance_read";
+    return run_read(c, who, out_host, "out_host", 1, [&](DenoiseState &s, float4 *out) { return render_denoised_variance(c, s, frameIndexBegin, spp, bounces, out, p, who); });
 }
 
 void trg_temporal_default_params(trg_temporal_params *p) {
@@ -1433,12 +1483,7 @@ int trg_temporal_view_proj(const trg_uniforms *u, float vp16[16]) {
 }
 
 int trg_guides_render_pos(trg_ctx *c, uint32_t frameIndex, void *guides_device, void *pos_device) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_guides_render_pos")) return rc;
-    if (!guides_device || !pos_device) return fail(c, TRG_ERR_INVALID, "trg_guides_render_pos: NULL buffer");
-    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
-    if (overlap(guides_device, 2 * bytes, pos_device, bytes)) return fail(c, TRG_ERR_INVALID, "trg_guides_render_pos: pos_device overlaps guides_device");
-    return guides_render(c, *s, frameIndex, static_cast<float4 *>(guides_device), static_cast<float4 *>(pos_device));
+    return guides_pos_device(c, "trg_guides_render_pos", frameIndex, guides_device, pos_device, false, nullptr);
 }
 
 int trg_temporal_reset(trg_ctx *c) {
@@ -1465,11 +1510,7 @@ int trg_temporal_history_read(trg_ctx *c, float *hist_host) {
 
 int trg_temporal_denoise(trg_ctx *c, const void *color_in_device, const void *guides_device, const void *pos_device, const float prev_view_proj[16], void *out_device,
                          const trg_temporal_params *p) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_temporal_denoise")) return rc;
-    if (!color_in_device || !guides_device || !pos_device || !prev_view_proj || !out_device) return fail(c, TRG_ERR_INVALID, "trg_temporal_denoise: NULL buffer");
-    return temporal_denoise(c, *s, static_cast<const float4 *>(color_in_device), static_cast<const float4 *>(guides_device), static_cast<const float4 *>(pos_device),
-                            prev_view_proj, true, static_cast<float4 *>(out_device), nullptr, nullptr, p, "trg_temporal_denoise");
+    return temporal_device(c, "trg_temporal_denoise", color_in_device, guides_device, pos_device, false, nullptr, prev_view_proj, out_device, p);
 }
 
 int trg_render_temporal(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, void *out_device, const trg_temporal_params *p) {
@@ -1480,48 +1521,22 @@ int trg_render_temporal(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint
 }
 
 int trg_render_temporal_own(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, const trg_temporal_params *p, void **out_device) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_render_temporal_own")) return rc;
-    if (!out_device) return fail(c, TRG_ERR_INVALID, "trg_render_temporal_own: out_device is NULL");
-    if (int rc = own_result(c, *s, "trg_render_temporal_own")) return rc;
-    if (int rc = render_temporal(c, *s, frameIndexBegin, spp, bounces, s->result, p, "trg_render_temporal_own")) return rc;
-    *out_device = s->result;
-    return TRG_OK;
+    const char *const who = "trg_render_temporal_own";
+    return run_own(c, who, out_device, [&](DenoiseState &s, float4 *out) { return render_temporal(c, s, frameIndexBegin, spp, bounces, out, p, who); });
 }
 
 int trg_guides_pos_read(trg_ctx *c, uint32_t frameIndex, float *guides_host, float *pos_host) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_guides_pos_read")) return rc;
-    if (!guides_host || !pos_host) return fail(c, TRG_ERR_INVALID, "trg_guides_pos_read: NULL buffer");
-    const size_t bytes = s->pixels * sizeof(float4);
-    HostTrip t(c, "trg_guides_pos_read");
-    float4 *g = t.result(guides_host, 2 * bytes), *x = t.result(pos_host, bytes);
-    if (t.rc == TRG_OK) t.rc = guides_render(c, *s, frameIndex, g, x);
-    return t.finish();
+    return guides_pos_host(c, "trg_guides_pos_read", frameIndex, guides_host, pos_host, false, nullptr);
 }
 
 int trg_temporal_denoise_host(trg_ctx *c, const float *color_in_host, const float *guides_host, const float *pos_host, const float prev_view_proj[16], float *out_host,
                               float *iv_host, float *var_host, const trg_temporal_params *p) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_temporal_denoise_host")) return rc;
-    if (!color_in_host || !guides_host || !pos_host || !prev_view_proj || !out_host) return fail(c, TRG_ERR_INVALID, "trg_temporal_denoise_host: NULL buffer");
-    const size_t bytes = s->pixels * sizeof(float4);
-    HostTrip t(c, "trg_temporal_denoise_host");
-    const float4 *in = t.upload(color_in_host, bytes), *g = t.upload(guides_host, 2 * bytes), *x = t.upload(pos_host, bytes);
-    float4 *out = t.result(out_host, bytes), *iv = t.result(iv_host, bytes);
-    float *var = t.result<float>(var_host, s->pixels * sizeof(float));
-    if (t.rc == TRG_OK) t.rc = temporal_denoise(c, *s, in, g, x, prev_view_proj, true, out, iv, var, p, "trg_temporal_denoise_host");
-    return t.finish();
+    return temporal_host(c, "trg_temporal_denoise_host", color_in_host, guides_host, pos_host, false, nullptr, prev_view_proj, out_host, iv_host, var_host, p);
 }
 
 int trg_render_temporal_read(trg_ctx *c, uint32_t frameIndexBegin, uint32_t spp, uint32_t bounces, float *out_host, const trg_temporal_params *p) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_render_temporal_read")) return rc;
-    if (!out_host) return fail(c, TRG_ERR_INVALID, "trg_render_temporal_read: out_host is NULL");
-    HostTrip t(c, "trg_render_temporal_read");
-    float4 *out = t.result(out_host, s->pixels * sizeof(float4));
-    if (t.rc == TRG_OK) t.rc = render_temporal(c, *s, frameIndexBegin, spp, bounces, out, p, "trg_render_temporal_read");
-    return t.finish();
+    const char *const who = "trg_render_temporal_read";
+    return run_read(c, who, out_host, "out_host", 1, [&](DenoiseState &s, float4 *out) { return render_temporal(c, s, frameIndexBegin, spp, bounces, out, p, who); });
 }
 
 int trg_temporal_set_previous_scene(trg_ctx *c, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris) {
@@ -1563,52 +1578,21 @@ int trg_temporal_set_previous_scene(trg_ctx *c, const float *positions3, const f
 }
 
 int trg_guides_render_motion(trg_ctx *c, uint32_t frameIndex, void *guides_device, void *pos_device, void *motion_device) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_guides_render_motion")) return rc;
-    if (!guides_device || !pos_device || !motion_device) return fail(c, TRG_ERR_INVALID, "trg_guides_render_motion: NULL buffer");
-    const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
-    if (overlap(guides_device, 2 * bytes, pos_device, bytes) || overlap(motion_device, 2 * bytes, guides_device, 2 * bytes) || overlap(motion_device, 2 * bytes, pos_device, bytes))
-        return fail(c, TRG_ERR_INVALID, "trg_guides_render_motion: the buffers overlap");
-    if (!have_previous_scene(c, *s)) return fail(c, TRG_ERR_INVALID, "trg_guides_render_motion: no previous scene of the loaded scene's triangle count (trg_temporal_set_previous_scene)");
-    return guides_render_motion(c, *s, frameIndex, static_cast<float4 *>(guides_device), static_cast<float4 *>(pos_device), static_cast<float4 *>(motion_device));
+    return guides_pos_device(c, "trg_guides_render_motion", frameIndex, guides_device, pos_device, true, motion_device);
 }
 
 int trg_temporal_denoise_motion(trg_ctx *c, const void *color_in_device, const void *guides_device, const void *pos_device, const void *motion_device,
                                 const float prev_view_proj[16], void *out_device, const trg_temporal_params *p) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_temporal_denoise_motion")) return rc;
-    if (!color_in_device || !guides_device || !pos_device || !motion_device || !prev_view_proj || !out_device)
-        return fail(c, TRG_ERR_INVALID, "trg_temporal_denoise_motion: NULL buffer");
-    return temporal_denoise(c, *s, static_cast<const float4 *>(color_in_device), static_cast<const float4 *>(guides_device), static_cast<const float4 *>(pos_device),
-                            prev_view_proj, true, static_cast<float4 *>(out_device), nullptr, nullptr, p, "trg_temporal_denoise_motion",
-                            static_cast<const float4 *>(motion_device));
+    return temporal_device(c, "trg_temporal_denoise_motion", color_in_device, guides_device, pos_device, true, motion_device, prev_view_proj, out_device, p);
 }
 
 int trg_guides_motion_read(trg_ctx *c, uint32_t frameIndex, float *guides_host, float *pos_host, float *motion_host) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_guides_motion_read")) return rc;
-    if (!guides_host || !pos_host || !motion_host) return fail(c, TRG_ERR_INVALID, "trg_guides_motion_read: NULL buffer");
-    if (!have_previous_scene(c, *s)) return fail(c, TRG_ERR_INVALID, "trg_guides_motion_read: no previous scene of the loaded scene's triangle count (trg_temporal_set_previous_scene)");
-    const size_t bytes = s->pixels * sizeof(float4);
-    HostTrip t(c, "trg_guides_motion_read");
-    float4 *g = t.result(guides_host, 2 * bytes), *x = t.result(pos_host, bytes), *m = t.result(motion_host, 2 * bytes);
-    if (t.rc == TRG_OK) t.rc = guides_render_motion(c, *s, frameIndex, g, x, m);
-    return t.finish();
+    return guides_pos_host(c, "trg_guides_motion_read", frameIndex, guides_host, pos_host, true, motion_host);
 }
 
 int trg_temporal_denoise_motion_host(trg_ctx *c, const float *color_in_host, const float *guides_host, const float *pos_host, const float *motion_host,
                                      const float prev_view_proj[16], float *out_host, float *iv_host, float *var_host, const trg_temporal_params *p) {
-    DenoiseState *s;
-    if (int rc = enter(c, s, "trg_temporal_denoise_motion_host")) return rc;
-    if (!color_in_host || !guides_host || !pos_host || !motion_host || !prev_view_proj || !out_host)
-        return fail(c, TRG_ERR_INVALID, "trg_temporal_denoise_motion_host: NULL buffer");
-    const size_t bytes = s->pixels * sizeof(float4);
-    HostTrip t(c, "trg_temporal_denoise_motion_host");
-    const float4 *in = t.upload(color_in_host, bytes), *g = t.upload(guides_host, 2 * bytes), *x = t.upload(pos_host, bytes), *m = t.upload(motion_host, 2 * bytes);
-    float4 *out = t.result(out_host, bytes), *iv = t.result(iv_host, bytes);
-    float *var = t.result<float>(var_host, s->pixels * sizeof(float));
-    if (t.rc == TRG_OK) t.rc = temporal_denoise(c, *s, in, g, x, prev_view_proj, true, out, iv, var, p, "trg_temporal_denoise_motion_host", m);
-    return t.finish();
+    return temporal_host(c, "trg_temporal_denoise_motion_host", color_in_host, guides_host, pos_host, true, motion_host, prev_view_proj, out_host, iv_host, var_host, p);
 }
 
 int trg_temporal_set_lag_correction(trg_ctx *c, float gate) {

@@ -186,17 +186,43 @@ def _chk(ctx, rc):
         raise capi.TrgError(rc, (ctx.L.trg_last_error(ctx.h_ctx) or b"").decode())
 
 
+def _run(ctx, device_entry, host_entry, outputs, inputs=(), head=(), mid=(), tail=(), host_only=(), host_only_error=None, shape_error=None):
+    """The one fork of the bindings.  Both entry points take (ctx, *head, *inputs, *mid, *outputs, *tail); inputs and outputs are lists of
+    (name, value, shape), host_only one of (wanted, shape) for the outputs that only the host entry point has, behind the others.
+    Torch tensors -- the first input, or without inputs a given first output -- go in place through the device entry point, which only enqueues
+    on the context's stream: every tensor is checked, an output that is None is allocated, a wanted host-only output is refused.  Otherwise the
+    host entry point, which waits: the inputs as contiguous float32 numpy arrays of their shapes, the outputs new numpy arrays.
+    Returns the outputs, the wanted host-only ones included, as a tuple; one output alone as itself."""
+    L = load()
+    first = inputs[0][1] if inputs else outputs[0][1]
+    if device_entry and first is not None and _is_tensor(first):
+        import torch
+        if any(wanted for wanted, _ in host_only):
+            raise ValueError(host_only_error)
+        ptrs = [_tensor_ptr(t, shape, what) for what, t, shape in inputs]
+        outs = [torch.empty(shape, dtype=torch.float32, device=first.device) if t is None else t for _, t, shape in outputs]
+        ptrs += mid + tuple(_tensor_ptr(t, shape, what) for t, (what, _, shape) in zip(outs, outputs))
+        _chk(ctx, getattr(L, device_entry)(ctx.h_ctx, *head, *ptrs, *tail))
+    else:
+        arrays = [np.ascontiguousarray(a, np.float32) for _, a, _ in inputs]
+        if any(a.shape != shape for a, (_, _, shape) in zip(arrays, inputs)):
+            raise ValueError(shape_error)
+        outs = [np.empty(shape, np.float32) for _, _, shape in outputs] + [np.empty(shape, np.float32) if wanted else None for wanted, shape in host_only]
+        ptrs = [a.ctypes.data for a in arrays] + list(mid) + [None if o is None else o.ctypes.data for o in outs]
+        _chk(ctx, getattr(L, host_entry)(ctx.h_ctx, *head, *ptrs, *tail))
+        outs = [o for o in outs if o is not None]
+    return outs[0] if len(outs) == 1 else tuple(outs)
+
+
+def _shapes(ctx):
+    """The shapes of an image and of a pair of planes."""
+    return (ctx.h, ctx.w, 4), (2, ctx.h, ctx.w, 4)
+
+
 def _fill(ctx, device_entry, read_entry, args, out, planes, what, *params):
     """`out` a float32 ROCm tensor: filled in place through the device entry point, on the context's stream (and returned); None: a numpy array
     through the _read entry point, which waits.  planes = 2: [2, h, w, 4], 0: [h, w, 4]."""
-    L = load()
-    shape = ((planes,) if planes else ()) + (ctx.h, ctx.w, 4)
-    if out is not None and _is_tensor(out):
-        _chk(ctx, getattr(L, device_entry)(ctx.h_ctx, *args, _tensor_ptr(out, shape, what), *params))
-        return out
-    o = np.empty(shape, np.float32)
-    _chk(ctx, getattr(L, read_entry)(ctx.h_ctx, *args, o.ctypes.data, *params))
-    return o
+    return _run(ctx, device_entry, read_entry, [(what, out, _shapes(ctx)[1 if planes else 0])], head=args, tail=params)
 
 
 def guides(ctx, frame_index, out=None):
@@ -206,22 +232,10 @@ def guides(ctx, frame_index, out=None):
 
 def denoise(ctx, color, guides, out=None, params=None, **kw):
     """trg_denoise.  All tensors (then `out` is a tensor too, or is allocated like `color`; enqueued only) or all numpy (waits)."""
-    L = load()
     p = make_params(params, **kw)
-    cs, gs = (ctx.h, ctx.w, 4), (2, ctx.h, ctx.w, 4)
-    if _is_tensor(color):
-        import torch
-        if out is None:
-            out = torch.empty_like(color)
-        _chk(ctx, L.trg_denoise(ctx.h_ctx, _tensor_ptr(color, cs, "color"), _tensor_ptr(guides, gs, "guides"), _tensor_ptr(out, cs, "out"), C.byref(p)))
-        return out
-    c = np.ascontiguousarray(color, np.float32)
-    g = np.ascontiguousarray(guides, np.float32)
-    if c.shape != cs or g.shape != gs:
-        raise ValueError("color must be %s and guides %s" % (cs, gs))
-    o = np.empty(cs, np.float32)
-    _chk(ctx, L.trg_denoise_host(ctx.h_ctx, c.ctypes.data, g.ctypes.data, o.ctypes.data, C.byref(p)))
-    return o
+    cs, gs = _shapes(ctx)
+    return _run(ctx, "trg_denoise", "trg_denoise_host", [("out", out, cs)], [("color", color, cs), ("guides", guides, gs)], tail=(C.byref(p),),
+                shape_error="color must be %s and guides %s" % (cs, gs))
 
 
 def render_denoised(ctx, frame_begin, spp, bounces, out=None, params=None, **kw):
@@ -238,25 +252,11 @@ def render_halves(ctx, frame_begin, spp, bounces, out=None):
 def denoise_variance(ctx, halves, guides, out=None, params=None, return_variance=False, **kw):
     """trg_denoise_variance.  All tensors (enqueued only) or all numpy (waits).  return_variance (numpy only): also V_N [h, w], the variance the
     filter carried to its end."""
-    L = load()
     p = make_var_params(params, **kw)
-    cs, gs = (ctx.h, ctx.w, 4), (2, ctx.h, ctx.w, 4)
-    if _is_tensor(halves):
-        import torch
-        if return_variance:
-            raise ValueError("return_variance needs numpy arrays (trg_denoise_variance_host)")
-        if out is None:
-            out = torch.empty(cs, dtype=torch.float32, device=halves.device)
-        _chk(ctx, L.trg_denoise_variance(ctx.h_ctx, _tensor_ptr(halves, gs, "halves"), _tensor_ptr(guides, gs, "guides"), _tensor_ptr(out, cs, "out"), C.byref(p)))
-        return out
-    hv = np.ascontiguousarray(halves, np.float32)
-    g = np.ascontiguousarray(guides, np.float32)
-    if hv.shape != gs or g.shape != gs:
-        raise ValueError("halves and guides must be %s" % (gs,))
-    o = np.empty(cs, np.float32)
-    v = np.empty((ctx.h, ctx.w), np.float32) if return_variance else None
-    _chk(ctx, L.trg_denoise_variance_host(ctx.h_ctx, hv.ctypes.data, g.ctypes.data, o.ctypes.data, v.ctypes.data if return_variance else None, C.byref(p)))
-    return (o, v) if return_variance else o
+    cs, gs = _shapes(ctx)
+    return _run(ctx, "trg_denoise_variance", "trg_denoise_variance_host", [("out", out, cs)], [("halves", halves, gs), ("guides", guides, gs)], tail=(C.byref(p),),
+                host_only=[(return_variance, cs[:2])], host_only_error="return_variance needs numpy arrays (trg_denoise_variance_host)",
+                shape_error="halves and guides must be %s" % (gs,))
 
 
 def render_denoised_variance(ctx, frame_begin, spp, bounces, out=None, params=None, **kw):
@@ -268,14 +268,8 @@ def render_denoised_variance(ctx, frame_begin, spp, bounces, out=None, params=No
 def guides_pos(ctx, frame_index, out=None, pos=None):
     """trg_guides_render_pos -> (guides [2, h, w, 4], X [h, w, 4]).  out, pos = float32 ROCm tensors: filled in place on the context's stream
     (and returned); None: numpy arrays."""
-    L = load()
-    gs, xs = (2, ctx.h, ctx.w, 4), (ctx.h, ctx.w, 4)
-    if out is not None and _is_tensor(out):
-        _chk(ctx, L.trg_guides_render_pos(ctx.h_ctx, frame_index, _tensor_ptr(out, gs, "guides"), _tensor_ptr(pos, xs, "pos")))
-        return out, pos
-    g, x = np.empty(gs, np.float32), np.empty(xs, np.float32)
-    _chk(ctx, L.trg_guides_pos_read(ctx.h_ctx, frame_index, g.ctypes.data, x.ctypes.data))
-    return g, x
+    xs, gs = _shapes(ctx)
+    return _run(ctx, "trg_guides_render_pos", "trg_guides_pos_read", [("guides", out, gs), ("pos", pos, xs)], head=(frame_index,))
 
 
 def temporal_view_proj(uniforms):
@@ -326,53 +320,22 @@ def guides_motion(ctx, frame_index, out=None, pos=None, motion=None):
     """trg_guides_render_motion -> (guides [2, h, w, 4], X [h, w, 4], motion [2, h, w, 4] = M0, M1: where the hit was and its normal then, by the
     previous scene of temporal_set_previous_scene).  out, pos, motion = float32 ROCm tensors: filled in place on the context's stream (and
     returned); None: numpy arrays."""
-    L = load()
-    gs, xs = (2, ctx.h, ctx.w, 4), (ctx.h, ctx.w, 4)
-    if out is not None and _is_tensor(out):
-        _chk(ctx, L.trg_guides_render_motion(ctx.h_ctx, frame_index, _tensor_ptr(out, gs, "guides"), _tensor_ptr(pos, xs, "pos"), _tensor_ptr(motion, gs, "motion")))
-        return out, pos, motion
-    g, x, m = np.empty(gs, np.float32), np.empty(xs, np.float32), np.empty(gs, np.float32)
-    _chk(ctx, L.trg_guides_motion_read(ctx.h_ctx, frame_index, g.ctypes.data, x.ctypes.data, m.ctypes.data))
-    return g, x, m
+    xs, gs = _shapes(ctx)
+    return _run(ctx, "trg_guides_render_motion", "trg_guides_motion_read", [("guides", out, gs), ("pos", pos, xs), ("motion", motion, gs)], head=(frame_index,))
 
 
 def temporal_denoise(ctx, color, guides, pos, prev_vp, out=None, params=None, return_iv=False, return_variance=False, motion=None, **kw):
     """trg_temporal_denoise; with motion [2, h, w, 4] (M0, M1 as guides_motion gives them) trg_temporal_denoise_motion.  All tensors (enqueued
     only) or all numpy (waits).  prev_vp: temporal_view_proj of the previous call's uniforms (host memory; None: zeros, for the first call
     after a reset).  numpy only: return_iv also gives (I.rgb, V_0) [h, w, 4], return_variance V_N [h, w]."""
-    L = load()
     p = make_temporal_params(params, **kw)
     vp = _vp_arg(prev_vp)
-    cs, gs = (ctx.h, ctx.w, 4), (2, ctx.h, ctx.w, 4)
-    if _is_tensor(color):
-        import torch
-        if return_iv or return_variance:
-            raise ValueError("return_iv / return_variance need numpy arrays (trg_temporal_denoise_host)")
-        if out is None:
-            out = torch.empty_like(color)
-        args = (_tensor_ptr(color, cs, "color"), _tensor_ptr(guides, gs, "guides"), _tensor_ptr(pos, cs, "pos"))
-        tail = (vp.ctypes.data_as(_F16), _tensor_ptr(out, cs, "out"), C.byref(p))
-        if motion is None:
-            _chk(ctx, L.trg_temporal_denoise(ctx.h_ctx, *args, *tail))
-        else:
-            _chk(ctx, L.trg_temporal_denoise_motion(ctx.h_ctx, *args, _tensor_ptr(motion, gs, "motion"), *tail))
-        return out
-    c = np.ascontiguousarray(color, np.float32)
-    g = np.ascontiguousarray(guides, np.float32)
-    x = np.ascontiguousarray(pos, np.float32)
-    m = None if motion is None else np.ascontiguousarray(motion, np.float32)
-    if c.shape != cs or g.shape != gs or x.shape != cs or (m is not None and m.shape != gs):
-        raise ValueError("color and pos must be %s, guides and motion %s" % (cs, gs))
-    o = np.empty(cs, np.float32)
-    iv = np.empty(cs, np.float32) if return_iv else None
-    v = np.empty((ctx.h, ctx.w), np.float32) if return_variance else None
-    tail = (vp.ctypes.data_as(_F16), o.ctypes.data, iv.ctypes.data if return_iv else None, v.ctypes.data if return_variance else None, C.byref(p))
-    if m is None:
-        _chk(ctx, L.trg_temporal_denoise_host(ctx.h_ctx, c.ctypes.data, g.ctypes.data, x.ctypes.data, *tail))
-    else:
-        _chk(ctx, L.trg_temporal_denoise_motion_host(ctx.h_ctx, c.ctypes.data, g.ctypes.data, x.ctypes.data, m.ctypes.data, *tail))
-    res = (o,) + ((iv,) if return_iv else ()) + ((v,) if return_variance else ())
-    return res if len(res) > 1 else o
+    cs, gs = _shapes(ctx)
+    name = "trg_temporal_denoise" if motion is None else "trg_temporal_denoise_motion"
+    inputs = [("color", color, cs), ("guides", guides, gs), ("pos", pos, cs)] + ([] if motion is None else [("motion", motion, gs)])
+    return _run(ctx, name, name + "_host", [("out", out, cs)], inputs, mid=(vp.ctypes.data_as(_F16),), tail=(C.byref(p),),
+                host_only=[(return_iv, cs), (return_variance, cs[:2])], host_only_error="return_iv / return_variance need numpy arrays (trg_temporal_denoise_host)",
+                shape_error="color and pos must be %s, guides and motion %s" % (cs, gs))
 
 
 def render_temporal(ctx, frame_begin, spp, bounces, out=None, params=None, **kw):
@@ -397,16 +360,9 @@ def temporal_lag_correction(ctx):
 def lag_correct(ctx, color, guides, hc, gate, sigma_normal=128.0, sigma_depth=1.0, demodulate=1):
     """trg_temporal_lag_correct_host: the correction alone (stage-level; numpy; waits).  color [h, w, 4], guides [2, h, w, 4], hc [h, w, 4] =
     (I.rgb, N) -> (Ic.rgb, N) [h, w, 4].  The context's own setting and history play no part."""
-    cs, gs = (ctx.h, ctx.w, 4), (2, ctx.h, ctx.w, 4)
-    c = np.ascontiguousarray(color, np.float32)
-    g = np.ascontiguousarray(guides, np.float32)
-    hcp = np.ascontiguousarray(hc, np.float32)
-    if c.shape != cs or g.shape != gs or hcp.shape != cs:
-        raise ValueError("color and hc must be %s and guides %s" % (cs, gs))
-    o = np.empty(cs, np.float32)
-    _chk(ctx, load().trg_temporal_lag_correct_host(ctx.h_ctx, c.ctypes.data, g.ctypes.data, hcp.ctypes.data, float(gate), float(sigma_normal), float(sigma_depth),
-                                                   int(demodulate), o.ctypes.data))
-    return o
+    cs, gs = _shapes(ctx)
+    return _run(ctx, None, "trg_temporal_lag_correct_host", [("out", None, cs)], [("color", color, cs), ("guides", guides, gs), ("hc", hc, cs)],
+                mid=(float(gate), float(sigma_normal), float(sigma_depth), int(demodulate)), shape_error="color and hc must be %s and guides %s" % (cs, gs))
 
 
 def release(ctx):
