@@ -78,6 +78,11 @@ public:
     //      it may be set before init() and survives loadScene.  False for a NaN, or when the library refuses.
     bool setLagCorrection(float gate);
     float getLagCorrection() const { return m_lagGate; }
+    // ---- a long history (trg_temporal_set_variance_of_mean): the temporal steps carry the variance of the ACCUMULATED colour through the
+    //      history and hand that to the filter, which narrows as the history grows.  Off by default.  Effective in temporal mode on one device;
+    //      it may be set before init() and survives loadScene.  A change forgets the temporal history.  False when the library refuses.
+    bool setVarianceOfMean(bool on);
+    bool getVarianceOfMean() const { return m_varianceOfMean; }
     int getFrameIndex() const { return m_frameIndex; }
     double getLastRenderMs() const;
     uint64_t getRayCount() const;                       // primary + bounce + shadow rays traced so far
@@ -104,6 +109,7 @@ protected:
     bool m_denoiseTemporal;      // ... or every batch a temporal step (trg_render_temporal_own)
     void *m_temporalOut;         // the last temporal step's output image (owned by the denoise state); null before the first
     float m_lagGate;             // the gate of the lag correction of the temporal steps; < 0 = off
+    bool m_varianceOfMean;       // the temporal steps track the variance of the accumulated colour
     // updateScene: the positions, normals and indices uploaded last (temporal mode, one device; else empty), whether they came with textures,
     // and whether the loadScene in progress keeps the temporal history
     std::vector<float> m_lastPositions, m_lastNormals;

@@ -202,7 +202,7 @@ TRG_API void trg_temporal_default_params(trg_temporal_params *p);
 /* --- HISTORY.  Four planes of width*height float4 per pixel, owned by the state (allocated on the first call, double-buffered, freed by
  *     trg_denoise_release):
  *       Hc = (I.rgb, N)      the accumulated (demodulated) colour and the history length
- *       Hm = (m1, m2, 0, 0)  the accumulated first and second moment of L(D)
+ *       Hm = (m1, m2, 0, 0)  the accumulated first and second moment of L(D)   (.z: A LONG HISTORY below, while that setting is on)
  *       F  = the filter's G0 of that frame (normal | z), emitters marked as misses (z = -1)
  *       X  = the world positions of that frame
  *     A new state has no history, and trg_temporal_reset forgets it (and the view-projection trg_render_temporal remembered;
@@ -288,7 +288,10 @@ TRG_API int trg_render_temporal_read(trg_ctx *ctx, uint32_t frameIndexBegin, uin
  * LIGHT below, off by default) removes what a 7 x 7 window can tell from noise -- a change of brightness almost at once, a moved shadow
  * hardly.  A changed TOPOLOGY (another
  * triangle count, or triangle k no longer the surface triangle k was): the caller calls trg_temporal_reset.  Device groups (trg_group_*).
- * Feeding filtered colour back into the history: as above, the history holds unfiltered values.
+ * Feeding filtered colour back into the history: as above, the history holds unfiltered values.  A float64 prototype of SVGF's feedback (the
+ * first filtered iteration and its V_1 written back) on top of the variance of the mean was better on two of six sequences and worse on three
+ * -- rmse 0.02277 against 0.02324 with the eye turning (8 calls x 2 spp), 0.03414 against 0.03375 at rest (24 x 1); the whole table stands
+ * under A LONG HISTORY below.
  * ============================================================================================================================================= */
 
 /* --- PREVIOUS GEOMETRY.  Call it AFTER trg_load_scene of the new geometry.  Triangle k here is the surface that triangle k of the loaded scene
@@ -392,6 +395,58 @@ TRG_API int trg_temporal_lag_correction(trg_ctx *ctx, float *gate);   /* what is
  * >= 0 and sigma_depth > 0, else TRG_ERR_INVALID.  The context's own setting and history are neither read nor changed. */
 TRG_API int trg_temporal_lag_correct_host(trg_ctx *ctx, const float *color_in_host, const float *guides_host, const float *hc_host, float gate,
                                           float sigma_normal, float sigma_depth, int32_t demodulate, float *out_hc_host);
+
+/* =============================================================================================================================================
+ * A LONG HISTORY: THE VARIANCE OF THE MEAN.  The step above hands the iterations the variance of ONE sample: from four frames on
+ * V_0 = max(0, m2 - m1 * m1), a figure that does not shrink as the history grows, so a pixel with 24 frames behind it is filtered as widely as
+ * one with four -- and the five default iterations then blur away what the accumulation had gained.  What the colour weight w_l wants is the
+ * variance of the colour it compares, the ACCUMULATED one.  For independent samples an exponential average I = (1 - a) I' + a D has
+ *       Var(I) = (1 - a)^2 Var(I') + a^2 Var(D)
+ * and the history plane Hm = (m1, m2, 0, 0) has two unused channels: the variance travels there, at no extra bytes and no extra gathers.
+ * Off by default, switched on per context; with it off every entry point enqueues what it did and gives the same bits.
+ * ============================================================================================================================================= */
+
+/* --- WITH THE SETTING ON, ONE TEMPORAL STEP (trg_temporal_denoise / _motion / _host, trg_render_temporal / _own / _read) differs in three places.
+ *     Notation: trg_temporal_denoise's; a prime marks the previous call's history planes.
+ *   History.   Hm = (m1, m2, Vc, 0): Vc = the variance estimate of L of the accumulated colour in Hc.  (Off: Hm.z stays 0.)
+ *              trg_temporal_history_read returns the plane as it is.  A miss has Vc = 0.
+ *   Reproject. Vh = (sum of b * Hm'.z over the valid taps) / W -- the taps, the order and the division of m1h.
+ *   Variance.  S = the V_0 of trg_temporal_denoise exactly as defined there: max(0, m2 - m1 * m1) for N >= 4, the 7 x 7 spatial estimate times
+ *              4 / N for N < 4.  a = max(alpha, 1 / N), the weight the colour was accumulated with.
+ *                No history, or N < 4:   Vc = S
+ *                otherwise:              Vc = ((1 - a) * (1 - a)) * Vh + (a * a) * S        every product and sum one fp32 operation, not contracted
+ *              V_0 := Vc: it is what (I, V_0) carries, what the iterations get, what iv_host returns; and Hm.z = Vc.
+ *     Everything else is the step as it stands: I, N, the moments, F, X, the motion substitutions (a step with M0 = (X.xyz, 1), M1 = (G0.xyz, 0)
+ *     is still the step without motion planes bit for bit), the iterations and the remodulation.  The lag correction leaves Vc alone as it leaves
+ *     the moments.  No new discrete decision: the choice of form is N against 4, which was there already.
+ *     Three consequences.  A first call has Vc = S.  Vc <= max(Vh, S) wherever there is history (a in (0, 1] makes (1 - a)^2 + a^2 <= 1).  With
+ *     the camera at rest, samples of constant variance S and a = 1 / N, Vc = S / N up to the error of S: the variance of an arithmetic mean.
+ *     The history below four frames has Vc = S, the variance of one sample scaled by 4 / N, not S / N: the spatial estimate is already a guess
+ *     made for want of history, and the recursion starts from it.
+ *     The float64 reference: toyraygun_amd/denoise.py reference_temporal(..., track=True).
+ *
+ *     NOT COVERED.  SVGF also writes the first filtered iteration and its V_1 back into the history ("feedback").  On a float64 prototype
+ *     (Cornell box 64 x 48, 3 bounces, rmse over the whole image against 512 spp at the last camera; plain / this setting / this setting with
+ *     feedback) it was better on two sequences and worse on three:
+ *       eye turning 1 degree per call, 8 calls x 2 spp, alpha 0.2:   0.02558 / 0.02324 / 0.02277
+ *       the same, alpha 0.05:                                        0.02586 / 0.02377 / 0.02263
+ *       at rest, 8 x 1, alpha 0.2:                                   0.03682 / 0.03548 / 0.03544
+ *       at rest, 24 x 1, alpha 0.2:                                  0.03579 / 0.03375 / 0.03414
+ *       at rest, 24 x 1, alpha 0.05:                                 0.03712 / 0.03454 / 0.03490
+ *       turning, 16 x 1, alpha 0.2:                                  0.03878 / 0.03688 / 0.03737
+ *     and it would put filtered values into a history that is defined to hold unfiltered ones: left out.  The light and the pixels on its edge,
+ *     which the step copies unaccumulated, are part of those figures and stay as they are.
+ *
+ *     On the device: the same launches.  The reprojection kernel reads .z of the Hm' float4 it gathers anyway and writes Vc into Hm.z and
+ *     (I, V_0).w; the spatial-estimate kernel writes its V_0 into (I, V_0).w as before and also into Hm.z of the pixels it owns.  It stages the
+ *     moments of neighbouring tiles while other workgroups write their Vc: with the setting on it reads the 8 bytes (m1, m2) of a staged pixel
+ *     and never the 4 bytes of Hm.z, so no byte is read by one workgroup and written by another.  No atomics, no scratch. */
+/* on != 0: on, for every later temporal step of this context; 0: off (the state of a new context).  Host only: allocates nothing on the device,
+ * harmless for a context that never denoised.  A call that CHANGES the setting also does what trg_temporal_reset does -- history written with
+ * the setting off has no variance in it --; a call that repeats the current value changes nothing.  The setting survives trg_temporal_reset and
+ * ends with trg_denoise_release. */
+TRG_API int trg_temporal_set_variance_of_mean(trg_ctx *ctx, int on);
+TRG_API int trg_temporal_variance_of_mean(trg_ctx *ctx, int *on);   /* what is set: 1 or 0 */
 
 #ifdef __cplusplus
 }

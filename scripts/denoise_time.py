@@ -8,7 +8,9 @@ call; `temporal_front_ms` = the emitter marking, the reprojection and the spatia
 copy is not separable here, so it is a step of 1 iteration minus one variance iteration of spacing 1).  The moving-geometry leg
 (trg_temporal_set_previous_scene, trg_guides_render_motion, trg_temporal_denoise_motion) comes last: the motion-plane launch, and the step with
 the motion planes beside the plain step at rest.  The changing-light leg (trg_temporal_set_lag_correction) is the plain step at rest with the
-lag correction on and, right beside it, off again: the two differ by the one launch of dn_temporal_lag_kernel."""
+lag correction on and, right beside it, off again: the two differ by the one launch of dn_temporal_lag_kernel.  The long-history leg
+(trg_temporal_set_variance_of_mean) is the 5-iteration step with the variance of the mean on and, right beside it, off, at rest and with the eye
+turning: the same launches, two kernels in their TRACK forms."""
 import json
 import os
 import sys
@@ -144,6 +146,15 @@ for name, gate in (("lag", denoise.LAG_GATE_DEFAULT), ("lag_off", -1.0)):
     res["temporal_5_%s_ms" % name] = timed(lambda: step(vp_rest))
     res["temporal_1_%s_ms" % name] = timed(lambda: step(vp_rest, iterations=1))
 res["lag_launch_ms"] = [res["temporal_%d_lag_ms" % it] - res["temporal_%d_lag_off_ms" % it] for it in (1, 5)]
+# a long history: the 5-iteration step with the variance of the mean on and, right beside it, off -- at rest after six calls (a change of the
+# setting forgets the history), and with the eye turning as in the moving leg above.  The same launches; the TRACK forms of two kernels
+for name, on in (("vmean", True), ("vmean_off", False)):
+    denoise.temporal_set_variance_of_mean(c, on)
+    for _ in range(6):
+        step(vp_rest)
+    res["temporal_5_rest_%s_ms" % name] = timed(lambda: step(vp_rest))
+    res["temporal_5_moving_%s_ms" % name] = moving()
+res["vmean_extra_ms"] = {leg: res["temporal_5_%s_vmean_ms" % leg] - res["temporal_5_%s_vmean_off_ms" % leg] for leg in ("rest", "moving")}
 print(json.dumps(res))
 c.bind_accum(None)
 c.set_stream(None)

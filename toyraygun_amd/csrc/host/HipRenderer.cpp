@@ -15,7 +15,7 @@ namespace toyraygun {
 
 HipRenderer::HipRenderer()
     : m_ctx(nullptr), m_group(nullptr), m_deviceCount(0), m_bounces(3), m_deviceBuild(0), m_offsetSeed(0x5EED0001u), m_sceneLoaded(false), m_synchronous(false), m_pending(0), m_pendingFirst(0),
-      m_launches(0), m_denoise(0), m_denoiseVar(false), m_denoiseTemporal(false), m_temporalOut(nullptr), m_lagGate(-1.0f), m_lastTextured(false), m_keepHistory(false) {
+      m_launches(0), m_denoise(0), m_denoiseVar(false), m_denoiseTemporal(false), m_temporalOut(nullptr), m_lagGate(-1.0f), m_varianceOfMean(false), m_lastTextured(false), m_keepHistory(false) {
     memset(&m_pendingUniforms, 0, sizeof(m_pendingUniforms));
 }
 HipRenderer::~HipRenderer() { destroy(); }
@@ -57,6 +57,10 @@ bool HipRenderer::init() {
         }
         // (the setting lives in the context's denoise state, which destroy() released)
         if (m_lagGate >= 0.0f && trg_temporal_set_lag_correction(m_ctx, m_lagGate) != TRG_OK) {
+            printf("HipRenderer: %s\n", trg_last_error(m_ctx));
+            return false;
+        }
+        if (m_varianceOfMean && trg_temporal_set_variance_of_mean(m_ctx, 1) != TRG_OK) {
             printf("HipRenderer: %s\n", trg_last_error(m_ctx));
             return false;
         }
@@ -299,6 +303,14 @@ bool HipRenderer::setLagCorrection(float gate) {
         if (trg_temporal_set_lag_correction(m_ctx, gate) != TRG_OK) { printf("HipRenderer: %s\n", trg_last_error(m_ctx)); return false; }
     }
     m_lagGate = gate;
+    return true;
+}
+bool HipRenderer::setVarianceOfMean(bool on) {
+    if (m_ctx && !m_group) {
+        flush();   // frames queued so far keep the setting they were queued under
+        if (trg_temporal_set_variance_of_mean(m_ctx, on ? 1 : 0) != TRG_OK) { printf("HipRenderer: %s\n", trg_last_error(m_ctx)); return false; }
+    }
+    m_varianceOfMean = on;
     return true;
 }
 bool HipRenderer::savePNG(const char *path) {

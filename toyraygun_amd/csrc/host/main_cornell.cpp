@@ -1,12 +1,14 @@
 // main_cornell.cpp -- headless demo following the reference app's call order (reference src/main.cpp:16-98):
 // engine init -> three shaders -> renderer init -> camera -> Cornell box -> frame loop; then writes a PNG.
-//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]]]] [orbit=DEG] [slide=D]]
+//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean]]] [orbit=DEG] [slide=D]]
 //     denoise=N    a-trous iterations of the written image, 0 = off (default)
 //     ,var         the variance-guided filter from two half-sample buffers
 //     ,temporal    the frames are rendered as `frames` calls of 1 spp, each a temporal step (reprojected history, temporal variance); the
 //                  picture is the last step's
 //     ,lag[=G]     (behind ,temporal) the gated lag correction of the accumulated colour at gate G (default 3): a moved shadow or a changed
 //                  light no longer waits for the history to fade (HipRenderer::setLagCorrection)
+//     ,vmean       (behind ,temporal, before or after ,lag) the steps track the variance of the ACCUMULATED colour and filter by that: the
+//                  filter narrows as the history grows (HipRenderer::setVarianceOfMean)
 //     orbit=DEG    the eye turns about the look-at point (about the vertical axis) by DEG degrees per call
 //     slide=D      before call k the box is rebuilt with the short box moved by k * D along x and handed to HipRenderer::updateScene: with
 //                  ,temporal the history follows the moving box (trg_temporal_set_previous_scene), otherwise it is a plain loadScene
@@ -55,9 +57,9 @@ int main(int argc, char **argv) {
     const int frames = argc > 3 ? atoi(argv[3]) : 64, bounces = argc > 4 ? atoi(argv[4]) : 3;
     const char *out = argc > 5 ? argv[5] : "cornell.png";
     int denoise = 0;
-    bool denoiseVar = false, denoiseTemporal = false;
+    bool denoiseVar = false, denoiseTemporal = false, varianceOfMean = false;
     double orbit = 0.0, slide = 0.0, lagGate = -1.0;
-    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]]]] [orbit=DEG] [slide=D]]";
+    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean]]] [orbit=DEG] [slide=D]]";
     for (int a = 6; a < argc; ++a) {
         if (strncmp(argv[a], "slide=", 6) == 0) {
             char *end = nullptr;
@@ -76,13 +78,25 @@ int main(int argc, char **argv) {
         const char *comma = strchr(argv[a] + 8, ',');
         if (comma) {
             if (strcmp(comma, ",var") == 0) denoiseVar = true;
-            else if (strcmp(comma, ",temporal") == 0) denoiseTemporal = true;
-            else if (strcmp(comma, ",temporal,lag") == 0) { denoiseTemporal = true; lagGate = TRG_TEMPORAL_LAG_GATE_DEFAULT; }
-            else if (strncmp(comma, ",temporal,lag=", 14) == 0) {
-                char *end = nullptr;
-                lagGate = strtod(comma + 14, &end);
-                if (end == comma + 14 || *end != 0 || !(lagGate >= 0.0)) { std::cout << usage << std::endl; return -1; }
+            else if (strncmp(comma, ",temporal", 9) == 0 && (comma[9] == 0 || comma[9] == ',')) {
                 denoiseTemporal = true;
+                // behind ,temporal: ,lag[=G] and ,vmean, each at most once, in either order
+                const char *tok = comma + 9;
+                bool sawLag = false;
+                while (*tok) {
+                    const char *next = strchr(tok + 1, ',');
+                    const size_t len = next ? (size_t)(next - tok) : strlen(tok);
+                    if (len == 6 && strncmp(tok, ",vmean", 6) == 0 && !varianceOfMean) varianceOfMean = true;
+                    else if (len == 4 && strncmp(tok, ",lag", 4) == 0 && !sawLag) { sawLag = true; lagGate = TRG_TEMPORAL_LAG_GATE_DEFAULT; }
+                    else if (len > 5 && strncmp(tok, ",lag=", 5) == 0 && !sawLag) {
+                        char *end = nullptr;
+                        lagGate = strtod(tok + 5, &end);
+                        if (end != tok + len || !(lagGate >= 0.0)) { std::cout << usage << std::endl; return -1; }
+                        sawLag = true;
+                    }
+                    else { std::cout << usage << std::endl; return -1; }
+                    tok += len;
+                }
             }
             else { std::cout << usage << std::endl; return -1; }
         }
@@ -116,6 +130,7 @@ int main(int argc, char **argv) {
     HipRenderer *hip = static_cast<HipRenderer *>(renderer);
     if (!hip->setDenoise(denoise, denoiseVar, denoiseTemporal)) { std::cout << "denoise must be 0.." << 6 << std::endl; return -1; }
     if (lagGate >= 0.0 && !hip->setLagCorrection((float)lagGate)) { std::cout << "the lag correction was refused" << std::endl; return -1; }
+    if (varianceOfMean && !hip->setVarianceOfMean(true)) { std::cout << "the variance of the mean was refused" << std::endl; return -1; }
     Scene *scene = createCornellBoxScene();
     renderer->loadScene(scene);
     hip->setBounces((unsigned int)bounces);

@@ -3,6 +3,7 @@
 // Behind them the variance-guided form of the filter and the temporal reprojection / accumulation that feeds it.
 // For geometry that moved: the previous scene, the motion planes and the MOTION form of the reprojection.
 // For lighting that changed: the gated lag correction of the accumulated colour.
+// For a long history: the variance of the accumulated colour, carried in Hm.z (the TRACK forms of the two temporal kernels).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -166,6 +167,8 @@ struct DenoiseState {
     float4 *tmotion = nullptr;
     // changing light (trg_temporal_set_lag_correction): the gate of the lag correction, < 0 = off.  Set on a state that may own nothing yet
     float lag_gate = -1.0f;
+    // a long history (trg_temporal_set_variance_of_mean): the steps carry the variance of the accumulated colour in Hm.z.  Set like the gate
+    bool track = false;
 };
 std::mutex g_mutex;
 std::unordered_map<trg_ctx *, DenoiseState> g_states;
@@ -893,7 +896,9 @@ __device__ __forceinline__ bool dn_unit(float &x, float &y, float &z) {
 // of L2.
 // MOTION (trg_temporal_denoise_motion): the history is looked for where the surface WAS -- M0.xyz takes X's place in the projection and in the
 // plane test, M1.xyz the current normal's in both tests -- and only where M0.w > 0; two more coalesced float4 per pixel.
-template <bool STRICT, bool MOTION>
+// TRACK (trg_temporal_set_variance_of_mean): Hm'.z of the float4 that is gathered anyway is the variance of the accumulated colour; it goes
+// through the taps like the moments, through the recursion of the header from four frames on, and out into Hm.z and (I, V_0).w.
+template <bool STRICT, bool MOTION, bool TRACK>
 __global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const ReprojectParams p) {
     const int x = (int)blockIdx.x * kDnTile + ((int)threadIdx.x & 15), y = (int)blockIdx.y * kDnTile + ((int)threadIdx.x >> 4);
     if (x >= p.w || y >= p.h) return;
@@ -912,6 +917,7 @@ __global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const Reproj
     if (p.demod) { const float4 d = dn_demodulate(c, p.g1[pix]); dr = d.x; dg = d.y; db = d.z; }
     const float l = dn_lum(make_float4(dr, dg, db, 0.0f));
     float ir = 0.0f, ig = 0.0f, ib = 0.0f, m1 = 0.0f, m2 = 0.0f, nh = 0.0f, W = 0.0f;
+    float vh = 0.0f;                                    // TRACK: Vh
     float nx = f.x, ny = f.y, nz = f.z;
     if (MOTION) { const float4 pn = p.m1[pix]; nx = pn.x; ny = pn.y; nz = pn.z; }
     if (p.hc && (!MOTION || R.w > 0.0f) && dn_unit<STRICT>(nx, ny, nz)) {
@@ -944,16 +950,19 @@ __global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const Reproj
                     const float4 hc = p.hc[q], hm = p.hm[q];
                     ir += b * hc.x; ig += b * hc.y; ib += b * hc.z; nh += b * hc.w;
                     m1 += b * hm.x; m2 += b * hm.y;
+                    if (TRACK) vh += b * hm.z;
                     W += b;
                 }
             }
         }
     }
-    float N = 1.0f, v0;
+    float N = 1.0f, v0, ac = 1.0f;
     if (W > 0.0f) {
         ir = ir / W; ig = ig / W; ib = ib / W; nh = nh / W; m1 = m1 / W; m2 = m2 / W;
+        if (TRACK) vh = vh / W;
         N = fminf(nh + 1.0f, p.max_history);
         const float a = fmaxf(p.alpha, 1.0f / N), am = fmaxf(p.alpha_moments, 1.0f / N);
+        if (TRACK) ac = a;
         ir = ir + a * (dr - ir); ig = ig + a * (dg - ig); ib = ib + a * (db - ib);
         m1 = m1 + am * (l - m1);
         m2 = m2 + am * (l * l - m2);
@@ -961,16 +970,21 @@ __global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const Reproj
         ir = dr; ig = dg; ib = db; m1 = l; m2 = l * l;
     }
     v0 = fmaxf(0.0f, m2 - m1 * m1);   // (N < 4: replaced by the spatial estimate of the next launch)
+    // TRACK: Vc of the header from four frames on (without history N = 1); below, the next launch writes the spatial estimate here and into Hm.z
+    if (TRACK && N >= 4.0f) v0 = ((1.0f - ac) * (1.0f - ac)) * vh + (ac * ac) * v0;
     p.oc[pix] = make_float4(ir, ig, ib, N);
-    p.om[pix] = make_float4(m1, m2, 0.0f, 0.0f);
+    p.om[pix] = make_float4(m1, m2, TRACK ? v0 : 0.0f, 0.0f);
     p.iv[pix] = make_float4(ir, ig, ib, v0);
 }
 
 // V_0 of the pixels whose history is shorter than four frames: the variance of the moments over the 7 x 7 window, with the prefilter's weights
 // (dn_window7, the payload is the two moments).  A tile in which no pixel needs it -- the usual case once the camera has stood still for four
 // frames -- leaves before staging anything: one ballot per wave, four flags in LDS.
-template <bool STRICT>
-__global__ __launch_bounds__(256) void dn_temporal_spatial_kernel(const float4 *hc, const float4 *hm, const float4 *g0, float4 *iv, int w, int h,
+// TRACK (trg_temporal_set_variance_of_mean): V_0 also goes to Hm.z of the pixel (the one form that writes `hm`).  Other workgroups stage this
+// pixel's moments at the same time, so with TRACK the staging reads the 8 bytes (m1, m2) of a pixel as a float2 and never its .z: no byte of
+// the plane is read by one workgroup and written by another, and the 4-byte store lies inside one aligned dword, which a store cannot tear.
+template <bool STRICT, bool TRACK>
+__global__ __launch_bounds__(256) void dn_temporal_spatial_kernel(const float4 *hc, float4 *hm, const float4 *g0, float4 *iv, int w, int h,
                                                                   float sigma_normal, float sigma_depth) {
     __shared__ int s_need[4];
     const int x = (int)blockIdx.x * kDnTile + ((int)threadIdx.x & 15), y = (int)blockIdx.y * kDnTile + ((int)threadIdx.x >> 4);
@@ -987,7 +1001,11 @@ __global__ __launch_bounds__(256) void dn_temporal_spatial_kernel(const float4 *
     __syncthreads();
     if (!(s_need[0] | s_need[1] | s_need[2] | s_need[3])) return;   // (uniform over the workgroup)
     float sm[2], gs;
-    const auto moments = [&](size_t q) { const float4 mm = hm[q]; return DnPayload<2>{ { mm.x, mm.y } }; };
+    const auto moments = [&](size_t q) {
+        if (TRACK) { const float2 mm = *reinterpret_cast<const float2 *>(hm + q); return DnPayload<2>{ { mm.x, mm.y } }; }
+        const float4 mm = hm[q];
+        return DnPayload<2>{ { mm.x, mm.y } };
+    };
     if (!dn_window7_sums<STRICT, 2>(g0, moments, w, h, sigma_normal, sigma_depth, need, sm, gs)) return;
     float v0 = 0.0f;
     if (gs > 0.0f) {
@@ -995,6 +1013,7 @@ __global__ __launch_bounds__(256) void dn_temporal_spatial_kernel(const float4 *
         v0 = fmaxf(0.0f, M2 - M1 * M1) * 4.0f / N;
     }
     iv[pix].w = v0;
+    if (TRACK) hm[pix].z = v0;
 }
 
 // The gated lag correction of the accumulated colour (trg_denoise.h, CHANGING LIGHT) over the 7 x 7 geometry window of dn_window7; a tap needs
@@ -1165,8 +1184,9 @@ int temporal_denoise(trg_ctx *c, DenoiseState &s, const float4 *color, const flo
     for (int k = 0; k < 16; ++k) r.vp[k] = vp[k];
     r.alpha = q.alpha; r.alpha_moments = q.alpha_moments; r.plane_tol = q.plane_tol; r.normal_tol = q.normal_tol; r.max_history = (float)q.max_history;
     if (motion) { r.m0 = motion; r.m1 = motion + n; }
-    if (int rc = launch_tiles(c, who, motion ? DN_FOR_SETTING(c, dn_temporal_reproject_kernel, true) : DN_FOR_SETTING(c, dn_temporal_reproject_kernel, false), r))
-        return rc;
+    const auto reproject = s.track ? (motion ? DN_FOR_SETTING(c, dn_temporal_reproject_kernel, true, true) : DN_FOR_SETTING(c, dn_temporal_reproject_kernel, false, true))
+                                   : (motion ? DN_FOR_SETTING(c, dn_temporal_reproject_kernel, true, false) : DN_FOR_SETTING(c, dn_temporal_reproject_kernel, false, false));
+    if (int rc = launch_tiles(c, who, reproject, r)) return rc;
     s.hist_cur ^= 1;          // (enqueued: from here on the new planes are the history, also if a later launch fails)
     s.hist_valid = true;
     // the lag correction, while it is on: (I, V_0) moves to the other ping-pong image, everything behind it starts from there
@@ -1175,7 +1195,9 @@ int temporal_denoise(trg_ctx *c, DenoiseState &s, const float4 *color, const flo
         if (int rc = lag_correct(c, s, who, color, guides, s.ping, r.oc, s.pong, s.lag_gate, q.sigma_normal, q.sigma_depth, q.demodulate != 0)) return rc;
         iv = s.pong;
     }
-    if (int rc = launch_tiles(c, who, DN_FOR_SETTING(c, dn_temporal_spatial_kernel), r.oc, r.om, s.fguide, iv, c->w, c->h, q.sigma_normal, q.sigma_depth)) return rc;
+    if (int rc = launch_tiles(c, who, s.track ? DN_FOR_SETTING(c, dn_temporal_spatial_kernel, true) : DN_FOR_SETTING(c, dn_temporal_spatial_kernel, false), r.oc, r.om,
+                              s.fguide, iv, c->w, c->h, q.sigma_normal, q.sigma_depth))
+        return rc;
     if (iv_out) DN_HIPCHK(c, hipMemcpyAsync(iv_out, iv, bytes, hipMemcpyDeviceToDevice, c->stream));
     if (q.iterations == 0) return launch_each(c, who, dn_temporal_finish_kernel, n, iv, color, s.fguide, guides + n, out, var_out, q.demodulate ? 1 : 0, n);
     AtrousParams p = atrous_params(c, s, guides, q.sigma_lum, q.sigma_normal, q.sigma_depth);
@@ -1613,6 +1635,31 @@ int trg_temporal_lag_correction(trg_ctx *c, float *gate) {
     std::lock_guard<std::mutex> lock(g_mutex);
     auto it = g_states.find(c);
     *gate = it == g_states.end() ? -1.0f : it->second.lag_gate;
+    return TRG_OK;
+}
+
+int trg_temporal_set_variance_of_mean(trg_ctx *c, int on) {
+    if (!c) return TRG_ERR_INVALID;
+    if (!ctx_ok(c)) return fail(c, TRG_ERR_INVALID, "trg_temporal_set_variance_of_mean: the denoiser's view of the context does not match the library's");
+    // allocates nothing, like the gate above
+    std::lock_guard<std::mutex> lock(g_mutex);
+    DenoiseState &s = g_states[c];
+    if (!s.pixels) s.device = c->device;
+    if (s.track == (on != 0)) return TRG_OK;
+    s.track = on != 0;
+    // a change is a reset: a history written with the setting off has no variance in it (and one written with it on has, where 0 is promised)
+    s.hist_valid = false;
+    s.have_prev_vp = false;
+    s.armed = false;
+    return TRG_OK;
+}
+
+int trg_temporal_variance_of_mean(trg_ctx *c, int *on) {
+    if (!c) return TRG_ERR_INVALID;
+    if (!on) return fail(c, TRG_ERR_INVALID, "trg_temporal_variance_of_mean: on is NULL");
+    std::lock_guard<std::mutex> lock(g_mutex);
+    auto it = g_states.find(c);
+    *on = it != g_states.end() && it->second.track ? 1 : 0;
     return TRG_OK;
 }
 

@@ -20,6 +20,8 @@
 
     temporal_set_lag_correction(ctx, 3.0)        # changing light: every later step corrects the accumulated colour by the gated lag of its
                                                  # 7 x 7 window (off again: a negative gate); lag_correct(...) is that stage alone
+    temporal_set_variance_of_mean(ctx, True)     # a long history: the variance of the ACCUMULATED colour travels in Hm.z and steers the
+                                                 # iterations, so the filter narrows as the history grows (a change forgets the history)
 
 numpy arrays go through temporary device copies and the call waits for the result; torch ROCm tensors (float32, contiguous) are used in place
 through data_ptr() -- like trg_bind_accum -- and the call only enqueues on the context's current stream.  `reference_denoise`,
@@ -99,6 +101,8 @@ _SYMBOLS = [
     ("trg_temporal_set_lag_correction", C.c_int, [_P, C.c_float]),
     ("trg_temporal_lag_correction", C.c_int, [_P, _F16]),
     ("trg_temporal_lag_correct_host", C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_int32, _P]),
+    ("trg_temporal_set_variance_of_mean", C.c_int, [_P, C.c_int]),
+    ("trg_temporal_variance_of_mean", C.c_int, [_P, C.POINTER(C.c_int)]),
 ]
 LAG_GATE_DEFAULT = 3.0   # TRG_TEMPORAL_LAG_GATE_DEFAULT
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
@@ -287,7 +291,8 @@ def temporal_reset(ctx):
 
 
 def temporal_history(ctx):
-    """trg_temporal_history_read -> [2, h, w, 4]: Hc = (I.rgb, N), Hm = (m1, m2, 0, 0) of the last step.  Waits."""
+    """trg_temporal_history_read -> [2, h, w, 4]: Hc = (I.rgb, N), Hm = (m1, m2, 0, 0) of the last step -- (m1, m2, Vc, 0) with the variance of the mean
+    on.  Waits."""
     hist = np.empty((2, ctx.h, ctx.w, 4), np.float32)
     _chk(ctx, load().trg_temporal_history_read(ctx.h_ctx, hist.ctypes.data))
     return hist
@@ -363,6 +368,20 @@ def lag_correct(ctx, color, guides, hc, gate, sigma_normal=128.0, sigma_depth=1.
     cs, gs = _shapes(ctx)
     return _run(ctx, None, "trg_temporal_lag_correct_host", [("out", None, cs)], [("color", color, cs), ("guides", guides, gs), ("hc", hc, cs)],
                 mid=(float(gate), float(sigma_normal), float(sigma_depth), int(demodulate)), shape_error="color and hc must be %s and guides %s" % (cs, gs))
+
+
+def temporal_set_variance_of_mean(ctx, on=True):
+    """trg_temporal_set_variance_of_mean: every later temporal step of this context carries the variance of the ACCUMULATED colour through the
+    history (Hm.z) and hands that to the iterations, so the filter narrows as the history grows.  Off: the state of a new context.  A call that
+    changes the setting forgets the history like temporal_reset."""
+    _chk(ctx, load().trg_temporal_set_variance_of_mean(ctx.h_ctx, 1 if on else 0))
+
+
+def temporal_variance_of_mean(ctx):
+    """trg_temporal_variance_of_mean: whether the setting is on."""
+    on = C.c_int(-1)
+    _chk(ctx, load().trg_temporal_variance_of_mean(ctx.h_ctx, C.byref(on)))
+    return bool(on.value)
 
 
 def release(ctx):
@@ -701,7 +720,8 @@ def reference_lag(color, g0, g1, hc, gate, params=None, material_ids=None, dtype
     return _lag(D, np.asarray(hc)[..., :3].astype(dtype), F, miss, gate, sn, sd, dtype)
 
 
-def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, material_ids=None, dtype=np.float64, near_parts=False, motion=None, lag=None, **kw):
+def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, material_ids=None, dtype=np.float64, near_parts=False, motion=None, lag=None,
+                       track=False, **kw):
     """float64 evaluation of ONE step of trg_temporal_denoise's definition up to the filter: reprojection, accumulation, V_0.
     color, g0, g1, pos [h, w, 4] (float32 as the device sees them); history: the previous call's four planes (Hc, Hm, F, X), each [h, w, 4], or
     None; prev_vp: 16 floats; params: a TemporalParams, a dict or keywords over the header's defaults (no library needed); material_ids: those
@@ -716,7 +736,10 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
     test, M1.xyz in place of the pixel's normal in the plane and the normal test, no history where M0.w is not > 0; `near` marks the same
     decisions, on the substituted operands.
     lag: None, or the gate of the lag correction (trg_temporal_set_lag_correction): Ic takes I's place in the new Hc and in iv; the moments, N
-    and V_0 are the uncorrected step's, and `near` gains nothing (the correction's one decision, G > 0, is the spatial estimate's)."""
+    and V_0 are the uncorrected step's, and `near` gains nothing (the correction's one decision, G > 0, is the spatial estimate's).
+    track: the variance of the mean (trg_temporal_set_variance_of_mean): history[1][..., 2] is read as Vc', the new Hm.z and iv[..., 3] are Vc of
+    the header's definition -- S for N < 4 or without history, else ((1 - a)(1 - a)) Vh + (a a) S --; everything else, `near` included, is the
+    plain step's exactly.  False: Hm.z is 0 and every array is what it was before the argument existed."""
     dtype = _dtype(dtype)
     q = _options(_TEMPORAL_DEFAULTS, TemporalParams, params, kw)
     alpha, alpha_m, plane_tol, normal_tol = (dtype(np.float32(q[k])) for k in ("alpha", "alpha_moments", "plane_tol", "normal_tol"))
@@ -741,6 +764,7 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
 
     W = np.zeros((h, w), dtype)
     acc = np.zeros((h, w, 6), dtype)                       # I.rgb, N, m1, m2
+    vh = np.zeros((h, w), dtype)                           # track: the sum of b * Hm'.z
     if history is not None:
         Hc, Hm, Hf, Hx = (np.asarray(p, np.float32).astype(dtype) for p in history)
         vp = np.asarray(prev_vp, np.float32).reshape(16).astype(dtype)
@@ -787,6 +811,8 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
                 acc[..., :4] += b[..., None] * hc
                 acc[..., 4] += b * hm[..., 0]
                 acc[..., 5] += b * hm[..., 1]
+                if track:
+                    vh += b * hm[..., 2]
                 W += b
         # W > 0: a sum of weights near 0 with a valid tap in it; or none in it while the sample sits within NEAR of a pixel centre's row or
         # column, where one rounding brings another tap pair into play with a weight near 0
@@ -817,6 +843,13 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
     if lag is not None:
         I = _lag(D.astype(dtype), I.astype(dtype), F, miss, lag, sn, sd, dtype)[0]
     new = np.zeros((4, h, w, 4), dtype)
+    if track:
+        # the variance of the accumulated colour: the recursion from four frames on, the variance of one sample (S = V_0 as above) before
+        ac = a[..., 0]
+        Vh = vh / np.where(have, W, 1.0)
+        Vc = ((one - ac) * (one - ac)) * Vh + (ac * ac) * V0
+        V0 = np.where(miss, 0.0, np.where(have & (N >= 4), Vc, V0)).astype(dtype)
+        new[1, ..., 2] = V0
     new[0, ..., :3], new[0, ..., 3] = I, N
     new[1, ..., 0], new[1, ..., 1] = m1, m2
     new[2] = F
