@@ -83,6 +83,12 @@ public:
     //      it may be set before init() and survives loadScene.  A change forgets the temporal history.  False when the library refuses.
     bool setVarianceOfMean(bool on);
     bool getVarianceOfMean() const { return m_varianceOfMean; }
+    // ---- pixel footprints (trg_temporal_set_coverage): the temporal steps take their guides from the pixel centres, accumulate how often the
+    //      frame's jittered ray agrees with them, and keep a pixel whose agreement is below covMin out of the filter (it shows its accumulated
+    //      colour).  0 <= covMin < 1: on; < 0: off, the default.  Effective in temporal mode on one device; it may be set before init() and
+    //      survives loadScene.  A change forgets the temporal history.  False for a NaN or covMin >= 1, or when the library refuses.
+    bool setCoverage(float covMin);
+    float getCoverage() const { return m_coverageMin; }
     int getFrameIndex() const { return m_frameIndex; }
     double getLastRenderMs() const;
     uint64_t getRayCount() const;                       // primary + bounce + shadow rays traced so far
@@ -110,6 +116,7 @@ protected:
     void *m_temporalOut;         // the last temporal step's output image (owned by the denoise state); null before the first
     float m_lagGate;             // the gate of the lag correction of the temporal steps; < 0 = off
     bool m_varianceOfMean;       // the temporal steps track the variance of the accumulated colour
+    float m_coverageMin;         // cov_min of the coverage history of the temporal steps; < 0 = off
     // updateScene: the positions, normals and indices uploaded last (temporal mode, one device; else empty), whether they came with textures,
     // and whether the loadScene in progress keeps the temporal history
     std::vector<float> m_lastPositions, m_lastNormals;

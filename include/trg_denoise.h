@@ -202,7 +202,7 @@ TRG_API void trg_temporal_default_params(trg_temporal_params *p);
 /* --- HISTORY.  Four planes of width*height float4 per pixel, owned by the state (allocated on the first call, double-buffered, freed by
  *     trg_denoise_release):
  *       Hc = (I.rgb, N)      the accumulated (demodulated) colour and the history length
- *       Hm = (m1, m2, 0, 0)  the accumulated first and second moment of L(D)   (.z: A LONG HISTORY below, while that setting is on)
+ *       Hm = (m1, m2, 0, 0)  the accumulated first and second moment of L(D)   (.z: A LONG HISTORY below, .w: PIXEL FOOTPRINTS below, while those settings are on)
  *       F  = the filter's G0 of that frame (normal | z), emitters marked as misses (z = -1)
  *       X  = the world positions of that frame
  *     A new state has no history, and trg_temporal_reset forgets it (and the view-projection trg_render_temporal remembered;
@@ -291,7 +291,8 @@ TRG_API int trg_render_temporal_read(trg_ctx *ctx, uint32_t frameIndexBegin, uin
  * Feeding filtered colour back into the history: as above, the history holds unfiltered values.  A float64 prototype of SVGF's feedback (the
  * first filtered iteration and its V_1 written back) on top of the variance of the mean was better on two of six sequences and worse on three
  * -- rmse 0.02277 against 0.02324 with the eye turning (8 calls x 2 spp), 0.03414 against 0.03375 at rest (24 x 1); the whole table stands
- * under A LONG HISTORY below.
+ * under A LONG HISTORY below.  Pixels whose footprint covers two surfaces: PIXEL FOOTPRINTS below (off by default) keeps them out of the
+ * filter; misses and directly seen emitters still copy the call's one sample, as listed there.
  * ============================================================================================================================================= */
 
 /* --- PREVIOUS GEOMETRY.  Call it AFTER trg_load_scene of the new geometry.  Triangle k here is the surface that triangle k of the loaded scene
@@ -447,6 +448,83 @@ TRG_API int trg_temporal_lag_correct_host(trg_ctx *ctx, const float *color_in_ho
  * ends with trg_denoise_release. */
 TRG_API int trg_temporal_set_variance_of_mean(trg_ctx *ctx, int on);
 TRG_API int trg_temporal_variance_of_mean(trg_ctx *ctx, int *on);   /* what is set: 1 or 0 */
+
+/* =============================================================================================================================================
+ * PIXEL FOOTPRINTS: CENTRE GUIDES AND A COVERAGE HISTORY.  The guides above describe ONE ray, and trg_raygen jitters that ray inside the pixel:
+ * a pixel whose footprint covers two surfaces is classified by whichever of them the ray of this frame index met.  Its class then changes from
+ * call to call (the history alternates between the planes of two surfaces), the call's colour is demodulated by one surface's albedo whatever
+ * its samples met, and its mixed colour is a full-weight tap for its neighbours.  Here the guides come from the ray through the pixel's CENTRE,
+ * which no frame index moves; whether the jittered ray of the frame agrees with it is recorded per pixel; that agreement is accumulated over
+ * time like the moments; and a pixel whose accumulated agreement is low is kept out of the filter as a miss is -- it shows its accumulated colour.
+ * Off by default, switched on per context; with it off every entry point enqueues what it did and gives the same bits.
+ * ============================================================================================================================================= */
+
+/* --- CENTRE GUIDES.  The CENTRE RAY of pixel (x, y) is trg_raygen's arithmetic with r0 = r1 = 0.5 in place of the two Halton values, so the
+ *     frame index plays no part in it.  Every operation is one fp32 operation, sums left to right:
+ *       uvx = ((x + 0.5) / width) * 2 - 1,  uvy = ((y + 0.5) / height) * 2 - 1
+ *       world_j = ((uvx * m[j*4] + uvy * m[j*4+1]) + 0 * m[j*4+2]) + 1 * m[j*4+3]          m = inv_view_proj, j = 0 .. 3
+ *       t = (world_0 / world_3, world_1 / world_3, world_2 / world_3) - cam_pos,  direction = t * (1 / sqrt((t.x t.x + t.y t.y) + t.z t.z))
+ *     origin = cam_pos, mask 3, maxDistance infinite, colour (1, 1, 1, 0).  The divisions are IEEE and the square root is the correctly rounded
+ *     one in BOTH settings of TRG_OPT_STRICT: the setting decides the intersector only, as it does for the guides above.
+ *     G0, G1 and X.xyz are what trg_guides_render_pos defines, from that ray's nearest hit.  X.w, which is 0 there and which no step reads
+ *     without the setting below, is the AGREEMENT FLAG A(p):
+ *       A(p) = 1  when the JITTERED primary ray of frameIndex (trg_raygen's, traced in the same pass) agrees with the centre hit,
+ *       A(p) = 0  when it does not, and on a centre miss.
+ *     The two AGREE iff both rays hit; both hits are emitters (material TRG_MATERIAL_EMISSIVE) or neither is; and, with n_c, X_c, z_c the centre
+ *     hit's interpolated normal, position and distance and n_j, X_j = o + z d (one fp32 multiply and add per component) the jittered hit's,
+ *       | nn(n_c) . (X_j - X_c) | <= plane_tol * z_c      and      nn(n_c) . nn(n_j) >= normal_tol
+ *     (nn and the sums of three products as in trg_temporal_denoise; sqrtf and IEEE divisions in both settings).  These are the reprojection's
+ *     two tap tests on purpose: agreement means "the history would accept it".  One jittered ray is tested, whatever the spp of the call.
+ *     plane_tol must be > 0 and normal_tol in [-1, 1] (trg_temporal_params' ranges), no buffer NULL and no two overlapping: TRG_ERR_INVALID.
+ *     _motion: M0, M1 as trg_guides_render_motion defines them, from the CENTRE hit's barycentrics.
+ *     On the device: dn_centre_raygen_kernel (streaming; three float4 per thread) writes the centre rays; the library's raygen and trace run for
+ *     the jittered rays into a second ray / hit scratch of the state, then the trace of the centre rays; the gather in its AGREE form also
+ *     reads the jittered hit, its ray and the normal rows of its primitive's record.  No atomics, no LDS, no scratch memory. */
+TRG_API int trg_guides_render_centre(trg_ctx *ctx, uint32_t frameIndex, float plane_tol, float normal_tol, void *guides_device, void *pos_device);
+TRG_API int trg_guides_render_centre_motion(trg_ctx *ctx, uint32_t frameIndex, float plane_tol, float normal_tol, void *guides_device, void *pos_device,
+                                            void *motion_device);
+/* with HOST buffers; they WAIT for the result (sizes as for trg_guides_pos_read and trg_guides_motion_read) */
+TRG_API int trg_guides_centre_read(trg_ctx *ctx, uint32_t frameIndex, float plane_tol, float normal_tol, float *guides_host, float *pos_host);
+TRG_API int trg_guides_centre_motion_read(trg_ctx *ctx, uint32_t frameIndex, float plane_tol, float normal_tol, float *guides_host, float *pos_host,
+                                          float *motion_host);
+
+/* --- WITH THE SETTING ON, ONE TEMPORAL STEP (every entry point of the family) differs in these places.  Notation: trg_temporal_denoise's;
+ *     A(p) = X(p).w of the position plane the step is given (trg_guides_render_centre writes it; a caller's own planes may carry any value in [0, 1]).
+ *   Reproject.  covh = (sum of b * Hm'.w over the valid taps) / W -- the taps, the order and the division of m1h.
+ *   Accumulate. No history: cov = A(p).  Otherwise cov = covh + am * (A(p) - covh).  A miss has cov = 0.  Hm = (m1, m2, Vc or 0, cov).
+ *   Mixed.      p is MIXED iff it is not a miss and cov < cov_min.
+ *   A mixed pixel counts as a MISS for everything behind the reprojection -- the spatial estimate, the lag correction and the iterations: it
+ *               copies, and it is nobody's tap.  Its (I, V_0).rgb is I * max(a_p, 1e-3) when `demodulate` (else I), so the output of the step
+ *               is its accumulated colour, remodulated once.  Its V_0 is the temporal form max(0, m2 - m1 * m1) whatever N (with the variance of
+ *               the mean on: what the recursion gives, the same form below four frames), never the spatial estimate; nothing reads it.
+ *   History.    The history plane F keeps the UNMARKED guide, so a later call still finds taps there.  Hc, the moments and N are untouched: the
+ *               history always holds demodulated values, mixed or not.
+ *     Consequences.  With A = 1 on every hit cov is exactly 1 and nobody is mixed (sum b / W over one order of summation is exactly 1, and
+ *     1 + am * 0 is exactly 1): every output but Hm.w is then the step's with the setting off, BIT FOR BIT.  With A = 0 everywhere every hit is
+ *     mixed from the first call on and the output is the remodulated accumulated colour.  The one new discrete decision is cov against cov_min;
+ *     the reference marks it `near` within 1e-4, like the others.
+ *     trg_render_temporal / _own / _read with the setting on: step 3 is trg_guides_render_centre(b, p.plane_tol, p.normal_tol) -- its motion
+ *     form while armed --; everything else is unchanged.
+ *     The float64 reference: toyraygun_amd/denoise.py reference_temporal(..., coverage=cov_min); reference_centre_rays, reference_agreement.
+ *
+ *     NOT COVERED.  Misses and directly seen emitters still copy the call's one sample: a pixel whose centre ray leaves the scene or meets the
+ *     light, but whose footprint holds geometry, keeps its 1-spp noise (misses have no position to reproject; letting emitters accumulate made
+ *     the whole image worse in a float64 prototype, 0.0295 against 0.0274, for a reason not yet understood).  Coverage for trg_denoise /
+ *     trg_denoise_variance (one call, no history).  Device groups.  trg_guides_render, _pos and _motion return what they returned.
+ *
+ *     On the device: no new launch.  The COVER forms of the reprojection kernel read .w of the Hm' float4 they gather anyway and X.w of the float4
+ *     they read anyway, and write Hm.w.  For a mixed pixel they write the remodulated (I, V_0) and set .w = -1 of THEIR OWN pixel of the filter's
+ *     copy of G0 -- the emitters' mechanism; the kernel reads that plane at its own pixel only, and the launches that stage neighbours come
+ *     after it, so no byte is read by one workgroup while another writes it.  No atomics, no scratch. */
+#define TRG_TEMPORAL_COVERAGE_MIN_DEFAULT 0.9f
+/* 0 <= cov_min < 1: on, for every later temporal step of this context; cov_min < 0: off (the state of a new context); NaN or cov_min >= 1:
+ * TRG_ERR_INVALID, nothing changes (at rest covh comes out as 1 - 1 ulp on half the picture: a threshold of 1 would flag pixels by rounding alone).
+ * cov_min = 0 is "centre guides, nobody mixed".  Host only: allocates nothing on the device, harmless for a context that never denoised.  A call
+ * that CHANGES the value also does what trg_temporal_reset does -- history written under the other setting has no coverage in it and comes from
+ * other guides --; a call that repeats the current value (or turns off what is off) changes nothing.  The setting survives trg_temporal_reset and
+ * ends with trg_denoise_release. */
+TRG_API int trg_temporal_set_coverage(trg_ctx *ctx, float cov_min);
+TRG_API int trg_temporal_coverage(trg_ctx *ctx, float *cov_min);   /* what is set; < 0 when off */
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,9 @@ copy is not separable here, so it is a step of 1 iteration minus one variance it
 the motion planes beside the plain step at rest.  The changing-light leg (trg_temporal_set_lag_correction) is the plain step at rest with the
 lag correction on and, right beside it, off again: the two differ by the one launch of dn_temporal_lag_kernel.  The long-history leg
 (trg_temporal_set_variance_of_mean) is the 5-iteration step with the variance of the mean on and, right beside it, off, at rest and with the eye
-turning: the same launches, two kernels in their TRACK forms."""
+turning: the same launches, two kernels in their TRACK forms.  The pixel-footprint leg (trg_guides_render_centre, trg_temporal_set_coverage)
+comes last: the centre guide pass beside trg_guides_render_pos (two raygen and two trace launches instead of one of each), and the 5-iteration
+step with the coverage history on and, right beside it, off, at rest and with the eye turning, on the centre guides' planes (X.w = A) in both."""
 import json
 import os
 import sys
@@ -93,10 +95,10 @@ u_back = O.make_uniforms(w, h, eye=(4.38 * np.sin(-t), 1.0, -1.0 + 4.38 * np.cos
 vp_back = denoise.temporal_view_proj(u_back)
 
 
-def moving(**kw):
+def moving(centre=False, **kw):
     c.set_uniforms(O.uniforms_bytes(u_back))
     g2, x2 = torch.empty_like(g), torch.empty_like(x)
-    denoise.guides_pos(c, 0, out=g2, pos=x2)
+    (denoise.guides_centre if centre else denoise.guides_pos)(c, 0, out=g2, pos=x2)   # (centre: the pixel-footprint leg, X.w = A)
     denoise.temporal_reset(c)
     denoise.temporal_denoise(c, acc, g2, x2, None, out=out, **kw)     # N = 1 everywhere at the other eye
     c.set_uniforms(O.uniforms_bytes(u_rest))
@@ -155,6 +157,20 @@ for name, on in (("vmean", True), ("vmean_off", False)):
     res["temporal_5_rest_%s_ms" % name] = timed(lambda: step(vp_rest))
     res["temporal_5_moving_%s_ms" % name] = moving()
 res["vmean_extra_ms"] = {leg: res["temporal_5_%s_vmean_ms" % leg] - res["temporal_5_%s_vmean_off_ms" % leg] for leg in ("rest", "moving")}
+# pixel footprints: the guide pass from the pixel centres with the agreement flag, then the step on ITS planes with the coverage history on and,
+# right beside it, off (a change of the setting forgets the history: six calls at rest first).  The same launches; the COVER form of one kernel
+denoise.temporal_set_variance_of_mean(c, False)
+res["guides_centre_ms"] = timed(lambda: denoise.guides_centre(c, 0, out=g, pos=x))
+res["guides_pos_again_ms"] = timed(lambda: denoise.guides_pos(c, 0, out=g, pos=x))
+res["guides_centre_extra_ms"] = res["guides_centre_ms"] - res["guides_pos_again_ms"]
+denoise.guides_centre(c, 0, out=g, pos=x)
+for name, cov in (("cover", denoise.COVERAGE_MIN_DEFAULT), ("cover_off", None)):
+    denoise.temporal_set_coverage(c, cov)
+    for _ in range(6):
+        step(vp_rest)
+    res["temporal_5_rest_%s_ms" % name] = timed(lambda: step(vp_rest))
+    res["temporal_5_moving_%s_ms" % name] = moving(centre=True)
+res["cover_extra_ms"] = {leg: res["temporal_5_%s_cover_ms" % leg] - res["temporal_5_%s_cover_off_ms" % leg] for leg in ("rest", "moving")}
 print(json.dumps(res))
 c.bind_accum(None)
 c.set_stream(None)

@@ -15,7 +15,7 @@ namespace toyraygun {
 
 HipRenderer::HipRenderer()
     : m_ctx(nullptr), m_group(nullptr), m_deviceCount(0), m_bounces(3), m_deviceBuild(0), m_offsetSeed(0x5EED0001u), m_sceneLoaded(false), m_synchronous(false), m_pending(0), m_pendingFirst(0),
-      m_launches(0), m_denoise(0), m_denoiseVar(false), m_denoiseTemporal(false), m_temporalOut(nullptr), m_lagGate(-1.0f), m_varianceOfMean(false), m_lastTextured(false), m_keepHistory(false) {
+      m_launches(0), m_denoise(0), m_denoiseVar(false), m_denoiseTemporal(false), m_temporalOut(nullptr), m_lagGate(-1.0f), m_varianceOfMean(false), m_coverageMin(-1.0f), m_lastTextured(false), m_keepHistory(false) {
     memset(&m_pendingUniforms, 0, sizeof(m_pendingUniforms));
 }
 HipRenderer::~HipRenderer() { destroy(); }
@@ -61,6 +61,10 @@ bool HipRenderer::init() {
             return false;
         }
         if (m_varianceOfMean && trg_temporal_set_variance_of_mean(m_ctx, 1) != TRG_OK) {
+            printf("HipRenderer: %s\n", trg_last_error(m_ctx));
+            return false;
+        }
+        if (m_coverageMin >= 0.0f && trg_temporal_set_coverage(m_ctx, m_coverageMin) != TRG_OK) {
             printf("HipRenderer: %s\n", trg_last_error(m_ctx));
             return false;
         }
@@ -311,6 +315,15 @@ bool HipRenderer::setVarianceOfMean(bool on) {
         if (trg_temporal_set_variance_of_mean(m_ctx, on ? 1 : 0) != TRG_OK) { printf("HipRenderer: %s\n", trg_last_error(m_ctx)); return false; }
     }
     m_varianceOfMean = on;
+    return true;
+}
+bool HipRenderer::setCoverage(float covMin) {
+    if (!(covMin < 1.0f)) return false;   // (NaN too)
+    if (m_ctx && !m_group) {
+        flush();   // frames queued so far keep the setting they were queued under
+        if (trg_temporal_set_coverage(m_ctx, covMin) != TRG_OK) { printf("HipRenderer: %s\n", trg_last_error(m_ctx)); return false; }
+    }
+    m_coverageMin = covMin;
     return true;
 }
 bool HipRenderer::savePNG(const char *path) {

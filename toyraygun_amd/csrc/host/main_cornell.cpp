@@ -1,6 +1,6 @@
 // main_cornell.cpp -- headless demo following the reference app's call order (reference src/main.cpp:16-98):
 // engine init -> three shaders -> renderer init -> camera -> Cornell box -> frame loop; then writes a PNG.
-//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean]]] [orbit=DEG] [slide=D]]
+//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D]]
 //     denoise=N    a-trous iterations of the written image, 0 = off (default)
 //     ,var         the variance-guided filter from two half-sample buffers
 //     ,temporal    the frames are rendered as `frames` calls of 1 spp, each a temporal step (reprojected history, temporal variance); the
@@ -9,6 +9,8 @@
 //                  light no longer waits for the history to fade (HipRenderer::setLagCorrection)
 //     ,vmean       (behind ,temporal, before or after ,lag) the steps track the variance of the ACCUMULATED colour and filter by that: the
 //                  filter narrows as the history grows (HipRenderer::setVarianceOfMean)
+//     ,cover[=C]   (behind ,temporal, in any order with the other two) guides from the pixel centres and a coverage history: a pixel whose footprint
+//                  holds two surfaces (accumulated agreement below C, default 0.9, 0 <= C < 1) stays out of the filter (HipRenderer::setCoverage)
 //     orbit=DEG    the eye turns about the look-at point (about the vertical axis) by DEG degrees per call
 //     slide=D      before call k the box is rebuilt with the short box moved by k * D along x and handed to HipRenderer::updateScene: with
 //                  ,temporal the history follows the moving box (trg_temporal_set_previous_scene), otherwise it is a plain loadScene
@@ -58,8 +60,8 @@ int main(int argc, char **argv) {
     const char *out = argc > 5 ? argv[5] : "cornell.png";
     int denoise = 0;
     bool denoiseVar = false, denoiseTemporal = false, varianceOfMean = false;
-    double orbit = 0.0, slide = 0.0, lagGate = -1.0;
-    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean]]] [orbit=DEG] [slide=D]]";
+    double orbit = 0.0, slide = 0.0, lagGate = -1.0, coverMin = -1.0;
+    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D]]";
     for (int a = 6; a < argc; ++a) {
         if (strncmp(argv[a], "slide=", 6) == 0) {
             char *end = nullptr;
@@ -80,9 +82,9 @@ int main(int argc, char **argv) {
             if (strcmp(comma, ",var") == 0) denoiseVar = true;
             else if (strncmp(comma, ",temporal", 9) == 0 && (comma[9] == 0 || comma[9] == ',')) {
                 denoiseTemporal = true;
-                // behind ,temporal: ,lag[=G] and ,vmean, each at most once, in either order
+                // behind ,temporal: ,lag[=G], ,vmean and ,cover[=C], each at most once, in any order
                 const char *tok = comma + 9;
-                bool sawLag = false;
+                bool sawLag = false, sawCover = false;
                 while (*tok) {
                     const char *next = strchr(tok + 1, ',');
                     const size_t len = next ? (size_t)(next - tok) : strlen(tok);
@@ -93,6 +95,13 @@ int main(int argc, char **argv) {
                         lagGate = strtod(tok + 5, &end);
                         if (end != tok + len || !(lagGate >= 0.0)) { std::cout << usage << std::endl; return -1; }
                         sawLag = true;
+                    }
+                    else if (len == 6 && strncmp(tok, ",cover", 6) == 0 && !sawCover) { sawCover = true; coverMin = TRG_TEMPORAL_COVERAGE_MIN_DEFAULT; }
+                    else if (len > 7 && strncmp(tok, ",cover=", 7) == 0 && !sawCover) {
+                        char *end = nullptr;
+                        coverMin = strtod(tok + 7, &end);
+                        if (end != tok + len || !(coverMin >= 0.0 && coverMin < 1.0)) { std::cout << usage << std::endl; return -1; }
+                        sawCover = true;
                     }
                     else { std::cout << usage << std::endl; return -1; }
                     tok += len;
@@ -130,6 +139,7 @@ int main(int argc, char **argv) {
     HipRenderer *hip = static_cast<HipRenderer *>(renderer);
     if (!hip->setDenoise(denoise, denoiseVar, denoiseTemporal)) { std::cout << "denoise must be 0.." << 6 << std::endl; return -1; }
     if (lagGate >= 0.0 && !hip->setLagCorrection((float)lagGate)) { std::cout << "the lag correction was refused" << std::endl; return -1; }
+    if (coverMin >= 0.0 && !hip->setCoverage((float)coverMin)) { std::cout << "the coverage history was refused" << std::endl; return -1; }
     if (varianceOfMean && !hip->setVarianceOfMean(true)) { std::cout << "the variance of the mean was refused" << std::endl; return -1; }
     Scene *scene = createCornellBoxScene();
     renderer->loadScene(scene);

@@ -4,6 +4,8 @@
 // For geometry that moved: the previous scene, the motion planes and the MOTION form of the reprojection.
 // For lighting that changed: the gated lag correction of the accumulated colour.
 // For a long history: the variance of the accumulated colour, carried in Hm.z (the TRACK forms of the two temporal kernels).
+// For pixels whose footprint covers two surfaces: guides from the pixel centres with an agreement flag, and its history in Hm.w (the COVER forms
+// of the reprojection kernel).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -169,6 +171,11 @@ struct DenoiseState {
     float lag_gate = -1.0f;
     // a long history (trg_temporal_set_variance_of_mean): the steps carry the variance of the accumulated colour in Hm.z.  Set like the gate
     bool track = false;
+    // pixel footprints (trg_temporal_set_coverage): cov_min of the coverage history, < 0 = off.  Set like the gate.  The second ray / hit scratch
+    // of the centre guides' jittered pass (allocated on its first use, for `pixels` rays)
+    float cov_min = -1.0f;
+    trg_ray *rays_j = nullptr;
+    trg_isect *isect_j = nullptr;
 };
 std::mutex g_mutex;
 std::unordered_map<trg_ctx *, DenoiseState> g_states;
@@ -179,7 +186,7 @@ void each_buffer(DenoiseState &s, F f) {
     f(s.rays, sizeof(trg_ray)); f(s.isect, sizeof(trg_isect)); f(s.ping, sizeof(float4)); f(s.pong, sizeof(float4)); f(s.guides, 2 * sizeof(float4));
     f(s.fguide, sizeof(float4));
     f(s.result, 0); f(s.rec_of_prim, 0); f(s.overflow, 0); f(s.half_acc, 0); f(s.halves, 0); f(s.hist[0], 0); f(s.hist[1], 0); f(s.timg, 0); f(s.tpos, 0);
-    f(s.prev_geo, 0); f(s.tmotion, 0);
+    f(s.prev_geo, 0); f(s.tmotion, 0); f(s.rays_j, 0); f(s.isect_j, 0);
 }
 
 void free_state(DenoiseState &s) {
@@ -228,6 +235,15 @@ int lazy_planes(trg_ctx *c, DenoiseState &s, float4 *&mem, size_t planes, const 
     return TRG_OK;
 }
 
+// the same for a buffer of one element of T per pixel
+template <typename T>
+int lazy_scratch(trg_ctx *c, DenoiseState &s, T *&mem, const char *what) {
+    if (mem) return TRG_OK;
+    const hipError_t e = hipMalloc((void **)&mem, s.pixels * sizeof(T));
+    if (e != hipSuccess) { mem = nullptr; return fail(c, TRG_ERR_NOMEM, "denoise: hipMalloc of %s failed: %s", what, hipGetErrorString(e)); }
+    return TRG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------------------
 // Guides
 // ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -242,9 +258,19 @@ __global__ void dn_record_map_kernel(const float4 *recs, uint32_t n_rec, uint32_
 }
 
 // POS: also the world-position plane X = (o + z d, 0) of trg_guides_render_pos, from the primary rays the hit records belong to (zero on a miss)
-template <bool POS>
-__global__ void dn_gather_kernel(const trg_isect *isect, const uint32_t *rec_of_prim, const float4 *recs, uint32_t n_prims, const TexDesc tex,
-                                 float4 *g0, float4 *g1, uint32_t n, const trg_ray *rays, float4 *pos) {
+// AGREE (trg_guides_render_centre; needs POS): `isect` and `rays` are those of the CENTRE rays, and pos.w becomes the agreement flag A of the
+// header -- 1 when the frame's jittered primary ray (ag.rays, its hit ag.isect) passes the reprojection's two tap tests against the centre hit
+// and both hits are emitters or neither is.  Three more coalesced reads per pixel (one float4 of the hit, two of the ray) and the rows 1, 3, 4, 5
+// of the jittered hit's record.  sqrtf and IEEE divisions whatever the build setting: the kernel has one form for both.
+struct GatherAgree {
+    const trg_isect *isect;
+    const trg_ray *rays;
+    float plane_tol, normal_tol;
+};
+template <bool POS, bool AGREE>
+__device__ __forceinline__ void dn_gather_pixel(const trg_isect *isect, const uint32_t *rec_of_prim, const float4 *recs, uint32_t n_prims, const TexDesc &tex,
+                                                float4 *g0, float4 *g1, uint32_t n, const trg_ray *rays, float4 *pos, const GatherAgree &ag) {
+    static_assert(POS || !AGREE, "the agreement flag travels in the position plane");
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float4 is = reinterpret_cast<const float4 *>(isect)[i];   // distance, primitiveIndex, coordinates[2]
@@ -255,10 +281,12 @@ __global__ void dn_gather_kernel(const trg_isect *isect, const uint32_t *rec_of_
         if (POS) pos[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
     }
+    float4 X = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (POS) {
         const float4 *r = reinterpret_cast<const float4 *>(rays) + (size_t)i * 3u;   // origin | mask, direction | maxDistance, colour
         const float4 o = r[0], d = r[1];
-        pos[i] = make_float4(o.x + is.x * d.x, o.y + is.x * d.y, o.z + is.x * d.z, 0.0f);
+        X = make_float4(o.x + is.x * d.x, o.y + is.x * d.y, o.z + is.x * d.z, 0.0f);
+        if (!AGREE) pos[i] = X;
     }
     const float4 *rec = recs + (size_t)rec_of_prim[prim] * 8u;
     const uint32_t mat = (uint32_t)__float_as_int(rec[1].w);
@@ -294,6 +322,60 @@ __global__ void dn_gather_kernel(const trg_isect *isect, const uint32_t *rec_of_
     }
     g0[i] = n4;
     g1[i] = a4;
+    if (AGREE) {
+        const float4 js = reinterpret_cast<const float4 *>(ag.isect)[i];
+        const int jprim = __float_as_int(js.y);
+        float A = 0.0f;
+        if (js.x >= 0.0f && jprim >= 0 && (uint32_t)jprim < n_prims) {
+            const float4 *jrec = recs + (size_t)rec_of_prim[jprim] * 8u;
+            const bool same_kind = ((uint32_t)__float_as_int(jrec[1].w) == TRG_MATERIAL_EMISSIVE) == (mat == TRG_MATERIAL_EMISSIVE);
+            const float4 j3 = jrec[3], j4 = jrec[4], j5 = jrec[5];
+            const float d0 = js.z, d1 = js.w, d2 = 1.0f - d0 - d1;
+            float jx = d0 * j3.x + d1 * j3.w + d2 * j4.z, jy = d0 * j3.y + d1 * j4.x + d2 * j4.w, jz = d0 * j3.z + d1 * j4.y + d2 * j5.x;
+            const float4 *r = reinterpret_cast<const float4 *>(ag.rays) + (size_t)i * 3u;
+            const float4 o = r[0], d = r[1];
+            const float xj = o.x + js.x * d.x, yj = o.y + js.x * d.y, zj = o.z + js.x * d.z;
+            float nx = n4.x, ny = n4.y, nz = n4.z;
+            const float lc = sqrtf(nx * nx + ny * ny + nz * nz), lj = sqrtf(jx * jx + jy * jy + jz * jz);
+            if (same_kind && lc > 0.0f && lj > 0.0f) {
+                nx = nx / lc; ny = ny / lc; nz = nz / lc;
+                jx = jx / lj; jy = jy / lj; jz = jz / lj;
+                const float dist = nx * (xj - X.x) + ny * (yj - X.y) + nz * (zj - X.z);
+                if (fabsf(dist) <= ag.plane_tol * is.x && nx * jx + ny * jy + nz * jz >= ag.normal_tol) A = 1.0f;
+            }
+        }
+        X.w = A;
+        pos[i] = X;
+    }
+}
+template <bool POS>
+__global__ void dn_gather_kernel(const trg_isect *isect, const uint32_t *rec_of_prim, const float4 *recs, uint32_t n_prims, const TexDesc tex,
+                                 float4 *g0, float4 *g1, uint32_t n, const trg_ray *rays, float4 *pos) {
+    dn_gather_pixel<POS, false>(isect, rec_of_prim, recs, n_prims, tex, g0, g1, n, rays, pos, GatherAgree{});
+}
+__global__ void dn_gather_agree_kernel(const trg_isect *isect, const uint32_t *rec_of_prim, const float4 *recs, uint32_t n_prims, const TexDesc tex,
+                                       float4 *g0, float4 *g1, uint32_t n, const trg_ray *rays, float4 *pos, const GatherAgree ag) {
+    dn_gather_pixel<true, true>(isect, rec_of_prim, recs, n_prims, tex, g0, g1, n, rays, pos, ag);
+}
+
+// The centre rays of trg_guides_render_centre: trg_raygen's arithmetic with 0.5 in place of the two Halton values, written out as the header
+// writes it -- one fp32 operation each (no contraction in this file), IEEE divisions and sqrtf in both build settings.  One pixel per thread,
+// a 48-byte trg_ray as three float4
+__global__ void dn_centre_raygen_kernel(const trg_uniforms u, uint32_t w, uint32_t h, float4 *rays) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= w * h) return;
+    const uint32_t y = i / w, x = i - y * w;
+    const float uvx = (((float)x + 0.5f) / (float)w) * 2.0f - 1.0f, uvy = (((float)y + 0.5f) / (float)h) * 2.0f - 1.0f;
+    const float *m = u.inv_view_proj;
+    float wd[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) wd[j] = ((uvx * m[j * 4 + 0] + uvy * m[j * 4 + 1]) + 0.0f * m[j * 4 + 2]) + 1.0f * m[j * 4 + 3];
+    const float tx = wd[0] / wd[3] - u.cam_pos[0], ty = wd[1] / wd[3] - u.cam_pos[1], tz = wd[2] / wd[3] - u.cam_pos[2];
+    const float inv = 1.0f / sqrtf((tx * tx + ty * ty) + tz * tz);
+    float4 *r = rays + (size_t)i * 3u;
+    r[0] = make_float4(u.cam_pos[0], u.cam_pos[1], u.cam_pos[2], __uint_as_float(3u));
+    r[1] = make_float4(tx * inv, ty * inv, tz * inv, __builtin_inff());
+    r[2] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
 }
 
 inline uint32_t align16(uint32_t v) { return (v + 15u) & ~15u; }
@@ -367,8 +449,10 @@ __global__ void dn_motion_kernel(const trg_isect *isect, const float4 *prev, uin
 bool have_previous_scene(const trg_ctx *c, const DenoiseState &s) { return c->scene_loaded && s.prev_tris != 0 && s.prev_tris == c->sc.n_tris; }
 
 // pos (may be null): the world-position plane of trg_guides_render_pos; motion (may be null, needs pos): behind it the two motion planes of
-// trg_guides_render_motion (the caller has checked have_previous_scene)
-int guides_render(trg_ctx *c, DenoiseState &s, uint32_t frameIndex, float4 *guides, float4 *pos = nullptr, float4 *motion = nullptr) {
+// trg_guides_render_motion (the caller has checked have_previous_scene).  centre (may be null, needs pos): the tolerances of
+// trg_guides_render_centre -- the guides come from the rays through the pixel centres and pos.w is the agreement flag
+struct CentreTol { float plane_tol, normal_tol; };
+int guides_render(trg_ctx *c, DenoiseState &s, uint32_t frameIndex, float4 *guides, float4 *pos = nullptr, float4 *motion = nullptr, const CentreTol *centre = nullptr) {
     if (!c->scene_loaded) return fail(c, TRG_ERR_INVALID, "trg_guides_render: no scene loaded");
     if (!c->have_uniforms || !c->have_offsets) return fail(c, TRG_ERR_INVALID, "trg_guides_render: uniforms / pixel offsets not set");
     const size_t n = (size_t)c->w * c->h;
@@ -388,11 +472,30 @@ int guides_render(trg_ctx *c, DenoiseState &s, uint32_t frameIndex, float4 *guid
     hipStream_t st = c->stream;
     trg_uniforms u = c->u;
     u.frameIndex = frameIndex;
-    hipError_t e = (c->opt_strict ? launch_raygen_strict : launch_raygen_fast)(u, c->offsets, s.rays, st);
+    if (centre) {
+        if (int rc = lazy_scratch(c, s, s.rays_j, "the jittered rays")) return rc;
+        if (int rc = lazy_scratch(c, s, s.isect_j, "the jittered hit records")) return rc;
+    }
+    // the frame's jittered rays: the guides' own, or with `centre` the ones the agreement flag tests, into the second scratch
+    trg_ray *const jrays = centre ? s.rays_j : s.rays;
+    tp.rays = jrays; tp.out = centre ? s.isect_j : s.isect;
+    hipError_t e = (c->opt_strict ? launch_raygen_strict : launch_raygen_fast)(u, c->offsets, jrays, st);
     if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_guides_render: raygen launch failed: %s", hipGetErrorString(e));
     e = (c->opt_strict ? launch_trace_strict : launch_trace_fast)(tp, plan.lds_scene, false, plan.total, st);
     if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_guides_render: trace launch failed: %s", hipGetErrorString(e));
+    if (centre) {
+        // the centre rays and, LAST, their trace: s.isect holds the centre hits for the gather and the motion kernel
+        if (int rc = launch_each(c, "trg_guides_render_centre", dn_centre_raygen_kernel, n, u, c->w, c->h, reinterpret_cast<float4 *>(s.rays))) return rc;
+        tp.rays = s.rays; tp.out = s.isect;
+        e = (c->opt_strict ? launch_trace_strict : launch_trace_fast)(tp, plan.lds_scene, false, plan.total, st);
+        if (e != hipSuccess) return fail(c, TRG_ERR_DEVICE, "trg_guides_render_centre: trace launch failed: %s", hipGetErrorString(e));
+    }
     if (int rc = record_map(c, s, "trg_guides_render")) return rc;
+    if (centre) {
+        if (int rc = launch_each(c, "trg_guides_render_centre", dn_gather_agree_kernel, n, s.isect, s.rec_of_prim, reinterpret_cast<const float4 *>(c->blob + sc.off_fat),
+                                 sc.n_tris, c->tex, guides, guides + n, n, s.rays, pos, GatherAgree{ s.isect_j, s.rays_j, centre->plane_tol, centre->normal_tol }))
+            return rc;
+    } else
     if (int rc = launch_each(c, "trg_guides_render", pos ? dn_gather_kernel<true> : dn_gather_kernel<false>, n, s.isect, s.rec_of_prim,
                              reinterpret_cast<const float4 *>(c->blob + sc.off_fat), sc.n_tris, c->tex, guides, guides + n, n, pos ? s.rays : nullptr, pos))
         return rc;
@@ -880,6 +983,8 @@ struct ReprojectParams {
     float vp[16];
     float alpha, alpha_moments, plane_tol, normal_tol, max_history;
     const float4 *m0, *m1;                            // MOTION: the previous-position planes M0, M1 (last: the other fields keep their offsets)
+    float4 *fmark;                                    // COVER: the filter's G0 again (= fguide), writable: a mixed pixel marks its own .w
+    float cov_min;
 };
 
 // n / |n| into (x, y, z); false when the length is not > 0
@@ -898,13 +1003,18 @@ __device__ __forceinline__ bool dn_unit(float &x, float &y, float &z) {
 // plane test, M1.xyz the current normal's in both tests -- and only where M0.w > 0; two more coalesced float4 per pixel.
 // TRACK (trg_temporal_set_variance_of_mean): Hm'.z of the float4 that is gathered anyway is the variance of the accumulated colour; it goes
 // through the taps like the moments, through the recursion of the header from four frames on, and out into Hm.z and (I, V_0).w.
-template <bool STRICT, bool MOTION, bool TRACK>
+// COVER (trg_temporal_set_coverage): Hm'.w of the same float4 is the accumulated agreement; it goes through the taps like the moments and is blended
+// with X.w, this call's agreement flag, at the moments' rate.  A hit whose result is below cov_min is MIXED: its (I, V_0) carries the remodulated
+// colour and the .w of ITS OWN pixel of the filter's G0 is set to -1, so every launch behind this one treats it as a miss (the history keeps
+// the unmarked guide, written before).
+template <bool STRICT, bool MOTION, bool TRACK, bool COVER>
 __global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const ReprojectParams p) {
     const int x = (int)blockIdx.x * kDnTile + ((int)threadIdx.x & 15), y = (int)blockIdx.y * kDnTile + ((int)threadIdx.x >> 4);
     if (x >= p.w || y >= p.h) return;
     const size_t pix = (size_t)y * (size_t)p.w + (size_t)x;
     const float4 c = p.color[pix], f = p.fguide[pix], X = p.pos[pix];
     const float4 R = MOTION ? p.m0[pix] : X;            // where the hit was when the history was written
+    const float agree = COVER ? p.pos[pix].w : 0.0f;    // COVER: A(p) (read beside X: taking X apart leaves a dead copy of it in LDS)
     p.of[pix] = f;
     p.ox[pix] = X;
     if (f.w < 0.0f) {   // a miss: nothing to accumulate
@@ -918,6 +1028,7 @@ __global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const Reproj
     const float l = dn_lum(make_float4(dr, dg, db, 0.0f));
     float ir = 0.0f, ig = 0.0f, ib = 0.0f, m1 = 0.0f, m2 = 0.0f, nh = 0.0f, W = 0.0f;
     float vh = 0.0f;                                    // TRACK: Vh
+    float cov = 0.0f;                                   // COVER: covh
     float nx = f.x, ny = f.y, nz = f.z;
     if (MOTION) { const float4 pn = p.m1[pix]; nx = pn.x; ny = pn.y; nz = pn.z; }
     if (p.hc && (!MOTION || R.w > 0.0f) && dn_unit<STRICT>(nx, ny, nz)) {
@@ -951,6 +1062,7 @@ __global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const Reproj
                     ir += b * hc.x; ig += b * hc.y; ib += b * hc.z; nh += b * hc.w;
                     m1 += b * hm.x; m2 += b * hm.y;
                     if (TRACK) vh += b * hm.z;
+                    if (COVER) cov += b * hm.w;
                     W += b;
                 }
             }
@@ -963,17 +1075,26 @@ __global__ __launch_bounds__(256) void dn_temporal_reproject_kernel(const Reproj
         N = fminf(nh + 1.0f, p.max_history);
         const float a = fmaxf(p.alpha, 1.0f / N), am = fmaxf(p.alpha_moments, 1.0f / N);
         if (TRACK) ac = a;
+        if (COVER) { cov = cov / W; cov = cov + am * (agree - cov); }
         ir = ir + a * (dr - ir); ig = ig + a * (dg - ig); ib = ib + a * (db - ib);
         m1 = m1 + am * (l - m1);
         m2 = m2 + am * (l * l - m2);
     } else {
         ir = dr; ig = dg; ib = db; m1 = l; m2 = l * l;
+        if (COVER) cov = agree;
     }
     v0 = fmaxf(0.0f, m2 - m1 * m1);   // (N < 4: replaced by the spatial estimate of the next launch)
     // TRACK: Vc of the header from four frames on (without history N = 1); below, the next launch writes the spatial estimate here and into Hm.z
     if (TRACK && N >= 4.0f) v0 = ((1.0f - ac) * (1.0f - ac)) * vh + (ac * ac) * v0;
     p.oc[pix] = make_float4(ir, ig, ib, N);
-    p.om[pix] = make_float4(m1, m2, TRACK ? v0 : 0.0f, 0.0f);
+    p.om[pix] = make_float4(m1, m2, TRACK ? v0 : 0.0f, COVER ? cov : 0.0f);
+    if (COVER && cov < p.cov_min) {   // mixed: the remodulated colour (dn_remodulate's products), and a miss from here on
+        if (p.demod) {
+            const float4 a = p.g1[pix];
+            ir = ir * fmaxf(a.x, 1e-3f); ig = ig * fmaxf(a.y, 1e-3f); ib = ib * fmaxf(a.z, 1e-3f);
+        }
+        p.fmark[pix].w = -1.0f;
+    }
     p.iv[pix] = make_float4(ir, ig, ib, v0);
 }
 
@@ -1184,8 +1305,15 @@ int temporal_denoise(trg_ctx *c, DenoiseState &s, const float4 *color, const flo
     for (int k = 0; k < 16; ++k) r.vp[k] = vp[k];
     r.alpha = q.alpha; r.alpha_moments = q.alpha_moments; r.plane_tol = q.plane_tol; r.normal_tol = q.normal_tol; r.max_history = (float)q.max_history;
     if (motion) { r.m0 = motion; r.m1 = motion + n; }
-    const auto reproject = s.track ? (motion ? DN_FOR_SETTING(c, dn_temporal_reproject_kernel, true, true) : DN_FOR_SETTING(c, dn_temporal_reproject_kernel, false, true))
-                                   : (motion ? DN_FOR_SETTING(c, dn_temporal_reproject_kernel, true, false) : DN_FOR_SETTING(c, dn_temporal_reproject_kernel, false, false));
+    const bool cover = s.cov_min >= 0.0f;
+    if (cover) { r.fmark = s.fguide; r.cov_min = s.cov_min; }
+    // the kernel's form, [MOTION][TRACK][COVER]
+#define DN_REPROJECT(M, T, C) DN_FOR_SETTING(c, dn_temporal_reproject_kernel, M, T, C)
+    void (*const forms[2][2][2])(ReprojectParams) = {
+        { { DN_REPROJECT(false, false, false), DN_REPROJECT(false, false, true) }, { DN_REPROJECT(false, true, false), DN_REPROJECT(false, true, true) } },
+        { { DN_REPROJECT(true, false, false), DN_REPROJECT(true, false, true) }, { DN_REPROJECT(true, true, false), DN_REPROJECT(true, true, true) } } };
+#undef DN_REPROJECT
+    const auto reproject = forms[motion ? 1 : 0][s.track ? 1 : 0][cover ? 1 : 0];
     if (int rc = launch_tiles(c, who, reproject, r)) return rc;
     s.hist_cur ^= 1;          // (enqueued: from here on the new planes are the history, also if a later launch fails)
     s.hist_valid = true;
@@ -1226,7 +1354,12 @@ int render_temporal(trg_ctx *c, DenoiseState &s, uint32_t b, uint32_t n, uint32_
     if (int rc = render_zeroed(c, s.timg, 1, b, n, bounces)) return rc;
     const float f = (float)((double)((uint64_t)b + n) / (double)n);
     if (int rc = launch_each(c, who, dn_scale_kernel, npix, s.timg, f, npix)) return rc;
-    if (int rc = guides_render(c, s, b, s.guides, s.tpos, armed ? s.tmotion : nullptr)) return rc;
+    // with the coverage history on the guides come from the pixel centres, under the step's own two tolerances
+    trg_temporal_params q;
+    trg_temporal_default_params(&q);
+    if (p) q = *p;
+    const CentreTol tol{ q.plane_tol, q.normal_tol };
+    if (int rc = guides_render(c, s, b, s.guides, s.tpos, armed ? s.tmotion : nullptr, s.cov_min >= 0.0f ? &tol : nullptr)) return rc;
     const float zero[16] = {};
     const int rc = temporal_denoise(c, s, s.timg, s.guides, s.tpos, s.have_prev_vp ? s.prev_vp : zero, s.have_prev_vp, out, nullptr, nullptr, p, who,
                                     armed ? s.tmotion : nullptr);
@@ -1318,28 +1451,31 @@ int run_read(trg_ctx *c, const char *who, float *host, const char *what, size_t 
     return t.finish();
 }
 // trg_guides_render_pos and, moving, trg_guides_render_motion
-int guides_pos_device(trg_ctx *c, const char *who, uint32_t frameIndex, void *guides, void *pos, bool moving, void *motion) {
+bool valid_centre(const CentreTol *t) { return !t || (t->plane_tol > 0.0f && t->normal_tol >= -1.0f && t->normal_tol <= 1.0f); }
+int guides_pos_device(trg_ctx *c, const char *who, uint32_t frameIndex, void *guides, void *pos, bool moving, void *motion, const CentreTol *centre = nullptr) {
     DenoiseState *s;
     if (int rc = enter(c, s, who)) return rc;
+    if (!valid_centre(centre)) return fail(c, TRG_ERR_INVALID, "%s: plane_tol must be positive and normal_tol in [-1, 1]", who);
     if (!guides || !pos || (moving && !motion)) return fail(c, TRG_ERR_INVALID, "%s: NULL buffer", who);
     const size_t bytes = (size_t)c->w * c->h * sizeof(float4);
     if (!disjoint({ { guides, 2 * bytes }, { pos, bytes }, { motion, 2 * bytes } }))
         return fail(c, TRG_ERR_INVALID, moving ? "%s: the buffers overlap" : "%s: pos_device overlaps guides_device", who);
     if (moving && !have_previous_scene(c, *s))
         return fail(c, TRG_ERR_INVALID, "%s: no previous scene of the loaded scene's triangle count (trg_temporal_set_previous_scene)", who);
-    return guides_render(c, *s, frameIndex, static_cast<float4 *>(guides), static_cast<float4 *>(pos), static_cast<float4 *>(motion));
+    return guides_render(c, *s, frameIndex, static_cast<float4 *>(guides), static_cast<float4 *>(pos), static_cast<float4 *>(motion), centre);
 }
 // trg_guides_pos_read and, moving, trg_guides_motion_read
-int guides_pos_host(trg_ctx *c, const char *who, uint32_t frameIndex, float *guides, float *pos, bool moving, float *motion) {
+int guides_pos_host(trg_ctx *c, const char *who, uint32_t frameIndex, float *guides, float *pos, bool moving, float *motion, const CentreTol *centre = nullptr) {
     DenoiseState *s;
     if (int rc = enter(c, s, who)) return rc;
+    if (!valid_centre(centre)) return fail(c, TRG_ERR_INVALID, "%s: plane_tol must be positive and normal_tol in [-1, 1]", who);
     if (!guides || !pos || (moving && !motion)) return fail(c, TRG_ERR_INVALID, "%s: NULL buffer", who);
     if (moving && !have_previous_scene(c, *s))
         return fail(c, TRG_ERR_INVALID, "%s: no previous scene of the loaded scene's triangle count (trg_temporal_set_previous_scene)", who);
     const size_t bytes = s->pixels * sizeof(float4);
     HostTrip t(c, who);
     float4 *g = t.result(guides, 2 * bytes), *x = t.result(pos, bytes), *m = t.result(motion, 2 * bytes);
-    if (t.rc == TRG_OK) t.rc = guides_render(c, *s, frameIndex, g, x, m);
+    if (t.rc == TRG_OK) t.rc = guides_render(c, *s, frameIndex, g, x, m, centre);
     return t.finish();
 }
 // trg_temporal_denoise and, moving, trg_temporal_denoise_motion
@@ -1660,6 +1796,52 @@ int trg_temporal_variance_of_mean(trg_ctx *c, int *on) {
     std::lock_guard<std::mutex> lock(g_mutex);
     auto it = g_states.find(c);
     *on = it != g_states.end() && it->second.track ? 1 : 0;
+    return TRG_OK;
+}
+
+int trg_guides_render_centre(trg_ctx *c, uint32_t frameIndex, float plane_tol, float normal_tol, void *guides_device, void *pos_device) {
+    const CentreTol tol{ plane_tol, normal_tol };
+    return guides_pos_device(c, "trg_guides_render_centre", frameIndex, guides_device, pos_device, false, nullptr, &tol);
+}
+
+int trg_guides_render_centre_motion(trg_ctx *c, uint32_t frameIndex, float plane_tol, float normal_tol, void *guides_device, void *pos_device, void *motion_device) {
+    const CentreTol tol{ plane_tol, normal_tol };
+    return guides_pos_device(c, "trg_guides_render_centre_motion", frameIndex, guides_device, pos_device, true, motion_device, &tol);
+}
+
+int trg_guides_centre_read(trg_ctx *c, uint32_t frameIndex, float plane_tol, float normal_tol, float *guides_host, float *pos_host) {
+    const CentreTol tol{ plane_tol, normal_tol };
+    return guides_pos_host(c, "trg_guides_centre_read", frameIndex, guides_host, pos_host, false, nullptr, &tol);
+}
+
+int trg_guides_centre_motion_read(trg_ctx *c, uint32_t frameIndex, float plane_tol, float normal_tol, float *guides_host, float *pos_host, float *motion_host) {
+    const CentreTol tol{ plane_tol, normal_tol };
+    return guides_pos_host(c, "trg_guides_centre_motion_read", frameIndex, guides_host, pos_host, true, motion_host, &tol);
+}
+
+int trg_temporal_set_coverage(trg_ctx *c, float cov_min) {
+    if (!c) return TRG_ERR_INVALID;
+    if (!ctx_ok(c)) return fail(c, TRG_ERR_INVALID, "trg_temporal_set_coverage: the denoiser's view of the context does not match the library's");
+    if (!(cov_min < 1.0f)) return fail(c, TRG_ERR_INVALID, "trg_temporal_set_coverage: cov_min must be below 1 (negative: off)");   // (NaN too)
+    // allocates nothing, like the gate above
+    std::lock_guard<std::mutex> lock(g_mutex);
+    DenoiseState &s = g_states[c];
+    if (!s.pixels) s.device = c->device;
+    if (s.cov_min == cov_min || (s.cov_min < 0.0f && cov_min < 0.0f)) return TRG_OK;
+    s.cov_min = cov_min;
+    // a change is a reset: a history written with the setting off has no coverage in it and comes from other guides
+    s.hist_valid = false;
+    s.have_prev_vp = false;
+    s.armed = false;
+    return TRG_OK;
+}
+
+int trg_temporal_coverage(trg_ctx *c, float *cov_min) {
+    if (!c) return TRG_ERR_INVALID;
+    if (!cov_min) return fail(c, TRG_ERR_INVALID, "trg_temporal_coverage: cov_min is NULL");
+    std::lock_guard<std::mutex> lock(g_mutex);
+    auto it = g_states.find(c);
+    *cov_min = it == g_states.end() ? -1.0f : it->second.cov_min;
     return TRG_OK;
 }
 

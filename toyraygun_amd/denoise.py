@@ -23,9 +23,13 @@
     temporal_set_variance_of_mean(ctx, True)     # a long history: the variance of the ACCUMULATED colour travels in Hm.z and steers the
                                                  # iterations, so the filter narrows as the history grows (a change forgets the history)
 
+    temporal_set_coverage(ctx, 0.9)              # pixel footprints: render_temporal takes its guides from the pixel CENTRES (guides_centre:
+                                                 # X.w = 1 where the frame's jittered ray agrees with the centre hit), the agreement is accumulated
+                                                 # in Hm.w, and a pixel below 0.9 stays out of the filter (a change forgets the history)
+
 numpy arrays go through temporary device copies and the call waits for the result; torch ROCm tensors (float32, contiguous) are used in place
 through data_ptr() -- like trg_bind_accum -- and the call only enqueues on the context's current stream.  `reference_denoise`,
-`reference_denoise_variance` (its iteration loop alone: `reference_atrous_variance`) and `reference_temporal` are the float64 numpy evaluations
+`reference_denoise_variance` (its iteration loop alone: `reference_atrous_variance`) and `reference_temporal` (with `reference_centre_rays` and `reference_agreement` for the centre guides) are the float64 numpy evaluations
 of the definitions in the header: what the GPU tests compare the kernels with.
 
 The context's denoise scratch lives until release(ctx); call it before ctx.close() (trg_destroy does not know about it).
@@ -103,8 +107,15 @@ _SYMBOLS = [
     ("trg_temporal_lag_correct_host", C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_int32, _P]),
     ("trg_temporal_set_variance_of_mean", C.c_int, [_P, C.c_int]),
     ("trg_temporal_variance_of_mean", C.c_int, [_P, C.POINTER(C.c_int)]),
+    ("trg_guides_render_centre", C.c_int, [_P, _U, C.c_float, C.c_float, _P, _P]),
+    ("trg_guides_render_centre_motion", C.c_int, [_P, _U, C.c_float, C.c_float, _P, _P, _P]),
+    ("trg_guides_centre_read", C.c_int, [_P, _U, C.c_float, C.c_float, _P, _P]),
+    ("trg_guides_centre_motion_read", C.c_int, [_P, _U, C.c_float, C.c_float, _P, _P, _P]),
+    ("trg_temporal_set_coverage", C.c_int, [_P, C.c_float]),
+    ("trg_temporal_coverage", C.c_int, [_P, _F16]),
 ]
 LAG_GATE_DEFAULT = 3.0   # TRG_TEMPORAL_LAG_GATE_DEFAULT
+COVERAGE_MIN_DEFAULT = 0.9   # TRG_TEMPORAL_COVERAGE_MIN_DEFAULT
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 
 _bound = None
@@ -382,6 +393,34 @@ def temporal_variance_of_mean(ctx):
     on = C.c_int(-1)
     _chk(ctx, load().trg_temporal_variance_of_mean(ctx.h_ctx, C.byref(on)))
     return bool(on.value)
+
+
+def guides_centre(ctx, frame_index, plane_tol=_TEMPORAL_DEFAULTS["plane_tol"], normal_tol=_TEMPORAL_DEFAULTS["normal_tol"], out=None, pos=None,
+                  motion=None, with_motion=False):
+    """trg_guides_render_centre -> (guides [2, h, w, 4], X [h, w, 4]) from the rays through the pixel CENTRES; X.w = A, 1 where the jittered
+    primary ray of frame_index agrees with the centre hit under the two tolerances, else 0.  with_motion (or a `motion` tensor):
+    trg_guides_render_centre_motion, which also gives M0, M1 [2, h, w, 4] from the centre hits.  out, pos, motion = float32 ROCm tensors: filled
+    in place on the context's stream (and returned); None: numpy arrays."""
+    xs, gs = _shapes(ctx)
+    head = (frame_index, float(plane_tol), float(normal_tol))
+    if motion is not None or with_motion:
+        return _run(ctx, "trg_guides_render_centre_motion", "trg_guides_centre_motion_read", [("guides", out, gs), ("pos", pos, xs), ("motion", motion, gs)], head=head)
+    return _run(ctx, "trg_guides_render_centre", "trg_guides_centre_read", [("guides", out, gs), ("pos", pos, xs)], head=head)
+
+
+def temporal_set_coverage(ctx, cov_min=COVERAGE_MIN_DEFAULT):
+    """trg_temporal_set_coverage: 0 <= cov_min < 1 switches the coverage history on for every later temporal step of this context -- render_temporal
+    then takes its guides from the pixel centres, and a pixel whose accumulated agreement is below cov_min is kept out of the filter and shows its
+    accumulated colour --, cov_min < 0 (or None) off, the state of a new context.  NaN and cov_min >= 1 are refused.  A call that changes the
+    value forgets the history like temporal_reset."""
+    _chk(ctx, load().trg_temporal_set_coverage(ctx.h_ctx, -1.0 if cov_min is None else float(cov_min)))
+
+
+def temporal_coverage(ctx):
+    """trg_temporal_coverage: the cov_min that is set; < 0 when the setting is off."""
+    v = C.c_float(0.0)
+    _chk(ctx, load().trg_temporal_coverage(ctx.h_ctx, C.byref(v)))
+    return float(v.value)
 
 
 def release(ctx):
@@ -720,8 +759,81 @@ def reference_lag(color, g0, g1, hc, gate, params=None, material_ids=None, dtype
     return _lag(D, np.asarray(hc)[..., :3].astype(dtype), F, miss, gate, sn, sd, dtype)
 
 
+def reference_centre_rays(uniforms, w, h):
+    """The centre rays of trg_guides_render_centre, fp32-exact by construction: trg_raygen's arithmetic with 0.5 in place of both Halton values,
+    every operation below one float32 operation in the header's order.  uniforms: a capi.Uniforms, any ctypes structure of that layout, or its
+    176 bytes (width, height and frameIndex are not read: w, h say the size).  Returns w * h records of capi.RAY_DTYPE, row 0 first."""
+    f = np.float32
+    raw = bytes(uniforms) if isinstance(uniforms, (bytes, bytearray)) else bytes(memoryview(uniforms))
+    cam = np.frombuffer(raw, np.float32, 3, 16)
+    m = np.frombuffer(raw, np.float32, 16, 32)
+    x, y = np.meshgrid(np.arange(w, dtype=f), np.arange(h, dtype=f))
+    uvx = ((x + f(0.5)) / f(w)) * f(2.0) - f(1.0)
+    uvy = ((y + f(0.5)) / f(h)) * f(2.0) - f(1.0)
+    zero, one = np.zeros_like(uvx), np.ones_like(uvx)
+    world = [((uvx * m[j * 4] + uvy * m[j * 4 + 1]) + zero * m[j * 4 + 2]) + one * m[j * 4 + 3] for j in range(4)]
+    t = [world[k] / world[3] - cam[k] for k in range(3)]
+    inv = f(1.0) / np.sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2])
+    rays = np.zeros(w * h, capi.RAY_DTYPE)
+    rays["origin"] = cam
+    rays["mask"] = 3
+    rays["direction"] = np.stack([(t[k] * inv).astype(f) for k in range(3)], -1).reshape(-1, 3)
+    rays["maxDistance"] = np.inf
+    rays["color"] = (1.0, 1.0, 1.0, 0.0)
+    return rays
+
+
+def reference_agreement(isect_centre, g0, pos, isect_jitter, rays_jitter, normals, material_ids, plane_tol=_TEMPORAL_DEFAULTS["plane_tol"],
+                        normal_tol=_TEMPORAL_DEFAULTS["normal_tol"]):
+    """The agreement flag A of trg_guides_render_centre.  isect_centre, isect_jitter: the hit records (capi.ISECT_DTYPE, h * w each) of the centre
+    rays and of the frame's jittered primary rays; rays_jitter: those jittered rays (capi.RAY_DTYPE); g0, pos [h, w, 4]: the centre guides' G0
+    and X (float32 as the device sees them); normals [3 * n_tris, 3], material_ids [n_tris]: the loaded scene's.  The jittered hit's n_j and
+    X_j = o + z d are formed in fp32 as the gather forms them; the two tests are then evaluated in float64.
+    Returns (A [h, w] float32 of 0 / 1, near [h, w] bool): near marks the pixels where the plane distance lies within NEAR of plane_tol z_c
+    (relative) or the cosine within NEAR of normal_tol (absolute), the rule of reference_temporal's tap tests."""
+    f = np.float32
+    g0 = np.asarray(g0, np.float32)
+    h, w = g0.shape[:2]
+    mats = np.asarray(material_ids).reshape(-1)
+    nrm = np.asarray(normals, np.float32).reshape(-1, 3, 3)
+
+    def fields(isect):
+        dist = np.asarray(isect["distance"], np.float32).reshape(h, w)
+        prim = np.asarray(isect["primitiveIndex"], np.int64).reshape(h, w)
+        hit = (dist >= 0) & (prim >= 0) & (prim < mats.shape[0])
+        return dist, np.where(hit, prim, 0), hit, np.asarray(isect["coordinates"], np.float32).reshape(h, w, 2)
+    _, pc, hit_c, _ = fields(isect_centre)
+    zj, pj, hit_j, co = fields(isect_jitter)
+    c0, c1 = co[..., 0:1], co[..., 1:2]
+    c2 = (f(1.0) - c0) - c1
+    a = nrm[pj]
+    nj = ((c0 * a[..., 0, :] + c1 * a[..., 1, :]) + c2 * a[..., 2, :]).astype(np.float32)
+    o = np.asarray(rays_jitter["origin"], np.float32).reshape(h, w, 3)
+    d = np.asarray(rays_jitter["direction"], np.float32).reshape(h, w, 3)
+    Xj = (o + (zj[..., None] * d).astype(np.float32)).astype(np.float32)
+
+    def unit(v):
+        v = v.astype(np.float64)
+        ln = np.sqrt((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2])
+        ok = ln > 0
+        return v / np.where(ok, ln, 1.0)[..., None], ok
+
+    def dot3(p, q):
+        return (p[..., 0] * q[..., 0] + p[..., 1] * q[..., 1]) + p[..., 2] * q[..., 2]
+    n, n_ok = unit(g0[..., :3])
+    nq, nq_ok = unit(nj)
+    both = hit_c & hit_j & ((mats[pc] == 2) == (mats[pj] == 2))
+    tol = float(f(plane_tol)) * g0[..., 3].astype(np.float64)
+    dist = np.abs(dot3(n, Xj.astype(np.float64) - np.asarray(pos, np.float32)[..., :3].astype(np.float64)))
+    cosn = dot3(n, nq)
+    with np.errstate(invalid="ignore"):
+        agree = both & n_ok & nq_ok & (dist <= tol) & (cosn >= float(f(normal_tol)))
+        near = both & n_ok & nq_ok & ((np.abs(dist - tol) <= NEAR * tol) | (np.abs(cosn - float(f(normal_tol))) <= NEAR))
+    return agree.astype(np.float32), near
+
+
 def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, material_ids=None, dtype=np.float64, near_parts=False, motion=None, lag=None,
-                       track=False, **kw):
+                       track=False, coverage=None, **kw):
     """float64 evaluation of ONE step of trg_temporal_denoise's definition up to the filter: reprojection, accumulation, V_0.
     color, g0, g1, pos [h, w, 4] (float32 as the device sees them); history: the previous call's four planes (Hc, Hm, F, X), each [h, w, 4], or
     None; prev_vp: 16 floats; params: a TemporalParams, a dict or keywords over the header's defaults (no library needed); material_ids: those
@@ -739,7 +851,12 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
     and V_0 are the uncorrected step's, and `near` gains nothing (the correction's one decision, G > 0, is the spatial estimate's).
     track: the variance of the mean (trg_temporal_set_variance_of_mean): history[1][..., 2] is read as Vc', the new Hm.z and iv[..., 3] are Vc of
     the header's definition -- S for N < 4 or without history, else ((1 - a)(1 - a)) Vh + (a a) S --; everything else, `near` included, is the
-    plain step's exactly.  False: Hm.z is 0 and every array is what it was before the argument existed."""
+    plain step's exactly.  False: Hm.z is 0 and every array is what it was before the argument existed.
+    coverage: None, or cov_min of the coverage history (trg_temporal_set_coverage): pos[..., 3] is read as the agreement flag A and history[1][..., 3]
+    as cov'; the new Hm.w is cov; a hit with cov < cov_min is MIXED: a miss for the spatial estimate, the lag correction and (through the marked G0)
+    the iterations, its iv.rgb remodulated, its V_0 the temporal form whatever N; `near` also marks cov within NEAR (absolute) of a cov_min > 0.
+    Two more results then: (new history, iv, near, mixed [h, w] bool, the filter's G0 [h, w, 4] with emitters AND mixed pixels marked) -- hand
+    that G0 to reference_atrous_variance with material_ids=None.  None: the result is what it was before the argument existed."""
     dtype = _dtype(dtype)
     q = _options(_TEMPORAL_DEFAULTS, TemporalParams, params, kw)
     alpha, alpha_m, plane_tol, normal_tol = (dtype(np.float32(q[k])) for k in ("alpha", "alpha_moments", "plane_tol", "normal_tol"))
@@ -765,6 +882,7 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
     W = np.zeros((h, w), dtype)
     acc = np.zeros((h, w, 6), dtype)                       # I.rgb, N, m1, m2
     vh = np.zeros((h, w), dtype)                           # track: the sum of b * Hm'.z
+    covh = np.zeros((h, w), dtype)                         # coverage: the sum of b * Hm'.w
     if history is not None:
         Hc, Hm, Hf, Hx = (np.asarray(p, np.float32).astype(dtype) for p in history)
         vp = np.asarray(prev_vp, np.float32).reshape(16).astype(dtype)
@@ -813,6 +931,8 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
                 acc[..., 5] += b * hm[..., 1]
                 if track:
                     vh += b * hm[..., 2]
+                if coverage is not None:
+                    covh += b * hm[..., 3]
                 W += b
         # W > 0: a sum of weights near 0 with a valid tap in it; or none in it while the sample sits within NEAR of a pixel centre's row or
         # column, where one rounding brings another tap pair into play with a weight near 0
@@ -833,13 +953,27 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
     N = np.where(miss, 0.0, N).astype(dtype)
     m1, m2 = np.where(miss, 0.0, m1).astype(dtype), np.where(miss, 0.0, m2).astype(dtype)
     near_n = ~miss & (np.abs(N - 4) <= NEAR * 4)
+    mixed = np.zeros((h, w), bool)
+    hit = ~miss                                             # (below, `miss` gains the mixed pixels: what counts as a miss behind the reprojection)
+    if coverage is not None:
+        cov_min = dtype(np.float32(coverage))
+        A = np.asarray(pos, np.float32)[..., 3].astype(dtype)
+        ch = covh / np.where(have, W, 1.0)
+        cov = np.where(miss, 0.0, np.where(have, ch + am * (A - ch), A)).astype(dtype)
+        mixed = hit & (cov < cov_min)
+        if cov_min > 0:
+            near |= hit & (np.abs(cov - cov_min) <= NEAR)
+        F_own = F
+        F = F.copy()
+        F[mixed, 3] = -1.0
+        miss = miss | mixed
     # V_0: temporal from four frames on, else the spatial estimate over this call's moments with the prefilter's weights
     G = geometry_weights(F, 1, sn, sd, kernel=(1.0,) * 7, dtype=dtype)
     gs = G.sum((0, 1))
     with np.errstate(invalid="ignore", divide="ignore"):
         M1, M2 = _gather(G, m1, 1) / gs, _gather(G, m2, 1) / gs
         spatial = np.where(gs > 0, np.maximum(0.0, M2 - M1 * M1) * dtype(4.0) / np.where(miss, 1.0, N), 0.0)
-    V0 = np.where(miss, 0.0, np.where(N >= 4, np.maximum(0.0, m2 - m1 * m1), spatial)).astype(dtype)
+    V0 = np.where(~hit, 0.0, np.where((N >= 4) | mixed, np.maximum(0.0, m2 - m1 * m1), spatial)).astype(dtype)
     if lag is not None:
         I = _lag(D.astype(dtype), I.astype(dtype), F, miss, lag, sn, sd, dtype)[0]
     new = np.zeros((4, h, w, 4), dtype)
@@ -848,12 +982,18 @@ def reference_temporal(color, g0, g1, pos, history, prev_vp, params=None, materi
         ac = a[..., 0]
         Vh = vh / np.where(have, W, 1.0)
         Vc = ((one - ac) * (one - ac)) * Vh + (ac * ac) * V0
-        V0 = np.where(miss, 0.0, np.where(have & (N >= 4), Vc, V0)).astype(dtype)
+        V0 = np.where(~hit, 0.0, np.where(have & (N >= 4), Vc, V0)).astype(dtype)
         new[1, ..., 2] = V0
     new[0, ..., :3], new[0, ..., 3] = I, N
     new[1, ..., 0], new[1, ..., 1] = m1, m2
     new[2] = F
     new[3, ..., :3] = X
     new[3, ..., 3] = np.asarray(pos, np.float32)[..., 3].astype(dtype)
-    iv = np.concatenate([I, V0[..., None]], -1).astype(dtype)
-    return new, iv, ((near, near_n) if near_parts else near | near_n)
+    if coverage is None:
+        iv = np.concatenate([I, V0[..., None]], -1).astype(dtype)
+        return new, iv, ((near, near_n) if near_parts else near | near_n)
+    new[1, ..., 3] = cov
+    new[2] = F_own                                          # the history keeps the unmarked guide
+    Iv = np.where(mixed[..., None], I * alb, I) if demod else I
+    iv = np.concatenate([Iv, V0[..., None]], -1).astype(dtype)
+    return new, iv, ((near, near_n) if near_parts else near | near_n), mixed, F
