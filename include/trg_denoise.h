@@ -139,6 +139,10 @@ TRG_API void trg_denoise_var_default_params(trg_denoise_var_params *p);
  *                GV_i(p) = sum_r b(r) V_i(r) / sum_r b(r) over the pixels r of the 3 x 3 window around p (spacing 1) that lie inside the image and
  *                are not misses, b = (1/4, 1/2, 1/4) along each axis
  *          I_{i+1}(p) = sum_q w I_i(q) / sum_q w          V_{i+1}(p) = sum_q w^2 V_i(q) / (sum_q w)^2      (sum of w not > 0: both copy)
+ *      Every w of pixel p is taken times 2^-k, k = floor(log2 (n_p . n_p)^sigma_normal) kept within [-126, 126] (0 for a zero normal) -- formed as
+ *      (h(dx) h(dy) w_n w_z * 2^-k) * w_l.  A power of two scales every sum exactly and cancels in both quotients, so the results are those of the
+ *      unscaled w bit for bit wherever fp32 holds the unscaled sums; it is there because V squares a weight that w_n lets grow to 1e20 for
+ *      normals of length 1.2 and shrink to 1e-25 for normals of length 0.8: unscaled, w^2 leaves fp32 and V_1 is not a number.
  *   End.   out(p).rgb = I_N(p) * max(a_p, 1e-3) when `demodulate` and p is not a miss, else I_N(p);  out(p).a = H1(p).a.
  *          iterations == 0: out.rgb = 0.5 * (H1 + H2), one fp32 add and one multiply per channel.
  *

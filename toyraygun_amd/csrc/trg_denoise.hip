@@ -653,6 +653,16 @@ __global__ __launch_bounds__(256) void dn_atrous_kernel(const AtrousParams p) {
     // the denominator of the colour term: w_c's sigma_color^2 (var + 1e-4), w_l's sigma_lum sqrt(max(0, GV)) + 1e-3
     const float cden = VAR ? p.sigma_color * dn_sqrt<STRICT>(fmaxf(0.0f, var)) + 1e-3f : p.sigma_color * p.sigma_color * (var + 1e-4f);
     const float lp = VAR ? dn_lum(cp) : 0.0f;
+    // VAR squares a weight that w_n lets grow to 1e20 for normals longer than 1 (and shrink to 1e-25 for shorter ones): every weight times 2^-k,
+    // k = the exponent of the centre's own w_n within [-126, 126], as the lag correction does -- exact, and it cancels in both quotients
+    float scale = 1.0f;
+    if (VAR) {
+        const float nn = gp.x * gp.x + gp.y * gp.y + gp.z * gp.z;
+        const float own = nn > 0.0f ? dn_pow<STRICT>(nn, p.sigma_normal) : 1.0f;
+        int k2 = (int)((__float_as_uint(own) >> 23) & 255u) - 127;
+        k2 = k2 < -126 ? -126 : (k2 > 126 ? 126 : k2);
+        scale = __uint_as_float((uint32_t)(127 - k2) << 23);
+    }
     const float hk[5] = { 1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f };
     float ar = 0.0f, ag = 0.0f, ab = 0.0f, av = 0.0f, wsum = 0.0f;
 #pragma unroll
@@ -674,7 +684,7 @@ __global__ __launch_bounds__(256) void dn_atrous_kernel(const AtrousParams p) {
                 const float dr = cp.x - cq.x, dg = cp.y - cq.y, db = cp.z - cq.z;
                 wc = dn_exp<STRICT>(-((dr * dr + dg * dg + db * db) / cden));
             }
-            const float wgt = wg * wc;
+            const float wgt = VAR ? (wg * scale) * wc : wg * wc;
             ar += wgt * cq.x; ag += wgt * cq.y; ab += wgt * cq.z;
             if (VAR) av += wgt * wgt * cq.w;
             wsum += wgt;
