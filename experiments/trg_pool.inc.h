@@ -254,16 +254,7 @@ __global__ __launch_bounds__(trg::kBlock) void render_pool_kernel(const trg::Ren
 #pragma unroll
         for (int j = 0; j < S; ++j) {
             const uint32_t f = f0 + j;
-            if (f < frame_end) {
-                if (f == 0) {
-                    acc = rad[j];
-                } else {
-                    const V3 prev = acc * (float)f;
-                    const V3 c = rad[j] + prev;
-                    const float f1 = (float)(f + 1u);
-                    acc = mk(c.x / f1, c.y / f1, c.z / f1);
-                }
-            }
+            if (f < frame_end) acc = running_average(acc, rad[j], f);
         }
     }
     if (valid) {

@@ -308,15 +308,7 @@ __global__ __launch_bounds__(256) void wf_accumulate_kernel(const trg::WfParams 
         const v4f rv4 = wf_ld(&w.rad[pid]), shv = wf_ld(&w.sh[pid]);
         V3 rad = mk(rv4.x, rv4.y, rv4.z);
         if (shv.w >= 0.0f) { const v4f c4 = wf_ld(&w.scol[pid]); rad = rad + mk(c4.x, c4.y, c4.z); }   // the path's last shadow ray found nothing
-        const uint32_t f = p.frame0 + fl;
-        if (f == 0) {
-            acc = rad;
-        } else {
-            const V3 prev = acc * (float)f;
-            const V3 c = rad + prev;
-            const float f1 = (float)(f + 1u);
-            acc = mk(c.x / f1, c.y / f1, c.z / f1);
-        }
+        acc = running_average(acc, rad, p.frame0 + fl);
     }
     v4f outv; outv.x = acc.x; outv.y = acc.y; outv.z = acc.z; outv.w = 1.0f;
     accum[pix] = outv;

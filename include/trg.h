@@ -365,6 +365,15 @@ TRG_API int trg_debug_leaf_records(const float *positions3, const float *normals
 TRG_API int trg_debug_plane_records(const float *positions3, const uint32_t *indices, const uint32_t *material_ids, uint32_t n_verts, uint32_t n_tris,
                                     float *planes12_out, uint16_t *meta_out, uint32_t records_cap, uint32_t *n_records, float *center3_out);
 
+/* host-only: the FLAT-ATTRIBUTE records of a scene, exactly as trg_load_scene computes them.  A triangle is flat when its three normals
+ * (normals3: 9 floats per triangle) are bitwise equal, finite and non-zero, its three colours (colors3: 9 floats per triangle) are bitwise equal,
+ * and cross(N, (0.0072, 1, 0.0034)) of the unit normal N has norm >= 1e-3; a scene is flat when every triangle is (and n_tris > 0), and
+ * TRG_FLAT_SHADING=0 in the environment makes every scene non-flat.  *flat_out = 1 or 0.  records12_out (may be NULL; n_tris x 12 floats, written
+ * only for a flat scene) = per ORIGINAL triangle index (N.xyz, r) (right.xyz, g) (forward.xyz, b), right = normalize(cross(N, helper)),
+ * forward = cross(right, N), computed in double.  The shipped build's shading event on an LDS-resident flat scene without textures reads these
+ * instead of interpolating attributes and building the frame per hit. */
+TRG_API int trg_debug_flat_attributes(const float *normals3, const float *colors3, uint32_t n_tris, int *flat_out, float *records12_out);
+
 /* host-only: the tile (bx, by) workgroup slot `slot` of a launch over tiles_x x tiles_y tiles renders under tile order `order` (0, 1, 2, 4, 8:
  * TRG_OPT_TILE_ORDER), exactly as the kernels compute it.  Returns 1, 0 for a padding slot of an XCD-aware order (or a slot beyond the
  * launch), negative on bad arguments; *n_slots = workgroup slots of the launch.  The slots with return 1 cover every tile exactly once. */

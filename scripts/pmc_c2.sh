@@ -12,7 +12,7 @@ import csv, glob, sys, collections
 agg = collections.defaultdict(list)
 for f in glob.glob(sys.argv[1] + "/*/*/*_counter_collection.csv"):
     for r in csv.DictReader(open(f)):
-        if "render_kernel<true, false>" in r["Kernel_Name"]:
+        if "render_kernel<true, false," in r["Kernel_Name"]:   # (LDS scene, no counters; the third argument: flat-attribute shading or the generic event)
             agg[r["Counter_Name"]].append(float(r["Counter_Value"]))
 m = {k: sorted(v)[len(v) // 2] for k, v in agg.items()}
 for k in sorted(m): print("%-26s %.5g" % (k, m[k]))

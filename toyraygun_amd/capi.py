@@ -131,6 +131,7 @@ _SYMBOLS = [
     ("trg_debug_tile_of_slot", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("trg_debug_build_bvh4q", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("trg_debug_boxes", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("trg_debug_flat_attributes", C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_int), _P]),
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 
@@ -557,6 +558,22 @@ def debug_boxes(positions, indices, material_ids):
         if rc != OK:
             raise TrgError(rc, "trg_debug_boxes")
     return out
+
+
+def debug_flat_attributes(normals, colors):
+    """Host-only: (flat, records[n_tris, 12] float32 or None) of a scene's per-corner normals and colours, [n_tris * 3, 3] each
+    (include/trg.h trg_debug_flat_attributes)."""
+    L = load()
+    nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 9)
+    col = np.ascontiguousarray(colors, np.float32).reshape(-1, 9)
+    if nrm.shape[0] != col.shape[0]:
+        raise ValueError("normals and colours of different triangle counts")
+    flat = C.c_int(0)
+    out = np.zeros((nrm.shape[0], 12), np.float32)
+    rc = L.trg_debug_flat_attributes(_ptr(nrm), _ptr(col), nrm.shape[0], C.byref(flat), _ptr(out))
+    if rc != OK:
+        raise TrgError(rc, "trg_debug_flat_attributes")
+    return bool(flat.value), (out if flat.value else None)
 
 
 def debug_build_bvh4(positions, indices, material_ids):

@@ -182,6 +182,7 @@ uint32_t pair_quads(const float *pos, const uint32_t *idx, const uint32_t *masks
 }
 
 bool boxes_enabled() { const char *e = getenv("TRG_BVH_BOXES"); return !e || atoi(e) != 0; }
+bool flat_shading_enabled() { const char *e = getenv("TRG_FLAT_SHADING"); return !e || atoi(e) != 0; }
 
 namespace {
 // Are triangles k .. k + 11 six quads that bound a parallelepiped (addCube, Scene.cpp:24-58)?  Geometry in double from the fp32 corners:

@@ -94,5 +94,6 @@ uint32_t pair_quads(const float *positions3, const uint32_t *indices, const uint
 // MetalRenderer.mm:276).  Deterministic for a given input.
 void build_bvh(const float *positions3, const uint32_t *indices, const uint32_t *masks, uint32_t ntris, Bvh &out, bool want_wide8 = false, bool want_boxes = false);
 bool boxes_enabled();   // TRG_BVH_BOXES != 0 (default on), read at every call: the switch for A/B runs and tests
+bool flat_shading_enabled();   // TRG_FLAT_SHADING != 0 (default on), read at every scene load: the flat-attribute records of trg_capi.cpp flat_attr_records
 
 }  // namespace trg

@@ -125,8 +125,9 @@ static bool plan_scene_layout(uint64_t n_nodes, uint32_t node_bytes, uint64_t nt
     const uint64_t off_boxrec = off_fat_planes + n_fat * kFatRecBytes;                     // ... and, right behind them at the SAME stride, the box records: box b is "record n_fat + b"
     const uint64_t off_tris_alt = off_boxrec + n_boxrec * kFatRecBytes;                    // the plane records of an LDS-sized scene (16-byte aligned)
     const uint64_t off_flat = (off_tris_alt + nt_rec * 48ull + 63ull) & ~63ull;            // the flat primitive list of a tiny scene (sc.n_flat set by the caller)
-    total = off_flat + (uint64_t)sc.n_flat * kFlatPrimBytes + 128ull;
-    sc.off_flat = (uint32_t)off_flat;
+    const uint64_t off_flat_attrs = align16_64(off_flat + (uint64_t)sc.n_flat * kFlatPrimBytes);   // the flat-attribute records of an LDS-sized scene: 48 bytes per original triangle
+    total = off_flat_attrs + attr_tris * 48ull + 128ull;
+    sc.off_flat = (uint32_t)off_flat; sc.off_flat_attrs = (uint32_t)off_flat_attrs;
     if (total > kBlobLimit) return false;
     sc.off_nodes4_box = n_nodes4_box ? (uint32_t)off_nodes4_box : (uint32_t)off_nodes4; sc.off_boxrec = (uint32_t)off_boxrec; sc.n_boxrec = n_nodes4_box ? (uint32_t)n_boxrec : 0u;
     sc.off_meta = (uint32_t)off_meta; sc.off_tris_alt = (uint32_t)off_tris_alt;
@@ -136,6 +137,35 @@ static bool plan_scene_layout(uint64_t n_nodes, uint32_t node_bytes, uint64_t nt
     sc.off_fat = (uint32_t)off_fat; sc.n_fat = (uint32_t)n_fat; sc.off_fat_planes = (uint32_t)off_fat_planes;
     sc.lds_stage_bytes = with_htab ? (uint32_t)stage_end : 0u;
     sc.blob_bytes = (uint32_t)total;
+    return true;
+}
+
+// The flat-attribute records (trg_kernels.h SceneDesc::off_flat_attrs).  A triangle is FLAT when its three normals are bitwise equal, finite and
+// non-zero, its three colours are bitwise equal, and the frame of align_hemisphere (common.h:95-110) is well defined for its unit normal N:
+// |cross(N, (0.0072, 1, 0.0034))| >= 1e-3.  That is every triangle the reference's Scene API makes (addCube, addPlane, addAreaLight).  A scene is
+// flat when every triangle is; any doubt leaves it to the generic shading event.  Per ORIGINAL triangle index, in double:
+// (N.xyz, r) (right.xyz, g) (forward.xyz, b), right = normalize(cross(N, helper)), forward = cross(right, N) -- the reference's frame.
+// `out` (may be null): n_tris x 12 floats.  TRG_FLAT_SHADING=0: no scene is flat (bvh_build.cpp flat_shading_enabled).
+static bool flat_attr_records(const float *nrm, const float *col, uint32_t n_tris, float *out) {
+    if (!n_tris || !nrm || !col || !flat_shading_enabled()) return false;
+    const double helper[3] = { (double)0.0072f, (double)1.0f, (double)0.0034f };   // the float constants of the device code
+    for (uint32_t t = 0; t < n_tris; ++t) {
+        const float *n = nrm + (size_t)t * 9, *c = col + (size_t)t * 9;
+        if (memcmp(n, n + 3, 12) != 0 || memcmp(n, n + 6, 12) != 0 || memcmp(c, c + 3, 12) != 0 || memcmp(c, c + 6, 12) != 0) return false;
+        if (!std::isfinite(n[0]) || !std::isfinite(n[1]) || !std::isfinite(n[2])) return false;
+        const double len = std::sqrt((double)n[0] * n[0] + (double)n[1] * n[1] + (double)n[2] * n[2]);
+        if (!(len > 0.0) || !std::isfinite(len)) return false;
+        const double N[3] = { n[0] / len, n[1] / len, n[2] / len };
+        double R[3] = { N[1] * helper[2] - N[2] * helper[1], N[2] * helper[0] - N[0] * helper[2], N[0] * helper[1] - N[1] * helper[0] };
+        const double rl = std::sqrt(R[0] * R[0] + R[1] * R[1] + R[2] * R[2]);
+        if (!(rl >= 1e-3)) return false;
+        for (int a = 0; a < 3; ++a) R[a] /= rl;
+        const double F[3] = { R[1] * N[2] - R[2] * N[1], R[2] * N[0] - R[0] * N[2], R[0] * N[1] - R[1] * N[0] };
+        if (out) {
+            float *o = out + (size_t)t * 12;
+            for (int a = 0; a < 3; ++a) { o[a] = (float)N[a]; o[4 + a] = (float)R[a]; o[8 + a] = (float)F[a]; o[4 * a + 3] = c[a]; }
+        }
+    }
     return true;
 }
 
@@ -736,6 +766,8 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
                 memcpy(dst + 48, row3, 16);
             }
         }
+        // (the records are written as they are found: a scene that turns out not to be flat leaves a few behind that nothing reads)
+        sc.flat_attrs = flat_attr_records(nrm, col, n_tris, reinterpret_cast<float *>(&host[sc.off_flat_attrs])) ? 1u : 0u;
         if (n_tris) {
             memcpy(&host[sc.off_normals], nrm, (size_t)n_tris * 36);
             memcpy(&host[sc.off_colors], col, (size_t)n_tris * 36);
@@ -1348,6 +1380,14 @@ int trg_debug_build_bvh(const float *positions3, const uint32_t *indices, const 
         if (tris_cap < nrec) return TRG_ERR_RANGE;
         memcpy(tris_out, bvh.tris.data(), (size_t)nrec * 48);
     }
+    return TRG_OK;
+}
+
+int trg_debug_flat_attributes(const float *normals3, const float *colors3, uint32_t n_tris, int *flat_out, float *records12_out) {
+    if (!flat_out || (n_tris && (!normals3 || !colors3))) return TRG_ERR_INVALID;
+    const bool flat = flat_attr_records(normals3, colors3, n_tris, nullptr);   // (decided first: the caller's buffer is written for a flat scene only)
+    if (flat && records12_out) flat_attr_records(normals3, colors3, n_tris, records12_out);
+    *flat_out = flat ? 1 : 0;
     return TRG_OK;
 }
 

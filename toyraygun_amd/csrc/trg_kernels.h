@@ -68,6 +68,11 @@ struct SceneDesc {
     // frame, row 3 = (its first leaf record, material id, face table low, high: 7 bits per face f = 2 k + (l_k > 0), 0..3 in the low word, 4..5 in
     // the high one -- X-record offset 0..10 | swap << 4 | negate s << 5 | negate t << 6; bit 31 of the high word: a lone quad dressed as a box).  A scene without boxes: off_nodes4_box = off_nodes4, n_boxrec = 0.
     uint32_t off_nodes4_box, off_boxrec, n_boxrec;
+    // FLAT-SHADED scenes, LDS-resident, shipped build: flat_attrs != 0 = every triangle has ONE normal and ONE colour (trg_capi.cpp flat_attr_records), and
+    // the blob holds, outside the staged part, 48 bytes per ORIGINAL primitive index: (unit normal | r) (right | g) (forward | b), the shading event's
+    // tangent frame and colour.  A launch without textures stages them over the normal / colour arrays (the region that starts at off_normals: 48 <= 72
+    // bytes per triangle) and its shading event reads three float4 instead of interpolating 18 floats and building the frame (trg_kernels.hip shade_event).
+    uint32_t off_flat_attrs, flat_attrs;
     // the planes are stored relative to this point (the centre of the scene's bounding box) and a ray's origin is shifted by it when its
     // traversal begins: n . o - d0 then cancels numbers of the size of the scene instead of its distance from the coordinate origin
     float center[3];

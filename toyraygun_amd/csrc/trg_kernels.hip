@@ -37,22 +37,35 @@ using namespace trgdev;
 
 namespace TRG_KNS {
 
-// Stage the scene blob into LDS (16-byte copies by the whole workgroup) or point at it in HBM.
-template <bool LDS_SCENE>
+// 16-byte copies by the whole workgroup: bytes [b0, b1) of LDS from `src` (every section of the blob is 16-byte aligned)
+TRG_DEV void stage_copy(unsigned char *smem, uint32_t b0, uint32_t b1, const unsigned char *src) {
+    const uint4 *s = reinterpret_cast<const uint4 *>(src);
+    uint4 *d = reinterpret_cast<uint4 *>(smem + b0);
+    const uint32_t n16 = b1 > b0 ? (b1 - b0) >> 4 : 0u;
+    for (uint32_t i = threadIdx.x; i < n16; i += trg::kBlock) d[i] = s[i];
+}
+
+// Stage the scene blob into LDS or point at it in HBM.  FLAT (shipped build, a kernel whose shading event reads the flat-attribute records,
+// trg_kernels.h SceneDesc::off_flat_attrs): those records instead of the normal and colour arrays, at the same place.
+template <bool LDS_SCENE, bool FLAT = false>
 TRG_DEV SceneView scene_view(const trg::SceneDesc &sc, unsigned char *smem) {
     SceneView v;
     if (LDS_SCENE) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(sc.blob);
-        uint4 *dst = reinterpret_cast<uint4 *>(smem);
-        const uint32_t n16 = sc.lds_stage_bytes >> 4;
-        for (uint32_t i = threadIdx.x; i < n16; i += trg::kBlock) dst[i] = src[i];
-        __syncthreads();
-        if (kShipped) {   // the shipped build tests triangles in their PLANE form: those records over the Moeller-Trumbore ones
-            const uint4 *alt = reinterpret_cast<const uint4 *>(sc.blob + sc.off_tris_alt);
-            uint4 *tr = reinterpret_cast<uint4 *>(smem + sc.off_tris);
-            for (uint32_t i = threadIdx.x; i < sc.n_tris_rec * 3u; i += trg::kBlock) tr[i] = alt[i];
-            __syncthreads();
+        if (kShipped) {
+            // one pass, one barrier: every section goes to its slot from where the shipped build wants it read -- the triangle slots take the
+            // PLANE records (the Moeller-Trumbore ones of the staged part are the strict build's and are not copied at all)
+            stage_copy(smem, 0u, sc.off_tris, sc.blob);
+            stage_copy(smem, sc.off_tris, sc.off_tris + sc.n_tris_rec * 48u, sc.blob + sc.off_tris_alt);
+            if (FLAT) {
+                stage_copy(smem, sc.off_normals, sc.off_normals + sc.n_tris * 48u, sc.blob + sc.off_flat_attrs);   // (ends before off_mats: 48 <= 72 per triangle)
+                stage_copy(smem, sc.off_mats, sc.lds_stage_bytes, sc.blob + sc.off_mats);
+            } else {
+                stage_copy(smem, sc.off_normals, sc.lds_stage_bytes, sc.blob + sc.off_normals);
+            }
+        } else {
+            stage_copy(smem, 0u, sc.lds_stage_bytes, sc.blob);
         }
+        __syncthreads();
         v.nodes = reinterpret_cast<const v4f *>(smem + sc.off_nodes);
         v.tris = reinterpret_cast<const v4f *>(smem + sc.off_tris);
         v.normals = reinterpret_cast<const float *>(smem + sc.off_normals);
@@ -107,7 +120,10 @@ TRG_DEV uint32_t image_row(const trg::RenderParams &p, uint32_t y_store) {
 // nearest-hit record: updates throughput / radiance / path state, moves the ray to the continuation ray and
 // returns the shadow ray to trace.  Shared by both loop shapes of render_kernel.
 struct ShadeOut { bool want_shadow, want_next, shaded; V3 sdir, scol; float smax; };
-template <bool TAB = false, bool FAT = false>
+// FLAT (shipped build, LDS-resident scene whose triangles each have one normal and one colour, no textures): the triangle's record -- (unit normal | r)
+// (right | g) (forward | b), staged where the normal array would be (scene_view<true, true>) -- gives the colour, the normal and the tangent frame of
+// align_hemisphere with three 16-byte LDS reads: no interpolation, no normalisation, no frame per hit.
+template <bool TAB = false, bool FAT = false, bool FLAT = false>
 TRG_DEV ShadeOut shade_event(const trg_uniforms &u, const SceneView &sc, const Hit &h, bool found, uint32_t b, bool last, uint32_t hidx,
                              V3 &o, V3 &d, V3 &thr, V3 &rad, uint32_t &rmask, bool &active, V3 light_color, const float *rpre = nullptr) {
     ShadeOut out;
@@ -123,9 +139,17 @@ TRG_DEV ShadeOut shade_event(const trg_uniforms &u, const SceneView &sc, const H
         // Raytracing.metal:150-199
         const V3 P = o + d * h.t;
         const float cx = 1.0f - h.u - h.v, cy = h.u;  // weights of vertex 0, 1
-        V3 vcol, nraw;
-        surf_interp<FAT>(sc, sf, cx, cy, vcol, nraw);
-        const V3 nrm = normalize(nraw);
+        V3 vcol, nrm, fright, fforward;
+        if (FLAT) {
+            const v4f *fr = reinterpret_cast<const v4f *>(sc.normals) + (uint32_t)h.prim * 3u;
+            const v4f f0 = fr[0], f1 = fr[1], f2 = fr[2];
+            nrm = mk(f0.x, f0.y, f0.z); fright = mk(f1.x, f1.y, f1.z); fforward = mk(f2.x, f2.y, f2.z);
+            vcol = mk(f0.w, f1.w, f2.w);
+        } else {
+            V3 nraw;
+            surf_interp<FAT>(sc, sf, cx, cy, vcol, nraw);
+            nrm = normalize(nraw);
+        }
         float r[4];
         // opaque copy: stops LICM from hoisting every bounce's Halton digits (all 60 dimensions) out of the
         // bounce loop and keeping them live in VGPRs
@@ -143,7 +167,8 @@ TRG_DEV ShadeOut shade_event(const trg_uniforms &u, const SceneView &sc, const H
         out.scol = ls.color * thr;
         out.want_shadow = out.smax >= 0.0f;  // inactive shadow rays are not traced (MPS skips maxDistance < 0)
         if (!last) {  // the reference also writes a continuation ray on the last bounce; nothing reads it
-            d = align_hemisphere(sample_cosine_hemisphere(r[2], r[3]), nrm);
+            const V3 hs = sample_cosine_hemisphere(r[2], r[3]);
+            d = FLAT ? hs.x * fright + hs.y * nrm + hs.z * fforward : align_hemisphere(hs, nrm);
             out.want_next = true;
         }
         rmask = 1u;  // RAY_MASK_SECONDARY
@@ -165,7 +190,7 @@ TRG_DEV ShadeOut shade_event(const trg_uniforms &u, const SceneView &sc, const H
 struct PathCounters { uint32_t primary, bounce, shadow, shaded; };
 TRG_DEV uint32_t wave_count(bool pred) { return (uint32_t)__popcll(__ballot(pred)); }
 typedef __attribute__((address_space(3))) float lds_float_t;
-template <bool LDS_SCENE, bool COUNT, typename STK>
+template <bool LDS_SCENE, bool COUNT, bool FLAT = false, typename STK>
 TRG_DEV V3 path_radiance(const trg::RenderParams &p, const SceneView &sc, STK stk, uint32_t x, uint32_t y, uint32_t offset, uint32_t frame, bool valid,
                          V3 light_color, PathCounters &pc, Counters &cnt, lds_float_t *path_park = nullptr) {
     // Halton index of this pixel-sample (Raytracing.metal:67: offset + uniforms.frameIndex, wraps mod 2^32).  `frame` is wave-uniform:
@@ -205,7 +230,7 @@ TRG_DEV V3 path_radiance(const trg::RenderParams &p, const SceneView &sc, STK st
                 Hit h;
                 const bool found = traverse<false, COUNT, trg::kBlock, false>(sc, o, d, INFINITY, TRG_RMASK, h, stk, cnt);
                 uint32_t rmask = TRG_RMASK;
-                so = shade_event<TAB>(TRG_U, sc, h, found, b, last, TRG_HIDX, o, d, thr, rad, rmask, active, light_color);
+                so = shade_event<TAB, false, FLAT>(TRG_U, sc, h, found, b, last, TRG_HIDX, o, d, thr, rad, rmask, active, light_color);
                 primary_ray = rmask == 3u;
                 if (so.want_shadow) {
                     Hit sh;
@@ -269,10 +294,11 @@ TRG_DEV V3 path_radiance(const trg::RenderParams &p, const SceneView &sc, STK st
 #ifndef TRG_EXP_WAVES_HBM
 #define TRG_EXP_WAVES_HBM 7
 #endif
-template <bool LDS_SCENE, bool COUNT>
+template <bool LDS_SCENE, bool COUNT, bool FLAT = false>   // FLAT: the flat-attribute shading event (shade_event), chosen per launch by the host
 __global__ __launch_bounds__(trg::kBlock, LDS_SCENE ? TRG_EXP_WAVES : TRG_EXP_WAVES_HBM) void render_kernel(const trg::RenderParams p) {
+    static_assert(!FLAT || (LDS_SCENE && kShipped), "flat-attribute records: LDS-resident scenes of the shipped build");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    SceneView sc = scene_view<LDS_SCENE>(p.sc, smem);
+    SceneView sc = scene_view<LDS_SCENE, FLAT>(p.sc, smem);
     sc.tex = p.tex;
     LdsStackT<trg::kBlock, !LDS_SCENE> stk;  // HBM scenes may spill deep stack levels to global scratch
     stk.set(smem, p.stack_off, p.stack.overflow, p.stack.klds);  // also writes the sentinel at level 0 of this thread's column
@@ -318,17 +344,9 @@ __global__ __launch_bounds__(trg::kBlock, LDS_SCENE ? TRG_EXP_WAVES : TRG_EXP_WA
         // amplification, 8 scratch reloads per frame).  Recomputing them costs a dozen VALU instructions per frame.
         const uint32_t lane_f = lane_id_opaque();
         const uint32_t xf = x0 + (lane_f & 7), yf = y0i + (lane_f >> 3);
-        const V3 rad = path_radiance<LDS_SCENE, COUNT>(p, sc, stk, xf, yf, offset, f, valid, light_color, pc, cnt, path_park);
+        const V3 rad = path_radiance<LDS_SCENE, COUNT, FLAT>(p, sc, stk, xf, yf, offset, f, valid, light_color, pc, cnt, path_park);
         if (PARK) acc = mk(park[0], park[trg::kBlock], park[2 * trg::kBlock]);
-        // Accumulate.metal:19-39
-        if (f == 0) {
-            acc = rad;
-        } else {
-            const V3 prev = acc * (float)f;
-            const V3 c = rad + prev;
-            const float f1 = (float)(f + 1u);
-            acc = mk(c.x / f1, c.y / f1, c.z / f1);
-        }
+        acc = running_average(acc, rad, f);
         if (PARK) { park[0] = acc.x; park[trg::kBlock] = acc.y; park[2 * trg::kBlock] = acc.z; }
     }
     const uint32_t lane = lane_id_opaque();
@@ -377,10 +395,11 @@ __global__ __launch_bounds__(trg::kBlock, LDS_SCENE ? TRG_EXP_WAVES : TRG_EXP_WA
 #ifndef TRG_EXP_WAVES_FP_HBM
 #define TRG_EXP_WAVES_FP_HBM 6   // HBM scene: 79 VGPRs and no scratch with throughput / radiance / offset parked in LDS (round 2: 72 VGPRs, 31 spilled, 96 B/lane at 7)
 #endif
-template <bool LDS_SCENE, bool COUNT>
+template <bool LDS_SCENE, bool COUNT, bool FLAT = false>
 __global__ __launch_bounds__(trg::kBlock, LDS_SCENE ? TRG_EXP_WAVES_FP : TRG_EXP_WAVES_FP_HBM) void render_fp_kernel(const trg::RenderParams p) {
+    static_assert(!FLAT || (LDS_SCENE && kShipped), "flat-attribute records: LDS-resident scenes of the shipped build");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    SceneView sc = scene_view<LDS_SCENE>(p.sc, smem);
+    SceneView sc = scene_view<LDS_SCENE, FLAT>(p.sc, smem);
     sc.tex = p.tex;
     LdsStackT<trg::kBlock, !LDS_SCENE> stk;
     stk.set(smem, p.stack_off, p.stack.overflow, p.stack.klds);  // also writes the sentinel at level 0 of this thread's column
@@ -425,7 +444,7 @@ __global__ __launch_bounds__(trg::kBlock, LDS_SCENE ? TRG_EXP_WAVES_FP : TRG_EXP
             const uint64_t i = rel + (uint64_t)r * F + fl;
             if (i >= p.spp) break;   // wave-uniform
             const uint32_t lane_f = lane_id_opaque();
-            const V3 rad = path_radiance<LDS_SCENE, COUNT>(p, sc, stk, x0 + (lane_f & 7), y0i + (lane_f >> 3), offset, p.frame_begin + (uint32_t)i, valid, light_color, pc, cnt, path_park);
+            const V3 rad = path_radiance<LDS_SCENE, COUNT, FLAT>(p, sc, stk, x0 + (lane_f & 7), y0i + (lane_f >> 3), offset, p.frame_begin + (uint32_t)i, valid, light_color, pc, cnt, path_park);
             float *slot = park + (size_t)(r * F + fl) * 3u * npx + sub * 64u + lane_id_opaque();
             slot[0] = rad.x; slot[npx] = rad.y; slot[2u * npx] = rad.z;
         }
@@ -436,15 +455,7 @@ __global__ __launch_bounds__(trg::kBlock, LDS_SCENE ? TRG_EXP_WAVES_FP : TRG_EXP
                 const uint32_t f = p.frame_begin + (uint32_t)(rel + s);
                 const float *slot = park + (size_t)s * 3u * npx + mypx;
                 const V3 rad = mk(slot[0], slot[npx], slot[2u * npx]);
-                // Accumulate.metal:19-39
-                if (f == 0) {
-                    acc = rad;
-                } else {
-                    const V3 prev = acc * (float)f;
-                    const V3 c = rad + prev;
-                    const float f1 = (float)(f + 1u);
-                    acc = mk(c.x / f1, c.y / f1, c.z / f1);
-                }
+                acc = running_average(acc, rad, f);
             }
         }
         __syncthreads();
@@ -598,8 +609,15 @@ using namespace TRG_KNS;
 namespace trg {
 
 #if TRG_UNIT != 2
+// The flat-attribute kernels (shade_event FLAT) run when the loaded scene has the records and NO textures are loaded -- decided per launch:
+// trg_load_textures may come after the scene.  Shipped build only (the strict build never sets the template argument).
+static bool flat_launch(const RenderParams &p) { return kShipped && p.sc.flat_attrs != 0u && p.tex.uv == nullptr; }
+
 hipError_t SFX(launch_render)(const RenderParams &p, bool lds_scene, bool counters, uint32_t grid, size_t lds_bytes, hipStream_t s) {
-    if (lds_scene) {
+    if (lds_scene && flat_launch(p)) {
+        if (counters) hipLaunchKernelGGL((render_kernel<true, true, kShipped>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
+        else hipLaunchKernelGGL((render_kernel<true, false, kShipped>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
+    } else if (lds_scene) {
         if (counters) hipLaunchKernelGGL((render_kernel<true, true>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
         else hipLaunchKernelGGL((render_kernel<true, false>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
     } else {
@@ -654,6 +672,10 @@ hipError_t SFX(launch_render_pool)(const RenderParams &p, bool lds_scene, bool c
 #endif  // TRG_EXPERIMENTS
 
 hipError_t SFX(launch_render_fp)(const RenderParams &p, bool lds_scene, bool counters, uint32_t grid, size_t lds_bytes, hipStream_t s) {
+    if (lds_scene && flat_launch(p)) {
+        if (counters) return launch_big_lds(render_fp_kernel<true, true, kShipped>, p, grid, lds_bytes, s);
+        return launch_big_lds(render_fp_kernel<true, false, kShipped>, p, grid, lds_bytes, s);
+    }
     if (lds_scene) {
         if (counters) return launch_big_lds(render_fp_kernel<true, true>, p, grid, lds_bytes, s);
         return launch_big_lds(render_fp_kernel<true, false>, p, grid, lds_bytes, s);
@@ -663,12 +685,18 @@ hipError_t SFX(launch_render_fp)(const RenderParams &p, bool lds_scene, bool cou
 }
 
 hipError_t SFX(launch_render_head)(const RenderParams &p, bool counters, uint32_t grid, size_t lds_bytes, hipStream_t s) {
-    if (counters) hipLaunchKernelGGL((render_head_kernel<true>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
+    if (flat_launch(p)) {
+        if (counters) hipLaunchKernelGGL((render_head_kernel<true, kShipped>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
+        else hipLaunchKernelGGL((render_head_kernel<false, kShipped>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
+    } else if (counters) hipLaunchKernelGGL((render_head_kernel<true>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
     else hipLaunchKernelGGL((render_head_kernel<false>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
     return hipGetLastError();
 }
 hipError_t SFX(launch_render_tail)(const RenderParams &p, bool counters, uint32_t grid, size_t lds_bytes, hipStream_t s) {
-    if (counters) hipLaunchKernelGGL((render_tail_kernel<true>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
+    if (flat_launch(p)) {
+        if (counters) hipLaunchKernelGGL((render_tail_kernel<true, kShipped>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
+        else hipLaunchKernelGGL((render_tail_kernel<false, kShipped>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
+    } else if (counters) hipLaunchKernelGGL((render_tail_kernel<true>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
     else hipLaunchKernelGGL((render_tail_kernel<false>), dim3(grid), dim3(kBlock), lds_bytes, s, p);
     return hipGetLastError();
 }

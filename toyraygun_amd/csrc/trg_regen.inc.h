@@ -364,15 +364,7 @@ __global__ __launch_bounds__(trg::kBlock) void regen_accumulate_kernel(const trg
     for (uint32_t fl = 0; fl < p.spp; ++fl) {
         const v4f r4 = stage[fl * trg::kBlock + pl];
         const V3 rad = mk(r4.x, r4.y, r4.z);
-        const uint32_t f = p.frame_begin + fl;
-        if (f == 0) {
-            acc = rad;
-        } else {
-            const V3 prev = acc * (float)f;
-            const V3 c = rad + prev;
-            const float f1 = (float)(f + 1u);
-            acc = mk(c.x / f1, c.y / f1, c.z / f1);
-        }
+        acc = running_average(acc, rad, p.frame_begin + fl);
     }
     v4f outv; outv.x = acc.x; outv.y = acc.y; outv.z = acc.z; outv.w = 1.0f;
     accum[pix] = outv;

@@ -15,7 +15,7 @@
 // entry = 3 float4: (o.xyz, bits pixel-in-band) (d.xyz, bits frame-in-chunk) (thr.xyz, 0); count[W]; radbuf[frame-in-chunk][pixel-in-band].
 
 // bounces [b0, b1) of one path per lane on an LDS-resident scene: the loop of path_radiance, re-entrant
-template <bool COUNT, typename STK>
+template <bool COUNT, bool FLAT = false, typename STK>
 TRG_DEV void path_segment_lds(const trg::RenderParams &p, const SceneView &sc, STK stk, uint32_t offset, uint32_t frame, uint32_t b0, uint32_t b1,
                               V3 &o, V3 &d, V3 &thr, V3 &rad, bool &active, bool &primary_ray, V3 light_color, PathCounters &pc, Counters &cnt) {
     constexpr bool TAB = !TRG_STRICT;
@@ -31,7 +31,7 @@ TRG_DEV void path_segment_lds(const trg::RenderParams &p, const SceneView &sc, S
             Hit h;
             const bool found = traverse<false, COUNT, trg::kBlock, false>(sc, o, d, INFINITY, primary_ray ? 3u : 1u, h, stk, cnt);
             uint32_t rmask = primary_ray ? 3u : 1u;
-            so = shade_event<TAB>(*(const trg_uniforms *)up, sc, h, found, b, last, offset + frame, o, d, thr, rad, rmask, active, light_color);
+            so = shade_event<TAB, false, FLAT>(*(const trg_uniforms *)up, sc, h, found, b, last, offset + frame, o, d, thr, rad, rmask, active, light_color);
             primary_ray = rmask == 3u;
             if (so.want_shadow) {
                 Hit sh;
@@ -62,10 +62,10 @@ TRG_DEV void flush_counters(const trg::RenderParams &p, unsigned char *smem, uin
 }
 
 // ---- head: raygen + bounces [0, K) of the chunk's frames; radiance so far -> radbuf; live paths -> the wavefront's queue segment ----
-template <bool COUNT>
+template <bool COUNT, bool FLAT = false>   // FLAT: the flat-attribute shading event (trg_kernels.hip shade_event)
 __global__ __launch_bounds__(trg::kBlock, TRG_EXP_WAVES) void render_head_kernel(const trg::RenderParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    SceneView sc = scene_view<true>(p.sc, smem);
+    SceneView sc = scene_view<true, FLAT>(p.sc, smem);
     sc.tex = p.tex;
     LdsStackT<trg::kBlock, false> stk;
     stk.set(smem, p.stack_off, p.stack.overflow, p.stack.klds);
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(trg::kBlock, TRG_EXP_WAVES) void render_head_kernel
         V3 thr = mk(1.0f, 1.0f, 1.0f), rad = mk(0.0f, 0.0f, 0.0f);
         bool active = valid, primary_ray = true;
         pc.primary += wave_count(active);
-        path_segment_lds<COUNT>(p, sc, stk, offset, f, 0u, p.tail_k, o, d, thr, rad, active, primary_ray, light_color, pc, cnt);
+        path_segment_lds<COUNT, FLAT>(p, sc, stk, offset, f, 0u, p.tail_k, o, d, thr, rad, active, primary_ray, light_color, pc, cnt);
         const uint32_t pl = (yf - p.row0) * p.u.width + xf;   // pixel in the band
         if (valid) {
             v4f r4; r4.x = rad.x; r4.y = rad.y; r4.z = rad.z; r4.w = 0.0f;
@@ -137,10 +137,10 @@ __global__ __launch_bounds__(trg::kBlock, TRG_EXP_WAVES) void render_head_kernel
 // lane, as the HBM kernels do.  Both rays are incoherent in a tail launch, so the wavefront would pay max(len_s + len_n) instead of
 // max(len_s) + max(len_n) -- but the pair loop needs the any-hit flag per lane and 72 VGPRs: C3 at 64 spp 15.65 -> 17.7 ms per step at
 // 7 waves/SIMD, 17.7 with spills at 8, 18.4 at 6.)
-template <bool COUNT>
+template <bool COUNT, bool FLAT = false>
 __global__ __launch_bounds__(trg::kBlock, TRG_EXP_WAVES) void render_tail_kernel(const trg::RenderParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    SceneView sc = scene_view<true>(p.sc, smem);
+    SceneView sc = scene_view<true, FLAT>(p.sc, smem);
     sc.tex = p.tex;
     LdsStackT<trg::kBlock, false> stk;
     stk.set(smem, p.stack_off, p.stack.overflow, p.stack.klds);
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(trg::kBlock, TRG_EXP_WAVES) void render_tail_kernel
         }
         // `frame` must be wave-uniform for path_segment_lds (Halton index = offset + frame): the entries of one round may belong
         // to different frames, so the per-lane frame rides in `offset` and the uniform part is zero
-        path_segment_lds<COUNT>(p, sc, stk, offset + p.frame_begin + fl, 0u, p.tail_k, p.tail_k_end, o, d, thr, rad, active, primary_ray, light_color, pc, cnt);
+        path_segment_lds<COUNT, FLAT>(p, sc, stk, offset + p.frame_begin + fl, 0u, p.tail_k, p.tail_k_end, o, d, thr, rad, active, primary_ray, light_color, pc, cnt);
         if (i < n) {
             v4f r4; r4.x = rad.x; r4.y = rad.y; r4.z = rad.z; r4.w = 0.0f;
             radbuf[(size_t)fl * p.tail_band_pixels + pl] = r4;
@@ -293,15 +293,7 @@ __global__ __launch_bounds__(256) void tail_accumulate_kernel(const trg::RenderP
     for (uint32_t fl = 0; fl < p.spp; ++fl) {
         const v4f r4 = radbuf[(size_t)fl * p.tail_band_pixels + pl];
         const V3 rad = mk(r4.x, r4.y, r4.z);
-        const uint32_t f = p.frame_begin + fl;
-        if (f == 0) {
-            acc = rad;
-        } else {
-            const V3 prev = acc * (float)f;
-            const V3 c = rad + prev;
-            const float f1 = (float)(f + 1u);
-            acc = mk(c.x / f1, c.y / f1, c.z / f1);
-        }
+        acc = running_average(acc, rad, p.frame_begin + fl);
     }
     v4f outv; outv.x = acc.x; outv.y = acc.y; outv.z = acc.z; outv.w = 1.0f;
     accum[pix] = outv;
