@@ -26,6 +26,13 @@ public:
     // trg_temporal_set_previous_scene (include/trg_denoise.h) -- triangle k of `scene` is the surface triangle k was -- and the next step looks
     // for every pixel's history where its surface was.  In every other case it is loadScene.
     void updateScene(Scene *scene);
+    // Off by default.  On: updateScene REFITS the loaded scene (trg_refit_scene, include/trg_refit.h) where it called loadScene, when the triangle
+    // count is the one of the scene uploaded last: the tree keeps its shape, the records, box frames and node boxes follow the vertices, colours,
+    // material ids and textures stay.  A refit the library refuses (a quad or a box of the loaded tree that the moved vertices no longer form) falls
+    // back to loadScene and says so on stdout.  The temporal hand-over above is the same either way.
+    void setRefit(bool on) { m_refit = on; }
+    bool getRefit() const { return m_refit; }
+    unsigned int getRefitCount() const { return m_refits; }    // updateScene calls that were served by a refit
     // One more sample per pixel into the running average.  ASYNCHRONOUS like the reference's (MetalRenderer.mm:373-552: encode,
     // commit, return; three frames in flight behind a semaphore, :33,377,385-387): the call never waits for the GPU to finish
     // a frame.  It takes a snapshot of the uniforms and either launches at once (GPU idle) or -- while earlier launches are
@@ -123,6 +130,10 @@ protected:
     std::vector<uint32_t> m_lastIndices;
     bool m_lastTextured;
     bool m_keepHistory;
+    // setRefit; whether the loadScene in progress may refit; the triangle count uploaded last; refits done
+    bool m_refit = false, m_refitNow = false;
+    size_t m_loadedTris = 0;
+    unsigned int m_refits = 0;
 };
 
 }  // namespace toyraygun

@@ -1,0 +1,109 @@
+"""Update time and render time of a refitted scene against a reloaded one (include/trg_refit.h).
+
+    python scripts/refit_time.py [--n 44] [--reps 5] [--w 1024 --h 768 --spp 4] [--out FILE]
+
+The Cornell box + n^3 cubes (n = 44: 1,022,244 triangles, n = 96: 10,616,868).  In ONE process, alternating, medians over `reps`:
+
+  update   trg_load_scene with the host builder, with TRG_OPT_GPU_BUILD=1, and trg_refit_scene of a tree of either builder -- with the positions
+           as they are (identity) and with every cube moved by its own small translation -- each followed by a wait for the stream;
+  render   ms per step of the tree as loaded, after an identity refit, after the small motion (with trg_refit_info's area ratio beside it) and
+           of a fresh load of the moved geometry, for both builders.
+
+Prints one JSON line (and writes it to --out)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from toyraygun_amd import capi, host, refit  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=44)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--w", type=int, default=1024)
+    ap.add_argument("--h", type=int, default=768)
+    ap.add_argument("--spp", type=int, default=4)
+    ap.add_argument("--bounces", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+
+    b = host.Scene.cornell_lattice(a.n).buffers()
+    pos0, nrm, col, idx, mat = b["positions"], b["normals"], b["colors"], b["indices"], b["material_ids"]
+    nt = mat.shape[0]
+    # every cube of the lattice (36 vertices each, behind the Cornell box's 108) moved by its own translation, a multiple of 2^-11 of at most 2^-9
+    # per axis: the sums are exact or lose one bit, so a cube stays the parallelepiped it was to the builders' tolerances
+    rng = np.random.default_rng(7)
+    n_cubes = (pos0.shape[0] - 108) // 36
+    d = (rng.integers(-4, 5, (n_cubes, 3)).astype(np.float32) * np.float32(2.0 ** -11))
+    pos1 = pos0.copy()
+    pos1[108:108 + 36 * n_cubes] += np.repeat(d, 36, axis=0)
+
+    c = capi.Context(a.w, a.h)
+    c.set_uniforms(host.uniforms(a.w, a.h)[0])
+    c.set_pixel_offsets_seed()
+    res = {"triangles": int(nt), "reps": a.reps, "image": [a.w, a.h, a.spp, a.bounces]}
+
+    def timed(f):
+        c.sync()
+        t0 = time.perf_counter()
+        f()
+        c.sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def load(builder, pos):
+        c.set_option(capi.OPT_GPU_BUILD, builder)
+        c.load_scene(pos, nrm, col, idx, mat)
+
+    def render_ms():
+        c.render(0, a.spp, a.bounces)                                      # warm-up (scratch, caches)
+        return statistics.median(timed(lambda: c.render(0, a.spp, a.bounces)) for _ in range(a.reps)) / a.spp
+
+    try:
+        for builder, name in ((0, "host"), (1, "device")):
+            t = {"load": [], "refit_identity": [], "refit_moved": []}
+            load(builder, pos0)
+            refit.refit_scene(c, pos0, nrm, idx)                           # (the scratch is allocated once)
+            for _ in range(a.reps):                                        # alternating: load, identity refit, moved refit
+                t["load"].append(timed(lambda: load(builder, pos0)))
+                t["refit_identity"].append(timed(lambda: refit.refit_scene(c, pos0, nrm, idx)))
+                t["refit_moved"].append(timed(lambda: refit.refit_scene(c, pos1, nrm, idx)))
+            info_moved = refit.refit_last(c)
+            r = {k + "_ms": statistics.median(v) for k, v in t.items()}
+            r.update({k + "_ms_all": [round(x, 3) for x in v] for k, v in t.items()})
+            load(builder, pos0)
+            r["build_ms_of_load"] = c.stats().last_build_ms              # the builder's own share of a load
+            # render time: as loaded, identity refit, moved refit, fresh load of the moved geometry
+            load(builder, pos0)
+            r["render_loaded_ms"] = render_ms()
+            refit.refit_scene(c, pos0, nrm, idx)
+            r["identity_area_ratio"] = refit.refit_last(c)["area_ratio"]
+            r["render_refit_identity_ms"] = render_ms()
+            refit.refit_scene(c, pos1, nrm, idx)
+            i = refit.refit_last(c)
+            r["moved_area_ratio"], r["moved_area_ratio_box"], r["passes"], r["path"] = i["area_ratio"], i["area_ratio_box"], i["passes"], i["path_name"]
+            r["n_quads"], r["n_boxes"] = i["n_quads"], i["n_boxes"]
+            r["render_refit_moved_ms"] = render_ms()
+            load(builder, pos1)
+            r["render_fresh_moved_ms"] = render_ms()
+            r["refit_last_ms_moved"] = info_moved["ms"]
+            res[name] = r
+        res["refit_beats_device_rebuild"] = bool(res["device"]["refit_moved_ms"] < res["device"]["load_ms"] and res["host"]["refit_moved_ms"] < res["device"]["load_ms"])
+    finally:
+        refit.release(c)
+        c.close()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,183 @@
+"""Host-side checks of the refit unit (include/trg_refit.h, toyraygun_amd/refit.py, toyraygun_amd/csrc/trg_refit_math.h): the exported surface, the
+files it must leave alone, and the arithmetic the kernels apply -- evaluated on the CPU from the same header -- against the builders.  No GPU."""
+import ctypes as C
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import refit_scenes as RS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "trg_refit.h")
+CSRC = os.path.join(ROOT, "toyraygun_amd", "csrc")
+HELPER = os.path.join(ROOT, "tests", "helpers", "refit_check.cpp")
+
+
+def test_library_exports_and_python_binds_every_declared_symbol(built):
+    from toyraygun_amd import capi, denoise, refit
+    declared = sorted(set(denoise.header_symbols(HEADER)))
+    assert declared == ["trg_group_refit_scene", "trg_refit_last", "trg_refit_release", "trg_refit_scene"]
+    out = subprocess.run(["nm", "-D", "--defined-only", capi.HIP_SO], capture_output=True, text=True).stdout
+    for name in declared:
+        assert re.search(r"\bT %s\b" % name, out), "libtoyraygun_hip.so does not export %s" % name
+    assert sorted(refit.SYMBOL_NAMES) == declared
+    L = refit.load()
+    for name in declared:
+        assert getattr(L, name).argtypes is not None
+    # the info block as the header lays it out: 8 dwords, 8 floats, 3 doubles
+    assert C.sizeof(refit.Info) == 88 and refit.Info.ms.offset == 64 and refit.Info.lo.offset == 32
+
+
+def test_render_abi_and_hashed_kernel_sources_are_untouched(built):
+    from toyraygun_amd import capi, refit
+    from toyraygun_amd.srchash import kernel_source_files, kernel_source_hash
+    trg_h = open(os.path.join(ROOT, "include", "trg.h")).read()
+    for name in refit.SYMBOL_NAMES + ["trg_refit_info"]:
+        assert name not in trg_h and name not in capi.SYMBOL_NAMES
+    assert not any("refit" in os.path.basename(p) for p in kernel_source_files())
+    with open(os.path.join(ROOT, "profiles", "r05", "c2_counters.json")) as f:
+        assert json.load(f)["kernel_source_hash"] == kernel_source_hash()
+
+
+def test_context_struct_copy_matches_the_c_abi_unit():
+    """trg_refit.hip repeats `struct trg_ctx` of trg_capi.cpp, as trg_denoise.hip does: the same tokens."""
+    def body(path):
+        src = open(os.path.join(CSRC, path)).read()
+        m = re.search(r"^struct trg_ctx \{\n(.*?)^\};", src, re.S | re.M)
+        assert m, path
+        return [re.sub(r"\s+", " ", re.sub(r"//.*", "", l)).strip() for l in m.group(1).splitlines() if re.sub(r"//.*", "", l).strip()]
+    assert body("trg_refit.hip") == body("trg_capi.cpp")
+    # ... and the unit cross-checks the copy against the library's accessors before it touches anything
+    src = open(os.path.join(CSRC, "trg_refit.hip")).read()
+    assert "ctx_device(c) == c->device" in src and "ctx_current_stream(c) == (void *)c->stream" in src and "if (!ctx_ok(c)) return fail(" in src
+
+
+def test_refit_arithmetic_against_fresh_builds_under_sanitizers(tmp_path):
+    """tests/helpers/refit_check.cpp as a program, with -fsanitize=address,undefined: scenes of a floor, 1 ... 700 cubes, lone triangles and lone quads
+    are built with box leaves, moved (identity, small, large: per-cube rigid-plus-shear maps) and refitted by the header's functions in the order the
+    kernels apply them.  Asserted: the passes settle in max(depth4, depth4_box); the quad marks read off the leaf codes are the builder's; the strict
+    rows are bitwise those of a fresh build of the moved geometry; every box -- parallelepiped or lone quad -- still passes the builder's test and its
+    frame is the fresh build's (measured difference: 0, the two evaluate the same double expressions); every triangle lies inside the decoded box of
+    every ancestor in BOTH node flavours; and the identity motion reproduces both loaded node arrays word for word."""
+    exe = str(tmp_path / "refit_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-pthread",
+                           "-fno-omit-frame-pointer", "-I" + CSRC, HELPER, os.path.join(CSRC, "bvh_build.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, TRG_BVH_THREADS="4"))
+    print(r.stdout)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    assert "refit check: every scene passed" in r.stdout and "ERROR" not in r.stderr and "runtime error" not in r.stderr
+    ident = re.findall(r"identity n (\d+): plain nodes differ in (\d+) of (\d+) words, box flavour in (\d+) of (\d+)", r.stdout)
+    assert len(ident) == 5 and all(int(a) == 0 and int(c) == 0 and int(b) > 0 and int(d) > 0 for _, a, b, c, d in ident)
+    assert "box frames against the fresh build: worst difference 0\n" in r.stdout
+    assert r.stdout.count("leaves walked") == 15
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    """The same helper as a shared object: the header's functions behind a C interface."""
+    so = str(tmp_path_factory.mktemp("refit") / "librefit_check.so")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-DREFIT_SHARED", "-I" + CSRC, HELPER, "-o", so])
+    L = C.CDLL(so)
+    L.rf_host_area.restype = C.c_double
+    return L
+
+
+def _p(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+def _leaf_records(capi, b):
+    L = capi.load()
+    args = (_p(b["positions"]), _p(b["normals"]), _p(b["colors"]), _p(b["indices"]), _p(b["material_ids"]), b["positions"].shape[0], b["material_ids"].shape[0])
+    n = C.c_uint32()
+    assert L.trg_debug_leaf_records(*args, None, 0, C.byref(n)) == capi.OK
+    rec = np.zeros((n.value, 32), np.float32)
+    assert L.trg_debug_leaf_records(*args, _p(rec), n.value, C.byref(n)) == capi.OK
+    return rec
+
+
+def test_header_over_the_debug_arrays_of_scene_a(built, shim):
+    """The header driven over what trg_debug_build_bvh4q, trg_debug_leaf_records, trg_debug_plane_records and trg_debug_boxes return for scene A,
+    then the vertices move (three steps).  Matched by primitive index, the re-derived records against a fresh debug build of the moved geometry:
+    strict rows bitwise; plane rows bitwise too -- MEASURED HERE: 0 ulp on every step, because trg_capi.cpp fill_plane_record and the header's
+    plane_rows are the same double expressions, neither contracted (x86-64 without FMA on the host, `fp contract(off)` in the header) --; box frames
+    (centre and rows of trg_debug_boxes) bitwise for the same reason.  Every triangle inside every ancestor's decoded box; identity reproduces the
+    loaded node array."""
+    from toyraygun_amd import capi
+    b0 = RS.scene_a(0)
+    nv, nt = b0["positions"].shape[0], b0["material_ids"].shape[0]
+    assert nt == RS.FLOOR_TRIS + RS.CUBE_TRIS + RS.SPHERE_TRIS == 706
+    nodes0 = capi.debug_build_bvh4q(b0["positions"], b0["indices"], b0["material_ids"])
+    _, depth4 = capi.debug_build_bvh4(b0["positions"], b0["indices"], b0["material_ids"])
+    rec0 = _leaf_records(capi, b0)
+    prim = np.ascontiguousarray(rec0[:, 3].view(np.uint32))
+    assert sorted(prim.tolist()) == list(range(nt))
+    boxes0 = capi.debug_boxes(b0["positions"], b0["indices"], b0["material_ids"])
+    assert boxes0.shape[0] == RS.N_CUBES                                   # every rotated cube is a box leaf
+    worst_plane = worst_frame = 0.0
+    for step in (0, 1, 2, 3):
+        b = RS.scene_a(step)
+        pos, idx = b["positions"], b["indices"]
+        lo, hi, ctr, pad = np.zeros(3, np.float32), np.zeros(3, np.float32), np.zeros(3, np.float32), C.c_float()
+        shim.rf_host_bounds(_p(pos), _p(idx), nv, nt, _p(lo), _p(hi), _p(ctr), C.byref(pad))
+        assert np.array_equal(lo, pos.min(0)) and np.array_equal(hi, pos.max(0))
+        planes_f, _, ctr_f = capi.debug_plane_records(pos, idx, b["material_ids"])
+        assert np.array_equal(ctr, ctr_f)
+        out = np.zeros_like(nodes0)
+        quadx = np.zeros(rec0.shape[0], np.uint8)
+        assert shim.rf_host_nodes(_p(pos), _p(idx), nv, nt, _p(nodes0), nodes0.shape[0], _p(prim), prim.shape[0], depth4, pad, _p(out), _p(quadx)) == 1
+        assert int(quadx.sum()) == 1 + 6 * RS.N_CUBES                      # the floor and six faces per cube
+        assert shim.rf_host_contained(_p(pos), _p(idx), nv, nt, _p(out), out.shape[0], _p(prim), prim.shape[0]) == 1
+        assert np.array_equal(out[:, 12:], nodes0[:, 12:])                 # child codes and unused slots do not change
+        if step == 0:
+            assert np.array_equal(out, nodes0)                             # identity motion: the loaded node array, word for word
+        else:
+            assert shim.rf_host_contained(_p(pos), _p(idx), nv, nt, _p(nodes0), nodes0.shape[0], _p(prim), prim.shape[0]) == 0   # (the check can fail: the stale tree does)
+        rec = rec0.copy()
+        planes = np.zeros((rec.shape[0], 12), np.float32)
+        shim.rf_host_records(_p(pos), _p(idx), nv, nt, _p(rec), rec.shape[0], _p(quadx), _p(ctr), _p(planes))
+        rec_f = _leaf_records(capi, b)
+        prim_f = rec_f[:, 3].view(np.uint32)
+        at = np.empty(nt, np.int64)
+        at[prim_f] = np.arange(nt)
+        rows = [0, 1, 2, 4, 5, 6, 8, 9, 10]
+        assert np.array_equal(rec[:, rows].view(np.uint32), rec_f[at[prim]][:, rows].view(np.uint32))
+        # a fresh build may pair or order a quad's records differently only if the geometry said so; here it does not: same X records, same planes
+        worst_plane = max(worst_plane, float(np.abs(planes.astype(np.float64) - planes_f[at[prim]].astype(np.float64)).max()))
+        assert np.array_equal(planes.view(np.uint32), planes_f[at[prim]].view(np.uint32))
+        boxes_f = capi.debug_boxes(pos, idx, b["material_ids"])
+        assert boxes_f.shape[0] == RS.N_CUBES
+        for i in range(RS.N_CUBES):
+            frame, rows12 = np.zeros(12, np.float32), np.zeros(12, np.float32)
+            assert shim.rf_host_box(_p(pos), _p(idx), nv, nt, RS.cube_first_triangle(i), _p(ctr), _p(frame), _p(rows12)) == 1
+            j = int(np.argmin(np.abs(boxes_f[:, 2:5] - frame[:3]).sum(1)))
+            worst_frame = max(worst_frame, float(np.abs(boxes_f[j, 2:14].astype(np.float64) - frame).max()))
+            assert np.array_equal(boxes_f[j, 2:14].view(np.uint32), frame.view(np.uint32))
+            assert np.array_equal(rows12.reshape(3, 4)[:, :3].reshape(-1), frame[3:])
+    print("plane rows: worst difference %g; box frames: %g" % (worst_plane, worst_frame))
+
+
+def test_refusal_rules_on_the_host(built, shim):
+    """What the device path refuses, by the same functions: a cube corner moved by 1e-3 of its edge breaks the quads that meet there and the box; a
+    bent quad is no parallelogram; the unmoved scene passes."""
+    b = RS.scene_a(1)
+    pos, idx = b["positions"].copy(), b["indices"]
+    nv, nt = pos.shape[0], b["material_ids"].shape[0]
+    ctr, frame, rows12 = np.zeros(3, np.float32), np.zeros(12, np.float32), np.zeros(12, np.float32)
+    k0 = RS.cube_first_triangle(9)
+    assert shim.rf_host_box(_p(pos), _p(idx), nv, nt, k0, _p(ctr), _p(frame), _p(rows12)) == 1
+    assert all(shim.rf_host_quad_still(_p(pos), _p(idx), nv, nt, k0 + 2 * q, k0 + 2 * q + 1) == 1 for q in range(6))
+    corner = pos[3 * k0].copy()
+    edge = float(np.linalg.norm(pos[3 * k0 + 1] - pos[3 * k0]))
+    pos[(pos == corner).all(1)] += np.float32(1e-3 * edge)
+    assert shim.rf_host_box(_p(pos), _p(idx), nv, nt, k0, _p(ctr), _p(frame), _p(rows12)) == 0
+    assert sum(shim.rf_host_quad_still(_p(pos), _p(idx), nv, nt, k0 + 2 * q, k0 + 2 * q + 1) for q in range(6)) == 3
+    pos = b["positions"].copy()
+    assert shim.rf_host_quad_still(_p(pos), _p(idx), nv, nt, 0, 1) == 1
+    pos[5, 1] += np.float32(0.01)                                          # the floor's fourth corner leaves its plane
+    assert shim.rf_host_quad_still(_p(pos), _p(idx), nv, nt, 0, 1) == 0
+    assert shim.rf_host_quad_still(_p(b["positions"]), _p(idx), nv, nt, 1, 0) == 0    # (the pair the other way round is not what the builder made)

@@ -78,6 +78,7 @@ def build_hip_library(hip_so, obj_tag="", defines=(), force=False, verbose=False
         ("bvh_build.o", os.path.join(CSRC, "bvh_build.cpp"), ["-x", "hip", "--offload-arch=" + ARCH]),
         ("trg_group.o", os.path.join(CSRC, "trg_group.cpp"), ["-x", "hip", "--offload-arch=" + ARCH, "-I/opt/rocm/include"]),
         ("trg_denoise.o", os.path.join(CSRC, "trg_denoise.hip"), dev),   # include/trg_denoise.h: guide buffers + the a-trous filter
+        ("trg_refit.o", os.path.join(CSRC, "trg_refit.hip"), dev),       # include/trg_refit.h: refit of a loaded scene from new vertex positions
     ]
     # (the regeneration units do not contain the experimental schedules: the variant shares those objects with the product build)
     shared_with_product = (("trg_kernels_fast_regen.o", "trg_kernels_strict_regen.o") if regen_shared else ()) + ("trg_build.o", "bvh_build.o", "trg_group.o")

@@ -10,6 +10,7 @@
 #include "png_writer.h"
 #include "trg.h"
 #include "trg_denoise.h"
+#include "trg_refit.h"
 
 namespace toyraygun {
 
@@ -80,8 +81,9 @@ bool HipRenderer::init() {
 
 void HipRenderer::destroy() {
     if (m_ctx) flush();
-    if (m_group) trg_group_destroy(m_group);   // owns every context, m_ctx included
-    else if (m_ctx) { trg_denoise_release(m_ctx); trg_destroy(m_ctx); }   // (the denoise scratch is not trg_destroy's)
+    // (the denoise and refit scratch is not trg_destroy's)
+    if (m_group) { for (int r = 0; r < trg_group_size(m_group); ++r) trg_refit_release(trg_group_ctx(m_group, r)); trg_group_destroy(m_group); }   // owns every context, m_ctx included
+    else if (m_ctx) { trg_denoise_release(m_ctx); trg_refit_release(m_ctx); trg_destroy(m_ctx); }
     m_group = nullptr;
     m_ctx = nullptr;
     m_sceneLoaded = false;
@@ -101,16 +103,28 @@ void HipRenderer::loadScene(Scene *scene) {
     const uint32_t *mat = nTris ? &scene->m_materialIDBuffer[0] : nullptr;
     // a device-built tree is traversed in HBM: scenes of a few hundred triangles are staged in LDS and keep the host builder
     const int builder = nTris >= 1024u ? m_deviceBuild : 0;
-    if (m_group) trg_group_set_option(m_group, TRG_OPT_GPU_BUILD, builder);
-    else trg_set_option(m_ctx, TRG_OPT_GPU_BUILD, builder);
-    const int rc = m_group ? trg_group_load_scene(m_group, pos, nrm, col, idx, mat, nVerts, nTris)
-                           : trg_load_scene(m_ctx, pos, nrm, col, idx, mat, nVerts, nTris);
+    // updateScene with setRefit(true): the loaded tree follows the vertices; what the library refuses is loaded instead
+    bool refitted = false;
+    if (m_refitNow) {
+        const int rrc = m_group ? trg_group_refit_scene(m_group, pos, nrm, idx, nVerts, nTris) : trg_refit_scene(m_ctx, pos, nrm, idx, nVerts, nTris);
+        refitted = rrc == TRG_OK;
+        if (refitted) ++m_refits;
+        else { printf("HipRenderer: refit refused (%s); loading the scene\n", trg_last_error(m_ctx)); fflush(stdout); }
+    }
+    if (!refitted) {
+        if (m_group) trg_group_set_option(m_group, TRG_OPT_GPU_BUILD, builder);
+        else trg_set_option(m_ctx, TRG_OPT_GPU_BUILD, builder);
+    }
+    const int rc = refitted ? TRG_OK
+                 : m_group  ? trg_group_load_scene(m_group, pos, nrm, col, idx, mat, nVerts, nTris)
+                            : trg_load_scene(m_ctx, pos, nrm, col, idx, mat, nVerts, nTris);
     if (rc != TRG_OK) {
         printf("HipRenderer: %s\n", m_group ? trg_group_last_error(m_group) : trg_last_error(m_ctx));
         m_sceneLoaded = false;
         return;
     }
     m_sceneLoaded = true;
+    m_loadedTris = nTris;
     // the temporal history belongs to the old scene (the library does not notice a changed one) -- unless updateScene vouches for it
     if (m_denoiseTemporal && !m_keepHistory) {
         if (trg_temporal_reset(m_ctx) != TRG_OK) printf("HipRenderer: %s\n", trg_last_error(m_ctx));
@@ -125,7 +139,7 @@ void HipRenderer::loadScene(Scene *scene) {
         m_lastIndices.assign(idx, idx + (size_t)nVerts);
     }
     // albedo textures of the scene (Scene::addMesh with a Texture): expanded to RGBA8 and uploaded with the texture coordinates
-    if (!scene->m_textures.empty() && nTris) {
+    if (!scene->m_textures.empty() && nTris && !refitted) {   // (a refitted scene keeps the textures it was loaded with)
         std::vector<float> uv(scene->m_uvBuffer);
         std::vector<uint32_t> ids(scene->m_textureIDBuffer);
         uv.resize((size_t)nVerts * 2, 0.0f);       // triangles added after the last textured mesh
@@ -161,13 +175,15 @@ void HipRenderer::updateScene(Scene *scene) {
     const size_t nTris = scene->m_materialIDBuffer.size();
     const bool keep = m_denoiseTemporal && !m_group && m_sceneLoaded && nTris != 0 && m_lastIndices.size() == nTris * 3 && !m_lastTextured &&
                       scene->m_textures.empty();
-    if (!keep) { loadScene(scene); return; }
+    m_refitNow = m_refit && m_sceneLoaded && nTris != 0 && nTris == m_loadedTris;
+    if (!keep) { loadScene(scene); m_refitNow = false; return; }
     std::vector<float> positions, normals;
     std::vector<uint32_t> indices;
     positions.swap(m_lastPositions); normals.swap(m_lastNormals); indices.swap(m_lastIndices);
     m_keepHistory = true;
     loadScene(scene);
     m_keepHistory = false;
+    m_refitNow = false;
     if (!m_sceneLoaded) return;
     if (trg_temporal_set_previous_scene(m_ctx, positions.data(), normals.data(), indices.data(), (uint32_t)(positions.size() / 3), (uint32_t)nTris) != TRG_OK) {
         printf("HipRenderer: %s\n", trg_last_error(m_ctx));

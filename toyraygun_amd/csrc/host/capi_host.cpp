@@ -200,6 +200,26 @@ int trh_render_scene_on(void *scene, int w, int h, int frames, int bounces, int 
     if (!r.readAccumulation(accumOut)) return -5;
     return 0;
 }
+// ---- HipRenderer::updateScene: loadScene(sceneA), setRefit(refit), updateScene(sceneB), `frames` samples, read back; how many updates a refit served ----
+int trh_update_scene(void *sceneA, void *sceneB, int w, int h, int frames, int bounces, int deviceBuild, int refit, int device, float *accumOut,
+                     unsigned int *refitsOut) {
+    Engine *engine = Engine::instance();
+    engine->setDevice(device);
+    engine->init(w, h);
+    HipRenderer r;
+    if (!r.init()) return -3;
+    if (!r.setDeviceBuild(deviceBuild)) return -2;
+    r.setCameraPosition(bx::Vec3(0.0f, 1.0f, 3.38f));
+    r.setCameraLookAt(bx::Vec3(0.0f, 1.0f, -1.0f));
+    r.setRefit(refit != 0);
+    r.loadScene(static_cast<Scene *>(sceneA));
+    r.updateScene(static_cast<Scene *>(sceneB));
+    r.setBounces((unsigned int)bounces);
+    if (!r.renderFrames((unsigned int)frames)) return -4;
+    if (!r.readAccumulation(accumOut)) return -5;
+    if (refitsOut) *refitsOut = r.getRefitCount();
+    return 0;
+}
 int trh_render_scene(void *scene, int w, int h, int frames, int bounces, int deviceBuild, int device, float *accumOut, double *loadMsOut) {
     return trh_render_scene_on(scene, w, h, frames, bounces, deviceBuild, device, nullptr, 0, accumOut, loadMsOut);
 }

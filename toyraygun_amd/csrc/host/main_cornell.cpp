@@ -1,6 +1,6 @@
 // main_cornell.cpp -- headless demo following the reference app's call order (reference src/main.cpp:16-98):
 // engine init -> three shaders -> renderer init -> camera -> Cornell box -> frame loop; then writes a PNG.
-//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D]]
+//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [refit]]
 //     denoise=N    a-trous iterations of the written image, 0 = off (default)
 //     ,var         the variance-guided filter from two half-sample buffers
 //     ,temporal    the frames are rendered as `frames` calls of 1 spp, each a temporal step (reprojected history, temporal variance); the
@@ -14,6 +14,8 @@
 //     orbit=DEG    the eye turns about the look-at point (about the vertical axis) by DEG degrees per call
 //     slide=D      before call k the box is rebuilt with the short box moved by k * D along x and handed to HipRenderer::updateScene: with
 //                  ,temporal the history follows the moving box (trg_temporal_set_previous_scene), otherwise it is a plain loadScene
+//     refit        (with slide=D) HipRenderer::setRefit(true): updateScene refits the loaded scene from the moved vertices (trg_refit_scene,
+//                  include/trg_refit.h) instead of loading it again; the last line of output counts the refits
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -61,7 +63,8 @@ int main(int argc, char **argv) {
     int denoise = 0;
     bool denoiseVar = false, denoiseTemporal = false, varianceOfMean = false;
     double orbit = 0.0, slide = 0.0, lagGate = -1.0, coverMin = -1.0;
-    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D]]";
+    bool refit = false;
+    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [refit]]";
     for (int a = 6; a < argc; ++a) {
         if (strncmp(argv[a], "slide=", 6) == 0) {
             char *end = nullptr;
@@ -69,6 +72,7 @@ int main(int argc, char **argv) {
             if (end == argv[a] + 6 || *end != 0) { std::cout << usage << std::endl; return -1; }
             continue;
         }
+        if (strcmp(argv[a], "refit") == 0) { refit = true; continue; }
         if (strncmp(argv[a], "orbit=", 6) == 0) {
             char *end = nullptr;
             orbit = strtod(argv[a] + 6, &end);
@@ -141,6 +145,7 @@ int main(int argc, char **argv) {
     if (lagGate >= 0.0 && !hip->setLagCorrection((float)lagGate)) { std::cout << "the lag correction was refused" << std::endl; return -1; }
     if (coverMin >= 0.0 && !hip->setCoverage((float)coverMin)) { std::cout << "the coverage history was refused" << std::endl; return -1; }
     if (varianceOfMean && !hip->setVarianceOfMean(true)) { std::cout << "the variance of the mean was refused" << std::endl; return -1; }
+    hip->setRefit(refit);
     Scene *scene = createCornellBoxScene();
     renderer->loadScene(scene);
     hip->setBounces((unsigned int)bounces);
@@ -163,6 +168,7 @@ int main(int argc, char **argv) {
         ++call;
     }
     printf("%d frames, %llu rays, last frame %.3f ms\n", hip->getFrameIndex(), (unsigned long long)hip->getRayCount(), hip->getLastRenderMs());
+    if (refit) printf("%u scene updates served by a refit\n", hip->getRefitCount());
     if (!hip->savePNG(out)) { std::cout << "Failed to write " << out << std::endl; return -1; }
     printf("wrote %s\n", out);
     return 0;

@@ -1,0 +1,605 @@
+// trg_refit.hip -- include/trg_refit.h: refit a loaded scene from new vertex positions.  A translation unit of its own beside the render path.
+// The arithmetic per record, per box and per node is trg_refit_math.h (host + device: the CPU tests evaluate the same functions); this file is the
+// kernels that apply it, the order they run in, and the small-scene path through the host builder.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/trg_refit.h"
+#include "trg_internal.h"
+#include "trg_kernels.h"
+#include "trg_refit_math.h"
+
+using namespace trg;
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The context.  trg_capi.cpp keeps `struct trg_ctx` to itself and its text is part of the kernel-source hash, so this unit REPEATS the definition,
+// token for token, as trg_denoise.hip does (the same class defined twice with the same tokens is one class).  tests/test_refit_host.py compares
+// the two texts, and ctx_ok() below cross-checks the copy against the library's own accessors before anything is touched.
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// BEGIN trg_ctx (copy of trg_capi.cpp)
+struct trg_ctx {
+    int device = 0;
+    uint32_t w = 0, h = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t fence[8] = {};
+    bool fence_set[8] = {};
+    float *accum_own = nullptr, *accum = nullptr;
+    uint32_t *offsets = nullptr;
+    unsigned long long *counters = nullptr;
+    unsigned char *blob = nullptr;
+    unsigned char *tex_mem = nullptr;   // uv | ids | table | texels (trg_load_textures)
+    TexDesc tex{};
+    // global overflow levels of the traversal stacks (grow-only), one buffer per launch the caller keeps in flight
+    // (TRG_OPT_LAUNCHES_IN_FLIGHT): launch k uses slot k mod in_flight, so overlapping launches never share one
+    static constexpr int kScratchSlots = 16;
+    hipStream_t slot_stream[kScratchSlots] = {};   // which stream owns scratch slot k (slot 0 = the context's own stream)
+    int slots_used = 1;
+    int *stack_scratch[kScratchSlots] = {};
+    size_t stack_scratch_bytes[kScratchSlots] = {};
+    // wavefront schedule: path state + ray queues of one batch, one set per launch in flight (grow-only)
+    unsigned char *wf_mem[kScratchSlots] = {};
+    size_t wf_bytes[kScratchSlots] = {};
+    int cu_count = 256;
+    uint32_t *xq = nullptr;   // kScratchSlots x 8 job-queue heads of the persistent regeneration launches (TRG_OPT_TILE_ORDER 64 + n), one set per stream
+    uint32_t bvh_depth4 = 0, bvh_nodes4 = 0;
+    SceneDesc sc{};
+    bool scene_loaded = false, have_uniforms = false, have_offsets = false;
+    trg_uniforms u{};
+    bool opt_strict = false, opt_counters = false, opt_force_global = false, opt_timing = true;
+    int opt_kernel = TRG_KERNEL_AUTO;
+    uint32_t last_kernel = TRG_KERNEL_DIRECT;
+    uint32_t last_tail_k = 0;
+    int opt_gpu_build = 0;   // TRG_OPT_GPU_BUILD: 0 host SAH, 1 device binned SAH, 2 device LBVH (Karras), 3 device PLOC
+    int opt_fsplit = 0;  // 0 = auto
+    int opt_tail = -1;   // TRG_OPT_TAIL_BOUNCE: -1 auto, 0 off, K
+    int opt_regen = -1;        // TRG_OPT_REGEN: 1 = path regeneration for HBM-resident scenes (direct kernel, frame-serial), -1 = from 32,768 triangles on, 0 = the lock-step kernel
+    uint32_t last_regen = 0;
+    int opt_tail_levels = 0;   // TRG_OPT_TAIL_LEVELS: 0 = re-compact every second bounce after K, 1 = once at K only
+    int opt_in_flight = 1;  // launches of this context the caller keeps in flight (TRG_OPT_LAUNCHES_IN_FLIGHT)
+    int opt_stack_levels = (int)TRG_STACK_LDS_LEVELS;   // TRG_OPT_STACK_LDS_LEVELS
+    int opt_tail_sort = 0;     // TRG_OPT_TAIL_SORT: 0 off, 1 direction octant, 2 / 3 octant + origin cell of a 2^3 / 4^3 grid
+    int opt_tail_refill = -1;  // TRG_OPT_TAIL_REFILL: 1 = the tail launches run ONE bounce each with in-wave refill (render_rtail_kernel); -1 = the library's choice
+    float scene_lo[3] = { 0.f, 0.f, 0.f }, scene_hi[3] = { 1.f, 1.f, 1.f };   // bounds of the loaded scene (tail sort: the origin grid)
+    int opt_tile_order = -1;   // TRG_OPT_TILE_ORDER: -1 auto, 0 image columns centre-out, 1 / 2 / 4 / 8 XCD regions with that many column strips
+    uint32_t last_xcd_cols = 0;
+    double last_build_ms = 0.0;
+    bool gpu_built = false;
+    uint32_t bvh_nodes = 0, bvh_depth = 0, bvh_leaves = 0, bvh_quads = 0, bvh_boxes = 0;
+    double last_ms = 0.0, total_ms = 0.0;
+    uint32_t renders = 0;
+    uint32_t last_fsplit = 1;
+    uint32_t launches = 0;   // trg_render launches since create (never reset: picks the scratch slot)
+    std::string err;
+};
+// END trg_ctx
+
+namespace {
+
+int fail(trg_ctx *c, int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    if (c) c->err = buf;
+    return code;
+}
+#define RF_HIPCHK(c, expr)                                                                                      \
+    do {                                                                                                        \
+        hipError_t e_ = (expr);                                                                                 \
+        if (e_ != hipSuccess) return fail((c), TRG_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// the copy of the struct above against what the library itself says about the context
+bool ctx_ok(trg_ctx *c) {
+    void *acc = nullptr;
+    return c && ctx_device(c) == c->device && ctx_current_stream(c) == (void *)c->stream && trg_accum_device_ptr(c, &acc) == TRG_OK && acc == (void *)c->accum &&
+           c->w != 0 && c->h != 0 && ctx_gpu_build_option(c) == c->opt_gpu_build;
+}
+
+// ---- what the device reports back: the flag words and the bounds, read by the host in the call's one wait ----
+enum { kFlagIndex = 0, kFlagFinite = 1, kFlagQuad = 2, kFlagBox = 3, kFlagNode = 4, kCountQuads = 5 };
+struct Hdr {
+    uint32_t flag[8];            // kFlag*: the smallest offending triangle (node for kFlagNode), ~0u = none; kCountQuads: a count
+    float lo[3], hi[3], center[3], pad;
+    double area[4];              // plain array as it is / refitted, box flavour as it is / refitted
+};
+constexpr uint32_t kNone = ~0u;
+constexpr int kT = 256;
+constexpr uint32_t kMaxPartials = 1024;
+
+// ---- step 2a: indices, finiteness, bounds of the indexed vertices (per-block partial results; no atomics on floats) ----
+__global__ void rf_bounds_kernel(refit::Geo g, const float *nrm, float *partial, uint32_t *flag) {
+    __shared__ float sh[6][kT];
+    float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (uint32_t t = blockIdx.x * kT + threadIdx.x; t < g.n_tris; t += gridDim.x * kT) {
+        bool bad_index = false, bad_value = false;
+        for (int j = 0; j < 3; ++j) {
+            const uint32_t i = g.idx[(size_t)t * 3 + j];
+            if (i >= g.n_verts) { bad_index = true; continue; }
+            const float *p = g.pos + (size_t)i * 3;
+            for (int a = 0; a < 3; ++a) { bad_value = bad_value || !isfinite(p[a]); lo[a] = fminf(lo[a], p[a]); hi[a] = fmaxf(hi[a], p[a]); }
+        }
+        if (nrm)
+            for (int k = 0; k < 9; ++k) bad_value = bad_value || !isfinite(nrm[(size_t)t * 9 + k]);
+        if (bad_index) atomicMin(&flag[kFlagIndex], t);
+        if (bad_value) atomicMin(&flag[kFlagFinite], t);
+    }
+    for (int a = 0; a < 3; ++a) { sh[a][threadIdx.x] = lo[a]; sh[3 + a][threadIdx.x] = hi[a]; }
+    __syncthreads();
+    for (int s = kT / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int a = 0; a < 3; ++a) {
+                sh[a][threadIdx.x] = fminf(sh[a][threadIdx.x], sh[a][threadIdx.x + s]);
+                sh[3 + a][threadIdx.x] = fmaxf(sh[3 + a][threadIdx.x], sh[3 + a][threadIdx.x + s]);
+            }
+        __syncthreads();
+    }
+    if (threadIdx.x < 6) partial[blockIdx.x * 6 + threadIdx.x] = sh[threadIdx.x][0];
+}
+// ... and the one block that finishes them: bounds, centre and padding as trg_load_scene computes them
+__global__ void rf_bounds_final_kernel(const float *partial, uint32_t n_partials, Hdr *hdr) {
+    __shared__ float sh[6][kT];
+    float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (uint32_t b = threadIdx.x; b < n_partials; b += kT)
+        for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], partial[b * 6 + a]); hi[a] = fmaxf(hi[a], partial[b * 6 + 3 + a]); }
+    for (int a = 0; a < 3; ++a) { sh[a][threadIdx.x] = lo[a]; sh[3 + a][threadIdx.x] = hi[a]; }
+    __syncthreads();
+    for (int s = kT / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int a = 0; a < 3; ++a) {
+                sh[a][threadIdx.x] = fminf(sh[a][threadIdx.x], sh[a][threadIdx.x + s]);
+                sh[3 + a][threadIdx.x] = fmaxf(sh[3 + a][threadIdx.x], sh[3 + a][threadIdx.x + s]);
+            }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        for (int a = 0; a < 3; ++a) { lo[a] = sh[a][0]; hi[a] = sh[3 + a][0]; hdr->lo[a] = lo[a]; hdr->hi[a] = hi[a]; }
+        refit::scene_center(lo, hi, hdr->center);
+        hdr->pad = refit::scene_pad(lo, hi);
+    }
+}
+
+// the loaded scene as the kernels of this unit see it
+struct View {
+    unsigned char *blob;
+    uint32_t off_fat, off_fat_planes, off_boxrec, n_fat, n_boxrec, n_tris;
+};
+__device__ inline uint32_t rec_prim(const View &v, uint32_t r) { return reinterpret_cast<const uint32_t *>(v.blob + v.off_fat + (size_t)r * kFatRecBytes)[3]; }
+__device__ inline const uint32_t *box_row3(const View &v, uint32_t b) { return reinterpret_cast<const uint32_t *>(v.blob + v.off_boxrec + (size_t)b * kFatRecBytes) + 12; }
+__device__ inline bool padding_node(const uint32_t *nd) { return (nd[12] | nd[13] | nd[14] | nd[15]) == 0u; }   // (zeroed bytes behind an odd number of nodes: no node has child 0)
+
+// ---- steps 2b + 5a, one thread per node of one node array: the unpadded box of every LEAF child from the moved triangles, their union, and --
+//      quadx != nullptr, the plain array -- the quad rule for every quad leaf and the mark on its X record ----
+__global__ void rf_leaf_kernel(refit::Geo g, View v, uint32_t off_nodes, uint32_t n_nodes, float *childbox, float *leafbox, unsigned char *quadx, uint32_t *flag) {
+    const uint32_t i = blockIdx.x * kT + threadIdx.x;
+    if (i >= n_nodes) return;
+    const uint32_t *nd = reinterpret_cast<const uint32_t *>(v.blob + off_nodes + (size_t)i * kQ4NodeBytes);
+    float L[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };
+    const bool padding = padding_node(nd);
+    for (int k = 0; k < 4; ++k) {
+        float b[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };
+        const int32_t c = (int32_t)nd[12 + k];
+        if (!padding && c < 0 && c != kQ4Empty) {
+            const uint32_t code = (uint32_t)~c, kind = code & 7u;
+            uint32_t first = code >> 3, count = 0;
+            if (kind == refit::kCodeBox) {
+                const uint32_t bx = first - v.n_fat;
+                if (first >= v.n_fat && bx < v.n_boxrec) { const uint32_t *row3 = box_row3(v, bx); first = row3[0]; count = (row3[3] >> 31) ? 2u : 12u; }
+            } else {
+                count = refit::code_records(code);
+            }
+            if (count == 0u || (uint64_t)first + count > v.n_fat) { atomicMin(&flag[kFlagNode], i); count = 0; }
+            for (uint32_t r = first; r < first + count; ++r) {
+                const uint32_t prim = rec_prim(v, r);
+                if (prim >= v.n_tris) { atomicMin(&flag[kFlagNode], i); continue; }
+                refit::grow_tri(g, prim, b, b + 3);
+            }
+            if (quadx && kind == refit::kCodeQuad && count == 2u) {
+                const uint32_t x = rec_prim(v, first), y = rec_prim(v, first + 1u);
+                if (x < v.n_tris && y < v.n_tris && !refit::quad_still(g, x, y)) atomicMin(&flag[kFlagQuad], x);
+                quadx[first] = 1;
+                atomicAdd(&flag[kCountQuads], 1u);
+            }
+        }
+        for (int a = 0; a < 6; ++a) childbox[((size_t)i * 4 + k) * 6 + a] = b[a];
+        for (int a = 0; a < 3; ++a) { L[a] = fminf(L[a], b[a]); L[3 + a] = fmaxf(L[3 + a], b[3 + a]); }
+    }
+    for (int a = 0; a < 6; ++a) leafbox[(size_t)i * 6 + a] = L[a];
+}
+
+// ---- step 5b, one bottom-up pass: a node's box = its leaf children's union and the boxes its inner children had after the pass before.
+//      changed != nullptr: the pass only CHECKS that nothing moves any more (the tree was deeper than the passes run) ----
+__global__ void rf_pass_kernel(const unsigned char *nodes, uint32_t n_nodes, const float *leafbox, const float *src, float *dst, uint32_t *changed) {
+    const uint32_t i = blockIdx.x * kT + threadIdx.x;
+    if (i >= n_nodes) return;
+    const uint32_t *nd = reinterpret_cast<const uint32_t *>(nodes + (size_t)i * kQ4NodeBytes);
+    float b[6];
+    for (int a = 0; a < 6; ++a) b[a] = leafbox[(size_t)i * 6 + a];
+    if (!padding_node(nd))
+        for (int k = 0; k < 4; ++k) {
+            const int32_t c = (int32_t)nd[12 + k];
+            if (c < 0 || (uint32_t)c >= n_nodes) continue;
+            for (int a = 0; a < 3; ++a) { b[a] = fminf(b[a], src[(size_t)c * 6 + a]); b[3 + a] = fmaxf(b[3 + a], src[(size_t)c * 6 + 3 + a]); }
+        }
+    if (changed) {
+        bool same = true;
+        for (int a = 0; a < 6; ++a) same = same && b[a] == src[(size_t)i * 6 + a];
+        if (!same) atomicMin(changed, i);
+        return;
+    }
+    for (int a = 0; a < 6; ++a) dst[(size_t)i * 6 + a] = b[a];
+}
+
+// ---- step 5c: pad and quantise every node (q4node.h) into scratch; child codes and unused slots as they are ----
+__global__ void rf_quantize_kernel(const unsigned char *nodes, uint32_t n_nodes, const float *childbox, const float *nodebox, const Hdr *hdr, uint32_t *out, uint32_t *flag) {
+    const uint32_t i = blockIdx.x * kT + threadIdx.x;
+    if (i >= n_nodes) return;
+    const uint32_t *nd = reinterpret_cast<const uint32_t *>(nodes + (size_t)i * kQ4NodeBytes);
+    uint32_t *o = out + (size_t)i * 16;
+    if (padding_node(nd)) { for (int k = 0; k < 16; ++k) o[k] = nd[k]; return; }
+    float cb[24], f32[32];
+    uint32_t child[4];
+    for (int k = 0; k < 4; ++k) {
+        child[k] = nd[12 + k];
+        const int32_t c = (int32_t)child[k];
+        const float *b = childbox + ((size_t)i * 4 + k) * 6;
+        if (c >= 0) {
+            if ((uint32_t)c >= n_nodes || (uint32_t)c <= i) { atomicMin(&flag[kFlagNode], i); b = nodebox + (size_t)i * 6; }
+            else b = nodebox + (size_t)c * 6;
+        }
+        for (int a = 0; a < 6; ++a) cb[k * 6 + a] = b[a];
+        if (c != kQ4Empty && !(b[0] <= b[3] && b[1] <= b[4] && b[2] <= b[5])) atomicMin(&flag[kFlagNode], i);
+    }
+    refit::node_floats(cb, child, hdr->pad, f32);
+    quantize_node4(f32, o);
+}
+
+// ---- the node-area figure of trg_refit_info: per-block partial sums in a fixed order, then one thread adds them in order ----
+__global__ void rf_area_kernel(const unsigned char *nodes, uint32_t n_nodes, double *partial) {
+    __shared__ double sh[kT];
+    double sum = 0.0;
+    for (uint32_t i = blockIdx.x * kT + threadIdx.x; i < n_nodes; i += gridDim.x * kT) {
+        const uint32_t *nd = reinterpret_cast<const uint32_t *>(nodes + (size_t)i * kQ4NodeBytes);
+        if (!padding_node(nd)) sum += refit::node_half_area(nd);
+    }
+    sh[threadIdx.x] = sum;
+    __syncthreads();
+    for (int s = kT / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+}
+__global__ void rf_area_final_kernel(const double *partial, uint32_t n_partials, double *out) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    double sum = 0.0;
+    for (uint32_t b = 0; b < n_partials; ++b) sum += partial[b];
+    *out = sum;
+}
+
+// ---- steps 2c + 4, one thread per box record: the frame from the box's twelve moved triangles (a lone quad dressed as a box: from its quad), checked
+//      by the builder's rule and against the face table the record keeps; the rows go to scratch ----
+__global__ void rf_box_kernel(refit::Geo g, View v, const Hdr *hdr, float *boxrows, uint32_t *flag) {
+    const uint32_t b = blockIdx.x * kT + threadIdx.x;
+    if (b >= v.n_boxrec) return;
+    const uint32_t *row3 = box_row3(v, b);
+    const uint32_t first = row3[0];
+    const bool lone = (row3[3] >> 31) != 0u;
+    const uint32_t count = lone ? 2u : 12u;
+    if ((uint64_t)first + count > v.n_fat) { atomicMin(&flag[kFlagNode], 0u); return; }
+    uint32_t prim[12], k0 = kNone;
+    for (uint32_t r = 0; r < count; ++r) {
+        prim[r] = rec_prim(v, first + r);
+        if (prim[r] >= v.n_tris) { atomicMin(&flag[kFlagNode], 0u); return; }
+        k0 = prim[r] < k0 ? prim[r] : k0;
+    }
+    refit::Frame fr;
+    bool ok;
+    if (lone) {
+        float xr[12], yr[12];
+        refit::tri_rows(g, prim[0], xr); refit::tri_rows(g, prim[1], yr);
+        ok = refit::lone_quad_frame(xr, yr + 8, fr);
+    } else {
+        uint32_t face_quad[6] = { 0, 0, 0, 0, 0, 0 };
+        ok = refit::box_group_pos(g, k0, fr, face_quad);
+        for (int f = 0; f < 6 && ok; ++f) {   // the face table of the loaded record must still name the quads the frame assigns
+            const uint32_t off = (row3[2 + f / 4] >> (7 * (f % 4))) & 15u;
+            if (off + 1u >= 12u) { ok = false; break; }
+            const uint32_t px = prim[off], py = prim[off + 1u];
+            ok = ((px < py ? px : py) - k0) / 2u == face_quad[f];
+        }
+    }
+    if (!ok) { atomicMin(&flag[kFlagBox], k0); return; }
+    refit::frame_rows(fr, hdr->center, boxrows + (size_t)b * 12);
+}
+__global__ void rf_box_write_kernel(View v, const float *boxrows) {
+    const uint32_t t = blockIdx.x * kT + threadIdx.x;
+    if (t >= v.n_boxrec * 12u) return;
+    reinterpret_cast<float *>(v.blob + v.off_boxrec + (size_t)(t / 12u) * kFatRecBytes)[t % 12u] = boxrows[t];
+}
+
+// ---- step 3, one thread per leaf record: both 128-byte forms from the true vertices of the record's triangle ----
+__global__ void rf_records_kernel(refit::Geo g, const float *nrm, View v, float cx, float cy, float cz, const unsigned char *quadx) {
+    const uint32_t r = blockIdx.x * kT + threadIdx.x;
+    if (r >= v.n_fat) return;
+    float *mt = reinterpret_cast<float *>(v.blob + v.off_fat + (size_t)r * kFatRecBytes);
+    float *pl = reinterpret_cast<float *>(v.blob + v.off_fat_planes + (size_t)r * kFatRecBytes);
+    const uint32_t prim = refit::f2u(mt[3]);
+    if (prim >= v.n_tris) return;
+    float rows[12], yrows[12], planes[12];
+    refit::tri_rows(g, prim, rows);
+    const float *e2row = rows + 8;
+    if (quadx[r] && r + 1u < v.n_fat) {   // the X of a quad: the parallelogram's second edge is its Y's
+        const uint32_t py = rec_prim(v, r + 1u);
+        if (py < v.n_tris) { refit::tri_rows(g, py, yrows); e2row = yrows + 8; }
+    }
+    const float center[3] = { cx, cy, cz };
+    refit::plane_rows(rows, e2row, center, planes);
+    for (int k = 0; k < 3; ++k) { mt[k] = rows[k]; mt[4 + k] = rows[4 + k]; mt[8 + k] = rows[8 + k]; }
+    for (int k = 0; k < 12; ++k) pl[k] = planes[k];
+    if (nrm)
+        for (int k = 0; k < 9; ++k) { const float n = nrm[(size_t)prim * 9 + k]; mt[12 + k] = n; pl[14 + k] = n; }
+}
+
+// ---- per-context scratch (grow-only), kept beside the contexts like the denoiser's ----
+struct Buf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+struct RefitState {
+    int device = 0;
+    Buf pos, idx, nrm, childbox, leafbox, ping, pong, qplain, qbox, quadx, boxrows, partial, hdr;
+    Hdr host{};                    // what the host sends and reads back
+    trg_refit_info last{};
+    const void *area_blob = nullptr;   // the blob whose as-loaded areas are remembered, and what its arrays summed to after this unit's last write
+    double loaded_area[2] = { 0.0, 0.0 }, written_area[2] = { 0.0, 0.0 };
+};
+std::mutex g_mutex;
+std::unordered_map<trg_ctx *, RefitState> g_states;
+
+template <typename F>
+void each_buffer(RefitState &s, F f) {
+    for (Buf *b : { &s.pos, &s.idx, &s.nrm, &s.childbox, &s.leafbox, &s.ping, &s.pong, &s.qplain, &s.qbox, &s.quadx, &s.boxrows, &s.partial, &s.hdr }) f(*b);
+}
+int grow(trg_ctx *c, Buf &b, size_t need, const char *what) {
+    if (need <= b.bytes && b.p) return TRG_OK;
+    if (b.p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; }
+    const size_t want = need + need / 8 + 256;
+    const hipError_t e = hipMalloc(&b.p, want);
+    if (e != hipSuccess) { b.p = nullptr; return fail(c, TRG_ERR_NOMEM, "trg_refit_scene: %s hipMalloc(%zu) failed: %s", what, want, hipGetErrorString(e)); }
+    b.bytes = want;
+    return TRG_OK;
+}
+RefitState &state_of(trg_ctx *c) {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    RefitState &s = g_states[c];
+    if (s.device != c->device) {   // a new context at the address of one that was destroyed without a release
+        each_buffer(s, [](Buf &b) { if (b.p) (void)hipFree(b.p); });
+        s = RefitState{};
+        s.device = c->device;
+    }
+    return s;
+}
+
+inline dim3 blocks_for(size_t n) { return dim3((uint32_t)((n + kT - 1) / kT)); }
+#define RF_LAUNCH(c, kernel, grid, ...)                                                                                                 \
+    do {                                                                                                                                \
+        hipLaunchKernelGGL(kernel, grid, dim3(kT), 0, (c)->stream, __VA_ARGS__);                                                        \
+        const hipError_t e_ = hipGetLastError();                                                                                        \
+        if (e_ != hipSuccess) return fail((c), TRG_ERR_DEVICE, "trg_refit_scene: launch of %s failed: %s", #kernel, hipGetErrorString(e_)); \
+    } while (0)
+
+// one node array: leaf boxes, the bottom-up passes, the check that they settled, the quantised nodes into `q`, and the area sums before / after
+int refit_node_array(trg_ctx *c, RefitState &s, const refit::Geo &g, const View &v, uint32_t off_nodes, uint32_t n_nodes, uint32_t passes, Buf &q, bool plain,
+                     double *area_before, double *area_after) {
+    Hdr *hdr = s.hdr.as<Hdr>();
+    const unsigned char *nodes = v.blob + off_nodes;
+    RF_LAUNCH(c, rf_leaf_kernel, blocks_for(n_nodes), g, v, off_nodes, n_nodes, s.childbox.as<float>(), s.leafbox.as<float>(), plain ? s.quadx.as<unsigned char>() : nullptr, hdr->flag);
+    RF_HIPCHK(c, hipMemcpyAsync(s.ping.p, s.leafbox.p, (size_t)n_nodes * 24, hipMemcpyDeviceToDevice, c->stream));
+    float *src = s.ping.as<float>(), *dst = s.pong.as<float>();
+    for (uint32_t p = 0; p < passes; ++p) {
+        RF_LAUNCH(c, rf_pass_kernel, blocks_for(n_nodes), nodes, n_nodes, s.leafbox.as<float>(), src, dst, nullptr);
+        std::swap(src, dst);
+    }
+    RF_LAUNCH(c, rf_pass_kernel, blocks_for(n_nodes), nodes, n_nodes, s.leafbox.as<float>(), src, dst, &hdr->flag[kFlagNode]);
+    RF_LAUNCH(c, rf_quantize_kernel, blocks_for(n_nodes), nodes, n_nodes, s.childbox.as<float>(), src, hdr, q.as<uint32_t>(), hdr->flag);
+    const uint32_t nb = std::min<uint32_t>(kMaxPartials, (n_nodes + kT - 1) / kT);
+    RF_LAUNCH(c, rf_area_kernel, dim3(nb), nodes, n_nodes, s.partial.as<double>());
+    RF_LAUNCH(c, rf_area_final_kernel, dim3(1), s.partial.as<double>(), nb, area_before);
+    RF_LAUNCH(c, rf_area_kernel, dim3(nb), q.as<unsigned char>(), n_nodes, s.partial.as<double>());
+    RF_LAUNCH(c, rf_area_final_kernel, dim3(1), s.partial.as<double>(), nb, area_after);
+    return TRG_OK;
+}
+
+int refit_device(trg_ctx *c, const float *pos, const float *nrm, const uint32_t *idx, uint32_t n_verts, uint32_t n_tris) {
+    const auto t0 = std::chrono::steady_clock::now();
+    RefitState &s = state_of(c);
+    const SceneDesc sc = c->sc;
+    const uint32_t n4 = sc.n_nodes4;
+    const bool has_box = sc.off_nodes4_box != sc.off_nodes4 && sc.off_fat > sc.off_nodes4_box;
+    const uint32_t n4b = has_box ? (sc.off_fat - sc.off_nodes4_box) / kQ4NodeBytes : 0u;   // (may count one zeroed line half of padding: padding_node)
+    const uint32_t nmax = std::max(n4, n4b);
+    if (n4 == 0 || sc.n_fat == 0) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: the loaded scene has no node array to refit");
+    // the blob's sections must lie where this unit expects them before a kernel is handed their offsets
+    if ((uint64_t)sc.off_nodes4 + (uint64_t)n4 * kQ4NodeBytes > sc.blob_bytes || (uint64_t)sc.off_fat_planes + (uint64_t)sc.n_fat * kFatRecBytes > sc.blob_bytes ||
+        (uint64_t)sc.off_fat + (uint64_t)sc.n_fat * kFatRecBytes > sc.off_fat_planes || (uint64_t)sc.off_boxrec + (uint64_t)sc.n_boxrec * kFatRecBytes > sc.blob_bytes)
+        return fail(c, TRG_ERR_INVALID, "trg_refit_scene: the loaded scene's layout is not the one this unit knows");
+
+    int rc = TRG_OK;
+    if ((rc = grow(c, s.pos, (size_t)n_verts * 12, "positions")) || (rc = grow(c, s.idx, (size_t)n_tris * 12, "indices")) ||
+        (nrm && (rc = grow(c, s.nrm, (size_t)n_tris * 36, "normals"))) || (rc = grow(c, s.childbox, (size_t)nmax * 96, "child boxes")) ||
+        (rc = grow(c, s.leafbox, (size_t)nmax * 24, "leaf boxes")) || (rc = grow(c, s.ping, (size_t)nmax * 24, "node boxes")) ||
+        (rc = grow(c, s.pong, (size_t)nmax * 24, "node boxes")) || (rc = grow(c, s.qplain, (size_t)n4 * kQ4NodeBytes, "nodes")) ||
+        (has_box && (rc = grow(c, s.qbox, (size_t)n4b * kQ4NodeBytes, "box-flavour nodes"))) || (rc = grow(c, s.quadx, (size_t)sc.n_fat, "quad marks")) ||
+        (sc.n_boxrec && (rc = grow(c, s.boxrows, (size_t)sc.n_boxrec * 48, "box frames"))) || (rc = grow(c, s.partial, (size_t)kMaxPartials * 48, "partial results")) ||
+        (rc = grow(c, s.hdr, sizeof(Hdr), "flags")))
+        return rc;
+
+    // step 1: upload
+    RF_HIPCHK(c, hipMemcpyAsync(s.pos.p, pos, (size_t)n_verts * 12, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(s.idx.p, idx, (size_t)n_tris * 12, hipMemcpyHostToDevice, c->stream));
+    if (nrm) RF_HIPCHK(c, hipMemcpyAsync(s.nrm.p, nrm, (size_t)n_tris * 36, hipMemcpyHostToDevice, c->stream));
+    s.host = Hdr{};
+    for (int k = 0; k < 5; ++k) s.host.flag[k] = kNone;
+    RF_HIPCHK(c, hipMemcpyAsync(s.hdr.p, &s.host, sizeof(Hdr), hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemsetAsync(s.quadx.p, 0, sc.n_fat, c->stream));
+
+    // step 2 (and everything that only READS the scene): bounds, checks, node boxes, quantised nodes and box frames into scratch
+    Hdr *hdr = s.hdr.as<Hdr>();
+    const refit::Geo g{ s.pos.as<float>(), s.idx.as<uint32_t>(), n_verts, n_tris };
+    const float *d_nrm = nrm ? s.nrm.as<float>() : nullptr;
+    const View v{ c->blob, sc.off_fat, sc.off_fat_planes, sc.off_boxrec, sc.n_fat, has_box ? sc.n_boxrec : 0u, n_tris };
+    const uint32_t nb = std::min<uint32_t>(kMaxPartials, (n_tris + kT - 1) / kT);
+    RF_LAUNCH(c, rf_bounds_kernel, dim3(nb), g, d_nrm, s.partial.as<float>(), hdr->flag);
+    RF_LAUNCH(c, rf_bounds_final_kernel, dim3(1), s.partial.as<float>(), nb, hdr);
+    const uint32_t passes = std::max(c->bvh_depth4, 1u);
+    if ((rc = refit_node_array(c, s, g, v, sc.off_nodes4, n4, passes, s.qplain, true, &hdr->area[0], &hdr->area[1]))) return rc;
+    if (has_box && (rc = refit_node_array(c, s, g, v, sc.off_nodes4_box, n4b, passes, s.qbox, false, &hdr->area[2], &hdr->area[3]))) return rc;
+    if (v.n_boxrec) RF_LAUNCH(c, rf_box_kernel, blocks_for(v.n_boxrec), g, v, hdr, s.boxrows.as<float>(), hdr->flag);
+
+    // the call's one wait: the bounds and the flag words
+    RF_HIPCHK(c, hipMemcpyAsync(&s.host, s.hdr.p, sizeof(Hdr), hipMemcpyDeviceToHost, c->stream));
+    RF_HIPCHK(c, hipStreamSynchronize(c->stream));
+    const Hdr &h = s.host;
+    if (h.flag[kFlagIndex] != kNone) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: triangle %u has an index out of range (%u vertices)", h.flag[kFlagIndex], n_verts);
+    if (h.flag[kFlagFinite] != kNone) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: triangle %u has a coordinate that is not finite", h.flag[kFlagFinite]);
+    if (h.flag[kFlagQuad] != kNone)
+        return fail(c, TRG_ERR_RANGE, "trg_refit_scene: triangle %u and its neighbour are a quad leaf of the loaded tree and no longer a parallelogram (reload the scene)", h.flag[kFlagQuad]);
+    if (h.flag[kFlagBox] != kNone)
+        return fail(c, TRG_ERR_RANGE, "trg_refit_scene: the box leaf that begins at triangle %u is no longer a parallelepiped to 1e-5 (reload the scene)", h.flag[kFlagBox]);
+    if (h.flag[kFlagNode] != kNone)
+        return fail(c, TRG_ERR_RANGE, "trg_refit_scene: node %u of the loaded tree could not be refitted (%u passes)", h.flag[kFlagNode], passes);
+
+    // steps 3 - 5: write
+    RF_LAUNCH(c, rf_records_kernel, blocks_for(sc.n_fat), g, d_nrm, v, h.center[0], h.center[1], h.center[2], s.quadx.as<unsigned char>());
+    if (v.n_boxrec) RF_LAUNCH(c, rf_box_write_kernel, blocks_for((size_t)v.n_boxrec * 12), v, s.boxrows.as<float>());
+    RF_HIPCHK(c, hipMemcpyAsync(c->blob + sc.off_nodes4, s.qplain.p, (size_t)n4 * kQ4NodeBytes, hipMemcpyDeviceToDevice, c->stream));
+    if (has_box) RF_HIPCHK(c, hipMemcpyAsync(c->blob + sc.off_nodes4_box, s.qbox.p, (size_t)n4b * kQ4NodeBytes, hipMemcpyDeviceToDevice, c->stream));
+    for (int a = 0; a < 3; ++a) { c->sc.center[a] = h.center[a]; c->scene_lo[a] = h.lo[a]; c->scene_hi[a] = h.hi[a]; }
+
+    // the tree "as loaded": the sums this blob's arrays had when this unit first saw them -- or saw them changed by somebody else
+    const bool ours = s.area_blob == (const void *)c->blob && s.written_area[0] == h.area[0] && s.written_area[1] == h.area[2];
+    if (!ours) { s.area_blob = c->blob; s.loaded_area[0] = h.area[0]; s.loaded_area[1] = h.area[2]; }
+    s.written_area[0] = h.area[1]; s.written_area[1] = h.area[3];
+    trg_refit_info &o = s.last;
+    o = trg_refit_info{};
+    o.path = TRG_REFIT_DEVICE;
+    o.n_records = sc.n_fat; o.n_quads = h.flag[kCountQuads]; o.n_boxes = v.n_boxrec; o.n_nodes = n4; o.n_nodes_box = n4b; o.passes = passes;
+    for (int a = 0; a < 3; ++a) { o.lo[a] = h.lo[a]; o.hi[a] = h.hi[a]; }
+    o.pad = h.pad;
+    o.area_ratio = s.loaded_area[0] > 0.0 ? h.area[1] / s.loaded_area[0] : 0.0;
+    o.area_ratio_box = (has_box && s.loaded_area[1] > 0.0) ? h.area[3] / s.loaded_area[1] : 0.0;
+    o.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return TRG_OK;
+}
+
+// the small-scene path: the host builder again, with the colours and material ids the blob holds; the textures stay
+int refit_rebuild(trg_ctx *c, const float *pos, const float *nrm, const uint32_t *idx, uint32_t n_verts, uint32_t n_tris) {
+    const auto t0 = std::chrono::steady_clock::now();
+    RefitState &s = state_of(c);
+    const SceneDesc sc = c->sc;
+    for (uint32_t t = 0; t < n_tris; ++t)
+        for (int j = 0; j < 3; ++j) {
+            const uint32_t i = idx[(size_t)t * 3 + j];
+            if (i >= n_verts) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: triangle %u has an index out of range (%u vertices)", t, n_verts);
+            bool finite = std::isfinite(pos[(size_t)i * 3]) && std::isfinite(pos[(size_t)i * 3 + 1]) && std::isfinite(pos[(size_t)i * 3 + 2]);
+            for (int k = 0; nrm && k < 3; ++k) finite = finite && std::isfinite(nrm[((size_t)t * 3 + j) * 3 + k]);
+            if (!finite) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: triangle %u has a coordinate that is not finite", t);
+        }
+    std::vector<float> col((size_t)n_tris * 9), own_nrm;
+    std::vector<uint32_t> mat(n_tris);
+    RF_HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n_tris) {
+        RF_HIPCHK(c, hipMemcpy(col.data(), c->blob + sc.off_colors, (size_t)n_tris * 36, hipMemcpyDeviceToHost));
+        RF_HIPCHK(c, hipMemcpy(mat.data(), c->blob + sc.off_mats, (size_t)n_tris * 4, hipMemcpyDeviceToHost));
+        if (!nrm) {
+            own_nrm.resize((size_t)n_tris * 9);
+            RF_HIPCHK(c, hipMemcpy(own_nrm.data(), c->blob + sc.off_normals, (size_t)n_tris * 36, hipMemcpyDeviceToHost));
+            nrm = own_nrm.data();
+        }
+    }
+    HostScene *hs = nullptr;
+    if (int rc = host_scene_build(c, pos, nrm, col.data(), idx, mat.data(), n_verts, n_tris, &hs)) return rc;
+    // host_scene_upload drops the textures of the scene it replaces; this scene is the same one, moved: they are kept out of its sight
+    unsigned char *tex_mem = c->tex_mem;
+    const TexDesc tex = c->tex;
+    c->tex_mem = nullptr;
+    const int rc = host_scene_upload(c, hs);
+    c->tex_mem = tex_mem; c->tex = tex;
+    trg_refit_info &o = s.last;
+    if (rc == TRG_OK) {
+        o = trg_refit_info{};
+        o.path = TRG_REFIT_REBUILD;
+        o.n_records = c->sc.n_fat; o.n_quads = c->bvh_quads; o.n_boxes = c->bvh_boxes; o.n_nodes = c->sc.n_nodes4;
+        for (int a = 0; a < 3; ++a) { o.lo[a] = c->scene_lo[a]; o.hi[a] = c->scene_hi[a]; }
+        o.pad = n_tris ? refit::scene_pad(o.lo, o.hi) : 0.f;
+        o.area_ratio = 1.0;   // a tree of its own: nothing has grown loose
+        o.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    host_scene_free(hs);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trg_refit_scene(trg_ctx *c, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris) {
+    if (!c) return TRG_ERR_INVALID;
+    if (!ctx_ok(c)) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: this unit's view of the context does not match the library's");
+#if TRG_WIDE8
+    return fail(c, TRG_ERR_INVALID, "trg_refit_scene: an 8-wide experiments build has no refit (reload the scene)");
+#endif
+    if (!c->scene_loaded || !c->blob) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: no scene loaded");
+    if (n_tris != c->sc.n_tris) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: %u triangles, the loaded scene has %u (a changed topology is a reload)", n_tris, c->sc.n_tris);
+    if (n_tris && (!positions3 || !indices || n_verts == 0)) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: null buffer");
+    RF_HIPCHK(c, hipSetDevice(c->device));
+    if (c->sc.n_nodes != 0 || n_tris == 0) return refit_rebuild(c, positions3, normals3, indices, n_verts, n_tris);
+    return refit_device(c, positions3, normals3, indices, n_verts, n_tris);
+}
+
+int trg_refit_last(trg_ctx *c, trg_refit_info *out) {
+    if (!c || !out) return TRG_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(g_mutex);
+    auto it = g_states.find(c);
+    *out = it == g_states.end() ? trg_refit_info{} : it->second.last;
+    return TRG_OK;
+}
+
+int trg_refit_release(trg_ctx *c) {
+    if (!c) return TRG_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(g_mutex);
+    auto it = g_states.find(c);
+    if (it == g_states.end()) return TRG_OK;
+    (void)hipSetDevice(it->second.device);
+    (void)hipDeviceSynchronize();
+    each_buffer(it->second, [](Buf &b) { if (b.p) (void)hipFree(b.p); });
+    g_states.erase(it);
+    return TRG_OK;
+}
+
+int trg_group_refit_scene(trg_group *g, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris) {
+    if (!g) return TRG_ERR_INVALID;
+    const int n = trg_group_size(g);
+    if (n <= 0) return TRG_ERR_INVALID;
+    if (int rc = trg_group_sync(g)) return rc;
+    for (int r = 0; r < n; ++r) {
+        trg_ctx *c = trg_group_ctx(g, r);
+        if (!c) return TRG_ERR_INVALID;
+        if (int rc = trg_refit_scene(c, positions3, normals3, indices, n_verts, n_tris)) return rc;
+    }
+    return TRG_OK;
+}
+
+}  // extern "C"

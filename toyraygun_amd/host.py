@@ -68,6 +68,8 @@ def load():
         L.trh_async_camera_move_on.restype = C.c_int
         L.trh_render_scene_on.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, F, C.POINTER(C.c_double)]
         L.trh_render_scene_on.restype = C.c_int
+        L.trh_update_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, F, C.POINTER(C.c_uint)]
+        L.trh_update_scene.restype = C.c_int
         _lib = L
     return _lib
 
@@ -263,6 +265,16 @@ def render_scene(scene, w, h, frames, bounces=3, device_build=0, device=0, devic
     if rc != 0:
         raise RuntimeError("trh_render_scene failed at step %d" % rc)
     return acc, ms.value
+
+
+def update_scene(scene_a, scene_b, w, h, frames, bounces=3, device_build=0, refit=False, device=0):
+    """HipRenderer: loadScene(scene_a), setRefit(refit), updateScene(scene_b), `frames` samples; returns (accum[h,w,4], updates served by a refit)."""
+    acc = np.zeros((h, w, 4), np.float32)
+    n = C.c_uint()
+    rc = load().trh_update_scene(scene_a.h, scene_b.h, w, h, frames, bounces, device_build, 1 if refit else 0, device, acc.ctypes.data, C.byref(n))
+    if rc != 0:
+        raise RuntimeError("trh_update_scene failed at step %d" % rc)
+    return acc, n.value
 
 
 def run_app(w, h, frames, bounces=3, batch=False, device=0, png_path=None, want_launches=False):
