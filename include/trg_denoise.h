@@ -7,7 +7,8 @@
  * stream (trg_set_stream) and nothing waits for the device, unless a function says so.
  *
  * STATE.  The first call allocates per-context scratch (primary rays and hit records of the guide pass, two ping-pong images of the filter;
- * the half-sample images of the variance-guided path and the history planes of the temporal path on their first use); it is grow-only and lives until trg_denoise_release(ctx).  trg_destroy does NOT know about it: call trg_denoise_release BEFORE trg_destroy.
+ * the half-sample images of the variance-guided path and the history planes of the temporal path on their first use); it is grow-only and
+ * belongs to the context: trg_destroy frees it, and trg_denoise_release(ctx) remains for freeing it earlier.
  */
 #ifndef TRG_DENOISE_H
 #define TRG_DENOISE_H
@@ -84,7 +85,7 @@ TRG_API int trg_render_denoised(trg_ctx *ctx, uint32_t frameIndexBegin, uint32_t
  *     function or trg_denoise_release).  Only enqueues.  To tone-map it: trg_bind_accum(ctx, *out_device), trg_postprocess, bind back. */
 TRG_API int trg_denoise_accum(trg_ctx *ctx, uint32_t frameIndex, const trg_denoise_params *p, void **out_device);
 
-/* frees the context's denoise state (waits for the device first).  Harmless without one.  Call before trg_destroy. */
+/* frees the context's denoise state early (waits for the device first); trg_destroy frees it too.  Harmless without one. */
 TRG_API int trg_denoise_release(trg_ctx *ctx);
 
 /* --- the same three with HOST buffers (tests, scripts, the plugin's PNG path): temporary device copies on the context's stream, and they

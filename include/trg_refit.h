@@ -63,7 +63,7 @@ typedef struct trg_refit_info {
  * vertices no longer form.  trg_last_error names the first offending triangle. */
 TRG_API int trg_refit_scene(trg_ctx *ctx, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris);
 TRG_API int trg_refit_last(trg_ctx *ctx, trg_refit_info *out);
-/* frees the unit's scratch of this context; call it before trg_destroy (which does not know about it) */
+/* frees the unit's scratch of this context early (trg_destroy frees it too) */
 TRG_API int trg_refit_release(trg_ctx *ctx);
 /* every context of the group refits its own copy; the first failure is returned (trg_last_error of that context has the text) */
 TRG_API int trg_group_refit_scene(trg_group *g, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris);

@@ -11,14 +11,23 @@ export TMPDIR=/tmp
 export GPU_MAX_HW_QUEUES=16
 OUT=$PWD/gpurun_out/profiles; mkdir -p "$OUT"
 WHAT="${*:-c2 c4}"
-C2="python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-secondary"
-C4="python3 bench.py --full --config c4 --steps 5 --warmup 1 --no-cpu-baseline"
-C3="python3 bench.py --full --config c3 --steps 3 --warmup 1 --no-cpu-baseline"
-C5="python3 bench.py --full --config c5 --steps 5 --warmup 1 --no-cpu-baseline"
-C4XL="python3 bench.py --full --config c4xl --steps 3 --warmup 1 --no-cpu-baseline"
-run() { name=$1; shift; rm -rf "$OUT/$name"; rocprofv3 "$@" > "$OUT/$name.log" 2>&1 || { echo "FAILED $name"; tail -5 "$OUT/$name.log"; }; }
+# the benched commands, each with its steps + warm-up steps beside it (what a pass's time limit is made of)
+C2="python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-secondary"; N_C2=12
+C4="python3 bench.py --full --config c4 --steps 5 --warmup 1 --no-cpu-baseline"; N_C4=6
+C3="python3 bench.py --full --config c3 --steps 3 --warmup 1 --no-cpu-baseline"; N_C3=4
+C5="python3 bench.py --full --config c5 --steps 5 --warmup 1 --no-cpu-baseline"; N_C5=6
+C4XL="python3 bench.py --full --config c4xl --steps 3 --warmup 1 --no-cpu-baseline"; N_C4XL=4
+# one profiler pass under a time limit of its own, LIMIT = 40 s (profiler, runtime, the scene's build) + 3 s per step of the benched command:
+# 76 s on C2 (a pass was measured at 1.8 s), 58 s on C4 and C5 (2 - 2.6 s), 52 s on C3 (2.5 s) and on c4xl (8 s, most of it the build of its ten
+# million triangles) -- six times the slowest pass, more on the others.  A pass that fails or runs out of time ENDS the script: nothing more is
+# started on a card that may have faulted
+run() {
+  name=$1; shift; rm -rf "$OUT/$name"
+  timeout -k 10 $LIMIT rocprofv3 "$@" > "$OUT/$name.log" 2>&1 || { echo "FAILED $name (exit $?, limit $LIMIT s)"; tail -5 "$OUT/$name.log"; exit 1; }
+}
 for cfg in $WHAT; do
-  if [ "$cfg" = c2 ]; then CMD=$C2; elif [ "$cfg" = c3 ]; then CMD=$C3; elif [ "$cfg" = c5 ]; then CMD=$C5; elif [ "$cfg" = c4xl ]; then CMD=$C4XL; else CMD=$C4; fi
+  if [ "$cfg" = c2 ]; then CMD=$C2; N=$N_C2; elif [ "$cfg" = c3 ]; then CMD=$C3; N=$N_C3; elif [ "$cfg" = c5 ]; then CMD=$C5; N=$N_C5; elif [ "$cfg" = c4xl ]; then CMD=$C4XL; N=$N_C4XL; else CMD=$C4; N=$N_C4; fi
+  LIMIT=$((40 + 3 * N))
   run ${cfg}_trace --kernel-trace --stats --output-format csv -d "$OUT/${cfg}_trace" -- $CMD
   run ${cfg}_fetch --pmc FETCH_SIZE --output-format csv -d "$OUT/${cfg}_fetch" -- $CMD
   run ${cfg}_write --pmc WRITE_SIZE --output-format csv -d "$OUT/${cfg}_write" -- $CMD

@@ -40,17 +40,6 @@ def test_render_abi_and_hashed_kernel_sources_are_untouched(built):
         assert json.load(f)["kernel_source_hash"] == kernel_source_hash()
 
 
-def test_context_struct_copy_matches_the_c_abi_unit():
-    """trg_denoise.hip repeats `struct trg_ctx` of trg_capi.cpp (which keeps it private and may not change: its text is part of the
-    kernel-source hash).  The two definitions must be the same tokens."""
-    def body(path):
-        src = open(os.path.join(ROOT, "toyraygun_amd", "csrc", path)).read()
-        m = re.search(r"^struct trg_ctx \{\n(.*?)^\};", src, re.S | re.M)
-        assert m, path
-        return [re.sub(r"\s+", " ", re.sub(r"//.*", "", l)).strip() for l in m.group(1).splitlines() if re.sub(r"//.*", "", l).strip()]
-    assert body("trg_denoise.hip") == body("trg_capi.cpp")
-
-
 # ---- the float64 reference --------------------------------------------------------------------------------------------------------------------
 def _flat_guides(h, w, normal=(0.0, 0.0, 1.0), depth=2.0, albedo=(0.5, 0.6, 0.7)):
     g0 = np.zeros((h, w, 4), np.float32)

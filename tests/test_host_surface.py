@@ -919,6 +919,26 @@ def test_committed_counters_belong_to_these_kernel_sources(built):
         bench.PROFILE_ROUNDS = rounds
 
 
+def test_context_struct_has_one_definition_and_it_is_hashed():
+    """`struct trg_ctx` is defined once (csrc/trg_ctx.h) and every unit includes it: that the units agree is the compiler's job.  What the
+    compiler cannot see: that nobody writes a second copy, that the kernel-source hash still covers the definition (launch planning reads
+    its fields), and that the denoise and refit units keep their state on the context and not in a table beside it."""
+    from toyraygun_amd.srchash import kernel_source_files
+    defining = []
+    for top in (os.path.join(ROOT, "toyraygun_amd", "csrc"), os.path.join(ROOT, "experiments")):
+        for d, _, files in os.walk(top):
+            for f in files:
+                if f.endswith((".h", ".hip", ".cpp", ".c", ".inc")):
+                    with open(os.path.join(d, f), errors="replace") as fh:
+                        if re.search(r"^struct trg_ctx \{", fh.read(), re.M):
+                            defining.append(os.path.join(d, f))
+    assert len(defining) == 1, defining
+    assert os.path.realpath(defining[0]) in [os.path.realpath(p) for p in kernel_source_files()]
+    for unit in ("trg_denoise.hip", "trg_refit.hip"):
+        with open(os.path.join(ROOT, "toyraygun_amd", "csrc", unit)) as fh:
+            assert "unordered_map" not in fh.read(), unit
+
+
 def test_every_tile_order_is_a_bijection(built):
     """TRG_OPT_TILE_ORDER (host replica of the kernels' slot -> tile map, trg_kernels.h tile_of_slot): for every order the valid slots of
     a launch cover every tile exactly once; the XCD-aware orders pad by less than one column / row of tiles per region, give the slots

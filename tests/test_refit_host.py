@@ -43,19 +43,6 @@ def test_render_abi_and_hashed_kernel_sources_are_untouched(built):
         assert json.load(f)["kernel_source_hash"] == kernel_source_hash()
 
 
-def test_context_struct_copy_matches_the_c_abi_unit():
-    """trg_refit.hip repeats `struct trg_ctx` of trg_capi.cpp, as trg_denoise.hip does: the same tokens."""
-    def body(path):
-        src = open(os.path.join(CSRC, path)).read()
-        m = re.search(r"^struct trg_ctx \{\n(.*?)^\};", src, re.S | re.M)
-        assert m, path
-        return [re.sub(r"\s+", " ", re.sub(r"//.*", "", l)).strip() for l in m.group(1).splitlines() if re.sub(r"//.*", "", l).strip()]
-    assert body("trg_refit.hip") == body("trg_capi.cpp")
-    # ... and the unit cross-checks the copy against the library's accessors before it touches anything
-    src = open(os.path.join(CSRC, "trg_refit.hip")).read()
-    assert "ctx_device(c) == c->device" in src and "ctx_current_stream(c) == (void *)c->stream" in src and "if (!ctx_ok(c)) return fail(" in src
-
-
 def test_refit_arithmetic_against_fresh_builds_under_sanitizers(tmp_path):
     """tests/helpers/refit_check.cpp as a program, with -fsanitize=address,undefined: scenes of a floor, 1 ... 700 cubes, lone triangles and lone quads
     are built with box leaves, moved (identity, small, large: per-cube rigid-plus-shear maps) and refitted by the header's functions in the order the

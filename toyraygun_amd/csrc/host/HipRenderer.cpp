@@ -81,9 +81,8 @@ bool HipRenderer::init() {
 
 void HipRenderer::destroy() {
     if (m_ctx) flush();
-    // (the denoise and refit scratch is not trg_destroy's)
-    if (m_group) { for (int r = 0; r < trg_group_size(m_group); ++r) trg_refit_release(trg_group_ctx(m_group, r)); trg_group_destroy(m_group); }   // owns every context, m_ctx included
-    else if (m_ctx) { trg_denoise_release(m_ctx); trg_refit_release(m_ctx); trg_destroy(m_ctx); }
+    if (m_group) trg_group_destroy(m_group);   // owns every context, m_ctx included
+    else if (m_ctx) trg_destroy(m_ctx);
     m_group = nullptr;
     m_ctx = nullptr;
     m_sceneLoaded = false;

@@ -11,13 +11,12 @@
 #include <cstdarg>
 #include <cstdio>
 #include <initializer_list>
-#include <mutex>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/trg_denoise.h"
 #include "bvh_build.h"
+#include "trg_ctx.h"
 #include "trg_internal.h"
 #include "trg_kernels.h"
 
@@ -25,70 +24,6 @@
 #pragma clang fp contract(off)
 
 using namespace trg;
-
-// ---------------------------------------------------------------------------------------------------------------------------------------------
-// The context.  trg_capi.cpp keeps `struct trg_ctx` to itself, and the kernel-source hash that ties the committed profiler counters to the
-// render path covers that file, so this unit REPEATS the definition, token for token (the same class defined twice with the same tokens is one
-// class).  tests/test_denoise_host.py compares the two texts, and ctx_ok() below cross-checks three fields against the library's own accessors
-// before anything is touched: whoever changes the struct over there is told to change it here.
-// ---------------------------------------------------------------------------------------------------------------------------------------------
-// BEGIN trg_ctx (copy of trg_capi.cpp)
-struct trg_ctx {
-    int device = 0;
-    uint32_t w = 0, h = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t fence[8] = {};
-    bool fence_set[8] = {};
-    float *accum_own = nullptr, *accum = nullptr;
-    uint32_t *offsets = nullptr;
-    unsigned long long *counters = nullptr;
-    unsigned char *blob = nullptr;
-    unsigned char *tex_mem = nullptr;   // uv | ids | table | texels (trg_load_textures)
-    TexDesc tex{};
-    // global overflow levels of the traversal stacks (grow-only), one buffer per launch the caller keeps in flight
-    // (TRG_OPT_LAUNCHES_IN_FLIGHT): launch k uses slot k mod in_flight, so overlapping launches never share one
-    static constexpr int kScratchSlots = 16;
-    hipStream_t slot_stream[kScratchSlots] = {};   // which stream owns scratch slot k (slot 0 = the context's own stream)
-    int slots_used = 1;
-    int *stack_scratch[kScratchSlots] = {};
-    size_t stack_scratch_bytes[kScratchSlots] = {};
-    // wavefront schedule: path state + ray queues of one batch, one set per launch in flight (grow-only)
-    unsigned char *wf_mem[kScratchSlots] = {};
-    size_t wf_bytes[kScratchSlots] = {};
-    int cu_count = 256;
-    uint32_t *xq = nullptr;   // kScratchSlots x 8 job-queue heads of the persistent regeneration launches (TRG_OPT_TILE_ORDER 64 + n), one set per stream
-    uint32_t bvh_depth4 = 0, bvh_nodes4 = 0;
-    SceneDesc sc{};
-    bool scene_loaded = false, have_uniforms = false, have_offsets = false;
-    trg_uniforms u{};
-    bool opt_strict = false, opt_counters = false, opt_force_global = false, opt_timing = true;
-    int opt_kernel = TRG_KERNEL_AUTO;
-    uint32_t last_kernel = TRG_KERNEL_DIRECT;
-    uint32_t last_tail_k = 0;
-    int opt_gpu_build = 0;   // TRG_OPT_GPU_BUILD: 0 host SAH, 1 device binned SAH, 2 device LBVH (Karras), 3 device PLOC
-    int opt_fsplit = 0;  // 0 = auto
-    int opt_tail = -1;   // TRG_OPT_TAIL_BOUNCE: -1 auto, 0 off, K
-    int opt_regen = -1;        // TRG_OPT_REGEN: 1 = path regeneration for HBM-resident scenes (direct kernel, frame-serial), -1 = from 32,768 triangles on, 0 = the lock-step kernel
-    uint32_t last_regen = 0;
-    int opt_tail_levels = 0;   // TRG_OPT_TAIL_LEVELS: 0 = re-compact every second bounce after K, 1 = once at K only
-    int opt_in_flight = 1;  // launches of this context the caller keeps in flight (TRG_OPT_LAUNCHES_IN_FLIGHT)
-    int opt_stack_levels = (int)TRG_STACK_LDS_LEVELS;   // TRG_OPT_STACK_LDS_LEVELS
-    int opt_tail_sort = 0;     // TRG_OPT_TAIL_SORT: 0 off, 1 direction octant, 2 / 3 octant + origin cell of a 2^3 / 4^3 grid
-    int opt_tail_refill = -1;  // TRG_OPT_TAIL_REFILL: 1 = the tail launches run ONE bounce each with in-wave refill (render_rtail_kernel); -1 = the library's choice
-    float scene_lo[3] = { 0.f, 0.f, 0.f }, scene_hi[3] = { 1.f, 1.f, 1.f };   // bounds of the loaded scene (tail sort: the origin grid)
-    int opt_tile_order = -1;   // TRG_OPT_TILE_ORDER: -1 auto, 0 image columns centre-out, 1 / 2 / 4 / 8 XCD regions with that many column strips
-    uint32_t last_xcd_cols = 0;
-    double last_build_ms = 0.0;
-    bool gpu_built = false;
-    uint32_t bvh_nodes = 0, bvh_depth = 0, bvh_leaves = 0, bvh_quads = 0, bvh_boxes = 0;
-    double last_ms = 0.0, total_ms = 0.0;
-    uint32_t renders = 0;
-    uint32_t last_fsplit = 1;
-    uint32_t launches = 0;   // trg_render launches since create (never reset: picks the scratch slot)
-    std::string err;
-};
-// END trg_ctx
 
 namespace {
 
@@ -129,16 +64,10 @@ int launch_tiles(trg_ctx *c, const char *who, Kernel kernel, Args... args) {
 // the instantiation of a kernel template for the context's build setting (STRICT is its first parameter): the arguments are written once
 #define DN_FOR_SETTING(c, kernel, ...) ((c)->opt_strict ? kernel<true, ##__VA_ARGS__> : kernel<false, ##__VA_ARGS__>)
 
-// the copy of the struct above against what the library itself says about the context
-bool ctx_ok(trg_ctx *c) {
-    void *acc = nullptr;
-    return c && ctx_device(c) == c->device && ctx_current_stream(c) == (void *)c->stream && trg_accum_device_ptr(c, &acc) == TRG_OK && acc == (void *)c->accum &&
-           c->w != 0 && c->h != 0;
-}
+}  // namespace
 
-// ---- per-context state (grow-only device scratch); trg_ctx has no room for it, so it is kept beside the contexts ----
-struct DenoiseState {
-    int device = 0;
+// ---- per-context state (grow-only device scratch): trg_ctx::denoise, created on first use, freed by denoise_state_free ----
+struct trg::DenoiseState {
     size_t pixels = 0;             // what rays / isect / ping / pong / guides are sized for
     trg_ray *rays = nullptr;
     trg_isect *isect = nullptr;
@@ -177,8 +106,8 @@ struct DenoiseState {
     trg_ray *rays_j = nullptr;
     trg_isect *isect_j = nullptr;
 };
-std::mutex g_mutex;
-std::unordered_map<trg_ctx *, DenoiseState> g_states;
+
+namespace {
 
 // every device buffer of a state, as f(pointer, bytes per pixel that state_of allocates with the state -- 0: the buffer is allocated on first use)
 template <typename F>
@@ -187,11 +116,6 @@ void each_buffer(DenoiseState &s, F f) {
     f(s.fguide, sizeof(float4));
     f(s.result, 0); f(s.rec_of_prim, 0); f(s.overflow, 0); f(s.half_acc, 0); f(s.halves, 0); f(s.hist[0], 0); f(s.hist[1], 0); f(s.timg, 0); f(s.tpos, 0);
     f(s.prev_geo, 0); f(s.tmotion, 0); f(s.rays_j, 0); f(s.isect_j, 0);
-}
-
-void free_state(DenoiseState &s) {
-    each_buffer(s, [](auto *mem, size_t) { (void)hipFree(mem); });
-    s = DenoiseState{};
 }
 
 template <typename T>
@@ -204,21 +128,23 @@ int grow(trg_ctx *c, T *&mem, size_t &have, size_t need, size_t elem, const char
     return TRG_OK;
 }
 
-// the state of a context, with the image-sized buffers allocated (a context is used by one host thread: trg.h)
+// the state of a context that owns no image yet (pixels == 0): what the setters need (a context is used by one host thread: trg.h)
+DenoiseState &bare_state(trg_ctx *c) {
+    if (!c->denoise) c->denoise = new DenoiseState;
+    return *c->denoise;
+}
+
+// the state of a context, with the image-sized buffers allocated
 int state_of(trg_ctx *c, DenoiseState *&out) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DenoiseState &s = g_states[c];
-    const size_t n = (size_t)c->w * c->h;
-    if (s.device != c->device || s.pixels != n) {   // a new context at the address of one that was destroyed without a release
-        if (s.pixels) { (void)hipDeviceSynchronize(); free_state(s); }
-        s.device = c->device;
+    DenoiseState &s = bare_state(c);
+    if (!s.pixels) {
+        const size_t n = (size_t)c->w * c->h;
         hipError_t e = hipSuccess;
         each_buffer(s, [&](auto *&mem, size_t per_pixel) {
             if (per_pixel && e == hipSuccess) e = hipMalloc((void **)&mem, n * per_pixel);
         });
         if (e != hipSuccess) {
-            free_state(s);
-            g_states.erase(c);
+            denoise_state_free(c);   // (`s` is gone from here on, and with it what the setters had set: as it always was on this path)
             return fail(c, TRG_ERR_NOMEM, "denoise: hipMalloc of the scratch images failed: %s", hipGetErrorString(e));
         }
         s.pixels = n;
@@ -1432,7 +1358,6 @@ int own_result(trg_ctx *c, DenoiseState &s, const char *who) {
 
 int enter(trg_ctx *c, DenoiseState *&s, const char *who) {
     if (!c) return TRG_ERR_INVALID;
-    if (!ctx_ok(c)) return fail(c, TRG_ERR_INVALID, "%s: the denoiser's view of the context does not match the library's", who);
     DN_HIPCHK(c, hipSetDevice(c->device));
     return state_of(c, s);
 }
@@ -1514,6 +1439,15 @@ int temporal_host(trg_ctx *c, const char *who, const float *color, const float *
 
 }  // namespace
 
+void trg::denoise_state_free(trg_ctx *c) {
+    if (!c->denoise) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    each_buffer(*c->denoise, [](auto *mem, size_t) { (void)hipFree(mem); });
+    delete c->denoise;
+    c->denoise = nullptr;
+}
+
 extern "C" {
 
 void trg_denoise_default_params(trg_denoise_params *p) {
@@ -1554,13 +1488,7 @@ int trg_denoise_accum(trg_ctx *c, uint32_t frameIndex, const trg_denoise_params 
 
 int trg_denoise_release(trg_ctx *c) {
     if (!c) return TRG_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(g_mutex);
-    auto it = g_states.find(c);
-    if (it == g_states.end()) return TRG_OK;
-    (void)hipSetDevice(it->second.device);
-    (void)hipDeviceSynchronize();
-    free_state(it->second);
-    g_states.erase(it);
+    denoise_state_free(c);
     return TRG_OK;
 }
 
@@ -1657,12 +1585,10 @@ int trg_guides_render_pos(trg_ctx *c, uint32_t frameIndex, void *guides_device, 
 int trg_temporal_reset(trg_ctx *c) {
     if (!c) return TRG_ERR_INVALID;
     // allocates nothing: a context that never denoised has no state, and a new state starts without history anyway
-    std::lock_guard<std::mutex> lock(g_mutex);
-    auto it = g_states.find(c);
-    if (it == g_states.end()) return TRG_OK;
-    it->second.hist_valid = false;
-    it->second.have_prev_vp = false;
-    it->second.armed = false;
+    if (!c->denoise) return TRG_OK;
+    c->denoise->hist_valid = false;
+    c->denoise->have_prev_vp = false;
+    c->denoise->armed = false;
     return TRG_OK;
 }
 
@@ -1765,12 +1691,9 @@ int trg_temporal_denoise_motion_host(trg_ctx *c, const float *color_in_host, con
 
 int trg_temporal_set_lag_correction(trg_ctx *c, float gate) {
     if (!c) return TRG_ERR_INVALID;
-    if (!ctx_ok(c)) return fail(c, TRG_ERR_INVALID, "trg_temporal_set_lag_correction: the denoiser's view of the context does not match the library's");
     if (gate != gate) return fail(c, TRG_ERR_INVALID, "trg_temporal_set_lag_correction: gate is NaN");
     // allocates nothing: a state created here owns no image yet (pixels == 0), and state_of fills it in on the first call that denoises
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DenoiseState &s = g_states[c];
-    if (!s.pixels) s.device = c->device;
+    DenoiseState &s = bare_state(c);
     s.lag_gate = gate;
     return TRG_OK;
 }
@@ -1778,19 +1701,14 @@ int trg_temporal_set_lag_correction(trg_ctx *c, float gate) {
 int trg_temporal_lag_correction(trg_ctx *c, float *gate) {
     if (!c) return TRG_ERR_INVALID;
     if (!gate) return fail(c, TRG_ERR_INVALID, "trg_temporal_lag_correction: gate is NULL");
-    std::lock_guard<std::mutex> lock(g_mutex);
-    auto it = g_states.find(c);
-    *gate = it == g_states.end() ? -1.0f : it->second.lag_gate;
+    *gate = c->denoise ? c->denoise->lag_gate : -1.0f;
     return TRG_OK;
 }
 
 int trg_temporal_set_variance_of_mean(trg_ctx *c, int on) {
     if (!c) return TRG_ERR_INVALID;
-    if (!ctx_ok(c)) return fail(c, TRG_ERR_INVALID, "trg_temporal_set_variance_of_mean: the denoiser's view of the context does not match the library's");
     // allocates nothing, like the gate above
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DenoiseState &s = g_states[c];
-    if (!s.pixels) s.device = c->device;
+    DenoiseState &s = bare_state(c);
     if (s.track == (on != 0)) return TRG_OK;
     s.track = on != 0;
     // a change is a reset: a history written with the setting off has no variance in it (and one written with it on has, where 0 is promised)
@@ -1803,9 +1721,7 @@ int trg_temporal_set_variance_of_mean(trg_ctx *c, int on) {
 int trg_temporal_variance_of_mean(trg_ctx *c, int *on) {
     if (!c) return TRG_ERR_INVALID;
     if (!on) return fail(c, TRG_ERR_INVALID, "trg_temporal_variance_of_mean: on is NULL");
-    std::lock_guard<std::mutex> lock(g_mutex);
-    auto it = g_states.find(c);
-    *on = it != g_states.end() && it->second.track ? 1 : 0;
+    *on = c->denoise && c->denoise->track ? 1 : 0;
     return TRG_OK;
 }
 
@@ -1831,12 +1747,9 @@ int trg_guides_centre_motion_read(trg_ctx *c, uint32_t frameIndex, float plane_t
 
 int trg_temporal_set_coverage(trg_ctx *c, float cov_min) {
     if (!c) return TRG_ERR_INVALID;
-    if (!ctx_ok(c)) return fail(c, TRG_ERR_INVALID, "trg_temporal_set_coverage: the denoiser's view of the context does not match the library's");
     if (!(cov_min < 1.0f)) return fail(c, TRG_ERR_INVALID, "trg_temporal_set_coverage: cov_min must be below 1 (negative: off)");   // (NaN too)
     // allocates nothing, like the gate above
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DenoiseState &s = g_states[c];
-    if (!s.pixels) s.device = c->device;
+    DenoiseState &s = bare_state(c);
     if (s.cov_min == cov_min || (s.cov_min < 0.0f && cov_min < 0.0f)) return TRG_OK;
     s.cov_min = cov_min;
     // a change is a reset: a history written with the setting off has no coverage in it and comes from other guides
@@ -1849,9 +1762,7 @@ int trg_temporal_set_coverage(trg_ctx *c, float cov_min) {
 int trg_temporal_coverage(trg_ctx *c, float *cov_min) {
     if (!c) return TRG_ERR_INVALID;
     if (!cov_min) return fail(c, TRG_ERR_INVALID, "trg_temporal_coverage: cov_min is NULL");
-    std::lock_guard<std::mutex> lock(g_mutex);
-    auto it = g_states.find(c);
-    *cov_min = it == g_states.end() ? -1.0f : it->second.cov_min;
+    *cov_min = c->denoise ? c->denoise->cov_min : -1.0f;
     return TRG_OK;
 }
 

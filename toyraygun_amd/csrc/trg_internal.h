@@ -20,4 +20,8 @@ void *ctx_current_stream(trg_ctx *c);         // the stream trg_render launches 
 int ctx_device(const trg_ctx *c);
 void ctx_forget_streams(trg_ctx *c);          // a DRAINED context forgets which streams owned its per-stream scratch slots (their buffers stay)
 
+// what trg_destroy needs from trg_denoise.hip / trg_refit.hip: set the device, wait for it, free the unit's state of the context (trg_ctx.h), if any
+void denoise_state_free(trg_ctx *c);
+void refit_state_free(trg_ctx *c);
+
 }  // namespace trg

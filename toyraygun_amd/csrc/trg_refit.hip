@@ -7,80 +7,16 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <mutex>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/trg_refit.h"
+#include "trg_ctx.h"
 #include "trg_internal.h"
 #include "trg_kernels.h"
 #include "trg_refit_math.h"
 
 using namespace trg;
-
-// ---------------------------------------------------------------------------------------------------------------------------------------------
-// The context.  trg_capi.cpp keeps `struct trg_ctx` to itself and its text is part of the kernel-source hash, so this unit REPEATS the definition,
-// token for token, as trg_denoise.hip does (the same class defined twice with the same tokens is one class).  tests/test_refit_host.py compares
-// the two texts, and ctx_ok() below cross-checks the copy against the library's own accessors before anything is touched.
-// ---------------------------------------------------------------------------------------------------------------------------------------------
-// BEGIN trg_ctx (copy of trg_capi.cpp)
-struct trg_ctx {
-    int device = 0;
-    uint32_t w = 0, h = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t fence[8] = {};
-    bool fence_set[8] = {};
-    float *accum_own = nullptr, *accum = nullptr;
-    uint32_t *offsets = nullptr;
-    unsigned long long *counters = nullptr;
-    unsigned char *blob = nullptr;
-    unsigned char *tex_mem = nullptr;   // uv | ids | table | texels (trg_load_textures)
-    TexDesc tex{};
-    // global overflow levels of the traversal stacks (grow-only), one buffer per launch the caller keeps in flight
-    // (TRG_OPT_LAUNCHES_IN_FLIGHT): launch k uses slot k mod in_flight, so overlapping launches never share one
-    static constexpr int kScratchSlots = 16;
-    hipStream_t slot_stream[kScratchSlots] = {};   // which stream owns scratch slot k (slot 0 = the context's own stream)
-    int slots_used = 1;
-    int *stack_scratch[kScratchSlots] = {};
-    size_t stack_scratch_bytes[kScratchSlots] = {};
-    // wavefront schedule: path state + ray queues of one batch, one set per launch in flight (grow-only)
-    unsigned char *wf_mem[kScratchSlots] = {};
-    size_t wf_bytes[kScratchSlots] = {};
-    int cu_count = 256;
-    uint32_t *xq = nullptr;   // kScratchSlots x 8 job-queue heads of the persistent regeneration launches (TRG_OPT_TILE_ORDER 64 + n), one set per stream
-    uint32_t bvh_depth4 = 0, bvh_nodes4 = 0;
-    SceneDesc sc{};
-    bool scene_loaded = false, have_uniforms = false, have_offsets = false;
-    trg_uniforms u{};
-    bool opt_strict = false, opt_counters = false, opt_force_global = false, opt_timing = true;
-    int opt_kernel = TRG_KERNEL_AUTO;
-    uint32_t last_kernel = TRG_KERNEL_DIRECT;
-    uint32_t last_tail_k = 0;
-    int opt_gpu_build = 0;   // TRG_OPT_GPU_BUILD: 0 host SAH, 1 device binned SAH, 2 device LBVH (Karras), 3 device PLOC
-    int opt_fsplit = 0;  // 0 = auto
-    int opt_tail = -1;   // TRG_OPT_TAIL_BOUNCE: -1 auto, 0 off, K
-    int opt_regen = -1;        // TRG_OPT_REGEN: 1 = path regeneration for HBM-resident scenes (direct kernel, frame-serial), -1 = from 32,768 triangles on, 0 = the lock-step kernel
-    uint32_t last_regen = 0;
-    int opt_tail_levels = 0;   // TRG_OPT_TAIL_LEVELS: 0 = re-compact every second bounce after K, 1 = once at K only
-    int opt_in_flight = 1;  // launches of this context the caller keeps in flight (TRG_OPT_LAUNCHES_IN_FLIGHT)
-    int opt_stack_levels = (int)TRG_STACK_LDS_LEVELS;   // TRG_OPT_STACK_LDS_LEVELS
-    int opt_tail_sort = 0;     // TRG_OPT_TAIL_SORT: 0 off, 1 direction octant, 2 / 3 octant + origin cell of a 2^3 / 4^3 grid
-    int opt_tail_refill = -1;  // TRG_OPT_TAIL_REFILL: 1 = the tail launches run ONE bounce each with in-wave refill (render_rtail_kernel); -1 = the library's choice
-    float scene_lo[3] = { 0.f, 0.f, 0.f }, scene_hi[3] = { 1.f, 1.f, 1.f };   // bounds of the loaded scene (tail sort: the origin grid)
-    int opt_tile_order = -1;   // TRG_OPT_TILE_ORDER: -1 auto, 0 image columns centre-out, 1 / 2 / 4 / 8 XCD regions with that many column strips
-    uint32_t last_xcd_cols = 0;
-    double last_build_ms = 0.0;
-    bool gpu_built = false;
-    uint32_t bvh_nodes = 0, bvh_depth = 0, bvh_leaves = 0, bvh_quads = 0, bvh_boxes = 0;
-    double last_ms = 0.0, total_ms = 0.0;
-    uint32_t renders = 0;
-    uint32_t last_fsplit = 1;
-    uint32_t launches = 0;   // trg_render launches since create (never reset: picks the scratch slot)
-    std::string err;
-};
-// END trg_ctx
 
 namespace {
 
@@ -98,13 +34,6 @@ int fail(trg_ctx *c, int code, const char *fmt, ...) {
         hipError_t e_ = (expr);                                                                                 \
         if (e_ != hipSuccess) return fail((c), TRG_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
-
-// the copy of the struct above against what the library itself says about the context
-bool ctx_ok(trg_ctx *c) {
-    void *acc = nullptr;
-    return c && ctx_device(c) == c->device && ctx_current_stream(c) == (void *)c->stream && trg_accum_device_ptr(c, &acc) == TRG_OK && acc == (void *)c->accum &&
-           c->w != 0 && c->h != 0 && ctx_gpu_build_option(c) == c->opt_gpu_build;
-}
 
 // ---- what the device reports back: the flag words and the bounds, read by the host in the call's one wait ----
 enum { kFlagIndex = 0, kFlagFinite = 1, kFlagQuad = 2, kFlagBox = 3, kFlagNode = 4, kCountQuads = 5 };
@@ -351,22 +280,23 @@ __global__ void rf_records_kernel(refit::Geo g, const float *nrm, View v, float 
         for (int k = 0; k < 9; ++k) { const float n = nrm[(size_t)prim * 9 + k]; mt[12 + k] = n; pl[14 + k] = n; }
 }
 
-// ---- per-context scratch (grow-only), kept beside the contexts like the denoiser's ----
+// ---- per-context scratch (grow-only): trg_ctx::refit, created on first use, freed by refit_state_free ----
 struct Buf {
     void *p = nullptr;
     size_t bytes = 0;
     template <typename T> T *as() const { return static_cast<T *>(p); }
 };
-struct RefitState {
-    int device = 0;
+}  // namespace
+
+struct trg::RefitState {
     Buf pos, idx, nrm, childbox, leafbox, ping, pong, qplain, qbox, quadx, boxrows, partial, hdr;
     Hdr host{};                    // what the host sends and reads back
     trg_refit_info last{};
     const void *area_blob = nullptr;   // the blob whose as-loaded areas are remembered, and what its arrays summed to after this unit's last write
     double loaded_area[2] = { 0.0, 0.0 }, written_area[2] = { 0.0, 0.0 };
 };
-std::mutex g_mutex;
-std::unordered_map<trg_ctx *, RefitState> g_states;
+
+namespace {
 
 template <typename F>
 void each_buffer(RefitState &s, F f) {
@@ -382,14 +312,8 @@ int grow(trg_ctx *c, Buf &b, size_t need, const char *what) {
     return TRG_OK;
 }
 RefitState &state_of(trg_ctx *c) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    RefitState &s = g_states[c];
-    if (s.device != c->device) {   // a new context at the address of one that was destroyed without a release
-        each_buffer(s, [](Buf &b) { if (b.p) (void)hipFree(b.p); });
-        s = RefitState{};
-        s.device = c->device;
-    }
-    return s;
+    if (!c->refit) c->refit = new RefitState;
+    return *c->refit;
 }
 
 inline dim3 blocks_for(size_t n) { return dim3((uint32_t)((n + kT - 1) / kT)); }
@@ -553,11 +477,19 @@ int refit_rebuild(trg_ctx *c, const float *pos, const float *nrm, const uint32_t
 
 }  // namespace
 
+void trg::refit_state_free(trg_ctx *c) {
+    if (!c->refit) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    each_buffer(*c->refit, [](Buf &b) { if (b.p) (void)hipFree(b.p); });
+    delete c->refit;
+    c->refit = nullptr;
+}
+
 extern "C" {
 
 int trg_refit_scene(trg_ctx *c, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris) {
     if (!c) return TRG_ERR_INVALID;
-    if (!ctx_ok(c)) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: this unit's view of the context does not match the library's");
 #if TRG_WIDE8
     return fail(c, TRG_ERR_INVALID, "trg_refit_scene: an 8-wide experiments build has no refit (reload the scene)");
 #endif
@@ -571,21 +503,13 @@ int trg_refit_scene(trg_ctx *c, const float *positions3, const float *normals3, 
 
 int trg_refit_last(trg_ctx *c, trg_refit_info *out) {
     if (!c || !out) return TRG_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(g_mutex);
-    auto it = g_states.find(c);
-    *out = it == g_states.end() ? trg_refit_info{} : it->second.last;
+    *out = c->refit ? c->refit->last : trg_refit_info{};
     return TRG_OK;
 }
 
 int trg_refit_release(trg_ctx *c) {
     if (!c) return TRG_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(g_mutex);
-    auto it = g_states.find(c);
-    if (it == g_states.end()) return TRG_OK;
-    (void)hipSetDevice(it->second.device);
-    (void)hipDeviceSynchronize();
-    each_buffer(it->second, [](Buf &b) { if (b.p) (void)hipFree(b.p); });
-    g_states.erase(it);
+    refit_state_free(c);
     return TRG_OK;
 }
 

@@ -32,7 +32,7 @@ through data_ptr() -- like trg_bind_accum -- and the call only enqueues on the c
 `reference_denoise_variance` (its iteration loop alone: `reference_atrous_variance`) and `reference_temporal` (with `reference_centre_rays` and `reference_agreement` for the centre guides) are the float64 numpy evaluations
 of the definitions in the header: what the GPU tests compare the kernels with.
 
-The context's denoise scratch lives until release(ctx); call it before ctx.close() (trg_destroy does not know about it).
+The context's denoise scratch belongs to the context: ctx.close() frees it, release(ctx) frees it earlier.
 """
 import ctypes as C
 import re

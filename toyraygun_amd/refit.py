@@ -9,7 +9,7 @@ a scene small enough for the LDS tier is rebuilt by the host builder (microsecon
 is not finite, a quad leaf or a box leaf of the loaded tree that the moved vertices no longer form -- raises capi.TrgError and leaves the loaded
 scene as it was; the text names the first offending triangle.
 
-The context's refit scratch lives until release(ctx); call it before ctx.close() (trg_destroy does not know about it).
+The context's refit scratch belongs to the context: ctx.close() frees it, release(ctx) frees it earlier.
 """
 import ctypes as C
 
