@@ -5,9 +5,11 @@
 //   * as a shared object (-DREFIT_SHARED, without bvh_build.cpp): the same steps behind a C interface, for tests that hold the arrays of the
 //     trg_debug_* entry points.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <random>
 #include <vector>
 
@@ -166,6 +168,26 @@ double rf_host_area(const uint32_t *nodes, uint32_t n_nodes) {
     for (uint32_t i = 0; i < n_nodes; ++i) s += refit::node_half_area(nodes + (size_t)i * 16);
     return s;
 }
+// the same sum in the order rf_area_kernel and rf_area_final_kernel add it: at most 1,024 blocks of 256 threads, every thread its strided share, the
+// tree over a block's 256 partial sums, then the blocks in order (doubles: the order decides the last bits)
+double rf_host_area_blocks(const uint32_t *nodes, uint32_t n_nodes) {
+    const uint32_t kT = 256, nb = std::min<uint32_t>(1024u, (n_nodes + kT - 1) / kT);
+    double total = 0.0;
+    for (uint32_t b = 0; b < nb; ++b) {
+        double sh[kT];
+        for (uint32_t t = 0; t < kT; ++t) {
+            sh[t] = 0.0;
+            for (uint64_t i = (uint64_t)b * kT + t; i < n_nodes; i += (uint64_t)nb * kT) {
+                const uint32_t *nd = nodes + (size_t)i * 16;
+                if ((nd[12] | nd[13] | nd[14] | nd[15]) != 0u) sh[t] += refit::node_half_area(nd);
+            }
+        }
+        for (uint32_t s = kT / 2; s > 0; s >>= 1)
+            for (uint32_t t = 0; t < s; ++t) sh[t] += sh[t + s];
+        total += sh[0];
+    }
+    return total;
+}
 
 }  // extern "C"
 
@@ -216,6 +238,37 @@ std::vector<float> moved(const Mesh &m, std::mt19937 &rng, double amount) {
     }
     return out;
 }
+// the same triangles as an INDEXED mesh: every corner of a body stored once, two vertices that no triangle names (one far outside the scene), and the
+// vertex buffer shuffled
+Mesh indexed_copy(const Mesh &m, std::mt19937 &rng) {
+    std::map<std::array<float, 4>, uint32_t> seen;
+    std::vector<std::array<float, 3>> verts;
+    std::vector<int> body;
+    std::vector<uint32_t> idx;
+    for (uint32_t i : m.idx) {
+        const std::array<float, 4> key = { (float)m.cube_of_vertex[i], m.pos[(size_t)i * 3], m.pos[(size_t)i * 3 + 1], m.pos[(size_t)i * 3 + 2] };
+        auto it = seen.find(key);
+        if (it == seen.end()) {
+            it = seen.emplace(key, (uint32_t)verts.size()).first;
+            verts.push_back({ key[1], key[2], key[3] }); body.push_back(m.cube_of_vertex[i]);
+        }
+        idx.push_back(it->second);
+    }
+    verts.push_back({ 1e6f, -1e6f, 1e6f }); body.push_back(-1);
+    verts.push_back({ 0.5f, 0.5f, 0.5f }); body.push_back(-1);
+    std::vector<uint32_t> perm(verts.size());
+    for (size_t v = 0; v < perm.size(); ++v) perm[v] = (uint32_t)v;
+    std::shuffle(perm.begin(), perm.end(), rng);
+    Mesh o;
+    o.mat = m.mat; o.cubes = m.cubes;
+    o.pos.resize(verts.size() * 3); o.cube_of_vertex.resize(verts.size());
+    for (size_t v = 0; v < verts.size(); ++v) {
+        for (int c = 0; c < 3; ++c) o.pos[(size_t)perm[v] * 3 + c] = verts[v][c];
+        o.cube_of_vertex[perm[v]] = body[v];
+    }
+    for (uint32_t i : idx) o.idx.push_back(perm[i]);
+    return o;
+}
 struct Arrays { std::vector<uint32_t> rec_prim; std::vector<BoxRef> boxes; };
 Arrays arrays_of(const Bvh &b) {
     Arrays a;
@@ -227,17 +280,27 @@ size_t words_differing(const std::vector<uint32_t> &x, const uint32_t *y) { size
 }  // namespace
 
 int main() {
-    std::mt19937 rng(11);
+    std::mt19937 rng_plain(11);
     std::uniform_real_distribution<float> U(-5.f, 5.f);
     bool all_ok = true;
     double worst_frame = 0.0;
-    for (int n : { 1, 2, 7, 60, 700 }) {
+    std::mt19937 rng_indexed(12);   // (the indexed scene draws from a generator of its own: the other scenes are the ones they always were)
+    struct Case { int n; bool indexed; };
+    for (const Case cs : { Case{ 1, false }, Case{ 2, false }, Case{ 7, false }, Case{ 60, false }, Case{ 60, true }, Case{ 700, false } }) {
+        const int n = cs.n;
+        std::mt19937 &rng = cs.indexed ? rng_indexed : rng_plain;
         Mesh m;
         const float fa[3] = { -6.f, -6.f, -6.f }, fe1[3] = { 12.f, 0.f, 0.f }, fe2[3] = { 0.f, 0.f, 12.f };
         add_quad(m, fa, fe1, fe2);                                        // a floor
         for (int i = 0; i < n; ++i) add_cube(m, U(rng), U(rng), U(rng), 0.1f + 0.02f * (float)(i % 9));
         for (int i = 0; i < 3 + n / 2; ++i) { float v[3][3]; for (auto &p : v) for (float &c : p) c = U(rng); add_tri(m, v); }
         for (int q = 0; q < 2; ++q) { const float a[3] = { U(rng), U(rng), U(rng) }, e1[3] = { 1.f, 0.25f, 0.f }, e2[3] = { 0.f, 0.5f, 2.f }; add_quad(m, a, e1, e2); }
+        if (cs.indexed) {
+            const size_t corners = m.pos.size() / 3;
+            m = indexed_copy(m, rng);
+            printf("indexed n %d: %zu corners are %zu vertices, two of them named by no triangle\n", n, corners, m.pos.size() / 3);
+            if (m.pos.size() / 3 >= corners) all_ok = false;
+        }
         const uint32_t nt = (uint32_t)m.mat.size(), nv = (uint32_t)(m.pos.size() / 3);
         Bvh b0;
         build_bvh(m.pos.data(), m.idx.data(), m.mat.data(), nt, b0, false, true);
@@ -248,6 +311,9 @@ int main() {
             const Geo g{ pos.data(), m.idx.data(), nv, nt };
             float lo[3], hi[3], center[3], pad;
             rf_host_bounds(pos.data(), m.idx.data(), nv, nt, lo, hi, center, &pad);
+            float ilo[3] = { INFINITY, INFINITY, INFINITY }, ihi[3] = { -INFINITY, -INFINITY, -INFINITY };   // the bounds are those of the vertices the triangles name
+            for (uint32_t i : m.idx) for (int a = 0; a < 3; ++a) { ilo[a] = std::min(ilo[a], pos[(size_t)i * 3 + a]); ihi[a] = std::max(ihi[a], pos[(size_t)i * 3 + a]); }
+            if (memcmp(lo, ilo, 12) || memcmp(hi, ihi, 12)) { printf("n %d motion %d: the bounds are not those of the indexed vertices\n", n, motion); all_ok = false; }
             std::vector<uint32_t> plain((size_t)b0.n_nodes4 * 16), boxf((size_t)b0.n_nodes4_box * 16);
             std::vector<uint8_t> quadx(n_rec, 0);
             bool ok = refit_array(g, b0.nodes4q.data(), b0.n_nodes4, A.rec_prim.data(), n_rec, nullptr, 0, passes, pad, plain.data(), quadx.data());

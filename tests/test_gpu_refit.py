@@ -69,11 +69,12 @@ def _move(refit, c, b, normals=True):
 HBM_KERNELS = (("lock-step", 0, 1), ("regen", 1, 1), ("frame-split", 0, 2))
 
 
-def _strict_bars(capi, O, c, scene, rays, what, kernels=HBM_KERNELS):
-    """Strict build: every kernel's frame and both kinds of trace records are the oracle's, bit for bit."""
+def _strict_bars(capi, O, c, scene, rays, what, kernels=HBM_KERNELS, uniforms=None):
+    """Strict build: every kernel's frame and both kinds of trace records are the oracle's, bit for bit.  uniforms: the block the context was given
+    (default: the one _ctx sets)."""
     O.set_trig_mode(O.TRIG_PORTABLE)
     try:
-        ref, rst = O.render(scene, W, H, SPP, BOUNCES)
+        ref, rst = O.render(scene, W, H, SPP, BOUNCES, uniforms=uniforms)
     finally:
         O.set_trig_mode(O.TRIG_LIBM)
     c.set_option(capi.OPT_STRICT, 1)
@@ -94,11 +95,11 @@ def _strict_bars(capi, O, c, scene, rays, what, kernels=HBM_KERNELS):
         c.set_option(capi.OPT_STRICT, 0)
 
 
-def _shipped_bars(capi, O, c, scene, b, rays, what, gpu_build=0):
+def _shipped_bars(capi, O, c, scene, b, rays, what, gpu_build=0, uniforms=None):
     """Shipped build: the frame inside fast_bar against the oracle; trace records against a fresh trg_load_scene of the moved geometry within
     DESIGN section 2's figures (distance 3e-6, weights 2e-5) wherever the two name the same primitive -- and they may name another one only where
     double precision cannot decide (margin below 1e-5, the rule of tests/test_gpu_parity.py test_intersector)."""
-    ref, _ = O.render(scene, W, H, SPP, BOUNCES)
+    ref, _ = O.render(scene, W, H, SPP, BOUNCES, uniforms=uniforms)
     c.set_option(capi.OPT_STRICT, 0)
     c.reset_stats()
     c.render(0, SPP, BOUNCES)
