@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+from tests.schedule_scenes import checker_texture as _checker_texture, uv_sphere as _uv_sphere
 from tests.util import TOL_FRAC, TOL_FRAC_C4, TOL_RMSE, edge_flip_allowance, image_metrics, make_ctx
 
 pytestmark = pytest.mark.gpu
@@ -1196,25 +1197,6 @@ def test_halton_table_path_of_the_shipped_megakernel(capi, O, ctx256, golden):
         ctx256.halton_table([1], [64])
 
 
-def _uv_sphere(nu, nv, radius, centre):
-    """Indexed UV sphere: vertices, unit normals, per-vertex colours (a smooth function of the normal), triangles."""
-    th = np.linspace(0.0, np.pi, nv + 1)
-    ph = np.linspace(0.0, 2 * np.pi, nu, endpoint=False)
-    n = np.array([[np.sin(t) * np.cos(p), np.cos(t), np.sin(t) * np.sin(p)] for t in th for p in ph])
-    v = n * radius + np.asarray(centre)
-    col = 0.15 + 0.7 * (0.5 + 0.5 * n[:, [0, 1, 2]]) * np.array([1.0, 0.8, 0.6])
-    tris = []
-    for a in range(nv):
-        for b in range(nu):
-            i0, i1 = a * nu + b, a * nu + (b + 1) % nu
-            j0, j1 = i0 + nu, i1 + nu
-            if a > 0:
-                tris.append((i0, i1, j0))      # at the poles one of the two triangles is degenerate: skip it
-            if a < nv - 1:
-                tris.append((i1, j1, j0))
-    return v.astype(np.float32), n.astype(np.float32), col.astype(np.float32), np.array(tris, np.uint32)
-
-
 @pytest.mark.parametrize("nu,nv,in_lds", [(8, 5, 1), (40, 24, 0)])
 def test_smooth_normal_vertex_colour_mesh(capi, O, nu, nv, in_lds):
     """VERDICT r01 missing #1 / weak #3: the barycentric interpolation of Raytracing.metal:95-112 (a8) was only ever fed
@@ -2032,15 +2014,6 @@ def test_interleaved_bands_render_the_same_frame(capi, O, cornell, schedule):
             assert st.last_regen == (1 if schedule == "hbm_regen" else 0) and st.scene_in_lds == (0 if schedule.startswith("hbm") else 1)
         finally:
             c.close()
-
-
-def _checker_texture(n, cells, a, b, seed):
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:n, 0:n]
-    chk = ((xx * cells // n) + (yy * cells // n)) % 2
-    img = np.where(chk[..., None] == 0, np.array(a, np.uint8), np.array(b, np.uint8)).astype(np.uint8)
-    img = np.clip(img.astype(int) + rng.integers(-20, 21, img.shape), 0, 255).astype(np.uint8)   # every texel distinct-ish
-    return np.concatenate([img, np.full((n, n, 1), 255, np.uint8)], -1)
 
 
 @pytest.mark.parametrize("nu,nv,in_lds", [(8, 5, 1), (40, 24, 0)])
