@@ -33,6 +33,16 @@ public:
     void setRefit(bool on) { m_refit = on; }
     bool getRefit() const { return m_refit; }
     unsigned int getRefitCount() const { return m_refits; }    // updateScene calls that were served by a refit
+    // Poses (include/trg_pose.h): the loaded scene as OBJECTS that move by a matrix each, without a new Scene and without an upload of vertices.
+    // bindObjects, after loadScene of the same `scene`: object j is triangles [firstTri[j], firstTri[j + 1]) -- nObjects + 1 entries, ascending from
+    // 0 to the triangle count; no vertex may belong to two objects.  poseObjects: nObjects x 12 floats, row-major [A | t] per object, applied to the
+    // geometry AS BOUND (not to the last pose); the loaded tree is refitted on the device.  In temporal mode on one device the pose before this one
+    // is handed to trg_temporal_set_previous_scene_device from the pose unit's own buffers: the history follows without a host copy.  A pose the
+    // library refuses (no binding, a loadScene since, a quad or a box of the loaded tree that the posed vertices no longer form) says so on stdout
+    // and changes nothing.  Both return false when refused.
+    bool bindObjects(Scene *scene, const uint32_t *firstTri, unsigned int nObjects);
+    bool poseObjects(const float *xforms12);
+    unsigned int getPoseCount() const { return m_poses; }      // poseObjects calls that succeeded
     // One more sample per pixel into the running average.  ASYNCHRONOUS like the reference's (MetalRenderer.mm:373-552: encode,
     // commit, return; three frames in flight behind a semaphore, :33,377,385-387): the call never waits for the GPU to finish
     // a frame.  It takes a snapshot of the uniforms and either launches at once (GPU idle) or -- while earlier launches are
@@ -134,6 +144,8 @@ protected:
     bool m_refit = false, m_refitNow = false;
     size_t m_loadedTris = 0;
     unsigned int m_refits = 0;
+    unsigned int m_poses = 0;    // poses applied
+    uint32_t m_poseVerts = 0;    // the vertex count bound by bindObjects
 };
 
 }  // namespace toyraygun

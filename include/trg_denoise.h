@@ -315,6 +315,12 @@ TRG_API int trg_render_temporal_read(trg_ctx *ctx, uint32_t frameIndexBegin, uin
  *     returns TRG_ERR_INVALID, before anything is enqueued or the history changes, when they differ (a trg_load_scene in between). */
 TRG_API int trg_temporal_set_previous_scene(trg_ctx *ctx, const float *positions3, const float *normals3 /* may be NULL */, const uint32_t *indices,
                                             uint32_t n_verts, uint32_t n_tris);
+/*     The same from buffers that are ALREADY ON THE DEVICE (the context's; the layouts above), e.g. the current pose of include/trg_pose.h before
+ *     the next one is applied: the same records, written by one kernel on the context's stream, the same arming and the same refusals -- but
+ *     nothing is copied and NOTHING IS WAITED FOR: the caller must not write the buffers before the stream has passed the call.  The caller vouches
+ *     for the buffers; an index >= n_verts is not refused but clamped to the last vertex, so that nothing is read out of bounds. */
+TRG_API int trg_temporal_set_previous_scene_device(trg_ctx *ctx, const void *positions3_dev, const void *normals3_dev /* may be NULL */,
+                                                   const void *indices_dev, uint32_t n_verts, uint32_t n_tris);
 
 /* --- MOTION PLANES.  G0, G1 and X are written as trg_guides_render_pos writes them, bit for bit.  motion_device: TWO planes of width*height
  *     float4, M0 then M1.  With c0, c1 = the hit's trg_isect.coordinates, c2 = 1 - c0 - c1 (as for the guides) and P0', P1', P2' / N0', N1', N2'

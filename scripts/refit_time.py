@@ -1,6 +1,6 @@
 """Update time and render time of a refitted scene against a reloaded one (include/trg_refit.h).
 
-    python scripts/refit_time.py [--n 44] [--reps 5] [--w 1024 --h 768 --spp 4] [--out FILE]
+    python scripts/refit_time.py [--n 44] [--reps 5] [--w 1024 --h 768 --spp 4] [--legs refit,pose] [--parent-so FILE] [--out FILE]
 
 The Cornell box + n^3 cubes (n = 44: 1,022,244 triangles, n = 96: 10,616,868).  In ONE process, alternating, medians over `reps`:
 
@@ -8,6 +8,16 @@ The Cornell box + n^3 cubes (n = 44: 1,022,244 triangles, n = 96: 10,616,868).  
            as they are (identity) and with every cube moved by its own small translation -- each followed by a wait for the stream;
   render   ms per step of the tree as loaded, after an identity refit, after the small motion (with trg_refit_info's area ratio beside it) and
            of a fresh load of the moved geometry, for both builders.
+
+The pose leg (include/trg_pose.h; device builder): objects = the Cornell box + one per cube, every cube moved by the same small translation, now as a
+matrix.  Alternating, medians over `reps`, each call followed by a wait for the stream: trg_pose_apply; trg_refit_scene_device from torch tensors
+of the same posed geometry; trg_refit_scene from host arrays of it; and -- with --parent-so, the library of the parent commit built into a side
+directory -- that library's trg_refit_scene in a context of its own.  Beside them the render time per step after a pose, and what the posing costs
+on top of the refit it feeds (trg_pose_apply minus trg_refit_scene_device: the 48-byte-per-object upload and the kernel).  The pose kernel's OWN time
+is not a host-side figure: run this leg once more under a kernel trace,
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/refit_time.py --legs pose
+and read rf_pose_kernel's row of the kernel statistics (without --output-format the run leaves a results database whose `kernels` view has one
+row per launch with its duration in ns).
 
 Prints one JSON line (and writes it to --out)."""
 import argparse
@@ -20,7 +30,22 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from toyraygun_amd import capi, host, refit  # noqa: E402
+from toyraygun_amd import capi, host, pose, refit  # noqa: E402
+
+
+def parent_context(path, w, h, pos, nrm, col, idx, mat):
+    """A context of ANOTHER build of the library (ctypes keeps the two apart), device-built scene loaded: (library, handle)."""
+    import ctypes as C
+    L = C.CDLL(path)
+    for name, res, args in capi._SYMBOLS:
+        if hasattr(L, name):
+            getattr(L, name).restype, getattr(L, name).argtypes = res, args
+    L.trg_refit_scene.restype, L.trg_refit_scene.argtypes = C.c_int, [C.c_void_p] * 4 + [C.c_uint32] * 2
+    h_ctx = C.c_void_p()
+    assert L.trg_create(C.byref(h_ctx), 0, w, h) == 0
+    assert L.trg_set_option(h_ctx, capi.OPT_GPU_BUILD, 1) == 0
+    assert L.trg_load_scene(h_ctx, pos.ctypes.data, nrm.ctypes.data, col.ctypes.data, idx.ctypes.data, mat.ctypes.data, pos.shape[0], mat.shape[0]) == 0
+    return L, h_ctx
 
 
 def main():
@@ -31,6 +56,8 @@ def main():
     ap.add_argument("--h", type=int, default=768)
     ap.add_argument("--spp", type=int, default=4)
     ap.add_argument("--bounces", type=int, default=3)
+    ap.add_argument("--legs", default="refit,pose")
+    ap.add_argument("--parent-so", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -66,7 +93,7 @@ def main():
         return statistics.median(timed(lambda: c.render(0, a.spp, a.bounces)) for _ in range(a.reps)) / a.spp
 
     try:
-        for builder, name in ((0, "host"), (1, "device")):
+        for builder, name in ((0, "host"), (1, "device")) if "refit" in a.legs.split(",") else ():
             t = {"load": [], "refit_identity": [], "refit_moved": []}
             load(builder, pos0)
             refit.refit_scene(c, pos0, nrm, idx)                           # (the scratch is allocated once)
@@ -94,7 +121,45 @@ def main():
             r["render_fresh_moved_ms"] = render_ms()
             r["refit_last_ms_moved"] = info_moved["ms"]
             res[name] = r
-        res["refit_beats_device_rebuild"] = bool(res["device"]["refit_moved_ms"] < res["device"]["load_ms"] and res["host"]["refit_moved_ms"] < res["device"]["load_ms"])
+        if "device" in res:
+            res["refit_beats_device_rebuild"] = bool(res["device"]["refit_moved_ms"] < res["device"]["load_ms"] and res["host"]["refit_moved_ms"] < res["device"]["load_ms"])
+        if "pose" in a.legs.split(","):
+            import torch
+            first = np.concatenate([[0], 36 + 12 * np.arange(n_cubes + 1)]).astype(np.uint32)
+            x0 = np.tile(np.eye(3, 4, dtype=np.float32).reshape(1, 12), (n_cubes + 1, 1))
+            x1 = x0.copy()
+            x1[1:, [3, 7, 11]] = d
+            load(1, pos0)
+            pose.bind(c, pos0, nrm, idx, first)
+            pose.apply(c, x1)
+            got, _ = pose.read(c, pos0.shape[0], nt)
+            assert (got == pos1).all()                                     # the same posed geometry as the host arrays of the refit leg
+            t_pos, t_nrm, t_idx = torch.from_numpy(pos1).cuda(), torch.from_numpy(nrm).cuda(), torch.from_numpy(idx.view(np.int32)).cuda()
+            torch.cuda.synchronize()
+            parent = parent_context(a.parent_so, a.w, a.h, pos0, nrm, col, idx, mat) if a.parent_so else None
+            calls = {"pose_apply": lambda k: pose.apply(c, x1 if k % 2 == 0 else x0),          # alternating poses: nothing is a no-op
+                     "refit_scene_device": lambda k: pose.refit_scene_device(c, t_pos, t_nrm, t_idx),
+                     "refit_scene": lambda k: refit.refit_scene(c, pos1, nrm, idx)}
+            if parent:
+                PL, ph = parent
+                calls["parent_refit_scene"] = lambda k: (PL.trg_refit_scene(ph, pos1.ctypes.data, nrm.ctypes.data, idx.ctypes.data, pos1.shape[0], nt), PL.trg_sync(ph))
+            for f in calls.values():                                       # (scratch is allocated once)
+                f(0)
+            t = {k: [] for k in calls}
+            for k in range(a.reps):
+                for name, f in calls.items():
+                    t[name].append(timed(lambda: f(k)))
+            r = {k + "_ms": statistics.median(v) for k, v in t.items()}
+            r.update({k + "_ms_all": [round(x, 3) for x in v] for k, v in t.items()})
+            r["objects"] = int(n_cubes + 1)
+            r["upload_bytes"] = {"pose_apply": int(48 * (n_cubes + 1)), "refit_scene": int(pos1.nbytes + idx.nbytes + nrm.nbytes)}
+            r["posing_on_top_of_the_refit_ms"] = r["pose_apply_ms"] - r["refit_scene_device_ms"]    # upload of the matrices + rf_pose_kernel
+            pose.apply(c, x1)
+            r["render_after_pose_ms"] = render_ms()
+            r["pose_not_slower_than_refit_scene"] = bool(r["pose_apply_ms"] <= r["refit_scene_ms"])
+            res["pose"] = r
+            if parent:
+                PL.trg_destroy(ph)
     finally:
         refit.release(c)
         c.close()

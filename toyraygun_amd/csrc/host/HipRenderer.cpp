@@ -10,6 +10,7 @@
 #include "png_writer.h"
 #include "trg.h"
 #include "trg_denoise.h"
+#include "trg_pose.h"
 #include "trg_refit.h"
 
 namespace toyraygun {
@@ -189,6 +190,68 @@ void HipRenderer::updateScene(Scene *scene) {
         trg_temporal_reset(m_ctx);   // the history cannot be followed: start over, as loadScene does
         m_temporalOut = nullptr;
     }
+}
+
+// a pose call on the one context, or on every context of the group in turn (what trg_group_pose_* do, after the same wait) -- done here so that
+// the text reported is that of the context which refused THIS call, not an older one another context still holds
+template <typename Call>
+static int poseEach(trg_group *group, trg_ctx *ctx, Call call, const char **text) {
+    *text = "";
+    if (!group) {
+        const int rc = call(ctx);
+        if (rc != TRG_OK) *text = trg_last_error(ctx);
+        return rc;
+    }
+    int rc = trg_group_sync(group);
+    if (rc != TRG_OK) { *text = trg_group_last_error(group); return rc; }
+    for (int r = 0; r < trg_group_size(group); ++r) {
+        trg_ctx *c = trg_group_ctx(group, r);
+        if (!c) return TRG_ERR_INVALID;
+        if ((rc = call(c)) != TRG_OK) { *text = trg_last_error(c); return rc; }
+    }
+    return TRG_OK;
+}
+
+bool HipRenderer::bindObjects(Scene *scene, const uint32_t *firstTri, unsigned int nObjects) {
+    if (!m_ctx || !scene || !m_sceneLoaded || !firstTri) return false;
+    flush();
+    const uint32_t nTris = (uint32_t)scene->m_materialIDBuffer.size();
+    const uint32_t nVerts = (uint32_t)scene->m_vertexBuffer.size();
+    if (!nVerts || !nTris || scene->m_indexBuffer.size() != (size_t)nTris * 3) return false;
+    // (a scene without a normal per corner is bound without normals: the loaded ones stay)
+    const float *pos = &scene->m_vertexBuffer[0].x, *nrm = scene->m_normalBuffer.size() == (size_t)nTris * 3 ? &scene->m_normalBuffer[0].x : nullptr;
+    const uint32_t *idx = &scene->m_indexBuffer[0];
+    const char *text = "";
+    const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) { return trg_pose_bind(c, pos, nrm, idx, nVerts, nTris, firstTri, nObjects); }, &text);
+    if (rc != TRG_OK) { printf("HipRenderer: objects not bound (%s)\n", text); fflush(stdout); }
+    else m_poseVerts = nVerts;
+    return rc == TRG_OK;
+}
+
+bool HipRenderer::poseObjects(const float *xforms12) {
+    if (!m_ctx || !m_sceneLoaded || !xforms12) return false;
+    flush();   // frames queued so far are rendered with the pose they were queued under
+    const char *text = "";
+    const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) { return trg_pose_apply(c, xforms12); }, &text);
+    if (rc != TRG_OK) {
+        printf("HipRenderer: pose refused (%s); nothing changed\n", text);
+        fflush(stdout);
+        return false;
+    }
+    ++m_poses;
+    // (updateScene's remembered vectors are no longer what the device holds: its next call loads)
+    m_lastPositions.clear(); m_lastNormals.clear(); m_lastIndices.clear();
+    if (m_denoiseTemporal && !m_group) {
+        // what was current is the unit's PREVIOUS pose now, and stays untouched through the next apply: the history is told where every triangle was
+        void *prevPos = nullptr, *prevNrm = nullptr, *idx = nullptr;
+        if (trg_pose_buffers(m_ctx, nullptr, nullptr, &idx, &prevPos, &prevNrm) != TRG_OK ||
+            trg_temporal_set_previous_scene_device(m_ctx, prevPos, prevNrm, idx, m_poseVerts, (uint32_t)m_loadedTris) != TRG_OK) {
+            printf("HipRenderer: %s\n", trg_last_error(m_ctx));
+            trg_temporal_reset(m_ctx);   // the history cannot be followed: start over, as loadScene does
+            m_temporalOut = nullptr;
+        }
+    }
+    return true;
 }
 
 // MetalRenderer.mm:340-371: inverse view-projection, fixed ceiling light, frame index.

@@ -1,6 +1,6 @@
 // main_cornell.cpp -- headless demo following the reference app's call order (reference src/main.cpp:16-98):
 // engine init -> three shaders -> renderer init -> camera -> Cornell box -> frame loop; then writes a PNG.
-//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [refit]]
+//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [refit|pose]]
 //     denoise=N    a-trous iterations of the written image, 0 = off (default)
 //     ,var         the variance-guided filter from two half-sample buffers
 //     ,temporal    the frames are rendered as `frames` calls of 1 spp, each a temporal step (reprojected history, temporal variance); the
@@ -16,6 +16,9 @@
 //                  ,temporal the history follows the moving box (trg_temporal_set_previous_scene), otherwise it is a plain loadScene
 //     refit        (with slide=D) HipRenderer::setRefit(true): updateScene refits the loaded scene from the moved vertices (trg_refit_scene,
 //                  include/trg_refit.h) instead of loading it again; the last line of output counts the refits
+//     pose         (with slide=D, not with refit) the box is bound once with the short box as an object of its own (HipRenderer::bindObjects) and
+//                  before call k the short box is moved by k * D through HipRenderer::poseObjects (include/trg_pose.h): 96 bytes go to the device,
+//                  not a scene; with ,temporal the history follows from the pose unit's own buffers.  The last line of output counts the poses
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -63,8 +66,8 @@ int main(int argc, char **argv) {
     int denoise = 0;
     bool denoiseVar = false, denoiseTemporal = false, varianceOfMean = false;
     double orbit = 0.0, slide = 0.0, lagGate = -1.0, coverMin = -1.0;
-    bool refit = false;
-    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [refit]]";
+    bool refit = false, pose = false;
+    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [refit|pose]]";
     for (int a = 6; a < argc; ++a) {
         if (strncmp(argv[a], "slide=", 6) == 0) {
             char *end = nullptr;
@@ -73,6 +76,7 @@ int main(int argc, char **argv) {
             continue;
         }
         if (strcmp(argv[a], "refit") == 0) { refit = true; continue; }
+        if (strcmp(argv[a], "pose") == 0) { pose = true; continue; }
         if (strncmp(argv[a], "orbit=", 6) == 0) {
             char *end = nullptr;
             orbit = strtod(argv[a] + 6, &end);
@@ -115,6 +119,8 @@ int main(int argc, char **argv) {
         }
     }
 
+    if (pose && refit) { std::cout << usage << std::endl; return -1; }
+
     Engine *engine = Engine::instance();
     engine->init(width, height);
     engine->setFrameBudget(frames);
@@ -149,6 +155,9 @@ int main(int argc, char **argv) {
     Scene *scene = createCornellBoxScene();
     renderer->loadScene(scene);
     hip->setBounces((unsigned int)bounces);
+    // pose: the short box (the first cube the scene adds: triangles 0 .. 11) is one object, everything else the other
+    const uint32_t firstTri[3] = { 0u, 12u, (uint32_t)scene->m_materialIDBuffer.size() };
+    if (pose && !hip->bindObjects(scene, firstTri, 2)) { std::cout << "the objects were refused" << std::endl; return -1; }
     const bx::Vec3 eye0(0.0f, 1.0f, 3.38f), at(0.0f, 1.0f, -1.0f);
     int call = 0;
     while (!engine->hasQuit()) {
@@ -159,7 +168,11 @@ int main(int argc, char **argv) {
             const double dx = (double)eye0.x - (double)at.x, dz = (double)eye0.z - (double)at.z;
             renderer->setCameraPosition(bx::Vec3((float)((double)at.x + dx * cos(t) + dz * sin(t)), eye0.y, (float)((double)at.z - dx * sin(t) + dz * cos(t))));
         }
-        if (slide != 0.0 && call > 0) {
+        if (pose && slide != 0.0 && call > 0) {
+            float x[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
+            x[3] = (float)((double)call * slide);
+            hip->poseObjects(x);
+        } else if (slide != 0.0 && call > 0) {
             Scene *moved = createSlidCornellBox((float)((double)call * slide));
             hip->updateScene(moved);
             delete moved;   // (the renderer borrows the scene for the call only)
@@ -171,5 +184,6 @@ int main(int argc, char **argv) {
     if (refit) printf("%u scene updates served by a refit\n", hip->getRefitCount());
     if (!hip->savePNG(out)) { std::cout << "Failed to write " << out << std::endl; return -1; }
     printf("wrote %s\n", out);
+    if (pose) printf("%u poses applied\n", hip->getPoseCount());
     return 0;
 }

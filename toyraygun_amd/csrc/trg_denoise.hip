@@ -345,6 +345,25 @@ int record_map(trg_ctx *c, DenoiseState &s, const char *who) {
 // One record per ORIGINAL primitive index, five float4: (P0.xyz P1.x) (P1.yz P2.xy) (P2.z N0.xyz) (N1.xyz N2.x) (N2.yz 0 0)
 constexpr uint32_t kPrevRecord = 5;
 
+// the records from buffers that are on the device already (trg_temporal_set_previous_scene_device), one thread per triangle.  An index out of range is
+// CLAMPED to the last vertex, as the refit unit clamps it: nothing is read out of bounds
+__global__ void dn_prev_pack_kernel(const float *pos, const float *nrm, const uint32_t *idx, uint32_t n_verts, uint32_t n_tris, float4 *prev) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tris) return;
+    float r[20];
+    for (int corner = 0; corner < 3; ++corner) {
+        uint32_t i = idx[(size_t)t * 3u + corner];
+        if (i >= n_verts) i = n_verts - 1u;
+        for (int k = 0; k < 3; ++k) {
+            r[corner * 3 + k] = pos[(size_t)i * 3u + k];
+            r[9 + corner * 3 + k] = nrm ? nrm[((size_t)t * 3u + corner) * 3u + k] : 0.0f;
+        }
+    }
+    r[18] = r[19] = 0.0f;
+    float4 *rec = prev + (size_t)t * kPrevRecord;
+    for (int q = 0; q < 5; ++q) rec[q] = make_float4(r[4 * q], r[4 * q + 1], r[4 * q + 2], r[4 * q + 3]);
+}
+
 // M0 = (the hit's barycentrics over the previous corners, 1), M1 = (the same over the previous normals, 0); zero on a miss -- the gather's test.
 // NORMALS = false: the previous scene came without normals, M1 = (G0.xyz, 0) and the two normal rows of the record are not read.
 template <bool NORMALS>
@@ -1667,6 +1686,33 @@ int trg_temporal_set_previous_scene(trg_ctx *c, const float *positions3, const f
     DN_HIPCHK(c, hipStreamSynchronize(c->stream));
     s->prev_tris = n_tris;
     s->prev_normals = normals3 != nullptr;
+    s->armed = true;
+    return TRG_OK;
+}
+
+int trg_temporal_set_previous_scene_device(trg_ctx *c, const void *positions3_dev, const void *normals3_dev, const void *indices_dev, uint32_t n_verts, uint32_t n_tris) {
+    const char *const who = "trg_temporal_set_previous_scene_device";
+    if (!c) return TRG_ERR_INVALID;
+    if (n_tris != 0 && (!positions3_dev || !indices_dev)) return fail(c, TRG_ERR_INVALID, "%s: positions3 / indices is NULL", who);
+    DenoiseState *s;
+    if (int rc = enter(c, s, who)) return rc;
+    if (!c->scene_loaded) return fail(c, TRG_ERR_INVALID, "%s: no scene loaded", who);
+    if (n_tris == 0) {
+        s->prev_tris = 0;
+        s->armed = false;
+        return TRG_OK;
+    }
+    if (n_tris != c->sc.n_tris) return fail(c, TRG_ERR_INVALID, "%s: %u triangles, the loaded scene has %u", who, n_tris, c->sc.n_tris);
+    if (n_verts == 0) return fail(c, TRG_ERR_INVALID, "%s: %u triangles and no vertices", who, n_tris);
+    if (int rc = grow(c, s->prev_geo, s->prev_cap, (size_t)n_tris * kPrevRecord, sizeof(float4), "previous scene")) {
+        s->prev_tris = 0;   // (the old array is gone)
+        s->armed = false;
+        return rc;
+    }
+    // ordered on the context's stream behind the launches that still read the array and in front of those that will; nothing is waited for
+    if (int rc = launch_each(c, who, dn_prev_pack_kernel, n_tris, positions3_dev, normals3_dev, indices_dev, n_verts, n_tris, s->prev_geo)) return rc;
+    s->prev_tris = n_tris;
+    s->prev_normals = normals3_dev != nullptr;
     s->armed = true;
     return TRG_OK;
 }

@@ -1,6 +1,8 @@
 // trg_refit.hip -- include/trg_refit.h: refit a loaded scene from new vertex positions.  A translation unit of its own beside the render path.
 // The arithmetic per record, per box and per node is trg_refit_math.h (host + device: the CPU tests evaluate the same functions); this file is the
-// kernels that apply it, the order they run in, and the small-scene path through the host builder.
+// kernels that apply it, the order they run in, and the small-scene path through the host builder.  include/trg_pose.h lives here too: it shares
+// refit_device and the context's RefitState -- the same refit from buffers already on the device, and the per-object poses that feed it
+// (arithmetic: trg_pose_math.h).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -10,10 +12,12 @@
 #include <string>
 #include <vector>
 
+#include "../../include/trg_pose.h"
 #include "../../include/trg_refit.h"
 #include "trg_ctx.h"
 #include "trg_internal.h"
 #include "trg_kernels.h"
+#include "trg_pose_math.h"
 #include "trg_refit_math.h"
 
 using namespace trg;
@@ -280,6 +284,37 @@ __global__ void rf_records_kernel(refit::Geo g, const float *nrm, View v, float 
         for (int k = 0; k < 9; ++k) { const float n = nrm[(size_t)prim * 9 + k]; mt[12 + k] = n; pl[14 + k] = n; }
 }
 
+// ---- include/trg_pose.h: one thread per vertex, then -- from the next whole block on, nrm_out != nullptr -- one per corner normal.  A thread
+//      reads its map word, its object's 12 floats and 12 bytes, and writes 12 bytes; as three dword accesses each: a vertex is only 4-byte aligned,
+//      and a wave's 64 lanes together still cover one contiguous 768-byte span, every cache line of it used whole ----
+__global__ void rf_pose_kernel(const float *rest_pos, const uint32_t *vtx_obj, uint32_t n_verts, const float *rest_nrm, const uint32_t *tri_obj, uint32_t n_corners,
+                               const float *xforms, float *pos_out, float *nrm_out) {
+    const uint32_t vertex_blocks = (n_verts + kT - 1) / kT;
+    if (blockIdx.x < vertex_blocks) {
+        const uint32_t v = blockIdx.x * kT + threadIdx.x;
+        if (v >= n_verts) return;
+        const uint32_t o = vtx_obj[v];
+        const float p[3] = { rest_pos[(size_t)v * 3], rest_pos[(size_t)v * 3 + 1], rest_pos[(size_t)v * 3 + 2] };
+        float q[3] = { p[0], p[1], p[2] };
+        if (o != pose::kNoObject) {
+            float m[12];
+            for (int k = 0; k < 12; ++k) m[k] = xforms[(size_t)o * 12 + k];
+            pose::point(m, p, q);
+        }
+        for (int k = 0; k < 3; ++k) pos_out[(size_t)v * 3 + k] = q[k];
+        return;
+    }
+    const uint32_t k = (blockIdx.x - vertex_blocks) * kT + threadIdx.x;
+    if (!nrm_out || k >= n_corners) return;
+    const uint32_t o = tri_obj[k / 3u];
+    float m[12];
+    for (int j = 0; j < 12; ++j) m[j] = xforms[(size_t)o * 12 + j];
+    const float n[3] = { rest_nrm[(size_t)k * 3], rest_nrm[(size_t)k * 3 + 1], rest_nrm[(size_t)k * 3 + 2] };
+    float q[3];
+    pose::normal(m, n, q);
+    for (int j = 0; j < 3; ++j) nrm_out[(size_t)k * 3 + j] = q[j];
+}
+
 // ---- per-context scratch (grow-only): trg_ctx::refit, created on first use, freed by refit_state_free ----
 struct Buf {
     void *p = nullptr;
@@ -294,13 +329,38 @@ struct trg::RefitState {
     trg_refit_info last{};
     const void *area_blob = nullptr;   // the blob whose as-loaded areas are remembered, and what its arrays summed to after this unit's last write
     double loaded_area[2] = { 0.0, 0.0 }, written_area[2] = { 0.0, 0.0 };
+    // include/trg_pose.h: the binding.  posed[cur] is the current pose, posed[prev] the one before, posed[3 - cur - prev] the copy the next apply
+    // poses into -- a refused refit then leaves current and previous alone
+    struct Pose {
+        Buf rest_pos, rest_nrm, idx, vtx_obj, tri_obj, xforms, posed[3], posed_nrm[3];
+        uint32_t n_verts = 0, n_tris = 0, n_objects = 0, cur = 0, prev = 1;
+        bool bound = false, has_nrm = false;
+        // the scene the binding was made for.  A HEURISTIC (trg_ctx.h has no load counter and stays as it is): its memory, its layout and -- a
+        // reload of as many bytes is usually handed the same address -- the time its build took, which every trg_load_scene measures anew
+        const void *blob = nullptr;
+        double build_ms = 0.0;
+        uint32_t blob_bytes = 0, n_nodes4 = 0, n_fat = 0, off_fat = 0;
+        bool same_scene(const trg_ctx *c) const {
+            return c->scene_loaded && blob == (const void *)c->blob && n_tris == c->sc.n_tris && build_ms == c->last_build_ms && blob_bytes == c->sc.blob_bytes &&
+                   n_nodes4 == c->sc.n_nodes4 && n_fat == c->sc.n_fat && off_fat == c->sc.off_fat;
+        }
+        void remember_scene(const trg_ctx *c) {
+            blob = c->blob; build_ms = c->last_build_ms; blob_bytes = c->sc.blob_bytes; n_nodes4 = c->sc.n_nodes4; n_fat = c->sc.n_fat; off_fat = c->sc.off_fat;
+        }
+    } pose;
 };
 
 namespace {
 
 template <typename F>
+void each_pose_buffer(RefitState &s, F f) {
+    RefitState::Pose &p = s.pose;
+    for (Buf *b : { &p.rest_pos, &p.rest_nrm, &p.idx, &p.vtx_obj, &p.tri_obj, &p.xforms, &p.posed[0], &p.posed[1], &p.posed[2], &p.posed_nrm[0], &p.posed_nrm[1], &p.posed_nrm[2] }) f(*b);
+}
+template <typename F>
 void each_buffer(RefitState &s, F f) {
     for (Buf *b : { &s.pos, &s.idx, &s.nrm, &s.childbox, &s.leafbox, &s.ping, &s.pong, &s.qplain, &s.qbox, &s.quadx, &s.boxrows, &s.partial, &s.hdr }) f(*b);
+    each_pose_buffer(s, f);
 }
 int grow(trg_ctx *c, Buf &b, size_t need, const char *what) {
     if (need <= b.bytes && b.p) return TRG_OK;
@@ -346,7 +406,9 @@ int refit_node_array(trg_ctx *c, RefitState &s, const refit::Geo &g, const View 
     return TRG_OK;
 }
 
-int refit_device(trg_ctx *c, const float *pos, const float *nrm, const uint32_t *idx, uint32_t n_verts, uint32_t n_tris) {
+// on_device: pos, nrm and idx are device memory of the context's device, read where they are; else host arrays, uploaded into scratch first.  That
+// upload is the only difference between the two.
+int refit_device(trg_ctx *c, const float *pos, const float *nrm, const uint32_t *idx, uint32_t n_verts, uint32_t n_tris, bool on_device) {
     const auto t0 = std::chrono::steady_clock::now();
     RefitState &s = state_of(c);
     const SceneDesc sc = c->sc;
@@ -361,8 +423,8 @@ int refit_device(trg_ctx *c, const float *pos, const float *nrm, const uint32_t 
         return fail(c, TRG_ERR_INVALID, "trg_refit_scene: the loaded scene's layout is not the one this unit knows");
 
     int rc = TRG_OK;
-    if ((rc = grow(c, s.pos, (size_t)n_verts * 12, "positions")) || (rc = grow(c, s.idx, (size_t)n_tris * 12, "indices")) ||
-        (nrm && (rc = grow(c, s.nrm, (size_t)n_tris * 36, "normals"))) || (rc = grow(c, s.childbox, (size_t)nmax * 96, "child boxes")) ||
+    if ((!on_device && ((rc = grow(c, s.pos, (size_t)n_verts * 12, "positions")) || (rc = grow(c, s.idx, (size_t)n_tris * 12, "indices")) ||
+                        (nrm && (rc = grow(c, s.nrm, (size_t)n_tris * 36, "normals"))))) || (rc = grow(c, s.childbox, (size_t)nmax * 96, "child boxes")) ||
         (rc = grow(c, s.leafbox, (size_t)nmax * 24, "leaf boxes")) || (rc = grow(c, s.ping, (size_t)nmax * 24, "node boxes")) ||
         (rc = grow(c, s.pong, (size_t)nmax * 24, "node boxes")) || (rc = grow(c, s.qplain, (size_t)n4 * kQ4NodeBytes, "nodes")) ||
         (has_box && (rc = grow(c, s.qbox, (size_t)n4b * kQ4NodeBytes, "box-flavour nodes"))) || (rc = grow(c, s.quadx, (size_t)sc.n_fat, "quad marks")) ||
@@ -371,9 +433,11 @@ int refit_device(trg_ctx *c, const float *pos, const float *nrm, const uint32_t 
         return rc;
 
     // step 1: upload
-    RF_HIPCHK(c, hipMemcpyAsync(s.pos.p, pos, (size_t)n_verts * 12, hipMemcpyHostToDevice, c->stream));
-    RF_HIPCHK(c, hipMemcpyAsync(s.idx.p, idx, (size_t)n_tris * 12, hipMemcpyHostToDevice, c->stream));
-    if (nrm) RF_HIPCHK(c, hipMemcpyAsync(s.nrm.p, nrm, (size_t)n_tris * 36, hipMemcpyHostToDevice, c->stream));
+    if (!on_device) {
+        RF_HIPCHK(c, hipMemcpyAsync(s.pos.p, pos, (size_t)n_verts * 12, hipMemcpyHostToDevice, c->stream));
+        RF_HIPCHK(c, hipMemcpyAsync(s.idx.p, idx, (size_t)n_tris * 12, hipMemcpyHostToDevice, c->stream));
+        if (nrm) RF_HIPCHK(c, hipMemcpyAsync(s.nrm.p, nrm, (size_t)n_tris * 36, hipMemcpyHostToDevice, c->stream));
+    }
     s.host = Hdr{};
     for (int k = 0; k < 5; ++k) s.host.flag[k] = kNone;
     RF_HIPCHK(c, hipMemcpyAsync(s.hdr.p, &s.host, sizeof(Hdr), hipMemcpyHostToDevice, c->stream));
@@ -381,8 +445,8 @@ int refit_device(trg_ctx *c, const float *pos, const float *nrm, const uint32_t 
 
     // step 2 (and everything that only READS the scene): bounds, checks, node boxes, quantised nodes and box frames into scratch
     Hdr *hdr = s.hdr.as<Hdr>();
-    const refit::Geo g{ s.pos.as<float>(), s.idx.as<uint32_t>(), n_verts, n_tris };
-    const float *d_nrm = nrm ? s.nrm.as<float>() : nullptr;
+    const refit::Geo g{ on_device ? pos : s.pos.as<float>(), on_device ? idx : s.idx.as<uint32_t>(), n_verts, n_tris };
+    const float *d_nrm = !nrm ? nullptr : on_device ? nrm : s.nrm.as<float>();
     const View v{ c->blob, sc.off_fat, sc.off_fat_planes, sc.off_boxrec, sc.n_fat, has_box ? sc.n_boxrec : 0u, n_tris };
     const uint32_t nb = std::min<uint32_t>(kMaxPartials, (n_tris + kT - 1) / kT);
     RF_LAUNCH(c, rf_bounds_kernel, dim3(nb), g, d_nrm, s.partial.as<float>(), hdr->flag);
@@ -475,6 +539,76 @@ int refit_rebuild(trg_ctx *c, const float *pos, const float *nrm, const uint32_t
     return rc;
 }
 
+// what both entry points check before they look at a buffer
+int refit_arguments(trg_ctx *c, const void *positions3, const void *indices, uint32_t n_verts, uint32_t n_tris) {
+#if TRG_WIDE8
+    return fail(c, TRG_ERR_INVALID, "trg_refit_scene: an 8-wide experiments build has no refit (reload the scene)");
+#endif
+    if (!c->scene_loaded || !c->blob) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: no scene loaded");
+    if (n_tris != c->sc.n_tris) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: %u triangles, the loaded scene has %u (a changed topology is a reload)", n_tris, c->sc.n_tris);
+    if (n_tris && (!positions3 || !indices || n_verts == 0)) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: null buffer");
+    RF_HIPCHK(c, hipSetDevice(c->device));
+    return TRG_OK;
+}
+
+// ---- include/trg_pose.h ----
+// `need` bytes from p on: device memory of the context's device, by the runtime's own records; nothing is enqueued
+int device_span(trg_ctx *c, const void *p, size_t need, const char *what) {
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, TRG_ERR_INVALID, "trg_refit_scene_device: %s: %p is not memory the device runtime knows", what, p);
+    }
+    if (attr.type != hipMemoryTypeDevice || attr.device != c->device)
+        return fail(c, TRG_ERR_INVALID, "trg_refit_scene_device: %s: %p is not device memory of device %d", what, p, c->device);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess || !base) {
+        (void)hipGetLastError();
+        return fail(c, TRG_ERR_INVALID, "trg_refit_scene_device: %s: no allocation holds %p", what, p);
+    }
+    const size_t at = (size_t)(static_cast<const char *>(p) - static_cast<const char *>(base));
+    if (at > size || size - at < need)
+        return fail(c, TRG_ERR_INVALID, "trg_refit_scene_device: %s: the allocation holds %zu bytes from %p on, the call reads %zu", what, at > size ? (size_t)0 : size - at, p, need);
+    return TRG_OK;
+}
+
+// buffers on the context's device (vouched for by the caller: device_span, or the pose unit's own): the device path reads them in place, a scene
+// of the LDS tier is rebuilt from a download of them
+int refit_from_device(trg_ctx *c, const float *pos, const float *nrm, const uint32_t *idx, uint32_t n_verts, uint32_t n_tris) {
+    if (c->sc.n_nodes == 0 && n_tris != 0) return refit_device(c, pos, nrm, idx, n_verts, n_tris, true);
+    std::vector<float> h_pos((size_t)n_verts * 3), h_nrm(nrm ? (size_t)n_tris * 9 : 0);
+    std::vector<uint32_t> h_idx((size_t)n_tris * 3);
+    if (n_tris) {
+        RF_HIPCHK(c, hipMemcpyAsync(h_pos.data(), pos, h_pos.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        RF_HIPCHK(c, hipMemcpyAsync(h_idx.data(), idx, h_idx.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        if (nrm) RF_HIPCHK(c, hipMemcpyAsync(h_nrm.data(), nrm, h_nrm.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        RF_HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return refit_rebuild(c, h_pos.data(), nrm ? h_nrm.data() : nullptr, h_idx.data(), n_verts, n_tris);
+}
+
+// the context's binding, or why there is none to use
+int pose_of(trg_ctx *c, const char *who, RefitState::Pose **out) {
+    if (!c) return TRG_ERR_INVALID;
+    if (!c->refit || !c->refit->pose.bound) return fail(c, TRG_ERR_INVALID, "%s: nothing bound (trg_pose_bind first)", who);
+    RefitState::Pose &p = c->refit->pose;
+    if (!p.same_scene(c))
+        return fail(c, TRG_ERR_INVALID, "%s: the binding was made for a scene that has been replaced since (bind again)", who);
+    RF_HIPCHK(c, hipSetDevice(c->device));
+    *out = &p;
+    return TRG_OK;
+}
+
+void pose_free(trg_ctx *c) {
+    if (!c->refit) return;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    each_pose_buffer(*c->refit, [](Buf &b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; });
+    c->refit->pose.bound = false;
+    c->refit->pose.blob = nullptr;
+}
+
 }  // namespace
 
 void trg::refit_state_free(trg_ctx *c) {
@@ -490,15 +624,155 @@ extern "C" {
 
 int trg_refit_scene(trg_ctx *c, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris) {
     if (!c) return TRG_ERR_INVALID;
-#if TRG_WIDE8
-    return fail(c, TRG_ERR_INVALID, "trg_refit_scene: an 8-wide experiments build has no refit (reload the scene)");
-#endif
-    if (!c->scene_loaded || !c->blob) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: no scene loaded");
-    if (n_tris != c->sc.n_tris) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: %u triangles, the loaded scene has %u (a changed topology is a reload)", n_tris, c->sc.n_tris);
-    if (n_tris && (!positions3 || !indices || n_verts == 0)) return fail(c, TRG_ERR_INVALID, "trg_refit_scene: null buffer");
-    RF_HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = refit_arguments(c, positions3, indices, n_verts, n_tris)) return rc;
     if (c->sc.n_nodes != 0 || n_tris == 0) return refit_rebuild(c, positions3, normals3, indices, n_verts, n_tris);
-    return refit_device(c, positions3, normals3, indices, n_verts, n_tris);
+    return refit_device(c, positions3, normals3, indices, n_verts, n_tris, false);
+}
+
+int trg_refit_scene_device(trg_ctx *c, const void *positions3_dev, const void *normals3_dev, const void *indices_dev, uint32_t n_verts, uint32_t n_tris) {
+    if (!c) return TRG_ERR_INVALID;
+    if (int rc = refit_arguments(c, positions3_dev, indices_dev, n_verts, n_tris)) return rc;
+    if (n_tris) {
+        int rc = TRG_OK;
+        if ((rc = device_span(c, positions3_dev, (size_t)n_verts * 12, "positions")) || (rc = device_span(c, indices_dev, (size_t)n_tris * 12, "indices")) ||
+            (normals3_dev && (rc = device_span(c, normals3_dev, (size_t)n_tris * 36, "normals"))))
+            return rc;
+    }
+    return refit_from_device(c, static_cast<const float *>(positions3_dev), static_cast<const float *>(normals3_dev), static_cast<const uint32_t *>(indices_dev), n_verts, n_tris);
+}
+
+int trg_pose_bind(trg_ctx *c, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris,
+                  const uint32_t *object_first_tri, uint32_t n_objects) {
+    if (!c) return TRG_ERR_INVALID;
+#if TRG_WIDE8
+    return fail(c, TRG_ERR_INVALID, "trg_pose_bind: an 8-wide experiments build has no poses");
+#endif
+    if (!c->scene_loaded || !c->blob) return fail(c, TRG_ERR_INVALID, "trg_pose_bind: no scene loaded");
+    if (n_tris != c->sc.n_tris) return fail(c, TRG_ERR_INVALID, "trg_pose_bind: %u triangles, the loaded scene has %u", n_tris, c->sc.n_tris);
+    if (!positions3 || !indices || !object_first_tri || n_verts == 0 || n_tris == 0 || n_objects == 0) return fail(c, TRG_ERR_INVALID, "trg_pose_bind: null or empty buffer");
+    uint32_t obj = 0, tri = 0, vert = 0;
+    switch (pose::table_check(object_first_tri, n_objects, n_tris, &obj)) {
+    case pose::kTableFirst: return fail(c, TRG_ERR_INVALID, "trg_pose_bind: object 0 begins at triangle %u, not at 0", object_first_tri[0]);
+    case pose::kTableOrder: return fail(c, TRG_ERR_INVALID, "trg_pose_bind: object %u begins at triangle %u and ends at %u: the table is not strictly ascending", obj, object_first_tri[obj], object_first_tri[obj + 1]);
+    case pose::kTableEnd: return fail(c, TRG_ERR_INVALID, "trg_pose_bind: object %u ends at triangle %u, the scene has %u", obj, object_first_tri[n_objects], n_tris);
+    default: break;
+    }
+    std::vector<uint32_t> tri_obj(n_tris), vtx_obj(n_verts);
+    pose::triangle_objects(object_first_tri, n_objects, tri_obj.data());
+    switch (pose::vertex_objects(indices, n_verts, n_tris, tri_obj.data(), vtx_obj.data(), &tri, &vert)) {
+    case pose::kVertsIndex: return fail(c, TRG_ERR_INVALID, "trg_pose_bind: triangle %u has an index out of range (%u vertices)", tri, n_verts);
+    case pose::kVertsShared: return fail(c, TRG_ERR_INVALID, "trg_pose_bind: vertex %u is named by triangle %u of object %u and by object %u: a vertex belongs to one object", vert, tri, tri_obj[tri], vtx_obj[vert]);
+    default: break;
+    }
+    for (uint32_t v = 0; v < n_verts; ++v)
+        if (!(std::isfinite(positions3[(size_t)v * 3]) && std::isfinite(positions3[(size_t)v * 3 + 1]) && std::isfinite(positions3[(size_t)v * 3 + 2])))
+            return fail(c, TRG_ERR_INVALID, "trg_pose_bind: vertex %u has a coordinate that is not finite", v);
+    for (size_t k = 0; normals3 && k < (size_t)n_tris * 9; ++k)
+        if (!std::isfinite(normals3[k])) return fail(c, TRG_ERR_INVALID, "trg_pose_bind: triangle %u has a normal that is not finite", (uint32_t)(k / 9));
+
+    RF_HIPCHK(c, hipSetDevice(c->device));
+    RefitState &s = state_of(c);
+    RefitState::Pose &p = s.pose;
+    p.bound = false;
+    const size_t pos_bytes = (size_t)n_verts * 12, idx_bytes = (size_t)n_tris * 12, nrm_bytes = (size_t)n_tris * 36;
+    int rc = TRG_OK;
+    if ((rc = grow(c, p.rest_pos, pos_bytes, "rest positions")) || (rc = grow(c, p.idx, idx_bytes, "bound indices")) || (rc = grow(c, p.vtx_obj, (size_t)n_verts * 4, "vertex map")) ||
+        (rc = grow(c, p.tri_obj, (size_t)n_tris * 4, "triangle map")) || (rc = grow(c, p.xforms, (size_t)n_objects * 48, "transforms")) ||
+        (normals3 && (rc = grow(c, p.rest_nrm, nrm_bytes, "rest normals"))))
+        return rc;
+    for (int k = 0; k < 3; ++k)
+        if ((rc = grow(c, p.posed[k], pos_bytes, "posed positions")) || (normals3 && (rc = grow(c, p.posed_nrm[k], nrm_bytes, "posed normals")))) return rc;
+    RF_HIPCHK(c, hipMemcpyAsync(p.rest_pos.p, positions3, pos_bytes, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(p.idx.p, indices, idx_bytes, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(p.vtx_obj.p, vtx_obj.data(), (size_t)n_verts * 4, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(p.tri_obj.p, tri_obj.data(), (size_t)n_tris * 4, hipMemcpyHostToDevice, c->stream));
+    if (normals3) RF_HIPCHK(c, hipMemcpyAsync(p.rest_nrm.p, normals3, nrm_bytes, hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < 3; ++k) {
+        RF_HIPCHK(c, hipMemcpyAsync(p.posed[k].p, p.rest_pos.p, pos_bytes, hipMemcpyDeviceToDevice, c->stream));
+        if (normals3) RF_HIPCHK(c, hipMemcpyAsync(p.posed_nrm[k].p, p.rest_nrm.p, nrm_bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
+    RF_HIPCHK(c, hipStreamSynchronize(c->stream));   // (the maps are this call's own arrays)
+    p.n_verts = n_verts; p.n_tris = n_tris; p.n_objects = n_objects;
+    p.cur = 0; p.prev = 1;
+    p.has_nrm = normals3 != nullptr;
+    p.remember_scene(c);
+    p.bound = true;
+    return TRG_OK;
+}
+
+int trg_pose_apply(trg_ctx *c, const float *xforms12) {
+    RefitState::Pose *pp = nullptr;
+    if (int rc = pose_of(c, "trg_pose_apply", &pp)) return rc;
+    RefitState::Pose &p = *pp;
+    if (!xforms12) return fail(c, TRG_ERR_INVALID, "trg_pose_apply: null transforms");
+    for (size_t k = 0; k < (size_t)p.n_objects * 12; ++k)
+        if (!std::isfinite(xforms12[k])) return fail(c, TRG_ERR_INVALID, "trg_pose_apply: the transform of object %u is not finite", (uint32_t)(k / 12));
+    const uint32_t spare = 3u - p.cur - p.prev;
+    float *pos_out = p.posed[spare].as<float>(), *nrm_out = p.has_nrm ? p.posed_nrm[spare].as<float>() : nullptr;
+    RF_HIPCHK(c, hipMemcpyAsync(p.xforms.p, xforms12, (size_t)p.n_objects * 48, hipMemcpyHostToDevice, c->stream));
+    const size_t blocks = ((size_t)p.n_verts + kT - 1) / kT + (p.has_nrm ? ((size_t)p.n_tris * 3 + kT - 1) / kT : 0);
+    RF_LAUNCH(c, rf_pose_kernel, dim3((uint32_t)blocks), p.rest_pos.as<float>(), p.vtx_obj.as<uint32_t>(), p.n_verts, p.rest_nrm.as<float>(), p.tri_obj.as<uint32_t>(),
+              p.n_tris * 3u, p.xforms.as<float>(), pos_out, nrm_out);
+    if (int rc = refit_from_device(c, pos_out, nrm_out, p.idx.as<uint32_t>(), p.n_verts, p.n_tris)) return rc;   // (current and previous are untouched)
+    p.prev = p.cur;
+    p.cur = spare;
+    p.remember_scene(c);   // (the small-scene path gives the same scene new memory, and builds it)
+    return TRG_OK;
+}
+
+int trg_pose_read(trg_ctx *c, float *positions3_host, float *normals3_host) {
+    RefitState::Pose *p = nullptr;
+    if (int rc = pose_of(c, "trg_pose_read", &p)) return rc;
+    if (!positions3_host) return fail(c, TRG_ERR_INVALID, "trg_pose_read: null buffer");
+    if (normals3_host && !p->has_nrm) return fail(c, TRG_ERR_INVALID, "trg_pose_read: bound without normals");
+    RF_HIPCHK(c, hipMemcpyAsync(positions3_host, p->posed[p->cur].p, (size_t)p->n_verts * 12, hipMemcpyDeviceToHost, c->stream));
+    if (normals3_host) RF_HIPCHK(c, hipMemcpyAsync(normals3_host, p->posed_nrm[p->cur].p, (size_t)p->n_tris * 36, hipMemcpyDeviceToHost, c->stream));
+    RF_HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TRG_OK;
+}
+
+int trg_pose_buffers(trg_ctx *c, void **pos_dev, void **nrm_dev, void **idx_dev, void **prev_pos_dev, void **prev_nrm_dev) {
+    RefitState::Pose *p = nullptr;
+    if (int rc = pose_of(c, "trg_pose_buffers", &p)) return rc;
+    if (pos_dev) *pos_dev = p->posed[p->cur].p;
+    if (nrm_dev) *nrm_dev = p->has_nrm ? p->posed_nrm[p->cur].p : nullptr;
+    if (idx_dev) *idx_dev = p->idx.p;
+    if (prev_pos_dev) *prev_pos_dev = p->posed[p->prev].p;
+    if (prev_nrm_dev) *prev_nrm_dev = p->has_nrm ? p->posed_nrm[p->prev].p : nullptr;
+    return TRG_OK;
+}
+
+int trg_pose_release(trg_ctx *c) {
+    if (!c) return TRG_ERR_INVALID;
+    pose_free(c);
+    return TRG_OK;
+}
+
+int trg_group_pose_bind(trg_group *g, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris,
+                        const uint32_t *object_first_tri, uint32_t n_objects) {
+    if (!g) return TRG_ERR_INVALID;
+    const int n = trg_group_size(g);
+    if (n <= 0) return TRG_ERR_INVALID;
+    if (int rc = trg_group_sync(g)) return rc;
+    for (int r = 0; r < n; ++r) {
+        trg_ctx *c = trg_group_ctx(g, r);
+        if (!c) return TRG_ERR_INVALID;
+        if (int rc = trg_pose_bind(c, positions3, normals3, indices, n_verts, n_tris, object_first_tri, n_objects)) return rc;
+    }
+    return TRG_OK;
+}
+
+int trg_group_pose_apply(trg_group *g, const float *xforms12) {
+    if (!g) return TRG_ERR_INVALID;
+    const int n = trg_group_size(g);
+    if (n <= 0) return TRG_ERR_INVALID;
+    if (int rc = trg_group_sync(g)) return rc;
+    for (int r = 0; r < n; ++r) {
+        trg_ctx *c = trg_group_ctx(g, r);
+        if (!c) return TRG_ERR_INVALID;
+        if (int rc = trg_pose_apply(c, xforms12)) return rc;
+    }
+    return TRG_OK;
 }
 
 int trg_refit_last(trg_ctx *c, trg_refit_info *out) {

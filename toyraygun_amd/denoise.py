@@ -98,6 +98,7 @@ _SYMBOLS = [
     ("trg_temporal_denoise_host", C.c_int, [_P, _P, _P, _P, _F16, _P, _P, _P, _TP]),
     ("trg_render_temporal_read", C.c_int, [_P, _U, _U, _U, _P, _TP]),
     ("trg_temporal_set_previous_scene", C.c_int, [_P, _P, _P, _P, _U, _U]),
+    ("trg_temporal_set_previous_scene_device", C.c_int, [_P, _P, _P, _P, _U, _U]),
     ("trg_guides_render_motion", C.c_int, [_P, _U, _P, _P, _P]),
     ("trg_temporal_denoise_motion", C.c_int, [_P, _P, _P, _P, _P, _F16, _P, _TP]),
     ("trg_guides_motion_read", C.c_int, [_P, _U, _P, _P, _P]),
@@ -330,6 +331,27 @@ def temporal_set_previous_scene(ctx, positions, normals, indices):
     if idx.shape[0] % 3 or (nrm is not None and nrm.shape[0] != idx.shape[0]):
         raise ValueError("expected 3*n_tris indices and, with normals, 3*n_tris of them")
     _chk(ctx, L.trg_temporal_set_previous_scene(ctx.h_ctx, pos.ctypes.data, None if nrm is None else nrm.ctypes.data, idx.ctypes.data, pos.shape[0], idx.shape[0] // 3))
+
+
+def temporal_set_previous_scene_device(ctx, positions, normals, indices, n_verts=None, n_tris=None):
+    """trg_temporal_set_previous_scene_device: the same from buffers on the context's device, without a copy and without a wait.  positions,
+    normals (or None), indices: contiguous float32 / float32 / int32-or-uint32 ROCm tensors in the layouts above -- or device addresses (int, as
+    pose.buffers gives them) with n_verts and n_tris.  The caller keeps them unchanged until the context's stream has passed the call."""
+    L = load()
+
+    def address(x, floats):
+        if x is None or isinstance(x, int):
+            return x
+        import torch
+        ok = (torch.float32,) if floats else tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in ok and x.is_contiguous()):
+            raise TypeError("expected a contiguous %s ROCm tensor or a device address" % ("float32" if floats else "int32 / uint32"))
+        return x.data_ptr()
+    if n_verts is None:
+        n_verts = positions.numel() // 3
+    if n_tris is None:
+        n_tris = indices.numel() // 3
+    _chk(ctx, L.trg_temporal_set_previous_scene_device(ctx.h_ctx, address(positions, True), address(normals, True), address(indices, False), int(n_verts), int(n_tris)))
 
 
 def guides_motion(ctx, frame_index, out=None, pos=None, motion=None):
