@@ -43,6 +43,14 @@ public:
     bool bindObjects(Scene *scene, const uint32_t *firstTri, unsigned int nObjects);
     bool poseObjects(const float *xforms12);
     unsigned int getPoseCount() const { return m_poses; }      // poseObjects calls that succeeded
+    // Skinning (include/trg_skin.h): the loaded scene as a mesh that BENDS -- every vertex follows a blend of up to four bone matrices.  bindSkin,
+    // after loadScene of the same `scene`: per vertex four bone ids (< nBones) and four weights (>= 0, summing to 1; they are not normalised here).
+    // poseSkin: nBones x 12 floats, row-major [A | t] per bone, applied to the geometry AS BOUND; the loaded tree is refitted on the device.  In
+    // temporal mode on one device the pose before this one goes to trg_temporal_set_previous_scene_device from the skin unit's own buffers.  A call
+    // the library refuses says so on stdout, changes nothing and arms nothing.  Both return false when refused.
+    bool bindSkin(Scene *scene, const uint32_t *boneIds4, const float *weights4, unsigned int nBones);
+    bool poseSkin(const float *bones12);
+    unsigned int getSkinCount() const { return m_skins; }      // poseSkin calls that succeeded
     // One more sample per pixel into the running average.  ASYNCHRONOUS like the reference's (MetalRenderer.mm:373-552: encode,
     // commit, return; three frames in flight behind a semaphore, :33,377,385-387): the call never waits for the GPU to finish
     // a frame.  It takes a snapshot of the uniforms and either launches at once (GPU idle) or -- while earlier launches are
@@ -146,6 +154,8 @@ protected:
     unsigned int m_refits = 0;
     unsigned int m_poses = 0;    // poses applied
     uint32_t m_poseVerts = 0;    // the vertex count bound by bindObjects
+    unsigned int m_skins = 0;    // skins applied
+    uint32_t m_skinVerts = 0;    // the vertex count bound by bindSkin
 };
 
 }  // namespace toyraygun

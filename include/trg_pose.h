@@ -40,7 +40,7 @@
  * The arithmetic, operation by operation, is toyraygun_amd/csrc/trg_pose_math.h.  Equal inputs give equal outputs: the copies of a shared corner stay
  * bitwise equal.  The identity gives values equal under == (a -0 becomes +0).
  *
- * Out of scope: per-vertex deformation computed by the library (the caller's own device buffers go through trg_refit_scene_device); changed
+ * Out of scope: per-vertex deformation (linear-blend skinning is include/trg_skin.h; the caller's own device buffers go through trg_refit_scene_device); changed
  * topology, colours or materials; the 8-wide experiments build.
  */
 #ifndef TRG_POSE_H

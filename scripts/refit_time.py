@@ -1,6 +1,6 @@
 """Update time and render time of a refitted scene against a reloaded one (include/trg_refit.h).
 
-    python scripts/refit_time.py [--n 44] [--reps 5] [--w 1024 --h 768 --spp 4] [--legs refit,pose] [--parent-so FILE] [--out FILE]
+    python scripts/refit_time.py [--n 44] [--reps 5] [--w 1024 --h 768 --spp 4] [--legs refit,pose,skin] [--parent-so FILE] [--out FILE]
 
 The Cornell box + n^3 cubes (n = 44: 1,022,244 triangles, n = 96: 10,616,868).  In ONE process, alternating, medians over `reps`:
 
@@ -19,6 +19,11 @@ is not a host-side figure: run this leg once more under a kernel trace,
 and read rf_pose_kernel's row of the kernel statistics (without --output-format the run leaves a results database whose `kernels` view has one
 row per launch with its duration in ns).
 
+The skin leg (include/trg_skin.h; device builder): bones = the Cornell box's + one per cube; every vertex names FOUR DISTINCT bones (its own and
+the next three), its weight 1 on its own -- the kernel's work does not depend on the weights' values --, every cube's bone the same small
+translation.  Alternating, medians over `reps`, each call followed by a wait: trg_skin_apply; trg_refit_scene_device and trg_refit_scene of the same
+skinned geometry; with --parent-so that library's trg_refit_scene.  rf_skin_kernel's own time: the same kernel-trace run, with --legs skin.
+
 Prints one JSON line (and writes it to --out)."""
 import argparse
 import json
@@ -30,7 +35,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from toyraygun_amd import capi, host, pose, refit  # noqa: E402
+from toyraygun_amd import capi, host, pose, refit, skin  # noqa: E402
 
 
 def parent_context(path, w, h, pos, nrm, col, idx, mat):
@@ -160,6 +165,57 @@ def main():
             res["pose"] = r
             if parent:
                 PL.trg_destroy(ph)
+        if "skin" in a.legs.split(","):
+            import torch
+            n_bones = n_cubes + 1
+            own = np.concatenate([np.zeros(108, np.int64), 1 + np.repeat(np.arange(n_cubes), 36)])
+            ids = ((own[:, None] + np.arange(4)[None, :]) % n_bones).astype(np.uint32)      # four distinct bones per vertex
+            wts = np.zeros((pos0.shape[0], 4), np.float32)
+            wts[:, 0] = 1.0
+            x0 = np.tile(np.eye(3, 4, dtype=np.float32).reshape(1, 12), (n_bones, 1))
+            x1 = x0.copy()
+            x1[1:, [3, 7, 11]] = d
+            load(1, pos0)
+            skin.bind(c, pos0, nrm, idx, ids, wts, n_bones)
+            skin.apply(c, x1)
+            got, _ = skin.read(c)
+            assert (got == pos1).all()                                     # the same geometry as the host arrays of the refit leg
+            t_pos, t_nrm, t_idx = torch.from_numpy(pos1).cuda(), torch.from_numpy(nrm).cuda(), torch.from_numpy(idx.view(np.int32)).cuda()
+            torch.cuda.synchronize()
+            parent = parent_context(a.parent_so, a.w, a.h, pos0, nrm, col, idx, mat) if a.parent_so else None
+            RL = refit.load()
+            # (trg_refit_scene of this library and of the parent's are called the same way, straight through ctypes: the wrapper's argument
+            # checks cost about 10 us, which is the size of the difference looked for)
+            calls = {"skin_apply": lambda k: skin.apply(c, x1 if k % 2 == 0 else x0),          # alternating: nothing is a no-op
+                     "refit_scene_device": lambda k: pose.refit_scene_device(c, t_pos, t_nrm, t_idx),
+                     "refit_scene": lambda k: (RL.trg_refit_scene(c.h_ctx, pos1.ctypes.data, nrm.ctypes.data, idx.ctypes.data, pos1.shape[0], nt), RL.trg_sync(c.h_ctx)),
+                     "refit_scene_through_refit_py": lambda k: refit.refit_scene(c, pos1, nrm, idx)}
+            if parent:
+                PL, ph = parent
+                calls["parent_refit_scene"] = lambda k: (PL.trg_refit_scene(ph, pos1.ctypes.data, nrm.ctypes.data, idx.ctypes.data, pos1.shape[0], nt), PL.trg_sync(ph))
+            for f in calls.values():                                       # (scratch is allocated once)
+                f(0)
+            t = {k: [] for k in calls}
+            for k in range(a.reps):
+                for name, f in calls.items():
+                    t[name].append(timed(lambda: f(k)))
+            r = {k + "_ms": statistics.median(v) for k, v in t.items()}
+            r.update({k + "_ms_all": [round(x, 3) for x in v] for k, v in t.items()})
+            r["bones"] = int(n_bones)
+            r["vertices"] = int(pos0.shape[0])
+            r["upload_bytes"] = {"skin_apply": int(48 * n_bones), "refit_scene": int(pos1.nbytes + idx.nbytes + nrm.nbytes)}
+            r["skinning_on_top_of_the_refit_ms"] = r["skin_apply_ms"] - r["refit_scene_device_ms"]  # upload of the bones + rf_skin_kernel
+            # what rf_skin_kernel streams: 16 + 16 + 12 + 12 per vertex, 4 + 16 + 16 + 12 + 12 per corner (the bones come from cache)
+            r["kernel_streamed_bytes"] = int(56 * pos0.shape[0] + 60 * 3 * nt)
+            skin.apply(c, x1)
+            r["render_after_skin_ms"] = render_ms()
+            if parent:
+                r["skin_not_slower_than_parent_refit_scene"] = bool(r["skin_apply_ms"] <= r["parent_refit_scene_ms"])
+                lo, hi = min(t["parent_refit_scene"]), max(t["parent_refit_scene"])
+                r["refit_scene_within_parent_spread"] = bool(lo <= r["refit_scene_ms"] <= hi)
+                PL.trg_destroy(ph)
+            skin.release(c)
+            res["skin"] = r
     finally:
         refit.release(c)
         c.close()

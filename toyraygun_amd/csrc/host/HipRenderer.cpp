@@ -11,6 +11,7 @@
 #include "trg.h"
 #include "trg_denoise.h"
 #include "trg_pose.h"
+#include "trg_skin.h"
 #include "trg_refit.h"
 
 namespace toyraygun {
@@ -246,6 +247,48 @@ bool HipRenderer::poseObjects(const float *xforms12) {
         void *prevPos = nullptr, *prevNrm = nullptr, *idx = nullptr;
         if (trg_pose_buffers(m_ctx, nullptr, nullptr, &idx, &prevPos, &prevNrm) != TRG_OK ||
             trg_temporal_set_previous_scene_device(m_ctx, prevPos, prevNrm, idx, m_poseVerts, (uint32_t)m_loadedTris) != TRG_OK) {
+            printf("HipRenderer: %s\n", trg_last_error(m_ctx));
+            trg_temporal_reset(m_ctx);   // the history cannot be followed: start over, as loadScene does
+            m_temporalOut = nullptr;
+        }
+    }
+    return true;
+}
+
+bool HipRenderer::bindSkin(Scene *scene, const uint32_t *boneIds4, const float *weights4, unsigned int nBones) {
+    if (!m_ctx || !scene || !m_sceneLoaded || !boneIds4 || !weights4) return false;
+    flush();
+    const uint32_t nTris = (uint32_t)scene->m_materialIDBuffer.size();
+    const uint32_t nVerts = (uint32_t)scene->m_vertexBuffer.size();
+    if (!nVerts || !nTris || scene->m_indexBuffer.size() != (size_t)nTris * 3) return false;
+    // (a scene without a normal per corner is bound without normals: the loaded ones stay)
+    const float *pos = &scene->m_vertexBuffer[0].x, *nrm = scene->m_normalBuffer.size() == (size_t)nTris * 3 ? &scene->m_normalBuffer[0].x : nullptr;
+    const uint32_t *idx = &scene->m_indexBuffer[0];
+    const char *text = "";
+    const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) { return trg_skin_bind(c, pos, nrm, idx, nVerts, nTris, boneIds4, weights4, nBones); }, &text);
+    if (rc != TRG_OK) { printf("HipRenderer: skin not bound (%s)\n", text); fflush(stdout); }
+    else m_skinVerts = nVerts;
+    return rc == TRG_OK;
+}
+
+bool HipRenderer::poseSkin(const float *bones12) {
+    if (!m_ctx || !m_sceneLoaded || !bones12) return false;
+    flush();   // frames queued so far are rendered with the pose they were queued under
+    const char *text = "";
+    const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) { return trg_skin_apply(c, bones12); }, &text);
+    if (rc != TRG_OK) {
+        printf("HipRenderer: skin refused (%s); nothing changed\n", text);
+        fflush(stdout);
+        return false;
+    }
+    ++m_skins;
+    // (updateScene's remembered vectors are no longer what the device holds: its next call loads)
+    m_lastPositions.clear(); m_lastNormals.clear(); m_lastIndices.clear();
+    if (m_denoiseTemporal && !m_group) {
+        // what was current is the unit's PREVIOUS pose now, and stays untouched through the next apply: the history is told where every triangle was
+        void *prevPos = nullptr, *prevNrm = nullptr, *idx = nullptr;
+        if (trg_skin_buffers(m_ctx, nullptr, nullptr, &idx, &prevPos, &prevNrm) != TRG_OK ||
+            trg_temporal_set_previous_scene_device(m_ctx, prevPos, prevNrm, idx, m_skinVerts, (uint32_t)m_loadedTris) != TRG_OK) {
             printf("HipRenderer: %s\n", trg_last_error(m_ctx));
             trg_temporal_reset(m_ctx);   // the history cannot be followed: start over, as loadScene does
             m_temporalOut = nullptr;

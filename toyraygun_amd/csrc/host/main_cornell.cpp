@@ -1,6 +1,6 @@
 // main_cornell.cpp -- headless demo following the reference app's call order (reference src/main.cpp:16-98):
 // engine init -> three shaders -> renderer init -> camera -> Cornell box -> frame loop; then writes a PNG.
-//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [refit|pose]]
+//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [twist=DEG] [refit|pose|skin]]
 //     denoise=N    a-trous iterations of the written image, 0 = off (default)
 //     ,var         the variance-guided filter from two half-sample buffers
 //     ,temporal    the frames are rendered as `frames` calls of 1 spp, each a temporal step (reprojected history, temporal variance); the
@@ -19,12 +19,17 @@
 //     pose         (with slide=D, not with refit) the box is bound once with the short box as an object of its own (HipRenderer::bindObjects) and
 //                  before call k the short box is moved by k * D through HipRenderer::poseObjects (include/trg_pose.h): 96 bytes go to the device,
 //                  not a scene; with ,temporal the history follows from the pose unit's own buffers.  The last line of output counts the poses
+//     skin         (with twist=DEG, not with refit or pose) the box is bound once with two bones (HipRenderer::bindSkin): bone 0 is the identity,
+//                  bone 1 a rotation about the short box's vertical axis, and the short box's corners are weighted to bone 1 by their height within
+//                  the box -- everything else has weight 1 on bone 0.  Before call k bone 1 turns by k * DEG degrees (HipRenderer::poseSkin,
+//                  include/trg_skin.h): the box twists (twist=0, like slide=0 under pose, applies nothing).  The last line of output counts the skins applied
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <iostream>
+#include <vector>
 
 #include "cornellBox.h"
 #include "engine/Engine.h"
@@ -66,8 +71,9 @@ int main(int argc, char **argv) {
     int denoise = 0;
     bool denoiseVar = false, denoiseTemporal = false, varianceOfMean = false;
     double orbit = 0.0, slide = 0.0, lagGate = -1.0, coverMin = -1.0;
-    bool refit = false, pose = false;
-    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [refit|pose]]";
+    double twist = 0.0;
+    bool refit = false, pose = false, skin = false;
+    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [twist=DEG] [refit|pose|skin]]";
     for (int a = 6; a < argc; ++a) {
         if (strncmp(argv[a], "slide=", 6) == 0) {
             char *end = nullptr;
@@ -77,6 +83,13 @@ int main(int argc, char **argv) {
         }
         if (strcmp(argv[a], "refit") == 0) { refit = true; continue; }
         if (strcmp(argv[a], "pose") == 0) { pose = true; continue; }
+        if (strcmp(argv[a], "skin") == 0) { skin = true; continue; }
+        if (strncmp(argv[a], "twist=", 6) == 0) {
+            char *end = nullptr;
+            twist = strtod(argv[a] + 6, &end);
+            if (end == argv[a] + 6 || *end != 0) { std::cout << usage << std::endl; return -1; }
+            continue;
+        }
         if (strncmp(argv[a], "orbit=", 6) == 0) {
             char *end = nullptr;
             orbit = strtod(argv[a] + 6, &end);
@@ -119,7 +132,7 @@ int main(int argc, char **argv) {
         }
     }
 
-    if (pose && refit) { std::cout << usage << std::endl; return -1; }
+    if ((pose && refit) || (skin && (pose || refit))) { std::cout << usage << std::endl; return -1; }
 
     Engine *engine = Engine::instance();
     engine->init(width, height);
@@ -158,6 +171,25 @@ int main(int argc, char **argv) {
     // pose: the short box (the first cube the scene adds: triangles 0 .. 11) is one object, everything else the other
     const uint32_t firstTri[3] = { 0u, 12u, (uint32_t)scene->m_materialIDBuffer.size() };
     if (pose && !hip->bindObjects(scene, firstTri, 2)) { std::cout << "the objects were refused" << std::endl; return -1; }
+    // skin: the short box's 36 corners (the first cube the scene adds) lean on bone 1 by their height within the box, the rest on bone 0
+    double axisX = 0.0, axisZ = 0.0;
+    if (skin) {
+        const size_t nVerts = scene->m_vertexBuffer.size();
+        if (nVerts < 36) { std::cout << "the skin was refused" << std::endl; return -1; }
+        float lo = scene->m_vertexBuffer[0].y, hi = lo;
+        for (size_t v = 0; v < 36; ++v) {
+            lo = fminf(lo, scene->m_vertexBuffer[v].y); hi = fmaxf(hi, scene->m_vertexBuffer[v].y);
+            axisX += (double)scene->m_vertexBuffer[v].x / 36.0; axisZ += (double)scene->m_vertexBuffer[v].z / 36.0;
+        }
+        std::vector<uint32_t> ids(nVerts * 4, 0u);
+        std::vector<float> weights(nVerts * 4, 0.0f);
+        for (size_t v = 0; v < nVerts; ++v) {
+            const float w1 = v < 36 && hi > lo ? (scene->m_vertexBuffer[v].y - lo) / (hi - lo) : 0.0f;
+            ids[v * 4 + 1] = 1u;
+            weights[v * 4] = 1.0f - w1; weights[v * 4 + 1] = w1;
+        }
+        if (!hip->bindSkin(scene, ids.data(), weights.data(), 2)) { std::cout << "the skin was refused" << std::endl; return -1; }
+    }
     const bx::Vec3 eye0(0.0f, 1.0f, 3.38f), at(0.0f, 1.0f, -1.0f);
     int call = 0;
     while (!engine->hasQuit()) {
@@ -168,7 +200,14 @@ int main(int argc, char **argv) {
             const double dx = (double)eye0.x - (double)at.x, dz = (double)eye0.z - (double)at.z;
             renderer->setCameraPosition(bx::Vec3((float)((double)at.x + dx * cos(t) + dz * sin(t)), eye0.y, (float)((double)at.z - dx * sin(t) + dz * cos(t))));
         }
-        if (pose && slide != 0.0 && call > 0) {
+        if (skin && twist != 0.0 && call > 0) {
+            // bone 1: x' = R (x - axis) + axis, R a turn by call * twist degrees about the vertical through (axisX, axisZ)
+            const double t = twist * (double)call * 3.14159265358979323846 / 180.0, cs = cos(t), sn = sin(t);
+            float bones[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
+            bones[12] = (float)cs; bones[14] = (float)sn; bones[15] = (float)(axisX - cs * axisX - sn * axisZ);
+            bones[20] = (float)-sn; bones[22] = (float)cs; bones[23] = (float)(axisZ + sn * axisX - cs * axisZ);
+            hip->poseSkin(bones);
+        } else if (pose && slide != 0.0 && call > 0) {
             float x[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
             x[3] = (float)((double)call * slide);
             hip->poseObjects(x);
@@ -185,5 +224,6 @@ int main(int argc, char **argv) {
     if (!hip->savePNG(out)) { std::cout << "Failed to write " << out << std::endl; return -1; }
     printf("wrote %s\n", out);
     if (pose) printf("%u poses applied\n", hip->getPoseCount());
+    if (skin) printf("%u skins applied\n", hip->getSkinCount());
     return 0;
 }

@@ -2,7 +2,7 @@
 // The arithmetic per record, per box and per node is trg_refit_math.h (host + device: the CPU tests evaluate the same functions); this file is the
 // kernels that apply it, the order they run in, and the small-scene path through the host builder.  include/trg_pose.h lives here too: it shares
 // refit_device and the context's RefitState -- the same refit from buffers already on the device, and the per-object poses that feed it
-// (arithmetic: trg_pose_math.h).
+// (arithmetic: trg_pose_math.h).  So does include/trg_skin.h: blended bone matrices per vertex in front of the same refit (trg_skin_math.h).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -13,11 +13,13 @@
 #include <vector>
 
 #include "../../include/trg_pose.h"
+#include "../../include/trg_skin.h"
 #include "../../include/trg_refit.h"
 #include "trg_ctx.h"
 #include "trg_internal.h"
 #include "trg_kernels.h"
 #include "trg_pose_math.h"
+#include "trg_skin_math.h"
 #include "trg_refit_math.h"
 
 using namespace trg;
@@ -315,6 +317,44 @@ __global__ void rf_pose_kernel(const float *rest_pos, const uint32_t *vtx_obj, u
     for (int j = 0; j < 3; ++j) nrm_out[(size_t)k * 3 + j] = q[j];
 }
 
+// ---- include/trg_skin.h: one thread per vertex, then -- from the next whole block on, nrm_out != nullptr -- one per corner normal.  A thread reads
+//      its ids and weights as one 16-byte record each, blends bone by bone (a bone is three 16-byte rows; twelve accumulators and one bone are live),
+//      and moves 12 bytes in and 12 out as the pose kernel does.  A corner thread reads its index first and blends its vertex's matrix again: no
+//      scratch, no second launch, and the same operations on the same inputs give the same bits ----
+__device__ inline void rf_skin_matrix(const float4 *bones, const uint4 id, const float4 w, float *M) {
+    const uint32_t ids[4] = { id.x, id.y, id.z, id.w };
+    const float ws[4] = { w.x, w.y, w.z, w.w };
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float4 *b = bones + (size_t)ids[j] * 3;
+        const float4 r0 = b[0], r1 = b[1], r2 = b[2];
+        const float bone[12] = { r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w };
+        if (j == 0) skin::blend_first(bone, ws[0], M);
+        else skin::blend_next(bone, ws[j], M);
+    }
+}
+__global__ void rf_skin_kernel(const float *rest_pos, const uint4 *ids, const float4 *weights, uint32_t n_verts, const float *rest_nrm, const uint32_t *idx,
+                               uint32_t n_corners, const float4 *bones, float *pos_out, float *nrm_out) {
+    const uint32_t vertex_blocks = (n_verts + kT - 1) / kT;
+    float M[12], q[3];
+    if (blockIdx.x < vertex_blocks) {
+        const uint32_t v = blockIdx.x * kT + threadIdx.x;
+        if (v >= n_verts) return;
+        const float p[3] = { rest_pos[(size_t)v * 3], rest_pos[(size_t)v * 3 + 1], rest_pos[(size_t)v * 3 + 2] };
+        rf_skin_matrix(bones, ids[v], weights[v], M);
+        pose::point(M, p, q);
+        for (int k = 0; k < 3; ++k) pos_out[(size_t)v * 3 + k] = q[k];
+        return;
+    }
+    const uint32_t k = (blockIdx.x - vertex_blocks) * kT + threadIdx.x;
+    if (!nrm_out || k >= n_corners) return;
+    const uint32_t v = idx[k];   // (< n_verts: trg_skin_bind checked the indices it uploaded)
+    const float n[3] = { rest_nrm[(size_t)k * 3], rest_nrm[(size_t)k * 3 + 1], rest_nrm[(size_t)k * 3 + 2] };
+    rf_skin_matrix(bones, ids[v], weights[v], M);
+    pose::normal(M, n, q);
+    for (int j = 0; j < 3; ++j) nrm_out[(size_t)k * 3 + j] = q[j];
+}
+
 // ---- per-context scratch (grow-only): trg_ctx::refit, created on first use, freed by refit_state_free ----
 struct Buf {
     void *p = nullptr;
@@ -329,14 +369,11 @@ struct trg::RefitState {
     trg_refit_info last{};
     const void *area_blob = nullptr;   // the blob whose as-loaded areas are remembered, and what its arrays summed to after this unit's last write
     double loaded_area[2] = { 0.0, 0.0 }, written_area[2] = { 0.0, 0.0 };
-    // include/trg_pose.h: the binding.  posed[cur] is the current pose, posed[prev] the one before, posed[3 - cur - prev] the copy the next apply
-    // poses into -- a refused refit then leaves current and previous alone
-    struct Pose {
-        Buf rest_pos, rest_nrm, idx, vtx_obj, tri_obj, xforms, posed[3], posed_nrm[3];
-        uint32_t n_verts = 0, n_tris = 0, n_objects = 0, cur = 0, prev = 1;
-        bool bound = false, has_nrm = false;
-        // the scene the binding was made for.  A HEURISTIC (trg_ctx.h has no load counter and stays as it is): its memory, its layout and -- a
-        // reload of as many bytes is usually handed the same address -- the time its build took, which every trg_load_scene measures anew
+    // the scene a binding was made for.  A HEURISTIC (trg_ctx.h has no load counter and stays as it is): its memory, its layout and -- a reload of
+    // as many bytes is usually handed the same address -- the time its build took, which every trg_load_scene measures anew.  Shared by the pose
+    // and the skin binding
+    struct SceneMark {
+        uint32_t n_tris = 0;
         const void *blob = nullptr;
         double build_ms = 0.0;
         uint32_t blob_bytes = 0, n_nodes4 = 0, n_fat = 0, off_fat = 0;
@@ -347,7 +384,20 @@ struct trg::RefitState {
         void remember_scene(const trg_ctx *c) {
             blob = c->blob; build_ms = c->last_build_ms; blob_bytes = c->sc.blob_bytes; n_nodes4 = c->sc.n_nodes4; n_fat = c->sc.n_fat; off_fat = c->sc.off_fat;
         }
+    };
+    // include/trg_pose.h: the binding.  posed[cur] is the current pose, posed[prev] the one before, posed[3 - cur - prev] the copy the next apply
+    // poses into -- a refused refit then leaves current and previous alone
+    struct Pose : SceneMark {
+        Buf rest_pos, rest_nrm, idx, vtx_obj, tri_obj, xforms, posed[3], posed_nrm[3];
+        uint32_t n_verts = 0, n_objects = 0, cur = 0, prev = 1;
+        bool bound = false, has_nrm = false;
     } pose;
+    // include/trg_skin.h: the binding, with the same three copies.  ids and weights are 16-byte records per vertex, bones 48 bytes each
+    struct Skin : SceneMark {
+        Buf rest_pos, rest_nrm, idx, ids, weights, bones, posed[3], posed_nrm[3];
+        uint32_t n_verts = 0, n_bones = 0, cur = 0, prev = 1;
+        bool bound = false, has_nrm = false;
+    } skin;
 };
 
 namespace {
@@ -358,9 +408,15 @@ void each_pose_buffer(RefitState &s, F f) {
     for (Buf *b : { &p.rest_pos, &p.rest_nrm, &p.idx, &p.vtx_obj, &p.tri_obj, &p.xforms, &p.posed[0], &p.posed[1], &p.posed[2], &p.posed_nrm[0], &p.posed_nrm[1], &p.posed_nrm[2] }) f(*b);
 }
 template <typename F>
+void each_skin_buffer(RefitState &s, F f) {
+    RefitState::Skin &k = s.skin;
+    for (Buf *b : { &k.rest_pos, &k.rest_nrm, &k.idx, &k.ids, &k.weights, &k.bones, &k.posed[0], &k.posed[1], &k.posed[2], &k.posed_nrm[0], &k.posed_nrm[1], &k.posed_nrm[2] }) f(*b);
+}
+template <typename F>
 void each_buffer(RefitState &s, F f) {
     for (Buf *b : { &s.pos, &s.idx, &s.nrm, &s.childbox, &s.leafbox, &s.ping, &s.pong, &s.qplain, &s.qbox, &s.quadx, &s.boxrows, &s.partial, &s.hdr }) f(*b);
     each_pose_buffer(s, f);
+    each_skin_buffer(s, f);
 }
 int grow(trg_ctx *c, Buf &b, size_t need, const char *what) {
     if (need <= b.bytes && b.p) return TRG_OK;
@@ -609,6 +665,27 @@ void pose_free(trg_ctx *c) {
     c->refit->pose.blob = nullptr;
 }
 
+// ---- include/trg_skin.h ----
+int skin_of(trg_ctx *c, const char *who, RefitState::Skin **out) {
+    if (!c) return TRG_ERR_INVALID;
+    if (!c->refit || !c->refit->skin.bound) return fail(c, TRG_ERR_INVALID, "%s: nothing bound (trg_skin_bind first)", who);
+    RefitState::Skin &k = c->refit->skin;
+    if (!k.same_scene(c))
+        return fail(c, TRG_ERR_INVALID, "%s: the binding was made for a scene that has been replaced since (bind again)", who);
+    RF_HIPCHK(c, hipSetDevice(c->device));
+    *out = &k;
+    return TRG_OK;
+}
+
+void skin_free(trg_ctx *c) {
+    if (!c->refit) return;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    each_skin_buffer(*c->refit, [](Buf &b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; });
+    c->refit->skin.bound = false;
+    c->refit->skin.blob = nullptr;
+}
+
 }  // namespace
 
 void trg::refit_state_free(trg_ctx *c) {
@@ -771,6 +848,140 @@ int trg_group_pose_apply(trg_group *g, const float *xforms12) {
         trg_ctx *c = trg_group_ctx(g, r);
         if (!c) return TRG_ERR_INVALID;
         if (int rc = trg_pose_apply(c, xforms12)) return rc;
+    }
+    return TRG_OK;
+}
+
+int trg_skin_bind(trg_ctx *c, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris,
+                  const uint32_t *bone_ids4, const float *weights4, uint32_t n_bones) {
+    if (!c) return TRG_ERR_INVALID;
+#if TRG_WIDE8
+    return fail(c, TRG_ERR_INVALID, "trg_skin_bind: an 8-wide experiments build has no skinning");
+#endif
+    if (!c->scene_loaded || !c->blob) return fail(c, TRG_ERR_INVALID, "trg_skin_bind: no scene loaded");
+    if (n_tris != c->sc.n_tris) return fail(c, TRG_ERR_INVALID, "trg_skin_bind: %u triangles, the loaded scene has %u", n_tris, c->sc.n_tris);
+    if (!positions3 || !indices || !bone_ids4 || !weights4 || n_verts == 0 || n_tris == 0 || n_bones == 0) return fail(c, TRG_ERR_INVALID, "trg_skin_bind: null or empty buffer");
+    for (size_t k = 0; k < (size_t)n_tris * 3; ++k)
+        if (indices[k] >= n_verts) return fail(c, TRG_ERR_INVALID, "trg_skin_bind: triangle %u has an index out of range (%u vertices)", (uint32_t)(k / 3), n_verts);
+    uint32_t vert = 0, slot = 0;
+    if (skin::ids_check(bone_ids4, n_verts, n_bones, &vert, &slot) != skin::kSkinOk)
+        return fail(c, TRG_ERR_INVALID, "trg_skin_bind: vertex %u names bone %u (id %u of its four), there are %u bones", vert, bone_ids4[(size_t)vert * 4 + slot], slot, n_bones);
+    switch (skin::weights_check(weights4, n_verts, &vert, &slot)) {
+    case skin::kSkinWeight: return fail(c, TRG_ERR_INVALID, "trg_skin_bind: vertex %u has a weight (%u of its four) that is negative or not finite", vert, slot);
+    case skin::kSkinSum: {
+        const float *w = weights4 + (size_t)vert * 4;
+        return fail(c, TRG_ERR_INVALID, "trg_skin_bind: vertex %u has weights that sum to %.9g, not to 1 within 1e-4 (weights are not normalised here)", vert,
+                    (double)w[0] + (double)w[1] + (double)w[2] + (double)w[3]);
+    }
+    default: break;
+    }
+    for (uint32_t v = 0; v < n_verts; ++v)
+        if (!(std::isfinite(positions3[(size_t)v * 3]) && std::isfinite(positions3[(size_t)v * 3 + 1]) && std::isfinite(positions3[(size_t)v * 3 + 2])))
+            return fail(c, TRG_ERR_INVALID, "trg_skin_bind: vertex %u has a coordinate that is not finite", v);
+    for (size_t k = 0; normals3 && k < (size_t)n_tris * 9; ++k)
+        if (!std::isfinite(normals3[k])) return fail(c, TRG_ERR_INVALID, "trg_skin_bind: triangle %u has a normal that is not finite", (uint32_t)(k / 9));
+
+    RF_HIPCHK(c, hipSetDevice(c->device));
+    RefitState &s = state_of(c);
+    RefitState::Skin &p = s.skin;
+    p.bound = false;
+    const size_t pos_bytes = (size_t)n_verts * 12, idx_bytes = (size_t)n_tris * 12, nrm_bytes = (size_t)n_tris * 36, rec_bytes = (size_t)n_verts * 16;
+    int rc = TRG_OK;
+    if ((rc = grow(c, p.rest_pos, pos_bytes, "rest positions")) || (rc = grow(c, p.idx, idx_bytes, "bound indices")) || (rc = grow(c, p.ids, rec_bytes, "bone ids")) ||
+        (rc = grow(c, p.weights, rec_bytes, "bone weights")) || (rc = grow(c, p.bones, (size_t)n_bones * 48, "bones")) ||
+        (normals3 && (rc = grow(c, p.rest_nrm, nrm_bytes, "rest normals"))))
+        return rc;
+    for (int k = 0; k < 3; ++k)
+        if ((rc = grow(c, p.posed[k], pos_bytes, "skinned positions")) || (normals3 && (rc = grow(c, p.posed_nrm[k], nrm_bytes, "skinned normals")))) return rc;
+    RF_HIPCHK(c, hipMemcpyAsync(p.rest_pos.p, positions3, pos_bytes, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(p.idx.p, indices, idx_bytes, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(p.ids.p, bone_ids4, rec_bytes, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(p.weights.p, weights4, rec_bytes, hipMemcpyHostToDevice, c->stream));
+    if (normals3) RF_HIPCHK(c, hipMemcpyAsync(p.rest_nrm.p, normals3, nrm_bytes, hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < 3; ++k) {
+        RF_HIPCHK(c, hipMemcpyAsync(p.posed[k].p, p.rest_pos.p, pos_bytes, hipMemcpyDeviceToDevice, c->stream));
+        if (normals3) RF_HIPCHK(c, hipMemcpyAsync(p.posed_nrm[k].p, p.rest_nrm.p, nrm_bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
+    RF_HIPCHK(c, hipStreamSynchronize(c->stream));   // (the caller's arrays are free again on return)
+    p.n_verts = n_verts; p.n_tris = n_tris; p.n_bones = n_bones;
+    p.cur = 0; p.prev = 1;
+    p.has_nrm = normals3 != nullptr;
+    p.remember_scene(c);
+    p.bound = true;
+    return TRG_OK;
+}
+
+int trg_skin_apply(trg_ctx *c, const float *bones12) {
+    RefitState::Skin *pp = nullptr;
+    if (int rc = skin_of(c, "trg_skin_apply", &pp)) return rc;
+    RefitState::Skin &p = *pp;
+    if (!bones12) return fail(c, TRG_ERR_INVALID, "trg_skin_apply: null bones");
+    for (size_t k = 0; k < (size_t)p.n_bones * 12; ++k)
+        if (!std::isfinite(bones12[k])) return fail(c, TRG_ERR_INVALID, "trg_skin_apply: bone %u is not finite", (uint32_t)(k / 12));
+    const uint32_t spare = 3u - p.cur - p.prev;
+    float *pos_out = p.posed[spare].as<float>(), *nrm_out = p.has_nrm ? p.posed_nrm[spare].as<float>() : nullptr;
+    RF_HIPCHK(c, hipMemcpyAsync(p.bones.p, bones12, (size_t)p.n_bones * 48, hipMemcpyHostToDevice, c->stream));
+    const size_t blocks = ((size_t)p.n_verts + kT - 1) / kT + (p.has_nrm ? ((size_t)p.n_tris * 3 + kT - 1) / kT : 0);
+    RF_LAUNCH(c, rf_skin_kernel, dim3((uint32_t)blocks), p.rest_pos.as<float>(), p.ids.as<uint4>(), p.weights.as<float4>(), p.n_verts, p.rest_nrm.as<float>(),
+              p.idx.as<uint32_t>(), p.n_tris * 3u, p.bones.as<float4>(), pos_out, nrm_out);
+    if (int rc = refit_from_device(c, pos_out, nrm_out, p.idx.as<uint32_t>(), p.n_verts, p.n_tris)) return rc;   // (current and previous are untouched)
+    p.prev = p.cur;
+    p.cur = spare;
+    p.remember_scene(c);   // (the small-scene path gives the same scene new memory, and builds it)
+    return TRG_OK;
+}
+
+int trg_skin_read(trg_ctx *c, float *positions3_host, float *normals3_host) {
+    RefitState::Skin *p = nullptr;
+    if (int rc = skin_of(c, "trg_skin_read", &p)) return rc;
+    if (!positions3_host) return fail(c, TRG_ERR_INVALID, "trg_skin_read: null buffer");
+    if (normals3_host && !p->has_nrm) return fail(c, TRG_ERR_INVALID, "trg_skin_read: bound without normals");
+    RF_HIPCHK(c, hipMemcpyAsync(positions3_host, p->posed[p->cur].p, (size_t)p->n_verts * 12, hipMemcpyDeviceToHost, c->stream));
+    if (normals3_host) RF_HIPCHK(c, hipMemcpyAsync(normals3_host, p->posed_nrm[p->cur].p, (size_t)p->n_tris * 36, hipMemcpyDeviceToHost, c->stream));
+    RF_HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TRG_OK;
+}
+
+int trg_skin_buffers(trg_ctx *c, void **pos_dev, void **nrm_dev, void **idx_dev, void **prev_pos_dev, void **prev_nrm_dev) {
+    RefitState::Skin *p = nullptr;
+    if (int rc = skin_of(c, "trg_skin_buffers", &p)) return rc;
+    if (pos_dev) *pos_dev = p->posed[p->cur].p;
+    if (nrm_dev) *nrm_dev = p->has_nrm ? p->posed_nrm[p->cur].p : nullptr;
+    if (idx_dev) *idx_dev = p->idx.p;
+    if (prev_pos_dev) *prev_pos_dev = p->posed[p->prev].p;
+    if (prev_nrm_dev) *prev_nrm_dev = p->has_nrm ? p->posed_nrm[p->prev].p : nullptr;
+    return TRG_OK;
+}
+
+int trg_skin_release(trg_ctx *c) {
+    if (!c) return TRG_ERR_INVALID;
+    skin_free(c);
+    return TRG_OK;
+}
+
+int trg_group_skin_bind(trg_group *g, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris,
+                        const uint32_t *bone_ids4, const float *weights4, uint32_t n_bones) {
+    if (!g) return TRG_ERR_INVALID;
+    const int n = trg_group_size(g);
+    if (n <= 0) return TRG_ERR_INVALID;
+    if (int rc = trg_group_sync(g)) return rc;
+    for (int r = 0; r < n; ++r) {
+        trg_ctx *c = trg_group_ctx(g, r);
+        if (!c) return TRG_ERR_INVALID;
+        if (int rc = trg_skin_bind(c, positions3, normals3, indices, n_verts, n_tris, bone_ids4, weights4, n_bones)) return rc;
+    }
+    return TRG_OK;
+}
+
+int trg_group_skin_apply(trg_group *g, const float *bones12) {
+    if (!g) return TRG_ERR_INVALID;
+    const int n = trg_group_size(g);
+    if (n <= 0) return TRG_ERR_INVALID;
+    if (int rc = trg_group_sync(g)) return rc;
+    for (int r = 0; r < n; ++r) {
+        trg_ctx *c = trg_group_ctx(g, r);
+        if (!c) return TRG_ERR_INVALID;
+        if (int rc = trg_skin_apply(c, bones12)) return rc;
     }
     return TRG_OK;
 }
