@@ -51,6 +51,16 @@ public:
     bool bindSkin(Scene *scene, const uint32_t *boneIds4, const float *weights4, unsigned int nBones);
     bool poseSkin(const float *bones12);
     unsigned int getSkinCount() const { return m_skins; }      // poseSkin calls that succeeded
+    // Blend shapes (include/trg_morph.h), in front of an optional skin.  bindMorph, after loadScene of the same `scene`: target k owns the entries
+    // [targetFirst[k], targetFirst[k + 1]), each a vertex, a position delta and -- entryDnrm3 may be null -- a normal delta; boneIds4, boneWeights4
+    // and nBones as bindSkin takes them, or null, null, 0.  poseMorph: nTargets weights and (exactly when bones were bound) nBones x 12 floats,
+    // applied to the geometry AS BOUND -- morph first, then skin; the loaded tree is refitted on the device.  In temporal mode on one device the
+    // pose before this one goes to trg_temporal_set_previous_scene_device from the morph unit's own buffers.  A call the library refuses says so
+    // on stdout, changes nothing and arms nothing.  Both return false when refused.
+    bool bindMorph(Scene *scene, unsigned int nTargets, const uint32_t *targetFirst, const uint32_t *entryVertex, const float *entryDpos3,
+                   const float *entryDnrm3, const uint32_t *boneIds4, const float *boneWeights4, unsigned int nBones);
+    bool poseMorph(const float *targetWeights, const float *bones12);
+    unsigned int getMorphCount() const { return m_morphs; }    // poseMorph calls that succeeded
     // One more sample per pixel into the running average.  ASYNCHRONOUS like the reference's (MetalRenderer.mm:373-552: encode,
     // commit, return; three frames in flight behind a semaphore, :33,377,385-387): the call never waits for the GPU to finish
     // a frame.  It takes a snapshot of the uniforms and either launches at once (GPU idle) or -- while earlier launches are
@@ -156,6 +166,8 @@ protected:
     uint32_t m_poseVerts = 0;    // the vertex count bound by bindObjects
     unsigned int m_skins = 0;    // skins applied
     uint32_t m_skinVerts = 0;    // the vertex count bound by bindSkin
+    unsigned int m_morphs = 0;   // morphs applied
+    uint32_t m_morphVerts = 0;   // the vertex count bound by bindMorph
 };
 
 }  // namespace toyraygun

@@ -1,6 +1,6 @@
 """Update time and render time of a refitted scene against a reloaded one (include/trg_refit.h).
 
-    python scripts/refit_time.py [--n 44] [--reps 5] [--w 1024 --h 768 --spp 4] [--legs refit,pose,skin] [--parent-so FILE] [--out FILE]
+    python scripts/refit_time.py [--n 44] [--reps 5] [--w 1024 --h 768 --spp 4] [--legs refit,pose,skin,morph] [--parent-so FILE] [--out FILE]
 
 The Cornell box + n^3 cubes (n = 44: 1,022,244 triangles, n = 96: 10,616,868).  In ONE process, alternating, medians over `reps`:
 
@@ -24,6 +24,13 @@ the next three), its weight 1 on its own -- the kernel's work does not depend on
 translation.  Alternating, medians over `reps`, each call followed by a wait: trg_skin_apply; trg_refit_scene_device and trg_refit_scene of the same
 skinned geometry; with --parent-so that library's trg_refit_scene.  rf_skin_kernel's own time: the same kernel-trace run, with --legs skin.
 
+The morph leg (include/trg_morph.h; device builder): eight targets -- two dense (every cube shifted by its own vector; every cube stretched about
+its own centre) and six that each shift a sixth of the cubes --, so every vertex holds three entries; two weight vectors with three active targets
+each alternate, so that no apply is a no-op.  Without bones, and with the skin leg's four-distinct-bones binding behind the targets.  Alternating,
+medians over `reps`, each call followed by a wait, both libraries straight through ctypes: trg_morph_apply; trg_skin_apply; trg_refit_scene of the
+same morphed geometry; with --parent-so that library's trg_refit_scene -- what a caller with blend shapes pays today, before the CPU morph itself.
+rf_morph_kernel's own time: the same kernel-trace run, with --legs morph.
+
 Prints one JSON line (and writes it to --out)."""
 import argparse
 import json
@@ -35,7 +42,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from toyraygun_amd import capi, host, pose, refit, skin  # noqa: E402
+from toyraygun_amd import capi, host, morph, pose, refit, skin  # noqa: E402
 
 
 def parent_context(path, w, h, pos, nrm, col, idx, mat):
@@ -216,6 +223,73 @@ def main():
                 PL.trg_destroy(ph)
             skin.release(c)
             res["skin"] = r
+        if "morph" in a.legs.split(","):
+            nv = pos0.shape[0]
+            cube = np.concatenate([np.full(108, -1, np.int64), np.repeat(np.arange(n_cubes), 36)])      # vertex -> cube (-1: the Cornell box)
+            centre = pos0[108:108 + 36 * n_cubes].astype(np.float64).reshape(n_cubes, 36, 3).mean(1)
+            shift = np.concatenate([np.zeros((108, 3), np.float32), np.repeat(d, 36, axis=0)])
+            stretch = np.zeros((nv, 3), np.float32)
+            stretch[108:] = (2.0 ** -5 * (pos0[108:].astype(np.float64) - np.repeat(centre, 36, axis=0))).astype(np.float32)
+            d6 = (rng.integers(-4, 5, (n_cubes, 3)).astype(np.float32) * np.float32(2.0 ** -11))
+            sixth = np.where(cube < 0, 0, cube % 6)
+            ev = [np.arange(nv), np.arange(nv)] + [np.flatnonzero(sixth == j) for j in range(6)]
+            dp = [shift, stretch] + [np.where(cube[v, None] < 0, np.float32(0), d6[np.maximum(cube[v], 0)]).astype(np.float32) for v in ev[2:]]
+            first = np.concatenate([[0], np.cumsum([v.shape[0] for v in ev])]).astype(np.uint32)
+            ev, dp = np.concatenate(ev).astype(np.uint32), np.ascontiguousarray(np.concatenate(dp))
+            assert (np.bincount(ev, minlength=nv) == 3).all()              # every vertex holds three entries
+            wA, wB = np.array([1, 0.5, 1, 0, 0, 0, 0, 0], np.float32), np.array([0.5, 1, 0, 0, 1, 0, 0, 1], np.float32)
+            n_bones = n_cubes + 1
+            own = np.concatenate([np.zeros(108, np.int64), 1 + np.repeat(np.arange(n_cubes), 36)])
+            ids = ((own[:, None] + np.arange(4)[None, :]) % n_bones).astype(np.uint32)      # four distinct bones per vertex
+            wts = np.zeros((nv, 4), np.float32)
+            wts[:, 0] = 1.0
+            x0 = np.tile(np.eye(3, 4, dtype=np.float32).reshape(1, 12), (n_bones, 1))
+            x1 = x0.copy()
+            x1[1:, [3, 7, 11]] = d
+            load(1, pos0)
+            parent = parent_context(a.parent_so, a.w, a.h, pos0, nrm, col, idx, mat) if a.parent_so else None
+            RL, ML, SL = refit.load(), morph.load(), skin.load()
+            skin.bind(c, pos0, nrm, idx, ids, wts, n_bones)
+            r = {"vertices": int(nv), "targets": 8, "entries": int(ev.shape[0]), "bones": int(n_bones)}
+            for with_bones in (False, True):
+                tag = "morph_apply_bones" if with_bones else "morph_apply"
+                morph.bind(c, pos0, nrm, idx, first, ev, dp, None, **(dict(bone_ids=ids, bone_weights=wts, n_bones=n_bones) if with_bones else {}))
+                morph.apply(c, wA, x1 if with_bones else None)
+                got, _ = morph.read(c)
+                ref, _ = morph.morph_reference(pos0, None, idx, first, ev, dp, None, wA, **(dict(bone_ids=ids, bone_weights=wts, bones=x1) if with_bones else {}))
+                assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+                posA = np.ascontiguousarray(got)                           # the morphed geometry a caller would have made on the CPU
+                bones = (x1.ctypes.data, x0.ctypes.data) if with_bones else (None, None)
+                calls = {tag: lambda k: (ML.trg_morph_apply(c.h_ctx, (wA, wB)[k % 2].ctypes.data, bones[k % 2]), RL.trg_sync(c.h_ctx)),
+                         "skin_apply": lambda k: (SL.trg_skin_apply(c.h_ctx, (x1, x0)[k % 2].ctypes.data), RL.trg_sync(c.h_ctx)),
+                         "refit_scene": lambda k: (RL.trg_refit_scene(c.h_ctx, posA.ctypes.data, nrm.ctypes.data, idx.ctypes.data, nv, nt), RL.trg_sync(c.h_ctx))}
+                if parent:
+                    PL, ph = parent
+                    calls["parent_refit_scene"] = lambda k: (PL.trg_refit_scene(ph, posA.ctypes.data, nrm.ctypes.data, idx.ctypes.data, nv, nt), PL.trg_sync(ph))
+                for name, f in calls.items():                              # (scratch is allocated once; and every call is accepted)
+                    assert f(0) == (0, 0), (name, RL.trg_last_error(c.h_ctx))
+                t = {k: [] for k in calls}
+                for k in range(a.reps):
+                    for name, f in calls.items():
+                        t[name].append(timed(lambda: f(k)))
+                assert all(f(1) == (0, 0) for f in calls.values())
+                for k, v in t.items():
+                    key = k if k == tag else k + ("_beside_bones" if with_bones else "")
+                    r[key + "_ms"], r[key + "_ms_all"] = statistics.median(v), [round(x, 3) for x in v]
+                if parent:
+                    r[tag + "_not_slower_than_parent_refit_scene"] = bool(statistics.median(t[tag]) <= statistics.median(t["parent_refit_scene"]))
+            r["upload_bytes"] = {"morph_apply": 4 * 8, "morph_apply_bones": int(4 * 8 + 48 * n_bones), "refit_scene": int(pos0.nbytes + idx.nbytes + nrm.nbytes)}
+            # what rf_morph_kernel streams.  Without bones (no normal deltas: the corner range is not launched): 12 in, 12 out, one range word and
+            # three 16-byte records per vertex.  With bones: 16 + 16 more per vertex, and 4 + 16 + 16 + 12 + 12 per corner (the bones and the
+            # weights come from cache)
+            r["kernel_streamed_bytes"] = {"morph_apply": int((12 + 12 + 4 + 48) * nv), "morph_apply_bones": int((12 + 12 + 4 + 48 + 32) * nv + 60 * 3 * nt),
+                                          "skin_apply": int(56 * nv + 60 * 3 * nt)}
+            r["render_after_morph_ms"] = render_ms()
+            if parent:
+                PL.trg_destroy(ph)
+            morph.release(c)
+            skin.release(c)
+            res["morph"] = r
     finally:
         refit.release(c)
         c.close()

@@ -10,6 +10,7 @@
 #include "png_writer.h"
 #include "trg.h"
 #include "trg_denoise.h"
+#include "trg_morph.h"
 #include "trg_pose.h"
 #include "trg_skin.h"
 #include "trg_refit.h"
@@ -289,6 +290,51 @@ bool HipRenderer::poseSkin(const float *bones12) {
         void *prevPos = nullptr, *prevNrm = nullptr, *idx = nullptr;
         if (trg_skin_buffers(m_ctx, nullptr, nullptr, &idx, &prevPos, &prevNrm) != TRG_OK ||
             trg_temporal_set_previous_scene_device(m_ctx, prevPos, prevNrm, idx, m_skinVerts, (uint32_t)m_loadedTris) != TRG_OK) {
+            printf("HipRenderer: %s\n", trg_last_error(m_ctx));
+            trg_temporal_reset(m_ctx);   // the history cannot be followed: start over, as loadScene does
+            m_temporalOut = nullptr;
+        }
+    }
+    return true;
+}
+
+bool HipRenderer::bindMorph(Scene *scene, unsigned int nTargets, const uint32_t *targetFirst, const uint32_t *entryVertex, const float *entryDpos3,
+                            const float *entryDnrm3, const uint32_t *boneIds4, const float *boneWeights4, unsigned int nBones) {
+    if (!m_ctx || !scene || !m_sceneLoaded || !nTargets || !targetFirst) return false;
+    flush();
+    const uint32_t nTris = (uint32_t)scene->m_materialIDBuffer.size();
+    const uint32_t nVerts = (uint32_t)scene->m_vertexBuffer.size();
+    if (!nVerts || !nTris || scene->m_indexBuffer.size() != (size_t)nTris * 3) return false;
+    // (a scene without a normal per corner is bound without normals: the loaded ones stay, and normal deltas are then refused)
+    const float *pos = &scene->m_vertexBuffer[0].x, *nrm = scene->m_normalBuffer.size() == (size_t)nTris * 3 ? &scene->m_normalBuffer[0].x : nullptr;
+    const uint32_t *idx = &scene->m_indexBuffer[0];
+    const char *text = "";
+    const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) {
+        return trg_morph_bind(c, pos, nrm, idx, nVerts, nTris, nTargets, targetFirst, targetFirst[nTargets], entryVertex, entryDpos3, entryDnrm3, boneIds4, boneWeights4, nBones);
+    }, &text);
+    if (rc != TRG_OK) { printf("HipRenderer: morph not bound (%s)\n", text); fflush(stdout); }
+    else m_morphVerts = nVerts;
+    return rc == TRG_OK;
+}
+
+bool HipRenderer::poseMorph(const float *targetWeights, const float *bones12) {
+    if (!m_ctx || !m_sceneLoaded || !targetWeights) return false;
+    flush();   // frames queued so far are rendered with the pose they were queued under
+    const char *text = "";
+    const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) { return trg_morph_apply(c, targetWeights, bones12); }, &text);
+    if (rc != TRG_OK) {
+        printf("HipRenderer: morph refused (%s); nothing changed\n", text);
+        fflush(stdout);
+        return false;
+    }
+    ++m_morphs;
+    // (updateScene's remembered vectors are no longer what the device holds: its next call loads)
+    m_lastPositions.clear(); m_lastNormals.clear(); m_lastIndices.clear();
+    if (m_denoiseTemporal && !m_group) {
+        // what was current is the unit's PREVIOUS pose now, and stays untouched through the next apply: the history is told where every triangle was
+        void *prevPos = nullptr, *prevNrm = nullptr, *idx = nullptr;
+        if (trg_morph_buffers(m_ctx, nullptr, nullptr, &idx, &prevPos, &prevNrm) != TRG_OK ||
+            trg_temporal_set_previous_scene_device(m_ctx, prevPos, prevNrm, idx, m_morphVerts, (uint32_t)m_loadedTris) != TRG_OK) {
             printf("HipRenderer: %s\n", trg_last_error(m_ctx));
             trg_temporal_reset(m_ctx);   // the history cannot be followed: start over, as loadScene does
             m_temporalOut = nullptr;

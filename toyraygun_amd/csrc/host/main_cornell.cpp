@@ -1,6 +1,6 @@
 // main_cornell.cpp -- headless demo following the reference app's call order (reference src/main.cpp:16-98):
 // engine init -> three shaders -> renderer init -> camera -> Cornell box -> frame loop; then writes a PNG.
-//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [twist=DEG] [refit|pose|skin]]
+//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [twist=DEG] [bulge=W] [refit|pose|skin|morph]]
 //     denoise=N    a-trous iterations of the written image, 0 = off (default)
 //     ,var         the variance-guided filter from two half-sample buffers
 //     ,temporal    the frames are rendered as `frames` calls of 1 spp, each a temporal step (reprojected history, temporal variance); the
@@ -23,6 +23,11 @@
 //                  bone 1 a rotation about the short box's vertical axis, and the short box's corners are weighted to bone 1 by their height within
 //                  the box -- everything else has weight 1 on bone 0.  Before call k bone 1 turns by k * DEG degrees (HipRenderer::poseSkin,
 //                  include/trg_skin.h): the box twists (twist=0, like slide=0 under pose, applies nothing).  The last line of output counts the skins applied
+//     morph        (with bulge=W, optionally twist=DEG; not with refit, pose or skin) the box is bound once with one blend-shape target
+//                  (HipRenderer::bindMorph): the copies of the short box's four top corners, each delta the corner's offset from the box's vertical
+//                  axis -- and, with twist=DEG, with the two bones of the skin option behind it.  Before call k the target gets the weight k * W
+//                  and bone 1 turns by k * DEG degrees (HipRenderer::poseMorph, include/trg_morph.h): the top of the box bulges, and twists.
+//                  bulge=0 without a twist applies nothing.  The last line of output counts the morphs applied
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -71,9 +76,9 @@ int main(int argc, char **argv) {
     int denoise = 0;
     bool denoiseVar = false, denoiseTemporal = false, varianceOfMean = false;
     double orbit = 0.0, slide = 0.0, lagGate = -1.0, coverMin = -1.0;
-    double twist = 0.0;
-    bool refit = false, pose = false, skin = false;
-    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [twist=DEG] [refit|pose|skin]]";
+    double twist = 0.0, bulge = 0.0;
+    bool refit = false, pose = false, skin = false, morph = false;
+    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [twist=DEG] [bulge=W] [refit|pose|skin|morph]]";
     for (int a = 6; a < argc; ++a) {
         if (strncmp(argv[a], "slide=", 6) == 0) {
             char *end = nullptr;
@@ -84,6 +89,13 @@ int main(int argc, char **argv) {
         if (strcmp(argv[a], "refit") == 0) { refit = true; continue; }
         if (strcmp(argv[a], "pose") == 0) { pose = true; continue; }
         if (strcmp(argv[a], "skin") == 0) { skin = true; continue; }
+        if (strcmp(argv[a], "morph") == 0) { morph = true; continue; }
+        if (strncmp(argv[a], "bulge=", 6) == 0) {
+            char *end = nullptr;
+            bulge = strtod(argv[a] + 6, &end);
+            if (end == argv[a] + 6 || *end != 0) { std::cout << usage << std::endl; return -1; }
+            continue;
+        }
         if (strncmp(argv[a], "twist=", 6) == 0) {
             char *end = nullptr;
             twist = strtod(argv[a] + 6, &end);
@@ -132,7 +144,7 @@ int main(int argc, char **argv) {
         }
     }
 
-    if ((pose && refit) || (skin && (pose || refit))) { std::cout << usage << std::endl; return -1; }
+    if ((pose && refit) || (skin && (pose || refit)) || (morph && (pose || refit || skin))) { std::cout << usage << std::endl; return -1; }
 
     Engine *engine = Engine::instance();
     engine->init(width, height);
@@ -172,10 +184,12 @@ int main(int argc, char **argv) {
     const uint32_t firstTri[3] = { 0u, 12u, (uint32_t)scene->m_materialIDBuffer.size() };
     if (pose && !hip->bindObjects(scene, firstTri, 2)) { std::cout << "the objects were refused" << std::endl; return -1; }
     // skin: the short box's 36 corners (the first cube the scene adds) lean on bone 1 by their height within the box, the rest on bone 0
+    // morph: one target, the copies of the short box's four top corners, each moved away from the box's vertical axis; behind it, with a twist, the
+    // skin's two bones
     double axisX = 0.0, axisZ = 0.0;
-    if (skin) {
+    if (skin || morph) {
         const size_t nVerts = scene->m_vertexBuffer.size();
-        if (nVerts < 36) { std::cout << "the skin was refused" << std::endl; return -1; }
+        if (nVerts < 36) { std::cout << (skin ? "the skin was refused" : "the morph was refused") << std::endl; return -1; }
         float lo = scene->m_vertexBuffer[0].y, hi = lo;
         for (size_t v = 0; v < 36; ++v) {
             lo = fminf(lo, scene->m_vertexBuffer[v].y); hi = fmaxf(hi, scene->m_vertexBuffer[v].y);
@@ -188,7 +202,22 @@ int main(int argc, char **argv) {
             ids[v * 4 + 1] = 1u;
             weights[v * 4] = 1.0f - w1; weights[v * 4 + 1] = w1;
         }
-        if (!hip->bindSkin(scene, ids.data(), weights.data(), 2)) { std::cout << "the skin was refused" << std::endl; return -1; }
+        if (skin && !hip->bindSkin(scene, ids.data(), weights.data(), 2)) { std::cout << "the skin was refused" << std::endl; return -1; }
+        if (morph) {
+            std::vector<uint32_t> entryVertex;
+            std::vector<float> dpos;
+            for (uint32_t v = 0; v < 36; ++v)
+                if (scene->m_vertexBuffer[v].y == hi) {
+                    entryVertex.push_back(v);
+                    dpos.push_back(scene->m_vertexBuffer[v].x - (float)axisX); dpos.push_back(0.0f); dpos.push_back(scene->m_vertexBuffer[v].z - (float)axisZ);
+                }
+            const uint32_t targetFirst[2] = { 0u, (uint32_t)entryVertex.size() };
+            const bool bones = twist != 0.0;
+            if (!hip->bindMorph(scene, 1, targetFirst, entryVertex.data(), dpos.data(), nullptr, bones ? ids.data() : nullptr, bones ? weights.data() : nullptr, bones ? 2 : 0)) {
+                std::cout << "the morph was refused" << std::endl;
+                return -1;
+            }
+        }
     }
     const bx::Vec3 eye0(0.0f, 1.0f, 3.38f), at(0.0f, 1.0f, -1.0f);
     int call = 0;
@@ -200,13 +229,15 @@ int main(int argc, char **argv) {
             const double dx = (double)eye0.x - (double)at.x, dz = (double)eye0.z - (double)at.z;
             renderer->setCameraPosition(bx::Vec3((float)((double)at.x + dx * cos(t) + dz * sin(t)), eye0.y, (float)((double)at.z - dx * sin(t) + dz * cos(t))));
         }
-        if (skin && twist != 0.0 && call > 0) {
+        if ((skin || morph) && (twist != 0.0 || (morph && bulge != 0.0)) && call > 0) {
             // bone 1: x' = R (x - axis) + axis, R a turn by call * twist degrees about the vertical through (axisX, axisZ)
             const double t = twist * (double)call * 3.14159265358979323846 / 180.0, cs = cos(t), sn = sin(t);
             float bones[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
             bones[12] = (float)cs; bones[14] = (float)sn; bones[15] = (float)(axisX - cs * axisX - sn * axisZ);
             bones[20] = (float)-sn; bones[22] = (float)cs; bones[23] = (float)(axisZ + sn * axisX - cs * axisZ);
-            hip->poseSkin(bones);
+            const float weight = (float)call * (float)bulge;
+            if (skin) hip->poseSkin(bones);
+            else hip->poseMorph(&weight, twist != 0.0 ? bones : nullptr);
         } else if (pose && slide != 0.0 && call > 0) {
             float x[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
             x[3] = (float)((double)call * slide);
@@ -225,5 +256,6 @@ int main(int argc, char **argv) {
     printf("wrote %s\n", out);
     if (pose) printf("%u poses applied\n", hip->getPoseCount());
     if (skin) printf("%u skins applied\n", hip->getSkinCount());
+    if (morph) printf("%u morphs applied\n", hip->getMorphCount());
     return 0;
 }

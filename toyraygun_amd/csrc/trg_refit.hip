@@ -3,6 +3,7 @@
 // kernels that apply it, the order they run in, and the small-scene path through the host builder.  include/trg_pose.h lives here too: it shares
 // refit_device and the context's RefitState -- the same refit from buffers already on the device, and the per-object poses that feed it
 // (arithmetic: trg_pose_math.h).  So does include/trg_skin.h: blended bone matrices per vertex in front of the same refit (trg_skin_math.h).
+// And include/trg_morph.h: blend shapes in front of that skin (trg_morph_math.h).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -12,12 +13,14 @@
 #include <string>
 #include <vector>
 
+#include "../../include/trg_morph.h"
 #include "../../include/trg_pose.h"
 #include "../../include/trg_skin.h"
 #include "../../include/trg_refit.h"
 #include "trg_ctx.h"
 #include "trg_internal.h"
 #include "trg_kernels.h"
+#include "trg_morph_math.h"
 #include "trg_pose_math.h"
 #include "trg_skin_math.h"
 #include "trg_refit_math.h"
@@ -355,6 +358,68 @@ __global__ void rf_skin_kernel(const float *rest_pos, const uint4 *ids, const fl
     for (int j = 0; j < 3; ++j) nrm_out[(size_t)k * 3 + j] = q[j];
 }
 
+// ---- include/trg_morph.h: the launch shape of the skin kernel -- one thread per vertex, then, from the next whole block on and only when a corner
+//      can change, one per corner normal.  A vertex thread reads the two ends of its range and walks its records, 16 bytes each and one load each;
+//      the weight comes from the n_targets-float table the apply uploaded, and a zero weight leaves the sum alone.  A corner thread reads its index and
+//      walks that vertex's NORMAL records; under bones both blend their vertex's matrix as the skin kernel does (no scratch, one launch).  The trip
+//      count differs per lane: the loop is NOT unrolled -- one record and three accumulators are live, nothing else grows with it ----
+__device__ inline bool rf_morph_walk(const float4 *recs, const uint32_t *vfirst, const float *tw, uint32_t v, float *acc) {
+    const uint32_t e0 = vfirst[v], e1 = vfirst[v + 1];
+    bool touched = false;
+#pragma unroll 1
+    for (uint32_t e = e0; e < e1; ++e) {
+        const float4 r = recs[e];
+        const float w = tw[__float_as_uint(r.w)];
+        // the skip as a SELECT: the whole record stays one 16-byte load issued before the weight is known (a branch lets the compiler sink the
+        // delta's load behind the weight's: three dependent loads per entry), and an inactive target still leaves the accumulator's bits alone
+        const bool on = w != 0.f;
+        const float d[3] = { r.x, r.y, r.z };
+        float sum[3] = { acc[0], acc[1], acc[2] };
+        morph::add(w, d, sum);
+        for (int a = 0; a < 3; ++a) acc[a] = on ? sum[a] : acc[a];
+        touched = touched || on;
+    }
+    return touched;
+}
+template <bool kBones, bool kNormalDeltas>
+__global__ void rf_morph_kernel(const float *rest_pos, const uint32_t *vfirst, const float4 *pos_recs, const float4 *nrm_recs, const float *tw, uint32_t n_verts,
+                                const float *rest_nrm, const uint32_t *idx, uint32_t n_corners, const uint4 *ids, const float4 *weights, const float4 *bones,
+                                float *pos_out, float *nrm_out) {
+    const uint32_t vertex_blocks = (n_verts + kT - 1) / kT;
+    float M[12], q[3];
+    if (blockIdx.x < vertex_blocks) {
+        const uint32_t v = blockIdx.x * kT + threadIdx.x;
+        if (v >= n_verts) return;
+        float p[3] = { rest_pos[(size_t)v * 3], rest_pos[(size_t)v * 3 + 1], rest_pos[(size_t)v * 3 + 2] };
+        rf_morph_walk(pos_recs, vfirst, tw, v, p);
+        if (kBones) {
+            rf_skin_matrix(bones, ids[v], weights[v], M);
+            pose::point(M, p, q);
+        } else {
+            for (int k = 0; k < 3; ++k) q[k] = p[k];
+        }
+        for (int k = 0; k < 3; ++k) pos_out[(size_t)v * 3 + k] = q[k];
+        return;
+    }
+    const uint32_t k = (blockIdx.x - vertex_blocks) * kT + threadIdx.x;
+    if (!nrm_out || k >= n_corners) return;
+    const uint32_t v = idx[k];   // (< n_verts: trg_morph_bind checked the indices it uploaded)
+    const float rest[3] = { rest_nrm[(size_t)k * 3], rest_nrm[(size_t)k * 3 + 1], rest_nrm[(size_t)k * 3 + 2] };
+    float n1[3] = { rest[0], rest[1], rest[2] };
+    if (kNormalDeltas) {
+        float n[3] = { rest[0], rest[1], rest[2] };
+        const bool touched = rf_morph_walk(nrm_recs, vfirst, tw, v, n);
+        morph::finish_normal(rest, n, touched, n1);
+    }
+    if (kBones) {
+        rf_skin_matrix(bones, ids[v], weights[v], M);
+        pose::normal(M, n1, q);
+    } else {
+        for (int j = 0; j < 3; ++j) q[j] = n1[j];
+    }
+    for (int j = 0; j < 3; ++j) nrm_out[(size_t)k * 3 + j] = q[j];
+}
+
 // ---- per-context scratch (grow-only): trg_ctx::refit, created on first use, freed by refit_state_free ----
 struct Buf {
     void *p = nullptr;
@@ -398,6 +463,27 @@ struct trg::RefitState {
         uint32_t n_verts = 0, n_bones = 0, cur = 0, prev = 1;
         bool bound = false, has_nrm = false;
     } skin;
+    // the rest geometry and the three copies of a binding, with their bookkeeping, written once (include/trg_morph.h uses it; the two bindings
+    // above keep their own, older, members): posed[cur] is the current pose, posed[prev] the one before, posed[spare()] the copy the next apply
+    // writes -- a refused refit then leaves current and previous alone
+    struct Copies {
+        Buf rest_pos, rest_nrm, idx, posed[3], posed_nrm[3];
+        uint32_t n_verts = 0, cur = 0, prev = 1;
+        bool has_nrm = false;
+        uint32_t spare() const { return 3u - cur - prev; }
+        void rotate() { const uint32_t s = spare(); prev = cur; cur = s; }
+        float *pos_of(uint32_t k) const { return posed[k].as<float>(); }
+        float *nrm_of(uint32_t k) const { return has_nrm ? posed_nrm[k].as<float>() : nullptr; }
+        template <typename F> void each(F f) { for (Buf *b : { &rest_pos, &rest_nrm, &idx, &posed[0], &posed[1], &posed[2], &posed_nrm[0], &posed_nrm[1], &posed_nrm[2] }) f(*b); }
+    };
+    // include/trg_morph.h: the binding.  vfirst is n_verts + 1 words; pos_recs and (has_dnrm) nrm_recs 16-byte records; tw the n_targets weights of
+    // the last apply; ids, weights, bones as the skin binding's, only with has_bones
+    struct Morph : SceneMark {
+        Copies g;
+        Buf vfirst, pos_recs, nrm_recs, tw, ids, weights, bones;
+        uint32_t n_targets = 0, n_bones = 0;
+        bool bound = false, has_dnrm = false, has_bones = false;
+    } morph;
 };
 
 namespace {
@@ -413,10 +499,17 @@ void each_skin_buffer(RefitState &s, F f) {
     for (Buf *b : { &k.rest_pos, &k.rest_nrm, &k.idx, &k.ids, &k.weights, &k.bones, &k.posed[0], &k.posed[1], &k.posed[2], &k.posed_nrm[0], &k.posed_nrm[1], &k.posed_nrm[2] }) f(*b);
 }
 template <typename F>
+void each_morph_buffer(RefitState &s, F f) {
+    RefitState::Morph &m = s.morph;
+    m.g.each(f);
+    for (Buf *b : { &m.vfirst, &m.pos_recs, &m.nrm_recs, &m.tw, &m.ids, &m.weights, &m.bones }) f(*b);
+}
+template <typename F>
 void each_buffer(RefitState &s, F f) {
     for (Buf *b : { &s.pos, &s.idx, &s.nrm, &s.childbox, &s.leafbox, &s.ping, &s.pong, &s.qplain, &s.qbox, &s.quadx, &s.boxrows, &s.partial, &s.hdr }) f(*b);
     each_pose_buffer(s, f);
     each_skin_buffer(s, f);
+    each_morph_buffer(s, f);
 }
 int grow(trg_ctx *c, Buf &b, size_t need, const char *what) {
     if (need <= b.bytes && b.p) return TRG_OK;
@@ -684,6 +777,87 @@ void skin_free(trg_ctx *c) {
     each_skin_buffer(*c->refit, [](Buf &b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; });
     c->refit->skin.bound = false;
     c->refit->skin.blob = nullptr;
+}
+
+// ---- the bookkeeping of RefitState::Copies: what bind checks and uploads, read, buffers ----
+// the geometry checks every bind makes, `who` named in the texts
+int geometry_check(trg_ctx *c, const char *who, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris) {
+    if (!c->scene_loaded || !c->blob) return fail(c, TRG_ERR_INVALID, "%s: no scene loaded", who);
+    if (n_tris != c->sc.n_tris) return fail(c, TRG_ERR_INVALID, "%s: %u triangles, the loaded scene has %u", who, n_tris, c->sc.n_tris);
+    if (!positions3 || !indices || n_verts == 0 || n_tris == 0) return fail(c, TRG_ERR_INVALID, "%s: null or empty buffer", who);
+    for (size_t k = 0; k < (size_t)n_tris * 3; ++k)
+        if (indices[k] >= n_verts) return fail(c, TRG_ERR_INVALID, "%s: triangle %u has an index out of range (%u vertices)", who, (uint32_t)(k / 3), n_verts);
+    for (uint32_t v = 0; v < n_verts; ++v)
+        if (!(std::isfinite(positions3[(size_t)v * 3]) && std::isfinite(positions3[(size_t)v * 3 + 1]) && std::isfinite(positions3[(size_t)v * 3 + 2])))
+            return fail(c, TRG_ERR_INVALID, "%s: vertex %u has a coordinate that is not finite", who, v);
+    for (size_t k = 0; normals3 && k < (size_t)n_tris * 9; ++k)
+        if (!std::isfinite(normals3[k])) return fail(c, TRG_ERR_INVALID, "%s: triangle %u has a normal that is not finite", who, (uint32_t)(k / 9));
+    return TRG_OK;
+}
+// rest geometry and indices to the device, the three copies set to the rest pose (enqueued: the caller waits)
+int copies_bind(trg_ctx *c, RefitState::Copies &g, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris) {
+    const size_t pos_bytes = (size_t)n_verts * 12, idx_bytes = (size_t)n_tris * 12, nrm_bytes = (size_t)n_tris * 36;
+    int rc = TRG_OK;
+    if ((rc = grow(c, g.rest_pos, pos_bytes, "rest positions")) || (rc = grow(c, g.idx, idx_bytes, "bound indices")) ||
+        (normals3 && (rc = grow(c, g.rest_nrm, nrm_bytes, "rest normals"))))
+        return rc;
+    for (int k = 0; k < 3; ++k)
+        if ((rc = grow(c, g.posed[k], pos_bytes, "posed positions")) || (normals3 && (rc = grow(c, g.posed_nrm[k], nrm_bytes, "posed normals")))) return rc;
+    RF_HIPCHK(c, hipMemcpyAsync(g.rest_pos.p, positions3, pos_bytes, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(g.idx.p, indices, idx_bytes, hipMemcpyHostToDevice, c->stream));
+    if (normals3) RF_HIPCHK(c, hipMemcpyAsync(g.rest_nrm.p, normals3, nrm_bytes, hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < 3; ++k) {
+        RF_HIPCHK(c, hipMemcpyAsync(g.posed[k].p, g.rest_pos.p, pos_bytes, hipMemcpyDeviceToDevice, c->stream));
+        if (normals3) RF_HIPCHK(c, hipMemcpyAsync(g.posed_nrm[k].p, g.rest_nrm.p, nrm_bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
+    g.n_verts = n_verts;
+    g.cur = 0; g.prev = 1;
+    g.has_nrm = normals3 != nullptr;
+    return TRG_OK;
+}
+int copies_read(trg_ctx *c, const char *who, const RefitState::Copies &g, uint32_t n_tris, float *positions3_host, float *normals3_host) {
+    if (!positions3_host) return fail(c, TRG_ERR_INVALID, "%s: null buffer", who);
+    if (normals3_host && !g.has_nrm) return fail(c, TRG_ERR_INVALID, "%s: bound without normals", who);
+    RF_HIPCHK(c, hipMemcpyAsync(positions3_host, g.posed[g.cur].p, (size_t)g.n_verts * 12, hipMemcpyDeviceToHost, c->stream));
+    if (normals3_host) RF_HIPCHK(c, hipMemcpyAsync(normals3_host, g.posed_nrm[g.cur].p, (size_t)n_tris * 36, hipMemcpyDeviceToHost, c->stream));
+    RF_HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TRG_OK;
+}
+void copies_buffers(const RefitState::Copies &g, void **pos_dev, void **nrm_dev, void **idx_dev, void **prev_pos_dev, void **prev_nrm_dev) {
+    if (pos_dev) *pos_dev = g.posed[g.cur].p;
+    if (nrm_dev) *nrm_dev = g.nrm_of(g.cur);
+    if (idx_dev) *idx_dev = g.idx.p;
+    if (prev_pos_dev) *prev_pos_dev = g.posed[g.prev].p;
+    if (prev_nrm_dev) *prev_nrm_dev = g.nrm_of(g.prev);
+}
+
+// ---- include/trg_morph.h ----
+int morph_of(trg_ctx *c, const char *who, RefitState::Morph **out) {
+    if (!c) return TRG_ERR_INVALID;
+    if (!c->refit || !c->refit->morph.bound) return fail(c, TRG_ERR_INVALID, "%s: nothing bound (trg_morph_bind first)", who);
+    RefitState::Morph &m = c->refit->morph;
+    if (!m.same_scene(c))
+        return fail(c, TRG_ERR_INVALID, "%s: the binding was made for a scene that has been replaced since (bind again)", who);
+    RF_HIPCHK(c, hipSetDevice(c->device));
+    *out = &m;
+    return TRG_OK;
+}
+
+void morph_free(trg_ctx *c) {
+    if (!c->refit) return;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    each_morph_buffer(*c->refit, [](Buf &b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; });
+    c->refit->morph.bound = false;
+    c->refit->morph.blob = nullptr;
+}
+
+template <bool kBones, bool kNormalDeltas>
+int morph_launch(trg_ctx *c, RefitState::Morph &m, size_t blocks, float *pos_out, float *nrm_out) {
+    RF_LAUNCH(c, (rf_morph_kernel<kBones, kNormalDeltas>), dim3((uint32_t)blocks), m.g.rest_pos.as<float>(), m.vfirst.as<uint32_t>(), m.pos_recs.as<float4>(),
+              m.nrm_recs.as<float4>(), m.tw.as<float>(), m.g.n_verts, m.g.rest_nrm.as<float>(), m.g.idx.as<uint32_t>(), m.n_tris * 3u, m.ids.as<uint4>(),
+              m.weights.as<float4>(), m.bones.as<float4>(), pos_out, nrm_out);
+    return TRG_OK;
 }
 
 }  // namespace
@@ -982,6 +1156,158 @@ int trg_group_skin_apply(trg_group *g, const float *bones12) {
         trg_ctx *c = trg_group_ctx(g, r);
         if (!c) return TRG_ERR_INVALID;
         if (int rc = trg_skin_apply(c, bones12)) return rc;
+    }
+    return TRG_OK;
+}
+
+int trg_morph_bind(trg_ctx *c, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris, uint32_t n_targets,
+                   const uint32_t *target_first, uint32_t n_entries, const uint32_t *entry_vertex, const float *entry_dpos3, const float *entry_dnrm3, const uint32_t *bone_ids4,
+                   const float *bone_weights4, uint32_t n_bones) {
+    if (!c) return TRG_ERR_INVALID;
+#if TRG_WIDE8
+    return fail(c, TRG_ERR_INVALID, "trg_morph_bind: an 8-wide experiments build has no blend shapes");
+#endif
+    if (int rc = geometry_check(c, "trg_morph_bind", positions3, normals3, indices, n_verts, n_tris)) return rc;
+    if (n_targets == 0 || !target_first) return fail(c, TRG_ERR_INVALID, "trg_morph_bind: no targets (at least one is needed, and its table)");
+    uint32_t target = 0, entry = 0;
+    switch (morph::targets_check(target_first, n_targets, n_entries, &target)) {
+    case morph::kTargetsFirst: return fail(c, TRG_ERR_INVALID, "trg_morph_bind: target 0 begins at entry %u, not at 0", target_first[0]);
+    case morph::kTargetsOrder: return fail(c, TRG_ERR_INVALID, "trg_morph_bind: target %u begins at entry %u and ends at %u: the table is descending", target, target_first[target], target_first[target + 1]);
+    case morph::kTargetsEnd: return fail(c, TRG_ERR_INVALID, "trg_morph_bind: target %u ends at entry %u, there are %u entries", target, target_first[n_targets], n_entries);
+    default: break;
+    }
+    if (n_entries && (!entry_vertex || !entry_dpos3)) return fail(c, TRG_ERR_INVALID, "trg_morph_bind: %u entries, and a null entry list", n_entries);
+    switch (morph::entries_check(target_first, n_targets, entry_vertex, n_verts, entry_dpos3, entry_dnrm3, &target, &entry)) {
+    case morph::kEntriesVertex: return fail(c, TRG_ERR_INVALID, "trg_morph_bind: entry %u of target %u names vertex %u, there are %u vertices", entry, target, entry_vertex[entry], n_verts);
+    case morph::kEntriesOrder: return fail(c, TRG_ERR_INVALID, "trg_morph_bind: entry %u of target %u names vertex %u after vertex %u: a target's vertices are strictly ascending", entry, target, entry_vertex[entry], entry_vertex[entry - 1]);
+    case morph::kEntriesDelta: return fail(c, TRG_ERR_INVALID, "trg_morph_bind: entry %u of target %u has a position delta that is not finite", entry, target);
+    case morph::kEntriesNormalDelta: return fail(c, TRG_ERR_INVALID, "trg_morph_bind: entry %u of target %u has a normal delta that is not finite", entry, target);
+    default: break;
+    }
+    if (entry_dnrm3 && !normals3) return fail(c, TRG_ERR_INVALID, "trg_morph_bind: normal deltas given without normals");
+    const bool has_bones = bone_ids4 && bone_weights4 && n_bones;
+    if (!has_bones && (bone_ids4 || bone_weights4 || n_bones))
+        return fail(c, TRG_ERR_INVALID, "trg_morph_bind: bone ids, bone weights and the number of bones are given all three or none (ids %s, weights %s, %u bones)",
+                    bone_ids4 ? "given" : "null", bone_weights4 ? "given" : "null", n_bones);
+    if (has_bones) {
+        uint32_t vert = 0, slot = 0;
+        if (skin::ids_check(bone_ids4, n_verts, n_bones, &vert, &slot) != skin::kSkinOk)
+            return fail(c, TRG_ERR_INVALID, "trg_morph_bind: vertex %u names bone %u (id %u of its four), there are %u bones", vert, bone_ids4[(size_t)vert * 4 + slot], slot, n_bones);
+        switch (skin::weights_check(bone_weights4, n_verts, &vert, &slot)) {
+        case skin::kSkinWeight: return fail(c, TRG_ERR_INVALID, "trg_morph_bind: vertex %u has a weight (%u of its four) that is negative or not finite", vert, slot);
+        case skin::kSkinSum: {
+            const float *w = bone_weights4 + (size_t)vert * 4;
+            return fail(c, TRG_ERR_INVALID, "trg_morph_bind: vertex %u has weights that sum to %.9g, not to 1 within 1e-4 (weights are not normalised here)", vert,
+                        (double)w[0] + (double)w[1] + (double)w[2] + (double)w[3]);
+        }
+        default: break;
+        }
+    }
+    // by-target lists -> per-vertex records.  (At least one record is allocated: a binding whose targets are all empty is legal.)
+    std::vector<uint32_t> vfirst((size_t)n_verts + 1), cursor(n_verts);
+    std::vector<morph::Rec> pos_recs(n_entries), nrm_recs(entry_dnrm3 ? n_entries : 0);
+    morph::transpose(target_first, n_targets, entry_vertex, entry_dpos3, entry_dnrm3, n_verts, vfirst.data(), cursor.data(), pos_recs.data(), entry_dnrm3 ? nrm_recs.data() : nullptr);
+
+    RF_HIPCHK(c, hipSetDevice(c->device));
+    RefitState &s = state_of(c);
+    RefitState::Morph &m = s.morph;
+    m.bound = false;
+    const size_t rec_bytes = (size_t)n_entries * sizeof(morph::Rec), skin_bytes = (size_t)n_verts * 16;
+    int rc = TRG_OK;
+    if ((rc = grow(c, m.vfirst, vfirst.size() * 4, "entry ranges")) || (rc = grow(c, m.pos_recs, rec_bytes + 16, "position deltas")) ||
+        (entry_dnrm3 && (rc = grow(c, m.nrm_recs, rec_bytes + 16, "normal deltas"))) || (rc = grow(c, m.tw, (size_t)n_targets * 4, "target weights")) ||
+        (has_bones && ((rc = grow(c, m.ids, skin_bytes, "bone ids")) || (rc = grow(c, m.weights, skin_bytes, "bone weights")) || (rc = grow(c, m.bones, (size_t)n_bones * 48, "bones")))))
+        return rc;
+    if ((rc = copies_bind(c, m.g, positions3, normals3, indices, n_verts, n_tris))) return rc;
+    RF_HIPCHK(c, hipMemcpyAsync(m.vfirst.p, vfirst.data(), vfirst.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (rec_bytes) RF_HIPCHK(c, hipMemcpyAsync(m.pos_recs.p, pos_recs.data(), rec_bytes, hipMemcpyHostToDevice, c->stream));
+    if (rec_bytes && entry_dnrm3) RF_HIPCHK(c, hipMemcpyAsync(m.nrm_recs.p, nrm_recs.data(), rec_bytes, hipMemcpyHostToDevice, c->stream));
+    if (has_bones) {
+        RF_HIPCHK(c, hipMemcpyAsync(m.ids.p, bone_ids4, skin_bytes, hipMemcpyHostToDevice, c->stream));
+        RF_HIPCHK(c, hipMemcpyAsync(m.weights.p, bone_weights4, skin_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    RF_HIPCHK(c, hipStreamSynchronize(c->stream));   // (the records are this call's own arrays, and the caller's are free again on return)
+    m.n_tris = n_tris; m.n_targets = n_targets; m.n_bones = has_bones ? n_bones : 0u;
+    m.has_dnrm = entry_dnrm3 != nullptr;
+    m.has_bones = has_bones;
+    m.remember_scene(c);
+    m.bound = true;
+    return TRG_OK;
+}
+
+int trg_morph_apply(trg_ctx *c, const float *target_weights, const float *bones12) {
+    RefitState::Morph *mp = nullptr;
+    if (int rc = morph_of(c, "trg_morph_apply", &mp)) return rc;
+    RefitState::Morph &m = *mp;
+    if (!target_weights) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: null target weights");
+    for (uint32_t k = 0; k < m.n_targets; ++k)
+        if (!std::isfinite(target_weights[k])) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: the weight of target %u is not finite", k);
+    if (m.has_bones && !bones12) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: null bones, the binding has %u", m.n_bones);
+    if (!m.has_bones && bones12) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: bones given, the binding has none");
+    for (size_t k = 0; k < (size_t)m.n_bones * 12; ++k)
+        if (!std::isfinite(bones12[k])) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: bone %u is not finite", (uint32_t)(k / 12));
+    const uint32_t spare = m.g.spare();
+    float *pos_out = m.g.pos_of(spare), *nrm_out = m.g.nrm_of(spare);
+    RF_HIPCHK(c, hipMemcpyAsync(m.tw.p, target_weights, (size_t)m.n_targets * 4, hipMemcpyHostToDevice, c->stream));
+    if (m.has_bones) RF_HIPCHK(c, hipMemcpyAsync(m.bones.p, bones12, (size_t)m.n_bones * 48, hipMemcpyHostToDevice, c->stream));
+    // no corner can change without normal deltas and without bones: that copy holds the rest normals since bind, and the range is left out
+    const bool corners = m.g.has_nrm && (m.has_dnrm || m.has_bones);
+    const size_t blocks = ((size_t)m.g.n_verts + kT - 1) / kT + (corners ? ((size_t)m.n_tris * 3 + kT - 1) / kT : 0);
+    int rc = TRG_OK;
+    if (m.has_bones) rc = m.has_dnrm ? morph_launch<true, true>(c, m, blocks, pos_out, nrm_out) : morph_launch<true, false>(c, m, blocks, pos_out, nrm_out);
+    else rc = m.has_dnrm ? morph_launch<false, true>(c, m, blocks, pos_out, nrm_out) : morph_launch<false, false>(c, m, blocks, pos_out, nrm_out);
+    if (rc) return rc;
+    if ((rc = refit_from_device(c, pos_out, nrm_out, m.g.idx.as<uint32_t>(), m.g.n_verts, m.n_tris))) return rc;   // (current and previous are untouched)
+    m.g.rotate();
+    m.remember_scene(c);   // (the small-scene path gives the same scene new memory, and builds it)
+    return TRG_OK;
+}
+
+int trg_morph_read(trg_ctx *c, float *positions3_host, float *normals3_host) {
+    RefitState::Morph *m = nullptr;
+    if (int rc = morph_of(c, "trg_morph_read", &m)) return rc;
+    return copies_read(c, "trg_morph_read", m->g, m->n_tris, positions3_host, normals3_host);
+}
+
+int trg_morph_buffers(trg_ctx *c, void **pos_dev, void **nrm_dev, void **idx_dev, void **prev_pos_dev, void **prev_nrm_dev) {
+    RefitState::Morph *m = nullptr;
+    if (int rc = morph_of(c, "trg_morph_buffers", &m)) return rc;
+    copies_buffers(m->g, pos_dev, nrm_dev, idx_dev, prev_pos_dev, prev_nrm_dev);
+    return TRG_OK;
+}
+
+int trg_morph_release(trg_ctx *c) {
+    if (!c) return TRG_ERR_INVALID;
+    morph_free(c);
+    return TRG_OK;
+}
+
+int trg_group_morph_bind(trg_group *g, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris, uint32_t n_targets,
+                         const uint32_t *target_first, uint32_t n_entries, const uint32_t *entry_vertex, const float *entry_dpos3, const float *entry_dnrm3, const uint32_t *bone_ids4,
+                         const float *bone_weights4, uint32_t n_bones) {
+    if (!g) return TRG_ERR_INVALID;
+    const int n = trg_group_size(g);
+    if (n <= 0) return TRG_ERR_INVALID;
+    if (int rc = trg_group_sync(g)) return rc;
+    for (int r = 0; r < n; ++r) {
+        trg_ctx *c = trg_group_ctx(g, r);
+        if (!c) return TRG_ERR_INVALID;
+        if (int rc = trg_morph_bind(c, positions3, normals3, indices, n_verts, n_tris, n_targets, target_first, n_entries, entry_vertex, entry_dpos3, entry_dnrm3, bone_ids4,
+                                    bone_weights4, n_bones))
+            return rc;
+    }
+    return TRG_OK;
+}
+
+int trg_group_morph_apply(trg_group *g, const float *target_weights, const float *bones12) {
+    if (!g) return TRG_ERR_INVALID;
+    const int n = trg_group_size(g);
+    if (n <= 0) return TRG_ERR_INVALID;
+    if (int rc = trg_group_sync(g)) return rc;
+    for (int r = 0; r < n; ++r) {
+        trg_ctx *c = trg_group_ctx(g, r);
+        if (!c) return TRG_ERR_INVALID;
+        if (int rc = trg_morph_apply(c, target_weights, bones12)) return rc;
     }
     return TRG_OK;
 }
