@@ -168,6 +168,7 @@ protected:
     uint32_t m_skinVerts = 0;    // the vertex count bound by bindSkin
     unsigned int m_morphs = 0;   // morphs applied
     uint32_t m_morphVerts = 0;   // the vertex count bound by bindMorph
+    void afterPose(int (*buffers)(trg_ctx *, void **, void **, void **, void **, void **), uint32_t nVerts);   // the history follows an apply
 };
 
 }  // namespace toyraygun

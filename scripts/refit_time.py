@@ -31,6 +31,11 @@ medians over `reps`, each call followed by a wait, both libraries straight throu
 same morphed geometry; with --parent-so that library's trg_refit_scene -- what a caller with blend shapes pays today, before the CPU morph itself.
 rf_morph_kernel's own time: the same kernel-trace run, with --legs morph.
 
+Every apply and every trg_refit_scene is called straight through ctypes, as the parent's are (the wrappers' argument checks cost about 10 us, the
+size of the differences looked for; the skin leg times refit.py's wrapper beside them).  With --parent-so every leg
+also binds the same data on the parent library, when it exports the leg's symbols, and times ITS trg_{pose,skin,morph}_apply in the same alternation:
+parent_<call>, and <call>_within_parent_spread -- this build's median lies between the smallest and the largest of the parent's samples.
+
 Prints one JSON line (and writes it to --out)."""
 import argparse
 import json
@@ -49,15 +54,58 @@ def parent_context(path, w, h, pos, nrm, col, idx, mat):
     """A context of ANOTHER build of the library (ctypes keeps the two apart), device-built scene loaded: (library, handle)."""
     import ctypes as C
     L = C.CDLL(path)
-    for name, res, args in capi._SYMBOLS:
+    for name, res, args in capi._SYMBOLS + refit._SYMBOLS + pose._SYMBOLS + skin._SYMBOLS + morph._SYMBOLS:
         if hasattr(L, name):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
-    L.trg_refit_scene.restype, L.trg_refit_scene.argtypes = C.c_int, [C.c_void_p] * 4 + [C.c_uint32] * 2
     h_ctx = C.c_void_p()
     assert L.trg_create(C.byref(h_ctx), 0, w, h) == 0
     assert L.trg_set_option(h_ctx, capi.OPT_GPU_BUILD, 1) == 0
     assert L.trg_load_scene(h_ctx, pos.ctypes.data, nrm.ctypes.data, col.ctypes.data, idx.ctypes.data, mat.ctypes.data, pos.shape[0], mat.shape[0]) == 0
     return L, h_ctx
+
+
+def raw(L, h, name, *args):
+    """A C call of either library straight through ctypes (arrays by their address, None as it is), then the wait for its stream."""
+    rc = getattr(L, name)(h, *[x.ctypes.data if isinstance(x, np.ndarray) else x for x in args])
+    assert rc == 0, (name, L.trg_last_error(h))
+    L.trg_sync(h)
+
+
+def cube_bones(n_verts, n_cubes, d):
+    """One bone for the Cornell box and one per cube: (ids, weights, bones at rest, bones moved, n_bones).  Every vertex names FOUR DISTINCT bones
+    (its own and the next three), its weight 1 on its own; every cube's moved bone is its translation d.  (The pose leg's objects are these bones.)"""
+    n_bones = n_cubes + 1
+    own = np.concatenate([np.zeros(108, np.int64), 1 + np.repeat(np.arange(n_cubes), 36)])
+    ids = ((own[:, None] + np.arange(4)[None, :]) % n_bones).astype(np.uint32)
+    wts = np.zeros((n_verts, 4), np.float32)
+    wts[:, 0] = 1.0
+    x0 = np.tile(np.eye(3, 4, dtype=np.float32).reshape(1, 12), (n_bones, 1))
+    x1 = x0.copy()
+    x1[1:, [3, 7, 11]] = d
+    return ids, wts, x0, x1, n_bones
+
+
+def alternate(calls, reps, timed):
+    """Every call once (scratch is allocated once, and every call is accepted), then alternating `reps` times: {name: [ms]}.  A call takes the
+    round's number: calls that alternate between two inputs are never a no-op."""
+    for f in calls.values():
+        f(0)
+    t = {k: [] for k in calls}
+    for k in range(reps):
+        for name, f in calls.items():
+            t[name].append(timed(lambda: f(k)))
+    return t
+
+
+def medians(t, key=lambda k: k):
+    """{<key>_ms: the median, <key>_ms_all: every sample} of alternate()'s samples."""
+    r = {key(k) + "_ms": statistics.median(v) for k, v in t.items()}
+    r.update({key(k) + "_ms_all": [round(x, 3) for x in v] for k, v in t.items()})
+    return r
+
+
+def within_spread(t, ours, parents):
+    return bool(min(t[parents]) <= statistics.median(t[ours]) <= max(t[parents]))
 
 
 def main():
@@ -135,96 +183,84 @@ def main():
             res[name] = r
         if "device" in res:
             res["refit_beats_device_rebuild"] = bool(res["device"]["refit_moved_ms"] < res["device"]["load_ms"] and res["host"]["refit_moved_ms"] < res["device"]["load_ms"])
-        if "pose" in a.legs.split(","):
+        RL, PoL, SL, ML = refit.load(), pose.load(), skin.load(), morph.load()
+        nv = pos0.shape[0]
+        ids, wts, x0, x1, n_bones = cube_bones(nv, n_cubes, d)
+
+        def refit_calls(parent, moved, tensors=None):
+            # trg_refit_scene of this library and of the parent's are called the same way, straight through ctypes (the size of the difference looked
+            # for is the wrapper's 10 us); trg_refit_scene_device from torch tensors of the same geometry
+            calls = {"refit_scene": lambda k: raw(RL, c.h_ctx, "trg_refit_scene", moved, nrm, idx, nv, nt)}
+            if tensors:
+                calls["refit_scene_device"] = lambda k: pose.refit_scene_device(c, *tensors)
+            if parent:
+                calls["parent_refit_scene"] = lambda k: raw(parent[0], parent[1], "trg_refit_scene", moved, nrm, idx, nv, nt)
+            return calls
+
+        def device_tensors():
             import torch
+            t = torch.from_numpy(pos1).cuda(), torch.from_numpy(nrm).cuda(), torch.from_numpy(idx.view(np.int32)).cuda()
+            torch.cuda.synchronize()
+            return t
+
+        if "pose" in a.legs.split(","):
             first = np.concatenate([[0], 36 + 12 * np.arange(n_cubes + 1)]).astype(np.uint32)
-            x0 = np.tile(np.eye(3, 4, dtype=np.float32).reshape(1, 12), (n_cubes + 1, 1))
-            x1 = x0.copy()
-            x1[1:, [3, 7, 11]] = d
             load(1, pos0)
             pose.bind(c, pos0, nrm, idx, first)
             pose.apply(c, x1)
-            got, _ = pose.read(c, pos0.shape[0], nt)
+            got, _ = pose.read(c, nv, nt)
             assert (got == pos1).all()                                     # the same posed geometry as the host arrays of the refit leg
-            t_pos, t_nrm, t_idx = torch.from_numpy(pos1).cuda(), torch.from_numpy(nrm).cuda(), torch.from_numpy(idx.view(np.int32)).cuda()
-            torch.cuda.synchronize()
             parent = parent_context(a.parent_so, a.w, a.h, pos0, nrm, col, idx, mat) if a.parent_so else None
-            calls = {"pose_apply": lambda k: pose.apply(c, x1 if k % 2 == 0 else x0),          # alternating poses: nothing is a no-op
-                     "refit_scene_device": lambda k: pose.refit_scene_device(c, t_pos, t_nrm, t_idx),
-                     "refit_scene": lambda k: refit.refit_scene(c, pos1, nrm, idx)}
-            if parent:
-                PL, ph = parent
-                calls["parent_refit_scene"] = lambda k: (PL.trg_refit_scene(ph, pos1.ctypes.data, nrm.ctypes.data, idx.ctypes.data, pos1.shape[0], nt), PL.trg_sync(ph))
-            for f in calls.values():                                       # (scratch is allocated once)
-                f(0)
-            t = {k: [] for k in calls}
-            for k in range(a.reps):
-                for name, f in calls.items():
-                    t[name].append(timed(lambda: f(k)))
-            r = {k + "_ms": statistics.median(v) for k, v in t.items()}
-            r.update({k + "_ms_all": [round(x, 3) for x in v] for k, v in t.items()})
-            r["objects"] = int(n_cubes + 1)
-            r["upload_bytes"] = {"pose_apply": int(48 * (n_cubes + 1)), "refit_scene": int(pos1.nbytes + idx.nbytes + nrm.nbytes)}
+            calls = {"pose_apply": lambda k: raw(PoL, c.h_ctx, "trg_pose_apply", (x1, x0)[k % 2])}
+            calls.update(refit_calls(parent, pos1, device_tensors()))
+            if parent and hasattr(parent[0], "trg_pose_apply"):
+                raw(parent[0], parent[1], "trg_pose_bind", pos0, nrm, idx, nv, nt, first, n_bones)
+                calls["parent_pose_apply"] = lambda k: raw(parent[0], parent[1], "trg_pose_apply", (x1, x0)[k % 2])
+            t = alternate(calls, a.reps, timed)
+            r = medians(t)
+            r["objects"] = int(n_bones)
+            r["upload_bytes"] = {"pose_apply": int(48 * n_bones), "refit_scene": int(pos1.nbytes + idx.nbytes + nrm.nbytes)}
             r["posing_on_top_of_the_refit_ms"] = r["pose_apply_ms"] - r["refit_scene_device_ms"]    # upload of the matrices + rf_pose_kernel
             pose.apply(c, x1)
             r["render_after_pose_ms"] = render_ms()
             r["pose_not_slower_than_refit_scene"] = bool(r["pose_apply_ms"] <= r["refit_scene_ms"])
+            if "parent_pose_apply" in t:
+                r["pose_apply_within_parent_spread"] = within_spread(t, "pose_apply", "parent_pose_apply")
             res["pose"] = r
             if parent:
-                PL.trg_destroy(ph)
+                parent[0].trg_destroy(parent[1])
         if "skin" in a.legs.split(","):
-            import torch
-            n_bones = n_cubes + 1
-            own = np.concatenate([np.zeros(108, np.int64), 1 + np.repeat(np.arange(n_cubes), 36)])
-            ids = ((own[:, None] + np.arange(4)[None, :]) % n_bones).astype(np.uint32)      # four distinct bones per vertex
-            wts = np.zeros((pos0.shape[0], 4), np.float32)
-            wts[:, 0] = 1.0
-            x0 = np.tile(np.eye(3, 4, dtype=np.float32).reshape(1, 12), (n_bones, 1))
-            x1 = x0.copy()
-            x1[1:, [3, 7, 11]] = d
             load(1, pos0)
             skin.bind(c, pos0, nrm, idx, ids, wts, n_bones)
             skin.apply(c, x1)
             got, _ = skin.read(c)
             assert (got == pos1).all()                                     # the same geometry as the host arrays of the refit leg
-            t_pos, t_nrm, t_idx = torch.from_numpy(pos1).cuda(), torch.from_numpy(nrm).cuda(), torch.from_numpy(idx.view(np.int32)).cuda()
-            torch.cuda.synchronize()
             parent = parent_context(a.parent_so, a.w, a.h, pos0, nrm, col, idx, mat) if a.parent_so else None
-            RL = refit.load()
-            # (trg_refit_scene of this library and of the parent's are called the same way, straight through ctypes: the wrapper's argument
-            # checks cost about 10 us, which is the size of the difference looked for)
-            calls = {"skin_apply": lambda k: skin.apply(c, x1 if k % 2 == 0 else x0),          # alternating: nothing is a no-op
-                     "refit_scene_device": lambda k: pose.refit_scene_device(c, t_pos, t_nrm, t_idx),
-                     "refit_scene": lambda k: (RL.trg_refit_scene(c.h_ctx, pos1.ctypes.data, nrm.ctypes.data, idx.ctypes.data, pos1.shape[0], nt), RL.trg_sync(c.h_ctx)),
-                     "refit_scene_through_refit_py": lambda k: refit.refit_scene(c, pos1, nrm, idx)}
-            if parent:
-                PL, ph = parent
-                calls["parent_refit_scene"] = lambda k: (PL.trg_refit_scene(ph, pos1.ctypes.data, nrm.ctypes.data, idx.ctypes.data, pos1.shape[0], nt), PL.trg_sync(ph))
-            for f in calls.values():                                       # (scratch is allocated once)
-                f(0)
-            t = {k: [] for k in calls}
-            for k in range(a.reps):
-                for name, f in calls.items():
-                    t[name].append(timed(lambda: f(k)))
-            r = {k + "_ms": statistics.median(v) for k, v in t.items()}
-            r.update({k + "_ms_all": [round(x, 3) for x in v] for k, v in t.items()})
+            calls = {"skin_apply": lambda k: raw(SL, c.h_ctx, "trg_skin_apply", (x1, x0)[k % 2])}
+            calls.update(refit_calls(parent, pos1, device_tensors()))
+            calls["refit_scene_through_refit_py"] = lambda k: refit.refit_scene(c, pos1, nrm, idx)
+            if parent and hasattr(parent[0], "trg_skin_apply"):
+                raw(parent[0], parent[1], "trg_skin_bind", pos0, nrm, idx, nv, nt, ids, wts, n_bones)
+                calls["parent_skin_apply"] = lambda k: raw(parent[0], parent[1], "trg_skin_apply", (x1, x0)[k % 2])
+            t = alternate(calls, a.reps, timed)
+            r = medians(t)
             r["bones"] = int(n_bones)
-            r["vertices"] = int(pos0.shape[0])
+            r["vertices"] = int(nv)
             r["upload_bytes"] = {"skin_apply": int(48 * n_bones), "refit_scene": int(pos1.nbytes + idx.nbytes + nrm.nbytes)}
             r["skinning_on_top_of_the_refit_ms"] = r["skin_apply_ms"] - r["refit_scene_device_ms"]  # upload of the bones + rf_skin_kernel
             # what rf_skin_kernel streams: 16 + 16 + 12 + 12 per vertex, 4 + 16 + 16 + 12 + 12 per corner (the bones come from cache)
-            r["kernel_streamed_bytes"] = int(56 * pos0.shape[0] + 60 * 3 * nt)
+            r["kernel_streamed_bytes"] = int(56 * nv + 60 * 3 * nt)
             skin.apply(c, x1)
             r["render_after_skin_ms"] = render_ms()
             if parent:
                 r["skin_not_slower_than_parent_refit_scene"] = bool(r["skin_apply_ms"] <= r["parent_refit_scene_ms"])
-                lo, hi = min(t["parent_refit_scene"]), max(t["parent_refit_scene"])
-                r["refit_scene_within_parent_spread"] = bool(lo <= r["refit_scene_ms"] <= hi)
-                PL.trg_destroy(ph)
+                r["refit_scene_within_parent_spread"] = within_spread(t, "refit_scene", "parent_refit_scene")
+                if "parent_skin_apply" in t:
+                    r["skin_apply_within_parent_spread"] = within_spread(t, "skin_apply", "parent_skin_apply")
+                parent[0].trg_destroy(parent[1])
             skin.release(c)
             res["skin"] = r
         if "morph" in a.legs.split(","):
-            nv = pos0.shape[0]
             cube = np.concatenate([np.full(108, -1, np.int64), np.repeat(np.arange(n_cubes), 36)])      # vertex -> cube (-1: the Cornell box)
             centre = pos0[108:108 + 36 * n_cubes].astype(np.float64).reshape(n_cubes, 36, 3).mean(1)
             shift = np.concatenate([np.zeros((108, 3), np.float32), np.repeat(d, 36, axis=0)])
@@ -238,17 +274,9 @@ def main():
             ev, dp = np.concatenate(ev).astype(np.uint32), np.ascontiguousarray(np.concatenate(dp))
             assert (np.bincount(ev, minlength=nv) == 3).all()              # every vertex holds three entries
             wA, wB = np.array([1, 0.5, 1, 0, 0, 0, 0, 0], np.float32), np.array([0.5, 1, 0, 0, 1, 0, 0, 1], np.float32)
-            n_bones = n_cubes + 1
-            own = np.concatenate([np.zeros(108, np.int64), 1 + np.repeat(np.arange(n_cubes), 36)])
-            ids = ((own[:, None] + np.arange(4)[None, :]) % n_bones).astype(np.uint32)      # four distinct bones per vertex
-            wts = np.zeros((nv, 4), np.float32)
-            wts[:, 0] = 1.0
-            x0 = np.tile(np.eye(3, 4, dtype=np.float32).reshape(1, 12), (n_bones, 1))
-            x1 = x0.copy()
-            x1[1:, [3, 7, 11]] = d
             load(1, pos0)
             parent = parent_context(a.parent_so, a.w, a.h, pos0, nrm, col, idx, mat) if a.parent_so else None
-            RL, ML, SL = refit.load(), morph.load(), skin.load()
+            parent_morphs = parent and hasattr(parent[0], "trg_morph_apply")
             skin.bind(c, pos0, nrm, idx, ids, wts, n_bones)
             r = {"vertices": int(nv), "targets": 8, "entries": int(ev.shape[0]), "bones": int(n_bones)}
             for with_bones in (False, True):
@@ -259,25 +287,20 @@ def main():
                 ref, _ = morph.morph_reference(pos0, None, idx, first, ev, dp, None, wA, **(dict(bone_ids=ids, bone_weights=wts, bones=x1) if with_bones else {}))
                 assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
                 posA = np.ascontiguousarray(got)                           # the morphed geometry a caller would have made on the CPU
-                bones = (x1.ctypes.data, x0.ctypes.data) if with_bones else (None, None)
-                calls = {tag: lambda k: (ML.trg_morph_apply(c.h_ctx, (wA, wB)[k % 2].ctypes.data, bones[k % 2]), RL.trg_sync(c.h_ctx)),
-                         "skin_apply": lambda k: (SL.trg_skin_apply(c.h_ctx, (x1, x0)[k % 2].ctypes.data), RL.trg_sync(c.h_ctx)),
-                         "refit_scene": lambda k: (RL.trg_refit_scene(c.h_ctx, posA.ctypes.data, nrm.ctypes.data, idx.ctypes.data, nv, nt), RL.trg_sync(c.h_ctx))}
-                if parent:
-                    PL, ph = parent
-                    calls["parent_refit_scene"] = lambda k: (PL.trg_refit_scene(ph, posA.ctypes.data, nrm.ctypes.data, idx.ctypes.data, nv, nt), PL.trg_sync(ph))
-                for name, f in calls.items():                              # (scratch is allocated once; and every call is accepted)
-                    assert f(0) == (0, 0), (name, RL.trg_last_error(c.h_ctx))
-                t = {k: [] for k in calls}
-                for k in range(a.reps):
-                    for name, f in calls.items():
-                        t[name].append(timed(lambda: f(k)))
-                assert all(f(1) == (0, 0) for f in calls.values())
-                for k, v in t.items():
-                    key = k if k == tag else k + ("_beside_bones" if with_bones else "")
-                    r[key + "_ms"], r[key + "_ms_all"] = statistics.median(v), [round(x, 3) for x in v]
+                bones = (x1, x0) if with_bones else (None, None)
+                calls = {tag: lambda k: raw(ML, c.h_ctx, "trg_morph_apply", (wA, wB)[k % 2], bones[k % 2]),
+                         "skin_apply": lambda k: raw(SL, c.h_ctx, "trg_skin_apply", (x1, x0)[k % 2])}
+                calls.update(refit_calls(parent, posA))
+                if parent_morphs:
+                    raw(parent[0], parent[1], "trg_morph_bind", pos0, nrm, idx, nv, nt, 8, first, int(ev.shape[0]), ev, dp, None,
+                        *((ids, wts, n_bones) if with_bones else (None, None, 0)))
+                    calls["parent_" + tag] = lambda k: raw(parent[0], parent[1], "trg_morph_apply", (wA, wB)[k % 2], bones[k % 2])
+                t = alternate(calls, a.reps, timed)
+                r.update(medians(t, lambda k: k if k.endswith(tag) else k + ("_beside_bones" if with_bones else "")))
                 if parent:
                     r[tag + "_not_slower_than_parent_refit_scene"] = bool(statistics.median(t[tag]) <= statistics.median(t["parent_refit_scene"]))
+                if parent_morphs:
+                    r[tag + "_within_parent_spread"] = within_spread(t, tag, "parent_" + tag)
             r["upload_bytes"] = {"morph_apply": 4 * 8, "morph_apply_bones": int(4 * 8 + 48 * n_bones), "refit_scene": int(pos0.nbytes + idx.nbytes + nrm.nbytes)}
             # what rf_morph_kernel streams.  Without bones (no normal deltas: the corner range is not launched): 12 in, 12 out, one range word and
             # three 16-byte records per vertex.  With bones: 16 + 16 more per vertex, and 4 + 16 + 16 + 12 + 12 per corner (the bones and the
@@ -286,7 +309,7 @@ def main():
                                           "skin_apply": int(56 * nv + 60 * 3 * nt)}
             r["render_after_morph_ms"] = render_ms()
             if parent:
-                PL.trg_destroy(ph)
+                parent[0].trg_destroy(parent[1])
             morph.release(c)
             skin.release(c)
             res["morph"] = r

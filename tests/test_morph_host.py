@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from tests import morph_scenes as MS
+from tests import pose_scenes as PS
 from tests import refit_scenes as RS
 from tests import skin_scenes as SS
 
@@ -344,3 +345,24 @@ def test_morph_reference_against_a_float64_evaluation(indexed):
                 worst_pos, worst_nrm = max(worst_pos, err), max(worst_nrm, np.abs(nrm - ref_nrm).max())
         print("morph_reference vs float64, %s, bones %d: positions %.3f ulp of the extent, normals %.3e" % ("indexed" if indexed else "per corner", with_bones, worst_pos, worst_nrm))
         assert worst_pos <= POS_ULP_BAR[with_bones] and worst_nrm <= NRM_BAR[with_bones]
+
+
+@SCENES
+def test_pose_and_one_hot_skin_share_one_normal_transform_bit_for_bit(indexed):
+    """pose_reference and skin_reference call ONE normal transform (toyraygun_amd/_binding.py): handed random affine matrices per object, and the
+    same matrices blended with one-hot weights (1 B + 0 B' = B exactly while no entry of B is zero), it gives the same bits -- what
+    test_one_hot_weights_are_trg_pose_apply asserts of the device.  A vertex no triangle names keeps its place under a pose and follows the
+    identity bone here."""
+    from toyraygun_amd import pose, skin
+    b = MS.scene(indexed)
+    ids, w, nb = SS.one_hot(b)
+    named = SS._objects(b) >= 0
+    for seed in (1, 2, 3):
+        X = np.random.default_rng(4100 + seed).normal(size=(PS.N_OBJECTS_A, 12)).astype(np.float32)
+        X[seed] *= np.float32(-1.0)                                         # one object mirrored against the others, whatever its sign was
+        assert (X != 0).all()
+        p_pos, p_nrm = pose.pose_reference(b["positions"], b["normals"], b["indices"], PS.scene_a_first(), X)
+        s_pos, s_nrm = skin.skin_reference(b["positions"], b["normals"], b["indices"], ids, w, np.concatenate([X, SS.identity(1)]))
+        assert (p_nrm != b["normals"]).any()
+        assert np.array_equal(p_nrm.view(np.uint32), s_nrm.view(np.uint32))
+        assert np.array_equal(p_pos[named].view(np.uint32), s_pos[named].view(np.uint32))

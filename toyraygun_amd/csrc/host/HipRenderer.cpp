@@ -214,19 +214,47 @@ static int poseEach(trg_group *group, trg_ctx *ctx, Call call, const char **text
     return TRG_OK;
 }
 
+// a Scene's arrays and counts as a bind takes them; false: there is nothing to bind
+struct BindGeometry {
+    const float *pos, *nrm;
+    const uint32_t *idx;
+    uint32_t nVerts, nTris;
+};
+static bool bindGeometry(Scene *scene, BindGeometry *g) {
+    g->nTris = (uint32_t)scene->m_materialIDBuffer.size();
+    g->nVerts = (uint32_t)scene->m_vertexBuffer.size();
+    if (!g->nVerts || !g->nTris || scene->m_indexBuffer.size() != (size_t)g->nTris * 3) return false;
+    // (a scene without a normal per corner is bound without normals: the loaded ones stay, and a morph's normal deltas are then refused)
+    g->pos = &scene->m_vertexBuffer[0].x;
+    g->nrm = scene->m_normalBuffer.size() == (size_t)g->nTris * 3 ? &scene->m_normalBuffer[0].x : nullptr;
+    g->idx = &scene->m_indexBuffer[0];
+    return true;
+}
+
+// after an apply of any unit that succeeded: `buffers` is the unit's trg_*_buffers, nVerts what its bind bound
+void HipRenderer::afterPose(int (*buffers)(trg_ctx *, void **, void **, void **, void **, void **), uint32_t nVerts) {
+    // (updateScene's remembered vectors are no longer what the device holds: its next call loads)
+    m_lastPositions.clear(); m_lastNormals.clear(); m_lastIndices.clear();
+    if (!m_denoiseTemporal || m_group) return;
+    // what was current is the unit's PREVIOUS pose now, and stays untouched through the next apply: the history is told where every triangle was
+    void *prevPos = nullptr, *prevNrm = nullptr, *idx = nullptr;
+    if (buffers(m_ctx, nullptr, nullptr, &idx, &prevPos, &prevNrm) != TRG_OK ||
+        trg_temporal_set_previous_scene_device(m_ctx, prevPos, prevNrm, idx, nVerts, (uint32_t)m_loadedTris) != TRG_OK) {
+        printf("HipRenderer: %s\n", trg_last_error(m_ctx));
+        trg_temporal_reset(m_ctx);   // the history cannot be followed: start over, as loadScene does
+        m_temporalOut = nullptr;
+    }
+}
+
 bool HipRenderer::bindObjects(Scene *scene, const uint32_t *firstTri, unsigned int nObjects) {
     if (!m_ctx || !scene || !m_sceneLoaded || !firstTri) return false;
     flush();
-    const uint32_t nTris = (uint32_t)scene->m_materialIDBuffer.size();
-    const uint32_t nVerts = (uint32_t)scene->m_vertexBuffer.size();
-    if (!nVerts || !nTris || scene->m_indexBuffer.size() != (size_t)nTris * 3) return false;
-    // (a scene without a normal per corner is bound without normals: the loaded ones stay)
-    const float *pos = &scene->m_vertexBuffer[0].x, *nrm = scene->m_normalBuffer.size() == (size_t)nTris * 3 ? &scene->m_normalBuffer[0].x : nullptr;
-    const uint32_t *idx = &scene->m_indexBuffer[0];
+    BindGeometry g;
+    if (!bindGeometry(scene, &g)) return false;
     const char *text = "";
-    const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) { return trg_pose_bind(c, pos, nrm, idx, nVerts, nTris, firstTri, nObjects); }, &text);
+    const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) { return trg_pose_bind(c, g.pos, g.nrm, g.idx, g.nVerts, g.nTris, firstTri, nObjects); }, &text);
     if (rc != TRG_OK) { printf("HipRenderer: objects not bound (%s)\n", text); fflush(stdout); }
-    else m_poseVerts = nVerts;
+    else m_poseVerts = g.nVerts;
     return rc == TRG_OK;
 }
 
@@ -241,34 +269,19 @@ bool HipRenderer::poseObjects(const float *xforms12) {
         return false;
     }
     ++m_poses;
-    // (updateScene's remembered vectors are no longer what the device holds: its next call loads)
-    m_lastPositions.clear(); m_lastNormals.clear(); m_lastIndices.clear();
-    if (m_denoiseTemporal && !m_group) {
-        // what was current is the unit's PREVIOUS pose now, and stays untouched through the next apply: the history is told where every triangle was
-        void *prevPos = nullptr, *prevNrm = nullptr, *idx = nullptr;
-        if (trg_pose_buffers(m_ctx, nullptr, nullptr, &idx, &prevPos, &prevNrm) != TRG_OK ||
-            trg_temporal_set_previous_scene_device(m_ctx, prevPos, prevNrm, idx, m_poseVerts, (uint32_t)m_loadedTris) != TRG_OK) {
-            printf("HipRenderer: %s\n", trg_last_error(m_ctx));
-            trg_temporal_reset(m_ctx);   // the history cannot be followed: start over, as loadScene does
-            m_temporalOut = nullptr;
-        }
-    }
+    afterPose(trg_pose_buffers, m_poseVerts);
     return true;
 }
 
 bool HipRenderer::bindSkin(Scene *scene, const uint32_t *boneIds4, const float *weights4, unsigned int nBones) {
     if (!m_ctx || !scene || !m_sceneLoaded || !boneIds4 || !weights4) return false;
     flush();
-    const uint32_t nTris = (uint32_t)scene->m_materialIDBuffer.size();
-    const uint32_t nVerts = (uint32_t)scene->m_vertexBuffer.size();
-    if (!nVerts || !nTris || scene->m_indexBuffer.size() != (size_t)nTris * 3) return false;
-    // (a scene without a normal per corner is bound without normals: the loaded ones stay)
-    const float *pos = &scene->m_vertexBuffer[0].x, *nrm = scene->m_normalBuffer.size() == (size_t)nTris * 3 ? &scene->m_normalBuffer[0].x : nullptr;
-    const uint32_t *idx = &scene->m_indexBuffer[0];
+    BindGeometry g;
+    if (!bindGeometry(scene, &g)) return false;
     const char *text = "";
-    const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) { return trg_skin_bind(c, pos, nrm, idx, nVerts, nTris, boneIds4, weights4, nBones); }, &text);
+    const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) { return trg_skin_bind(c, g.pos, g.nrm, g.idx, g.nVerts, g.nTris, boneIds4, weights4, nBones); }, &text);
     if (rc != TRG_OK) { printf("HipRenderer: skin not bound (%s)\n", text); fflush(stdout); }
-    else m_skinVerts = nVerts;
+    else m_skinVerts = g.nVerts;
     return rc == TRG_OK;
 }
 
@@ -283,18 +296,7 @@ bool HipRenderer::poseSkin(const float *bones12) {
         return false;
     }
     ++m_skins;
-    // (updateScene's remembered vectors are no longer what the device holds: its next call loads)
-    m_lastPositions.clear(); m_lastNormals.clear(); m_lastIndices.clear();
-    if (m_denoiseTemporal && !m_group) {
-        // what was current is the unit's PREVIOUS pose now, and stays untouched through the next apply: the history is told where every triangle was
-        void *prevPos = nullptr, *prevNrm = nullptr, *idx = nullptr;
-        if (trg_skin_buffers(m_ctx, nullptr, nullptr, &idx, &prevPos, &prevNrm) != TRG_OK ||
-            trg_temporal_set_previous_scene_device(m_ctx, prevPos, prevNrm, idx, m_skinVerts, (uint32_t)m_loadedTris) != TRG_OK) {
-            printf("HipRenderer: %s\n", trg_last_error(m_ctx));
-            trg_temporal_reset(m_ctx);   // the history cannot be followed: start over, as loadScene does
-            m_temporalOut = nullptr;
-        }
-    }
+    afterPose(trg_skin_buffers, m_skinVerts);
     return true;
 }
 
@@ -302,18 +304,14 @@ bool HipRenderer::bindMorph(Scene *scene, unsigned int nTargets, const uint32_t 
                             const float *entryDnrm3, const uint32_t *boneIds4, const float *boneWeights4, unsigned int nBones) {
     if (!m_ctx || !scene || !m_sceneLoaded || !nTargets || !targetFirst) return false;
     flush();
-    const uint32_t nTris = (uint32_t)scene->m_materialIDBuffer.size();
-    const uint32_t nVerts = (uint32_t)scene->m_vertexBuffer.size();
-    if (!nVerts || !nTris || scene->m_indexBuffer.size() != (size_t)nTris * 3) return false;
-    // (a scene without a normal per corner is bound without normals: the loaded ones stay, and normal deltas are then refused)
-    const float *pos = &scene->m_vertexBuffer[0].x, *nrm = scene->m_normalBuffer.size() == (size_t)nTris * 3 ? &scene->m_normalBuffer[0].x : nullptr;
-    const uint32_t *idx = &scene->m_indexBuffer[0];
+    BindGeometry g;
+    if (!bindGeometry(scene, &g)) return false;
     const char *text = "";
     const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) {
-        return trg_morph_bind(c, pos, nrm, idx, nVerts, nTris, nTargets, targetFirst, targetFirst[nTargets], entryVertex, entryDpos3, entryDnrm3, boneIds4, boneWeights4, nBones);
+        return trg_morph_bind(c, g.pos, g.nrm, g.idx, g.nVerts, g.nTris, nTargets, targetFirst, targetFirst[nTargets], entryVertex, entryDpos3, entryDnrm3, boneIds4, boneWeights4, nBones);
     }, &text);
     if (rc != TRG_OK) { printf("HipRenderer: morph not bound (%s)\n", text); fflush(stdout); }
-    else m_morphVerts = nVerts;
+    else m_morphVerts = g.nVerts;
     return rc == TRG_OK;
 }
 
@@ -328,18 +326,7 @@ bool HipRenderer::poseMorph(const float *targetWeights, const float *bones12) {
         return false;
     }
     ++m_morphs;
-    // (updateScene's remembered vectors are no longer what the device holds: its next call loads)
-    m_lastPositions.clear(); m_lastNormals.clear(); m_lastIndices.clear();
-    if (m_denoiseTemporal && !m_group) {
-        // what was current is the unit's PREVIOUS pose now, and stays untouched through the next apply: the history is told where every triangle was
-        void *prevPos = nullptr, *prevNrm = nullptr, *idx = nullptr;
-        if (trg_morph_buffers(m_ctx, nullptr, nullptr, &idx, &prevPos, &prevNrm) != TRG_OK ||
-            trg_temporal_set_previous_scene_device(m_ctx, prevPos, prevNrm, idx, m_morphVerts, (uint32_t)m_loadedTris) != TRG_OK) {
-            printf("HipRenderer: %s\n", trg_last_error(m_ctx));
-            trg_temporal_reset(m_ctx);   // the history cannot be followed: start over, as loadScene does
-            m_temporalOut = nullptr;
-        }
-    }
+    afterPose(trg_morph_buffers, m_morphVerts);
     return true;
 }
 

@@ -3,7 +3,7 @@
 // kernels that apply it, the order they run in, and the small-scene path through the host builder.  include/trg_pose.h lives here too: it shares
 // refit_device and the context's RefitState -- the same refit from buffers already on the device, and the per-object poses that feed it
 // (arithmetic: trg_pose_math.h).  So does include/trg_skin.h: blended bone matrices per vertex in front of the same refit (trg_skin_math.h).
-// And include/trg_morph.h: blend shapes in front of that skin (trg_morph_math.h).
+// And include/trg_morph.h: blend shapes in front of that skin (trg_morph_math.h).  The three keep one binding protocol: RefitState::Binding.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -434,11 +434,20 @@ struct trg::RefitState {
     trg_refit_info last{};
     const void *area_blob = nullptr;   // the blob whose as-loaded areas are remembered, and what its arrays summed to after this unit's last write
     double loaded_area[2] = { 0.0, 0.0 }, written_area[2] = { 0.0, 0.0 };
-    // the scene a binding was made for.  A HEURISTIC (trg_ctx.h has no load counter and stays as it is): its memory, its layout and -- a reload of
-    // as many bytes is usually handed the same address -- the time its build took, which every trg_load_scene measures anew.  Shared by the pose
-    // and the skin binding
-    struct SceneMark {
-        uint32_t n_tris = 0;
+    // ---- THE BINDING PROTOCOL, once, for include/trg_pose.h, trg_skin.h and trg_morph.h (a unit adds its own inputs and its kernel) ----
+    // bind     validates on the host FIRST -- a refusal there leaves an earlier binding as it was -- then marks the unit unbound, uploads the rest
+    //          geometry and the indices, sets all three copies to the rest pose, waits, remembers the scene and marks the unit bound.  A failure
+    //          while allocating or copying leaves it unbound.
+    // apply    poses into posed[spare()], refits the loaded scene from that copy (apply_finish) and only then rotates: posed[cur] is the current
+    //          pose, posed[prev] the one before.  A refused apply or refit has written the spare copy alone: current, previous and scene stay.
+    // read / buffers  the current copy to the host / the addresses of current and previous.  release frees one unit's buffers.
+    // The three bindings of a context are independent: bound together, each with its own current and previous pose; the loaded scene is the last
+    // apply's.  The scene a binding was made for is known by a HEURISTIC (trg_ctx.h has no load counter and stays as it is): its memory, its layout
+    // and -- a reload of as many bytes is usually handed the same address -- the time its build took, which every trg_load_scene measures anew.
+    struct Binding {
+        Buf rest_pos, rest_nrm, idx, posed[3], posed_nrm[3];
+        uint32_t n_verts = 0, n_tris = 0, cur = 0, prev = 1;
+        bool bound = false, has_nrm = false;
         const void *blob = nullptr;
         double build_ms = 0.0;
         uint32_t blob_bytes = 0, n_nodes4 = 0, n_fat = 0, off_fat = 0;
@@ -449,67 +458,49 @@ struct trg::RefitState {
         void remember_scene(const trg_ctx *c) {
             blob = c->blob; build_ms = c->last_build_ms; blob_bytes = c->sc.blob_bytes; n_nodes4 = c->sc.n_nodes4; n_fat = c->sc.n_fat; off_fat = c->sc.off_fat;
         }
-    };
-    // include/trg_pose.h: the binding.  posed[cur] is the current pose, posed[prev] the one before, posed[3 - cur - prev] the copy the next apply
-    // poses into -- a refused refit then leaves current and previous alone
-    struct Pose : SceneMark {
-        Buf rest_pos, rest_nrm, idx, vtx_obj, tri_obj, xforms, posed[3], posed_nrm[3];
-        uint32_t n_verts = 0, n_objects = 0, cur = 0, prev = 1;
-        bool bound = false, has_nrm = false;
-    } pose;
-    // include/trg_skin.h: the binding, with the same three copies.  ids and weights are 16-byte records per vertex, bones 48 bytes each
-    struct Skin : SceneMark {
-        Buf rest_pos, rest_nrm, idx, ids, weights, bones, posed[3], posed_nrm[3];
-        uint32_t n_verts = 0, n_bones = 0, cur = 0, prev = 1;
-        bool bound = false, has_nrm = false;
-    } skin;
-    // the rest geometry and the three copies of a binding, with their bookkeeping, written once (include/trg_morph.h uses it; the two bindings
-    // above keep their own, older, members): posed[cur] is the current pose, posed[prev] the one before, posed[spare()] the copy the next apply
-    // writes -- a refused refit then leaves current and previous alone
-    struct Copies {
-        Buf rest_pos, rest_nrm, idx, posed[3], posed_nrm[3];
-        uint32_t n_verts = 0, cur = 0, prev = 1;
-        bool has_nrm = false;
         uint32_t spare() const { return 3u - cur - prev; }
         void rotate() { const uint32_t s = spare(); prev = cur; cur = s; }
         float *pos_of(uint32_t k) const { return posed[k].as<float>(); }
         float *nrm_of(uint32_t k) const { return has_nrm ? posed_nrm[k].as<float>() : nullptr; }
-        template <typename F> void each(F f) { for (Buf *b : { &rest_pos, &rest_nrm, &idx, &posed[0], &posed[1], &posed[2], &posed_nrm[0], &posed_nrm[1], &posed_nrm[2] }) f(*b); }
+        // vertex blocks, then -- corners -- corner blocks: the grid of every apply kernel
+        uint32_t blocks(bool corners) const { return (uint32_t)(((size_t)n_verts + kT - 1) / kT + (corners ? ((size_t)n_tris * 3 + kT - 1) / kT : 0)); }
+        template <typename F> void each_shared(F f) { for (Buf *b : { &rest_pos, &rest_nrm, &idx, &posed[0], &posed[1], &posed[2], &posed_nrm[0], &posed_nrm[1], &posed_nrm[2] }) f(*b); }
     };
-    // include/trg_morph.h: the binding.  vfirst is n_verts + 1 words; pos_recs and (has_dnrm) nrm_recs 16-byte records; tw the n_targets weights of
-    // the last apply; ids, weights, bones as the skin binding's, only with has_bones
-    struct Morph : SceneMark {
-        Copies g;
+    // what each unit adds: its own buffers, listed once (each_own), and their counts
+    struct Pose : Binding {
+        Buf vtx_obj, tri_obj, xforms;
+        uint32_t n_objects = 0;
+        template <typename F> void each_own(F f) { for (Buf *b : { &vtx_obj, &tri_obj, &xforms }) f(*b); }
+    } pose;
+    // ids and weights are 16-byte records per vertex, bones 48 bytes each
+    struct Skin : Binding {
+        Buf ids, weights, bones;
+        uint32_t n_bones = 0;
+        template <typename F> void each_own(F f) { for (Buf *b : { &ids, &weights, &bones }) f(*b); }
+    } skin;
+    // vfirst is n_verts + 1 words; pos_recs and (has_dnrm) nrm_recs 16-byte records; tw the n_targets weights of the last apply; ids, weights, bones as
+    // the skin binding's, only with has_bones
+    struct Morph : Binding {
         Buf vfirst, pos_recs, nrm_recs, tw, ids, weights, bones;
         uint32_t n_targets = 0, n_bones = 0;
-        bool bound = false, has_dnrm = false, has_bones = false;
+        bool has_dnrm = false, has_bones = false;
+        template <typename F> void each_own(F f) { for (Buf *b : { &vfirst, &pos_recs, &nrm_recs, &tw, &ids, &weights, &bones }) f(*b); }
     } morph;
 };
 
 namespace {
 
-template <typename F>
-void each_pose_buffer(RefitState &s, F f) {
-    RefitState::Pose &p = s.pose;
-    for (Buf *b : { &p.rest_pos, &p.rest_nrm, &p.idx, &p.vtx_obj, &p.tri_obj, &p.xforms, &p.posed[0], &p.posed[1], &p.posed[2], &p.posed_nrm[0], &p.posed_nrm[1], &p.posed_nrm[2] }) f(*b);
-}
-template <typename F>
-void each_skin_buffer(RefitState &s, F f) {
-    RefitState::Skin &k = s.skin;
-    for (Buf *b : { &k.rest_pos, &k.rest_nrm, &k.idx, &k.ids, &k.weights, &k.bones, &k.posed[0], &k.posed[1], &k.posed[2], &k.posed_nrm[0], &k.posed_nrm[1], &k.posed_nrm[2] }) f(*b);
-}
-template <typename F>
-void each_morph_buffer(RefitState &s, F f) {
-    RefitState::Morph &m = s.morph;
-    m.g.each(f);
-    for (Buf *b : { &m.vfirst, &m.pos_recs, &m.nrm_recs, &m.tw, &m.ids, &m.weights, &m.bones }) f(*b);
+template <typename B, typename F>
+void each_binding_buffer(B &b, F f) {
+    b.each_shared(f);
+    b.each_own(f);
 }
 template <typename F>
 void each_buffer(RefitState &s, F f) {
     for (Buf *b : { &s.pos, &s.idx, &s.nrm, &s.childbox, &s.leafbox, &s.ping, &s.pong, &s.qplain, &s.qbox, &s.quadx, &s.boxrows, &s.partial, &s.hdr }) f(*b);
-    each_pose_buffer(s, f);
-    each_skin_buffer(s, f);
-    each_morph_buffer(s, f);
+    each_binding_buffer(s.pose, f);
+    each_binding_buffer(s.skin, f);
+    each_binding_buffer(s.morph, f);
 }
 int grow(trg_ctx *c, Buf &b, size_t need, const char *what) {
     if (need <= b.bytes && b.p) return TRG_OK;
@@ -700,7 +691,7 @@ int refit_arguments(trg_ctx *c, const void *positions3, const void *indices, uin
     return TRG_OK;
 }
 
-// ---- include/trg_pose.h ----
+// ---- include/trg_pose.h: trg_refit_scene_device ----
 // `need` bytes from p on: device memory of the context's device, by the runtime's own records; nothing is enqueued
 int device_span(trg_ctx *c, const void *p, size_t need, const char *what) {
     hipPointerAttribute_t attr{};
@@ -722,7 +713,7 @@ int device_span(trg_ctx *c, const void *p, size_t need, const char *what) {
     return TRG_OK;
 }
 
-// buffers on the context's device (vouched for by the caller: device_span, or the pose unit's own): the device path reads them in place, a scene
+// buffers on the context's device (vouched for by the caller: device_span, or a binding's own): the device path reads them in place, a scene
 // of the LDS tier is rebuilt from a download of them
 int refit_from_device(trg_ctx *c, const float *pos, const float *nrm, const uint32_t *idx, uint32_t n_verts, uint32_t n_tris) {
     if (c->sc.n_nodes == 0 && n_tris != 0) return refit_device(c, pos, nrm, idx, n_verts, n_tris, true);
@@ -737,56 +728,46 @@ int refit_from_device(trg_ctx *c, const float *pos, const float *nrm, const uint
     return refit_rebuild(c, h_pos.data(), nrm ? h_nrm.data() : nullptr, h_idx.data(), n_verts, n_tris);
 }
 
-// the context's binding, or why there is none to use
-int pose_of(trg_ctx *c, const char *who, RefitState::Pose **out) {
+// ---- the binding protocol (RefitState::Binding), `who` the entry point named in the texts ----
+// the context's binding `unit`, or why there is none to use
+template <typename B>
+int binding_of(trg_ctx *c, const char *who, B RefitState::*unit, const char *bind_name, B **out) {
     if (!c) return TRG_ERR_INVALID;
-    if (!c->refit || !c->refit->pose.bound) return fail(c, TRG_ERR_INVALID, "%s: nothing bound (trg_pose_bind first)", who);
-    RefitState::Pose &p = c->refit->pose;
-    if (!p.same_scene(c))
+    if (!c->refit || !(c->refit->*unit).bound) return fail(c, TRG_ERR_INVALID, "%s: nothing bound (%s first)", who, bind_name);
+    B &b = c->refit->*unit;
+    if (!b.same_scene(c))
         return fail(c, TRG_ERR_INVALID, "%s: the binding was made for a scene that has been replaced since (bind again)", who);
     RF_HIPCHK(c, hipSetDevice(c->device));
-    *out = &p;
+    *out = &b;
     return TRG_OK;
 }
 
-void pose_free(trg_ctx *c) {
-    if (!c->refit) return;
+template <typename B>
+int binding_release(trg_ctx *c, B RefitState::*unit) {
+    if (!c) return TRG_ERR_INVALID;
+    if (!c->refit) return TRG_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    each_pose_buffer(*c->refit, [](Buf &b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; });
-    c->refit->pose.bound = false;
-    c->refit->pose.blob = nullptr;
-}
-
-// ---- include/trg_skin.h ----
-int skin_of(trg_ctx *c, const char *who, RefitState::Skin **out) {
-    if (!c) return TRG_ERR_INVALID;
-    if (!c->refit || !c->refit->skin.bound) return fail(c, TRG_ERR_INVALID, "%s: nothing bound (trg_skin_bind first)", who);
-    RefitState::Skin &k = c->refit->skin;
-    if (!k.same_scene(c))
-        return fail(c, TRG_ERR_INVALID, "%s: the binding was made for a scene that has been replaced since (bind again)", who);
-    RF_HIPCHK(c, hipSetDevice(c->device));
-    *out = &k;
+    B &b = c->refit->*unit;
+    each_binding_buffer(b, [](Buf &buf) { if (buf.p) (void)hipFree(buf.p); buf.p = nullptr; buf.bytes = 0; });
+    b.bound = false;
+    b.blob = nullptr;
     return TRG_OK;
 }
 
-void skin_free(trg_ctx *c) {
-    if (!c->refit) return;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    each_skin_buffer(*c->refit, [](Buf &b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; });
-    c->refit->skin.bound = false;
-    c->refit->skin.blob = nullptr;
-}
-
-// ---- the bookkeeping of RefitState::Copies: what bind checks and uploads, read, buffers ----
-// the geometry checks every bind makes, `who` named in the texts
-int geometry_check(trg_ctx *c, const char *who, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris) {
+// what a bind checks of the geometry, in three pieces: every bind reports its first offence in an order of its own
+int scene_check(trg_ctx *c, const char *who, uint32_t n_tris, bool null_or_empty) {
     if (!c->scene_loaded || !c->blob) return fail(c, TRG_ERR_INVALID, "%s: no scene loaded", who);
     if (n_tris != c->sc.n_tris) return fail(c, TRG_ERR_INVALID, "%s: %u triangles, the loaded scene has %u", who, n_tris, c->sc.n_tris);
-    if (!positions3 || !indices || n_verts == 0 || n_tris == 0) return fail(c, TRG_ERR_INVALID, "%s: null or empty buffer", who);
+    if (null_or_empty) return fail(c, TRG_ERR_INVALID, "%s: null or empty buffer", who);
+    return TRG_OK;
+}
+int indices_check(trg_ctx *c, const char *who, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris) {
     for (size_t k = 0; k < (size_t)n_tris * 3; ++k)
         if (indices[k] >= n_verts) return fail(c, TRG_ERR_INVALID, "%s: triangle %u has an index out of range (%u vertices)", who, (uint32_t)(k / 3), n_verts);
+    return TRG_OK;
+}
+int finite_check(trg_ctx *c, const char *who, const float *positions3, const float *normals3, uint32_t n_verts, uint32_t n_tris) {
     for (uint32_t v = 0; v < n_verts; ++v)
         if (!(std::isfinite(positions3[(size_t)v * 3]) && std::isfinite(positions3[(size_t)v * 3 + 1]) && std::isfinite(positions3[(size_t)v * 3 + 2])))
             return fail(c, TRG_ERR_INVALID, "%s: vertex %u has a coordinate that is not finite", who, v);
@@ -794,8 +775,32 @@ int geometry_check(trg_ctx *c, const char *who, const float *positions3, const f
         if (!std::isfinite(normals3[k])) return fail(c, TRG_ERR_INVALID, "%s: triangle %u has a normal that is not finite", who, (uint32_t)(k / 9));
     return TRG_OK;
 }
-// rest geometry and indices to the device, the three copies set to the rest pose (enqueued: the caller waits)
-int copies_bind(trg_ctx *c, RefitState::Copies &g, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris) {
+// the skin unit's rules for ids and weights (trg_skin_math.h), for the binds that take them
+int skin_check(trg_ctx *c, const char *who, const uint32_t *bone_ids4, const float *weights4, uint32_t n_verts, uint32_t n_bones) {
+    uint32_t vert = 0, slot = 0;
+    if (skin::ids_check(bone_ids4, n_verts, n_bones, &vert, &slot) != skin::kSkinOk)
+        return fail(c, TRG_ERR_INVALID, "%s: vertex %u names bone %u (id %u of its four), there are %u bones", who, vert, bone_ids4[(size_t)vert * 4 + slot], slot, n_bones);
+    switch (skin::weights_check(weights4, n_verts, &vert, &slot)) {
+    case skin::kSkinWeight: return fail(c, TRG_ERR_INVALID, "%s: vertex %u has a weight (%u of its four) that is negative or not finite", who, vert, slot);
+    case skin::kSkinSum: {
+        const float *w = weights4 + (size_t)vert * 4;
+        return fail(c, TRG_ERR_INVALID, "%s: vertex %u has weights that sum to %.9g, not to 1 within 1e-4 (weights are not normalised here)", who, vert,
+                    (double)w[0] + (double)w[1] + (double)w[2] + (double)w[3]);
+    }
+    default: return TRG_OK;
+    }
+}
+int bones_finite(trg_ctx *c, const char *who, const float *bones12, uint32_t n_bones) {
+    for (size_t k = 0; k < (size_t)n_bones * 12; ++k)
+        if (!std::isfinite(bones12[k])) return fail(c, TRG_ERR_INVALID, "%s: bone %u is not finite", who, (uint32_t)(k / 12));
+    return TRG_OK;
+}
+
+// bind, after validation: the unit is unbound from here on; rest geometry and indices to the device, the three copies set to the rest pose
+// (enqueued: the unit adds its own uploads, and bind_finish waits)
+int copies_bind(trg_ctx *c, RefitState::Binding &g, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris) {
+    RF_HIPCHK(c, hipSetDevice(c->device));
+    g.bound = false;
     const size_t pos_bytes = (size_t)n_verts * 12, idx_bytes = (size_t)n_tris * 12, nrm_bytes = (size_t)n_tris * 36;
     int rc = TRG_OK;
     if ((rc = grow(c, g.rest_pos, pos_bytes, "rest positions")) || (rc = grow(c, g.idx, idx_bytes, "bound indices")) ||
@@ -815,47 +820,64 @@ int copies_bind(trg_ctx *c, RefitState::Copies &g, const float *positions3, cons
     g.has_nrm = normals3 != nullptr;
     return TRG_OK;
 }
-int copies_read(trg_ctx *c, const char *who, const RefitState::Copies &g, uint32_t n_tris, float *positions3_host, float *normals3_host) {
+int bind_finish(trg_ctx *c, RefitState::Binding &g, uint32_t n_tris) {
+    RF_HIPCHK(c, hipStreamSynchronize(c->stream));   // (the caller's arrays, and the bind's own, are free again on return)
+    g.n_tris = n_tris;
+    g.remember_scene(c);
+    g.bound = true;
+    return TRG_OK;
+}
+// apply, after the unit's kernel wrote the spare copy: the loaded scene from it, and only then is it the current pose
+int apply_finish(trg_ctx *c, RefitState::Binding &g) {
+    const uint32_t spare = g.spare();
+    if (int rc = refit_from_device(c, g.pos_of(spare), g.nrm_of(spare), g.idx.as<uint32_t>(), g.n_verts, g.n_tris)) return rc;   // (current and previous are untouched)
+    g.rotate();
+    g.remember_scene(c);   // (the small-scene path gives the same scene new memory, and builds it)
+    return TRG_OK;
+}
+template <typename B>
+int binding_read(trg_ctx *c, const char *who, B RefitState::*unit, const char *bind_name, float *positions3_host, float *normals3_host) {
+    B *g = nullptr;
+    if (int rc = binding_of(c, who, unit, bind_name, &g)) return rc;
     if (!positions3_host) return fail(c, TRG_ERR_INVALID, "%s: null buffer", who);
-    if (normals3_host && !g.has_nrm) return fail(c, TRG_ERR_INVALID, "%s: bound without normals", who);
-    RF_HIPCHK(c, hipMemcpyAsync(positions3_host, g.posed[g.cur].p, (size_t)g.n_verts * 12, hipMemcpyDeviceToHost, c->stream));
-    if (normals3_host) RF_HIPCHK(c, hipMemcpyAsync(normals3_host, g.posed_nrm[g.cur].p, (size_t)n_tris * 36, hipMemcpyDeviceToHost, c->stream));
+    if (normals3_host && !g->has_nrm) return fail(c, TRG_ERR_INVALID, "%s: bound without normals", who);
+    RF_HIPCHK(c, hipMemcpyAsync(positions3_host, g->posed[g->cur].p, (size_t)g->n_verts * 12, hipMemcpyDeviceToHost, c->stream));
+    if (normals3_host) RF_HIPCHK(c, hipMemcpyAsync(normals3_host, g->posed_nrm[g->cur].p, (size_t)g->n_tris * 36, hipMemcpyDeviceToHost, c->stream));
     RF_HIPCHK(c, hipStreamSynchronize(c->stream));
     return TRG_OK;
 }
-void copies_buffers(const RefitState::Copies &g, void **pos_dev, void **nrm_dev, void **idx_dev, void **prev_pos_dev, void **prev_nrm_dev) {
-    if (pos_dev) *pos_dev = g.posed[g.cur].p;
-    if (nrm_dev) *nrm_dev = g.nrm_of(g.cur);
-    if (idx_dev) *idx_dev = g.idx.p;
-    if (prev_pos_dev) *prev_pos_dev = g.posed[g.prev].p;
-    if (prev_nrm_dev) *prev_nrm_dev = g.nrm_of(g.prev);
-}
-
-// ---- include/trg_morph.h ----
-int morph_of(trg_ctx *c, const char *who, RefitState::Morph **out) {
-    if (!c) return TRG_ERR_INVALID;
-    if (!c->refit || !c->refit->morph.bound) return fail(c, TRG_ERR_INVALID, "%s: nothing bound (trg_morph_bind first)", who);
-    RefitState::Morph &m = c->refit->morph;
-    if (!m.same_scene(c))
-        return fail(c, TRG_ERR_INVALID, "%s: the binding was made for a scene that has been replaced since (bind again)", who);
-    RF_HIPCHK(c, hipSetDevice(c->device));
-    *out = &m;
+template <typename B>
+int binding_buffers(trg_ctx *c, const char *who, B RefitState::*unit, const char *bind_name, void **pos_dev, void **nrm_dev, void **idx_dev, void **prev_pos_dev,
+                    void **prev_nrm_dev) {
+    B *g = nullptr;
+    if (int rc = binding_of(c, who, unit, bind_name, &g)) return rc;
+    if (pos_dev) *pos_dev = g->posed[g->cur].p;
+    if (nrm_dev) *nrm_dev = g->nrm_of(g->cur);
+    if (idx_dev) *idx_dev = g->idx.p;
+    if (prev_pos_dev) *prev_pos_dev = g->posed[g->prev].p;
+    if (prev_nrm_dev) *prev_nrm_dev = g->nrm_of(g->prev);
     return TRG_OK;
 }
 
-void morph_free(trg_ctx *c) {
-    if (!c->refit) return;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    each_morph_buffer(*c->refit, [](Buf &b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; });
-    c->refit->morph.bound = false;
-    c->refit->morph.blob = nullptr;
+// a call on every context of a group in turn, after the group's wait; the first refusal ends it
+template <typename Call>
+int group_each(trg_group *g, Call call) {
+    if (!g) return TRG_ERR_INVALID;
+    const int n = trg_group_size(g);
+    if (n <= 0) return TRG_ERR_INVALID;
+    if (int rc = trg_group_sync(g)) return rc;
+    for (int r = 0; r < n; ++r) {
+        trg_ctx *c = trg_group_ctx(g, r);
+        if (!c) return TRG_ERR_INVALID;
+        if (int rc = call(c)) return rc;
+    }
+    return TRG_OK;
 }
 
 template <bool kBones, bool kNormalDeltas>
-int morph_launch(trg_ctx *c, RefitState::Morph &m, size_t blocks, float *pos_out, float *nrm_out) {
-    RF_LAUNCH(c, (rf_morph_kernel<kBones, kNormalDeltas>), dim3((uint32_t)blocks), m.g.rest_pos.as<float>(), m.vfirst.as<uint32_t>(), m.pos_recs.as<float4>(),
-              m.nrm_recs.as<float4>(), m.tw.as<float>(), m.g.n_verts, m.g.rest_nrm.as<float>(), m.g.idx.as<uint32_t>(), m.n_tris * 3u, m.ids.as<uint4>(),
+int morph_launch(trg_ctx *c, RefitState::Morph &m, uint32_t blocks, float *pos_out, float *nrm_out) {
+    RF_LAUNCH(c, (rf_morph_kernel<kBones, kNormalDeltas>), dim3(blocks), m.rest_pos.as<float>(), m.vfirst.as<uint32_t>(), m.pos_recs.as<float4>(),
+              m.nrm_recs.as<float4>(), m.tw.as<float>(), m.n_verts, m.rest_nrm.as<float>(), m.idx.as<uint32_t>(), m.n_tris * 3u, m.ids.as<uint4>(),
               m.weights.as<float4>(), m.bones.as<float4>(), pos_out, nrm_out);
     return TRG_OK;
 }
@@ -898,9 +920,8 @@ int trg_pose_bind(trg_ctx *c, const float *positions3, const float *normals3, co
 #if TRG_WIDE8
     return fail(c, TRG_ERR_INVALID, "trg_pose_bind: an 8-wide experiments build has no poses");
 #endif
-    if (!c->scene_loaded || !c->blob) return fail(c, TRG_ERR_INVALID, "trg_pose_bind: no scene loaded");
-    if (n_tris != c->sc.n_tris) return fail(c, TRG_ERR_INVALID, "trg_pose_bind: %u triangles, the loaded scene has %u", n_tris, c->sc.n_tris);
-    if (!positions3 || !indices || !object_first_tri || n_verts == 0 || n_tris == 0 || n_objects == 0) return fail(c, TRG_ERR_INVALID, "trg_pose_bind: null or empty buffer");
+    const char *who = "trg_pose_bind";
+    if (int rc = scene_check(c, who, n_tris, !positions3 || !indices || !object_first_tri || n_verts == 0 || n_tris == 0 || n_objects == 0)) return rc;
     uint32_t obj = 0, tri = 0, vert = 0;
     switch (pose::table_check(object_first_tri, n_objects, n_tris, &obj)) {
     case pose::kTableFirst: return fail(c, TRG_ERR_INVALID, "trg_pose_bind: object 0 begins at triangle %u, not at 0", object_first_tri[0]);
@@ -910,120 +931,54 @@ int trg_pose_bind(trg_ctx *c, const float *positions3, const float *normals3, co
     }
     std::vector<uint32_t> tri_obj(n_tris), vtx_obj(n_verts);
     pose::triangle_objects(object_first_tri, n_objects, tri_obj.data());
-    switch (pose::vertex_objects(indices, n_verts, n_tris, tri_obj.data(), vtx_obj.data(), &tri, &vert)) {
+    switch (pose::vertex_objects(indices, n_verts, n_tris, tri_obj.data(), vtx_obj.data(), &tri, &vert)) {   // (which finds an index out of range)
     case pose::kVertsIndex: return fail(c, TRG_ERR_INVALID, "trg_pose_bind: triangle %u has an index out of range (%u vertices)", tri, n_verts);
     case pose::kVertsShared: return fail(c, TRG_ERR_INVALID, "trg_pose_bind: vertex %u is named by triangle %u of object %u and by object %u: a vertex belongs to one object", vert, tri, tri_obj[tri], vtx_obj[vert]);
     default: break;
     }
-    for (uint32_t v = 0; v < n_verts; ++v)
-        if (!(std::isfinite(positions3[(size_t)v * 3]) && std::isfinite(positions3[(size_t)v * 3 + 1]) && std::isfinite(positions3[(size_t)v * 3 + 2])))
-            return fail(c, TRG_ERR_INVALID, "trg_pose_bind: vertex %u has a coordinate that is not finite", v);
-    for (size_t k = 0; normals3 && k < (size_t)n_tris * 9; ++k)
-        if (!std::isfinite(normals3[k])) return fail(c, TRG_ERR_INVALID, "trg_pose_bind: triangle %u has a normal that is not finite", (uint32_t)(k / 9));
+    if (int rc = finite_check(c, who, positions3, normals3, n_verts, n_tris)) return rc;
 
-    RF_HIPCHK(c, hipSetDevice(c->device));
-    RefitState &s = state_of(c);
-    RefitState::Pose &p = s.pose;
-    p.bound = false;
-    const size_t pos_bytes = (size_t)n_verts * 12, idx_bytes = (size_t)n_tris * 12, nrm_bytes = (size_t)n_tris * 36;
+    RefitState::Pose &p = state_of(c).pose;
     int rc = TRG_OK;
-    if ((rc = grow(c, p.rest_pos, pos_bytes, "rest positions")) || (rc = grow(c, p.idx, idx_bytes, "bound indices")) || (rc = grow(c, p.vtx_obj, (size_t)n_verts * 4, "vertex map")) ||
-        (rc = grow(c, p.tri_obj, (size_t)n_tris * 4, "triangle map")) || (rc = grow(c, p.xforms, (size_t)n_objects * 48, "transforms")) ||
-        (normals3 && (rc = grow(c, p.rest_nrm, nrm_bytes, "rest normals"))))
+    if ((rc = copies_bind(c, p, positions3, normals3, indices, n_verts, n_tris)) || (rc = grow(c, p.vtx_obj, (size_t)n_verts * 4, "vertex map")) ||
+        (rc = grow(c, p.tri_obj, (size_t)n_tris * 4, "triangle map")) || (rc = grow(c, p.xforms, (size_t)n_objects * 48, "transforms")))
         return rc;
-    for (int k = 0; k < 3; ++k)
-        if ((rc = grow(c, p.posed[k], pos_bytes, "posed positions")) || (normals3 && (rc = grow(c, p.posed_nrm[k], nrm_bytes, "posed normals")))) return rc;
-    RF_HIPCHK(c, hipMemcpyAsync(p.rest_pos.p, positions3, pos_bytes, hipMemcpyHostToDevice, c->stream));
-    RF_HIPCHK(c, hipMemcpyAsync(p.idx.p, indices, idx_bytes, hipMemcpyHostToDevice, c->stream));
     RF_HIPCHK(c, hipMemcpyAsync(p.vtx_obj.p, vtx_obj.data(), (size_t)n_verts * 4, hipMemcpyHostToDevice, c->stream));
     RF_HIPCHK(c, hipMemcpyAsync(p.tri_obj.p, tri_obj.data(), (size_t)n_tris * 4, hipMemcpyHostToDevice, c->stream));
-    if (normals3) RF_HIPCHK(c, hipMemcpyAsync(p.rest_nrm.p, normals3, nrm_bytes, hipMemcpyHostToDevice, c->stream));
-    for (int k = 0; k < 3; ++k) {
-        RF_HIPCHK(c, hipMemcpyAsync(p.posed[k].p, p.rest_pos.p, pos_bytes, hipMemcpyDeviceToDevice, c->stream));
-        if (normals3) RF_HIPCHK(c, hipMemcpyAsync(p.posed_nrm[k].p, p.rest_nrm.p, nrm_bytes, hipMemcpyDeviceToDevice, c->stream));
-    }
-    RF_HIPCHK(c, hipStreamSynchronize(c->stream));   // (the maps are this call's own arrays)
-    p.n_verts = n_verts; p.n_tris = n_tris; p.n_objects = n_objects;
-    p.cur = 0; p.prev = 1;
-    p.has_nrm = normals3 != nullptr;
-    p.remember_scene(c);
-    p.bound = true;
-    return TRG_OK;
+    p.n_objects = n_objects;
+    return bind_finish(c, p, n_tris);
 }
 
 int trg_pose_apply(trg_ctx *c, const float *xforms12) {
     RefitState::Pose *pp = nullptr;
-    if (int rc = pose_of(c, "trg_pose_apply", &pp)) return rc;
+    if (int rc = binding_of(c, "trg_pose_apply", &RefitState::pose, "trg_pose_bind", &pp)) return rc;
     RefitState::Pose &p = *pp;
     if (!xforms12) return fail(c, TRG_ERR_INVALID, "trg_pose_apply: null transforms");
     for (size_t k = 0; k < (size_t)p.n_objects * 12; ++k)
         if (!std::isfinite(xforms12[k])) return fail(c, TRG_ERR_INVALID, "trg_pose_apply: the transform of object %u is not finite", (uint32_t)(k / 12));
-    const uint32_t spare = 3u - p.cur - p.prev;
-    float *pos_out = p.posed[spare].as<float>(), *nrm_out = p.has_nrm ? p.posed_nrm[spare].as<float>() : nullptr;
     RF_HIPCHK(c, hipMemcpyAsync(p.xforms.p, xforms12, (size_t)p.n_objects * 48, hipMemcpyHostToDevice, c->stream));
-    const size_t blocks = ((size_t)p.n_verts + kT - 1) / kT + (p.has_nrm ? ((size_t)p.n_tris * 3 + kT - 1) / kT : 0);
-    RF_LAUNCH(c, rf_pose_kernel, dim3((uint32_t)blocks), p.rest_pos.as<float>(), p.vtx_obj.as<uint32_t>(), p.n_verts, p.rest_nrm.as<float>(), p.tri_obj.as<uint32_t>(),
-              p.n_tris * 3u, p.xforms.as<float>(), pos_out, nrm_out);
-    if (int rc = refit_from_device(c, pos_out, nrm_out, p.idx.as<uint32_t>(), p.n_verts, p.n_tris)) return rc;   // (current and previous are untouched)
-    p.prev = p.cur;
-    p.cur = spare;
-    p.remember_scene(c);   // (the small-scene path gives the same scene new memory, and builds it)
-    return TRG_OK;
+    RF_LAUNCH(c, rf_pose_kernel, dim3(p.blocks(p.has_nrm)), p.rest_pos.as<float>(), p.vtx_obj.as<uint32_t>(), p.n_verts, p.rest_nrm.as<float>(), p.tri_obj.as<uint32_t>(),
+              p.n_tris * 3u, p.xforms.as<float>(), p.pos_of(p.spare()), p.nrm_of(p.spare()));
+    return apply_finish(c, p);
 }
 
 int trg_pose_read(trg_ctx *c, float *positions3_host, float *normals3_host) {
-    RefitState::Pose *p = nullptr;
-    if (int rc = pose_of(c, "trg_pose_read", &p)) return rc;
-    if (!positions3_host) return fail(c, TRG_ERR_INVALID, "trg_pose_read: null buffer");
-    if (normals3_host && !p->has_nrm) return fail(c, TRG_ERR_INVALID, "trg_pose_read: bound without normals");
-    RF_HIPCHK(c, hipMemcpyAsync(positions3_host, p->posed[p->cur].p, (size_t)p->n_verts * 12, hipMemcpyDeviceToHost, c->stream));
-    if (normals3_host) RF_HIPCHK(c, hipMemcpyAsync(normals3_host, p->posed_nrm[p->cur].p, (size_t)p->n_tris * 36, hipMemcpyDeviceToHost, c->stream));
-    RF_HIPCHK(c, hipStreamSynchronize(c->stream));
-    return TRG_OK;
+    return binding_read(c, "trg_pose_read", &RefitState::pose, "trg_pose_bind", positions3_host, normals3_host);
 }
 
 int trg_pose_buffers(trg_ctx *c, void **pos_dev, void **nrm_dev, void **idx_dev, void **prev_pos_dev, void **prev_nrm_dev) {
-    RefitState::Pose *p = nullptr;
-    if (int rc = pose_of(c, "trg_pose_buffers", &p)) return rc;
-    if (pos_dev) *pos_dev = p->posed[p->cur].p;
-    if (nrm_dev) *nrm_dev = p->has_nrm ? p->posed_nrm[p->cur].p : nullptr;
-    if (idx_dev) *idx_dev = p->idx.p;
-    if (prev_pos_dev) *prev_pos_dev = p->posed[p->prev].p;
-    if (prev_nrm_dev) *prev_nrm_dev = p->has_nrm ? p->posed_nrm[p->prev].p : nullptr;
-    return TRG_OK;
+    return binding_buffers(c, "trg_pose_buffers", &RefitState::pose, "trg_pose_bind", pos_dev, nrm_dev, idx_dev, prev_pos_dev, prev_nrm_dev);
 }
 
-int trg_pose_release(trg_ctx *c) {
-    if (!c) return TRG_ERR_INVALID;
-    pose_free(c);
-    return TRG_OK;
-}
+int trg_pose_release(trg_ctx *c) { return binding_release(c, &RefitState::pose); }
 
 int trg_group_pose_bind(trg_group *g, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris,
                         const uint32_t *object_first_tri, uint32_t n_objects) {
-    if (!g) return TRG_ERR_INVALID;
-    const int n = trg_group_size(g);
-    if (n <= 0) return TRG_ERR_INVALID;
-    if (int rc = trg_group_sync(g)) return rc;
-    for (int r = 0; r < n; ++r) {
-        trg_ctx *c = trg_group_ctx(g, r);
-        if (!c) return TRG_ERR_INVALID;
-        if (int rc = trg_pose_bind(c, positions3, normals3, indices, n_verts, n_tris, object_first_tri, n_objects)) return rc;
-    }
-    return TRG_OK;
+    return group_each(g, [&](trg_ctx *c) { return trg_pose_bind(c, positions3, normals3, indices, n_verts, n_tris, object_first_tri, n_objects); });
 }
 
 int trg_group_pose_apply(trg_group *g, const float *xforms12) {
-    if (!g) return TRG_ERR_INVALID;
-    const int n = trg_group_size(g);
-    if (n <= 0) return TRG_ERR_INVALID;
-    if (int rc = trg_group_sync(g)) return rc;
-    for (int r = 0; r < n; ++r) {
-        trg_ctx *c = trg_group_ctx(g, r);
-        if (!c) return TRG_ERR_INVALID;
-        if (int rc = trg_pose_apply(c, xforms12)) return rc;
-    }
-    return TRG_OK;
+    return group_each(g, [&](trg_ctx *c) { return trg_pose_apply(c, xforms12); });
 }
 
 int trg_skin_bind(trg_ctx *c, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris,
@@ -1032,132 +987,53 @@ int trg_skin_bind(trg_ctx *c, const float *positions3, const float *normals3, co
 #if TRG_WIDE8
     return fail(c, TRG_ERR_INVALID, "trg_skin_bind: an 8-wide experiments build has no skinning");
 #endif
-    if (!c->scene_loaded || !c->blob) return fail(c, TRG_ERR_INVALID, "trg_skin_bind: no scene loaded");
-    if (n_tris != c->sc.n_tris) return fail(c, TRG_ERR_INVALID, "trg_skin_bind: %u triangles, the loaded scene has %u", n_tris, c->sc.n_tris);
-    if (!positions3 || !indices || !bone_ids4 || !weights4 || n_verts == 0 || n_tris == 0 || n_bones == 0) return fail(c, TRG_ERR_INVALID, "trg_skin_bind: null or empty buffer");
-    for (size_t k = 0; k < (size_t)n_tris * 3; ++k)
-        if (indices[k] >= n_verts) return fail(c, TRG_ERR_INVALID, "trg_skin_bind: triangle %u has an index out of range (%u vertices)", (uint32_t)(k / 3), n_verts);
-    uint32_t vert = 0, slot = 0;
-    if (skin::ids_check(bone_ids4, n_verts, n_bones, &vert, &slot) != skin::kSkinOk)
-        return fail(c, TRG_ERR_INVALID, "trg_skin_bind: vertex %u names bone %u (id %u of its four), there are %u bones", vert, bone_ids4[(size_t)vert * 4 + slot], slot, n_bones);
-    switch (skin::weights_check(weights4, n_verts, &vert, &slot)) {
-    case skin::kSkinWeight: return fail(c, TRG_ERR_INVALID, "trg_skin_bind: vertex %u has a weight (%u of its four) that is negative or not finite", vert, slot);
-    case skin::kSkinSum: {
-        const float *w = weights4 + (size_t)vert * 4;
-        return fail(c, TRG_ERR_INVALID, "trg_skin_bind: vertex %u has weights that sum to %.9g, not to 1 within 1e-4 (weights are not normalised here)", vert,
-                    (double)w[0] + (double)w[1] + (double)w[2] + (double)w[3]);
-    }
-    default: break;
-    }
-    for (uint32_t v = 0; v < n_verts; ++v)
-        if (!(std::isfinite(positions3[(size_t)v * 3]) && std::isfinite(positions3[(size_t)v * 3 + 1]) && std::isfinite(positions3[(size_t)v * 3 + 2])))
-            return fail(c, TRG_ERR_INVALID, "trg_skin_bind: vertex %u has a coordinate that is not finite", v);
-    for (size_t k = 0; normals3 && k < (size_t)n_tris * 9; ++k)
-        if (!std::isfinite(normals3[k])) return fail(c, TRG_ERR_INVALID, "trg_skin_bind: triangle %u has a normal that is not finite", (uint32_t)(k / 9));
-
-    RF_HIPCHK(c, hipSetDevice(c->device));
-    RefitState &s = state_of(c);
-    RefitState::Skin &p = s.skin;
-    p.bound = false;
-    const size_t pos_bytes = (size_t)n_verts * 12, idx_bytes = (size_t)n_tris * 12, nrm_bytes = (size_t)n_tris * 36, rec_bytes = (size_t)n_verts * 16;
+    const char *who = "trg_skin_bind";
     int rc = TRG_OK;
-    if ((rc = grow(c, p.rest_pos, pos_bytes, "rest positions")) || (rc = grow(c, p.idx, idx_bytes, "bound indices")) || (rc = grow(c, p.ids, rec_bytes, "bone ids")) ||
-        (rc = grow(c, p.weights, rec_bytes, "bone weights")) || (rc = grow(c, p.bones, (size_t)n_bones * 48, "bones")) ||
-        (normals3 && (rc = grow(c, p.rest_nrm, nrm_bytes, "rest normals"))))
+    if ((rc = scene_check(c, who, n_tris, !positions3 || !indices || !bone_ids4 || !weights4 || n_verts == 0 || n_tris == 0 || n_bones == 0)) ||
+        (rc = indices_check(c, who, indices, n_verts, n_tris)) || (rc = skin_check(c, who, bone_ids4, weights4, n_verts, n_bones)) ||
+        (rc = finite_check(c, who, positions3, normals3, n_verts, n_tris)))
         return rc;
-    for (int k = 0; k < 3; ++k)
-        if ((rc = grow(c, p.posed[k], pos_bytes, "skinned positions")) || (normals3 && (rc = grow(c, p.posed_nrm[k], nrm_bytes, "skinned normals")))) return rc;
-    RF_HIPCHK(c, hipMemcpyAsync(p.rest_pos.p, positions3, pos_bytes, hipMemcpyHostToDevice, c->stream));
-    RF_HIPCHK(c, hipMemcpyAsync(p.idx.p, indices, idx_bytes, hipMemcpyHostToDevice, c->stream));
+
+    RefitState::Skin &p = state_of(c).skin;
+    const size_t rec_bytes = (size_t)n_verts * 16;
+    if ((rc = copies_bind(c, p, positions3, normals3, indices, n_verts, n_tris)) || (rc = grow(c, p.ids, rec_bytes, "bone ids")) ||
+        (rc = grow(c, p.weights, rec_bytes, "bone weights")) || (rc = grow(c, p.bones, (size_t)n_bones * 48, "bones")))
+        return rc;
     RF_HIPCHK(c, hipMemcpyAsync(p.ids.p, bone_ids4, rec_bytes, hipMemcpyHostToDevice, c->stream));
     RF_HIPCHK(c, hipMemcpyAsync(p.weights.p, weights4, rec_bytes, hipMemcpyHostToDevice, c->stream));
-    if (normals3) RF_HIPCHK(c, hipMemcpyAsync(p.rest_nrm.p, normals3, nrm_bytes, hipMemcpyHostToDevice, c->stream));
-    for (int k = 0; k < 3; ++k) {
-        RF_HIPCHK(c, hipMemcpyAsync(p.posed[k].p, p.rest_pos.p, pos_bytes, hipMemcpyDeviceToDevice, c->stream));
-        if (normals3) RF_HIPCHK(c, hipMemcpyAsync(p.posed_nrm[k].p, p.rest_nrm.p, nrm_bytes, hipMemcpyDeviceToDevice, c->stream));
-    }
-    RF_HIPCHK(c, hipStreamSynchronize(c->stream));   // (the caller's arrays are free again on return)
-    p.n_verts = n_verts; p.n_tris = n_tris; p.n_bones = n_bones;
-    p.cur = 0; p.prev = 1;
-    p.has_nrm = normals3 != nullptr;
-    p.remember_scene(c);
-    p.bound = true;
-    return TRG_OK;
+    p.n_bones = n_bones;
+    return bind_finish(c, p, n_tris);
 }
 
 int trg_skin_apply(trg_ctx *c, const float *bones12) {
     RefitState::Skin *pp = nullptr;
-    if (int rc = skin_of(c, "trg_skin_apply", &pp)) return rc;
+    if (int rc = binding_of(c, "trg_skin_apply", &RefitState::skin, "trg_skin_bind", &pp)) return rc;
     RefitState::Skin &p = *pp;
     if (!bones12) return fail(c, TRG_ERR_INVALID, "trg_skin_apply: null bones");
-    for (size_t k = 0; k < (size_t)p.n_bones * 12; ++k)
-        if (!std::isfinite(bones12[k])) return fail(c, TRG_ERR_INVALID, "trg_skin_apply: bone %u is not finite", (uint32_t)(k / 12));
-    const uint32_t spare = 3u - p.cur - p.prev;
-    float *pos_out = p.posed[spare].as<float>(), *nrm_out = p.has_nrm ? p.posed_nrm[spare].as<float>() : nullptr;
+    if (int rc = bones_finite(c, "trg_skin_apply", bones12, p.n_bones)) return rc;
     RF_HIPCHK(c, hipMemcpyAsync(p.bones.p, bones12, (size_t)p.n_bones * 48, hipMemcpyHostToDevice, c->stream));
-    const size_t blocks = ((size_t)p.n_verts + kT - 1) / kT + (p.has_nrm ? ((size_t)p.n_tris * 3 + kT - 1) / kT : 0);
-    RF_LAUNCH(c, rf_skin_kernel, dim3((uint32_t)blocks), p.rest_pos.as<float>(), p.ids.as<uint4>(), p.weights.as<float4>(), p.n_verts, p.rest_nrm.as<float>(),
-              p.idx.as<uint32_t>(), p.n_tris * 3u, p.bones.as<float4>(), pos_out, nrm_out);
-    if (int rc = refit_from_device(c, pos_out, nrm_out, p.idx.as<uint32_t>(), p.n_verts, p.n_tris)) return rc;   // (current and previous are untouched)
-    p.prev = p.cur;
-    p.cur = spare;
-    p.remember_scene(c);   // (the small-scene path gives the same scene new memory, and builds it)
-    return TRG_OK;
+    RF_LAUNCH(c, rf_skin_kernel, dim3(p.blocks(p.has_nrm)), p.rest_pos.as<float>(), p.ids.as<uint4>(), p.weights.as<float4>(), p.n_verts, p.rest_nrm.as<float>(),
+              p.idx.as<uint32_t>(), p.n_tris * 3u, p.bones.as<float4>(), p.pos_of(p.spare()), p.nrm_of(p.spare()));
+    return apply_finish(c, p);
 }
 
 int trg_skin_read(trg_ctx *c, float *positions3_host, float *normals3_host) {
-    RefitState::Skin *p = nullptr;
-    if (int rc = skin_of(c, "trg_skin_read", &p)) return rc;
-    if (!positions3_host) return fail(c, TRG_ERR_INVALID, "trg_skin_read: null buffer");
-    if (normals3_host && !p->has_nrm) return fail(c, TRG_ERR_INVALID, "trg_skin_read: bound without normals");
-    RF_HIPCHK(c, hipMemcpyAsync(positions3_host, p->posed[p->cur].p, (size_t)p->n_verts * 12, hipMemcpyDeviceToHost, c->stream));
-    if (normals3_host) RF_HIPCHK(c, hipMemcpyAsync(normals3_host, p->posed_nrm[p->cur].p, (size_t)p->n_tris * 36, hipMemcpyDeviceToHost, c->stream));
-    RF_HIPCHK(c, hipStreamSynchronize(c->stream));
-    return TRG_OK;
+    return binding_read(c, "trg_skin_read", &RefitState::skin, "trg_skin_bind", positions3_host, normals3_host);
 }
 
 int trg_skin_buffers(trg_ctx *c, void **pos_dev, void **nrm_dev, void **idx_dev, void **prev_pos_dev, void **prev_nrm_dev) {
-    RefitState::Skin *p = nullptr;
-    if (int rc = skin_of(c, "trg_skin_buffers", &p)) return rc;
-    if (pos_dev) *pos_dev = p->posed[p->cur].p;
-    if (nrm_dev) *nrm_dev = p->has_nrm ? p->posed_nrm[p->cur].p : nullptr;
-    if (idx_dev) *idx_dev = p->idx.p;
-    if (prev_pos_dev) *prev_pos_dev = p->posed[p->prev].p;
-    if (prev_nrm_dev) *prev_nrm_dev = p->has_nrm ? p->posed_nrm[p->prev].p : nullptr;
-    return TRG_OK;
+    return binding_buffers(c, "trg_skin_buffers", &RefitState::skin, "trg_skin_bind", pos_dev, nrm_dev, idx_dev, prev_pos_dev, prev_nrm_dev);
 }
 
-int trg_skin_release(trg_ctx *c) {
-    if (!c) return TRG_ERR_INVALID;
-    skin_free(c);
-    return TRG_OK;
-}
+int trg_skin_release(trg_ctx *c) { return binding_release(c, &RefitState::skin); }
 
 int trg_group_skin_bind(trg_group *g, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris,
                         const uint32_t *bone_ids4, const float *weights4, uint32_t n_bones) {
-    if (!g) return TRG_ERR_INVALID;
-    const int n = trg_group_size(g);
-    if (n <= 0) return TRG_ERR_INVALID;
-    if (int rc = trg_group_sync(g)) return rc;
-    for (int r = 0; r < n; ++r) {
-        trg_ctx *c = trg_group_ctx(g, r);
-        if (!c) return TRG_ERR_INVALID;
-        if (int rc = trg_skin_bind(c, positions3, normals3, indices, n_verts, n_tris, bone_ids4, weights4, n_bones)) return rc;
-    }
-    return TRG_OK;
+    return group_each(g, [&](trg_ctx *c) { return trg_skin_bind(c, positions3, normals3, indices, n_verts, n_tris, bone_ids4, weights4, n_bones); });
 }
 
 int trg_group_skin_apply(trg_group *g, const float *bones12) {
-    if (!g) return TRG_ERR_INVALID;
-    const int n = trg_group_size(g);
-    if (n <= 0) return TRG_ERR_INVALID;
-    if (int rc = trg_group_sync(g)) return rc;
-    for (int r = 0; r < n; ++r) {
-        trg_ctx *c = trg_group_ctx(g, r);
-        if (!c) return TRG_ERR_INVALID;
-        if (int rc = trg_skin_apply(c, bones12)) return rc;
-    }
-    return TRG_OK;
+    return group_each(g, [&](trg_ctx *c) { return trg_skin_apply(c, bones12); });
 }
 
 int trg_morph_bind(trg_ctx *c, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris, uint32_t n_targets,
@@ -1167,7 +1043,11 @@ int trg_morph_bind(trg_ctx *c, const float *positions3, const float *normals3, c
 #if TRG_WIDE8
     return fail(c, TRG_ERR_INVALID, "trg_morph_bind: an 8-wide experiments build has no blend shapes");
 #endif
-    if (int rc = geometry_check(c, "trg_morph_bind", positions3, normals3, indices, n_verts, n_tris)) return rc;
+    const char *who = "trg_morph_bind";
+    int rc = TRG_OK;
+    if ((rc = scene_check(c, who, n_tris, !positions3 || !indices || n_verts == 0 || n_tris == 0)) || (rc = indices_check(c, who, indices, n_verts, n_tris)) ||
+        (rc = finite_check(c, who, positions3, normals3, n_verts, n_tris)))
+        return rc;
     if (n_targets == 0 || !target_first) return fail(c, TRG_ERR_INVALID, "trg_morph_bind: no targets (at least one is needed, and its table)");
     uint32_t target = 0, entry = 0;
     switch (morph::targets_check(target_first, n_targets, n_entries, &target)) {
@@ -1189,36 +1069,19 @@ int trg_morph_bind(trg_ctx *c, const float *positions3, const float *normals3, c
     if (!has_bones && (bone_ids4 || bone_weights4 || n_bones))
         return fail(c, TRG_ERR_INVALID, "trg_morph_bind: bone ids, bone weights and the number of bones are given all three or none (ids %s, weights %s, %u bones)",
                     bone_ids4 ? "given" : "null", bone_weights4 ? "given" : "null", n_bones);
-    if (has_bones) {
-        uint32_t vert = 0, slot = 0;
-        if (skin::ids_check(bone_ids4, n_verts, n_bones, &vert, &slot) != skin::kSkinOk)
-            return fail(c, TRG_ERR_INVALID, "trg_morph_bind: vertex %u names bone %u (id %u of its four), there are %u bones", vert, bone_ids4[(size_t)vert * 4 + slot], slot, n_bones);
-        switch (skin::weights_check(bone_weights4, n_verts, &vert, &slot)) {
-        case skin::kSkinWeight: return fail(c, TRG_ERR_INVALID, "trg_morph_bind: vertex %u has a weight (%u of its four) that is negative or not finite", vert, slot);
-        case skin::kSkinSum: {
-            const float *w = bone_weights4 + (size_t)vert * 4;
-            return fail(c, TRG_ERR_INVALID, "trg_morph_bind: vertex %u has weights that sum to %.9g, not to 1 within 1e-4 (weights are not normalised here)", vert,
-                        (double)w[0] + (double)w[1] + (double)w[2] + (double)w[3]);
-        }
-        default: break;
-        }
-    }
+    if (has_bones && (rc = skin_check(c, who, bone_ids4, bone_weights4, n_verts, n_bones))) return rc;
     // by-target lists -> per-vertex records.  (At least one record is allocated: a binding whose targets are all empty is legal.)
     std::vector<uint32_t> vfirst((size_t)n_verts + 1), cursor(n_verts);
     std::vector<morph::Rec> pos_recs(n_entries), nrm_recs(entry_dnrm3 ? n_entries : 0);
     morph::transpose(target_first, n_targets, entry_vertex, entry_dpos3, entry_dnrm3, n_verts, vfirst.data(), cursor.data(), pos_recs.data(), entry_dnrm3 ? nrm_recs.data() : nullptr);
 
-    RF_HIPCHK(c, hipSetDevice(c->device));
-    RefitState &s = state_of(c);
-    RefitState::Morph &m = s.morph;
-    m.bound = false;
+    RefitState::Morph &m = state_of(c).morph;
     const size_t rec_bytes = (size_t)n_entries * sizeof(morph::Rec), skin_bytes = (size_t)n_verts * 16;
-    int rc = TRG_OK;
-    if ((rc = grow(c, m.vfirst, vfirst.size() * 4, "entry ranges")) || (rc = grow(c, m.pos_recs, rec_bytes + 16, "position deltas")) ||
-        (entry_dnrm3 && (rc = grow(c, m.nrm_recs, rec_bytes + 16, "normal deltas"))) || (rc = grow(c, m.tw, (size_t)n_targets * 4, "target weights")) ||
+    if ((rc = copies_bind(c, m, positions3, normals3, indices, n_verts, n_tris)) || (rc = grow(c, m.vfirst, vfirst.size() * 4, "entry ranges")) ||
+        (rc = grow(c, m.pos_recs, rec_bytes + 16, "position deltas")) || (entry_dnrm3 && (rc = grow(c, m.nrm_recs, rec_bytes + 16, "normal deltas"))) ||
+        (rc = grow(c, m.tw, (size_t)n_targets * 4, "target weights")) ||
         (has_bones && ((rc = grow(c, m.ids, skin_bytes, "bone ids")) || (rc = grow(c, m.weights, skin_bytes, "bone weights")) || (rc = grow(c, m.bones, (size_t)n_bones * 48, "bones")))))
         return rc;
-    if ((rc = copies_bind(c, m.g, positions3, normals3, indices, n_verts, n_tris))) return rc;
     RF_HIPCHK(c, hipMemcpyAsync(m.vfirst.p, vfirst.data(), vfirst.size() * 4, hipMemcpyHostToDevice, c->stream));
     if (rec_bytes) RF_HIPCHK(c, hipMemcpyAsync(m.pos_recs.p, pos_recs.data(), rec_bytes, hipMemcpyHostToDevice, c->stream));
     if (rec_bytes && entry_dnrm3) RF_HIPCHK(c, hipMemcpyAsync(m.nrm_recs.p, nrm_recs.data(), rec_bytes, hipMemcpyHostToDevice, c->stream));
@@ -1226,90 +1089,54 @@ int trg_morph_bind(trg_ctx *c, const float *positions3, const float *normals3, c
         RF_HIPCHK(c, hipMemcpyAsync(m.ids.p, bone_ids4, skin_bytes, hipMemcpyHostToDevice, c->stream));
         RF_HIPCHK(c, hipMemcpyAsync(m.weights.p, bone_weights4, skin_bytes, hipMemcpyHostToDevice, c->stream));
     }
-    RF_HIPCHK(c, hipStreamSynchronize(c->stream));   // (the records are this call's own arrays, and the caller's are free again on return)
-    m.n_tris = n_tris; m.n_targets = n_targets; m.n_bones = has_bones ? n_bones : 0u;
+    m.n_targets = n_targets; m.n_bones = has_bones ? n_bones : 0u;
     m.has_dnrm = entry_dnrm3 != nullptr;
     m.has_bones = has_bones;
-    m.remember_scene(c);
-    m.bound = true;
-    return TRG_OK;
+    return bind_finish(c, m, n_tris);
 }
 
 int trg_morph_apply(trg_ctx *c, const float *target_weights, const float *bones12) {
     RefitState::Morph *mp = nullptr;
-    if (int rc = morph_of(c, "trg_morph_apply", &mp)) return rc;
+    if (int rc = binding_of(c, "trg_morph_apply", &RefitState::morph, "trg_morph_bind", &mp)) return rc;
     RefitState::Morph &m = *mp;
     if (!target_weights) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: null target weights");
     for (uint32_t k = 0; k < m.n_targets; ++k)
         if (!std::isfinite(target_weights[k])) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: the weight of target %u is not finite", k);
     if (m.has_bones && !bones12) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: null bones, the binding has %u", m.n_bones);
     if (!m.has_bones && bones12) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: bones given, the binding has none");
-    for (size_t k = 0; k < (size_t)m.n_bones * 12; ++k)
-        if (!std::isfinite(bones12[k])) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: bone %u is not finite", (uint32_t)(k / 12));
-    const uint32_t spare = m.g.spare();
-    float *pos_out = m.g.pos_of(spare), *nrm_out = m.g.nrm_of(spare);
+    if (int rc = bones_finite(c, "trg_morph_apply", bones12, m.n_bones)) return rc;
+    float *pos_out = m.pos_of(m.spare()), *nrm_out = m.nrm_of(m.spare());
     RF_HIPCHK(c, hipMemcpyAsync(m.tw.p, target_weights, (size_t)m.n_targets * 4, hipMemcpyHostToDevice, c->stream));
     if (m.has_bones) RF_HIPCHK(c, hipMemcpyAsync(m.bones.p, bones12, (size_t)m.n_bones * 48, hipMemcpyHostToDevice, c->stream));
     // no corner can change without normal deltas and without bones: that copy holds the rest normals since bind, and the range is left out
-    const bool corners = m.g.has_nrm && (m.has_dnrm || m.has_bones);
-    const size_t blocks = ((size_t)m.g.n_verts + kT - 1) / kT + (corners ? ((size_t)m.n_tris * 3 + kT - 1) / kT : 0);
+    const uint32_t blocks = m.blocks(m.has_nrm && (m.has_dnrm || m.has_bones));
     int rc = TRG_OK;
     if (m.has_bones) rc = m.has_dnrm ? morph_launch<true, true>(c, m, blocks, pos_out, nrm_out) : morph_launch<true, false>(c, m, blocks, pos_out, nrm_out);
     else rc = m.has_dnrm ? morph_launch<false, true>(c, m, blocks, pos_out, nrm_out) : morph_launch<false, false>(c, m, blocks, pos_out, nrm_out);
     if (rc) return rc;
-    if ((rc = refit_from_device(c, pos_out, nrm_out, m.g.idx.as<uint32_t>(), m.g.n_verts, m.n_tris))) return rc;   // (current and previous are untouched)
-    m.g.rotate();
-    m.remember_scene(c);   // (the small-scene path gives the same scene new memory, and builds it)
-    return TRG_OK;
+    return apply_finish(c, m);
 }
 
 int trg_morph_read(trg_ctx *c, float *positions3_host, float *normals3_host) {
-    RefitState::Morph *m = nullptr;
-    if (int rc = morph_of(c, "trg_morph_read", &m)) return rc;
-    return copies_read(c, "trg_morph_read", m->g, m->n_tris, positions3_host, normals3_host);
+    return binding_read(c, "trg_morph_read", &RefitState::morph, "trg_morph_bind", positions3_host, normals3_host);
 }
 
 int trg_morph_buffers(trg_ctx *c, void **pos_dev, void **nrm_dev, void **idx_dev, void **prev_pos_dev, void **prev_nrm_dev) {
-    RefitState::Morph *m = nullptr;
-    if (int rc = morph_of(c, "trg_morph_buffers", &m)) return rc;
-    copies_buffers(m->g, pos_dev, nrm_dev, idx_dev, prev_pos_dev, prev_nrm_dev);
-    return TRG_OK;
+    return binding_buffers(c, "trg_morph_buffers", &RefitState::morph, "trg_morph_bind", pos_dev, nrm_dev, idx_dev, prev_pos_dev, prev_nrm_dev);
 }
 
-int trg_morph_release(trg_ctx *c) {
-    if (!c) return TRG_ERR_INVALID;
-    morph_free(c);
-    return TRG_OK;
-}
+int trg_morph_release(trg_ctx *c) { return binding_release(c, &RefitState::morph); }
 
 int trg_group_morph_bind(trg_group *g, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris, uint32_t n_targets,
                          const uint32_t *target_first, uint32_t n_entries, const uint32_t *entry_vertex, const float *entry_dpos3, const float *entry_dnrm3, const uint32_t *bone_ids4,
                          const float *bone_weights4, uint32_t n_bones) {
-    if (!g) return TRG_ERR_INVALID;
-    const int n = trg_group_size(g);
-    if (n <= 0) return TRG_ERR_INVALID;
-    if (int rc = trg_group_sync(g)) return rc;
-    for (int r = 0; r < n; ++r) {
-        trg_ctx *c = trg_group_ctx(g, r);
-        if (!c) return TRG_ERR_INVALID;
-        if (int rc = trg_morph_bind(c, positions3, normals3, indices, n_verts, n_tris, n_targets, target_first, n_entries, entry_vertex, entry_dpos3, entry_dnrm3, bone_ids4,
-                                    bone_weights4, n_bones))
-            return rc;
-    }
-    return TRG_OK;
+    return group_each(g, [&](trg_ctx *c) {
+        return trg_morph_bind(c, positions3, normals3, indices, n_verts, n_tris, n_targets, target_first, n_entries, entry_vertex, entry_dpos3, entry_dnrm3, bone_ids4, bone_weights4, n_bones);
+    });
 }
 
 int trg_group_morph_apply(trg_group *g, const float *target_weights, const float *bones12) {
-    if (!g) return TRG_ERR_INVALID;
-    const int n = trg_group_size(g);
-    if (n <= 0) return TRG_ERR_INVALID;
-    if (int rc = trg_group_sync(g)) return rc;
-    for (int r = 0; r < n; ++r) {
-        trg_ctx *c = trg_group_ctx(g, r);
-        if (!c) return TRG_ERR_INVALID;
-        if (int rc = trg_morph_apply(c, target_weights, bones12)) return rc;
-    }
-    return TRG_OK;
+    return group_each(g, [&](trg_ctx *c) { return trg_morph_apply(c, target_weights, bones12); });
 }
 
 int trg_refit_last(trg_ctx *c, trg_refit_info *out) {
@@ -1325,16 +1152,7 @@ int trg_refit_release(trg_ctx *c) {
 }
 
 int trg_group_refit_scene(trg_group *g, const float *positions3, const float *normals3, const uint32_t *indices, uint32_t n_verts, uint32_t n_tris) {
-    if (!g) return TRG_ERR_INVALID;
-    const int n = trg_group_size(g);
-    if (n <= 0) return TRG_ERR_INVALID;
-    if (int rc = trg_group_sync(g)) return rc;
-    for (int r = 0; r < n; ++r) {
-        trg_ctx *c = trg_group_ctx(g, r);
-        if (!c) return TRG_ERR_INVALID;
-        if (int rc = trg_refit_scene(c, positions3, normals3, indices, n_verts, n_tris)) return rc;
-    }
-    return TRG_OK;
+    return group_each(g, [&](trg_ctx *c) { return trg_refit_scene(c, positions3, normals3, indices, n_verts, n_tris); });
 }
 
 }  // extern "C"

@@ -15,8 +15,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
-from .pose import _group_chk
+from . import _binding, capi
 from .skin import check_binding, skin_reference
 
 _P = C.c_void_p
@@ -34,20 +33,10 @@ _SYMBOLS = [
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 
-_bound = None
-
 
 def load():
     """The library handle of capi.load() with the symbols of include/trg_morph.h bound.  No fallback: a library without them is an error."""
-    global _bound
-    L = capi.load()
-    if _bound is not L:
-        for name, res, args in _SYMBOLS:
-            fn = getattr(L, name)   # AttributeError if the .so lacks a declared symbol
-            fn.restype = res
-            fn.argtypes = args
-        _bound = L
-    return L
+    return _binding.load(_SYMBOLS)
 
 
 def bind(ctx, positions, normals, indices, target_first, entry_vertex, dpos, dnrm=None, bone_ids=None, bone_weights=None, n_bones=0, n_tris=None,
@@ -56,55 +45,34 @@ def bind(ctx, positions, normals, indices, target_first, entry_vertex, dpos, dnr
     [n_entries, 3] float32; bone_ids / bone_weights [n_verts, 4] and n_bones as skin.bind takes them, or None / None / 0.  n_tris, n_entries: the
     counts to pass (default: len(indices) / 3, len(entry_vertex))."""
     L = load()
-    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
-    idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+    pos, nrm, idx, nt = _binding.geometry(positions, normals, indices, n_tris)
     first = np.ascontiguousarray(target_first, np.uint32).reshape(-1)
     ev = np.ascontiguousarray(entry_vertex, np.uint32).reshape(-1)
     dp = np.ascontiguousarray(dpos, np.float32).reshape(-1, 3)
     dn = None if dnrm is None else np.ascontiguousarray(dnrm, np.float32).reshape(-1, 3)
-    if idx.shape[0] % 3:
-        raise ValueError("expected 3 indices per triangle")
     if first.shape[0] < 1:
         raise ValueError("expected n_targets + 1 words in target_first")
     if dp.shape[0] != ev.shape[0] or (dn is not None and dn.shape[0] != ev.shape[0]):
         raise ValueError("expected one delta for each of %d entries" % ev.shape[0])
-    nt = idx.shape[0] // 3 if n_tris is None else int(n_tris)
     ne = ev.shape[0] if n_entries is None else int(n_entries)
     if ne > ev.shape[0]:
         raise ValueError("n_entries %d, the entry arrays hold %d (the C call reads that many)" % (ne, ev.shape[0]))
-    nrm = None
-    if normals is not None:
-        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
-        if nrm.shape[0] != idx.shape[0]:
-            raise ValueError("expected 3*n_tris normals for %d triangles" % (idx.shape[0] // 3))
     ids = None if bone_ids is None else np.ascontiguousarray(bone_ids, np.uint32).reshape(-1, 4)
     wts = None if bone_weights is None else np.ascontiguousarray(bone_weights, np.float32).reshape(-1, 4)
     for a in (ids, wts):
         if a is not None and a.shape[0] != pos.shape[0]:
             raise ValueError("expected four bone ids and four weights for each of %d vertices" % pos.shape[0])
-    args = (capi._ptr(pos), capi._ptr(nrm), capi._ptr(idx), pos.shape[0], nt, first.shape[0] - 1, capi._ptr(first), ne, capi._ptr(ev), capi._ptr(dp), capi._ptr(dn),
-            capi._ptr(ids), capi._ptr(wts), int(n_bones))
-    ctx._morph_counts = None
-    if isinstance(ctx, capi.Group):
-        _group_chk(L, ctx, L.trg_group_morph_bind(ctx.g, *args))
-    else:
-        ctx._chk(L.trg_morph_bind(ctx.h_ctx, *args))
-    # the C calls that follow carry no counts: what was bound is remembered here, so that apply and read can size and check their host arrays
-    ctx._morph_counts = (pos.shape[0], nt, first.shape[0] - 1, int(n_bones), nrm is not None)
-
-
-def _counts(ctx):
-    counts = getattr(ctx, "_morph_counts", None)
-    if counts is None:
-        raise capi.TrgError(capi.ERR_INVALID, "morph: nothing bound (trg_morph_bind, through bind of this module, first)")
-    return counts
+    _binding.remember(ctx, "morph", None)
+    _binding.call(L, ctx, "morph_bind", capi._ptr(pos), capi._ptr(nrm), capi._ptr(idx), pos.shape[0], nt, first.shape[0] - 1, capi._ptr(first), ne, capi._ptr(ev),
+                  capi._ptr(dp), capi._ptr(dn), capi._ptr(ids), capi._ptr(wts), int(n_bones))
+    _binding.remember(ctx, "morph", (pos.shape[0], nt, first.shape[0] - 1, int(n_bones), nrm is not None))
 
 
 def apply(ctx, target_weights, bones=None):
     """trg_morph_apply / trg_group_morph_apply: [n_targets] float32 and, exactly when bones were bound, [n_bones, 12] float32 (ValueError for a wrong
     count: the C call reads n_targets and n_bones x 12 floats; bones given or missing against the binding is the C call's refusal)."""
     L = load()
-    _, _, n_targets, n_bones, _ = _counts(ctx)
+    _, _, n_targets, n_bones, _ = _binding.counts(ctx, "morph")
     tw = np.ascontiguousarray(target_weights, np.float32).reshape(-1)
     if tw.shape[0] != n_targets:
         raise ValueError("expected %d target weights, as bound, got %d" % (n_targets, tw.shape[0]))
@@ -113,43 +81,24 @@ def apply(ctx, target_weights, bones=None):
         x = np.ascontiguousarray(bones, np.float32).reshape(-1, 12)
         if n_bones and x.shape[0] != n_bones:
             raise ValueError("expected %d bones, as bound, got %d" % (n_bones, x.shape[0]))
-    if isinstance(ctx, capi.Group):
-        _group_chk(L, ctx, L.trg_group_morph_apply(ctx.g, capi._ptr(tw), capi._ptr(x)))
-    else:
-        ctx._chk(L.trg_morph_apply(ctx.h_ctx, capi._ptr(tw), capi._ptr(x)))
+    _binding.call(L, ctx, "morph_apply", capi._ptr(tw), capi._ptr(x))
 
 
 def buffers(ctx):
     """trg_morph_buffers: dict of device addresses (int, or None) -- pos, nrm, idx, prev_pos, prev_nrm."""
-    L = load()
-    out = [C.c_void_p() for _ in range(5)]
-    ctx._chk(L.trg_morph_buffers(ctx.h_ctx, *[C.byref(p) for p in out]))
-    return dict(zip(("pos", "nrm", "idx", "prev_pos", "prev_nrm"), (p.value for p in out)))
+    return _binding.buffers(load(), ctx, "morph")
 
 
 def read(ctx, n_verts=None, n_tris=None, normals=True):
     """trg_morph_read: (positions [n_verts, 3], normals [3 n_tris, 3] or None) of the current pose.  The arrays are sized by the counts bind
     remembered; n_verts / n_tris, if given, must be those (ValueError)."""
-    L = load()
-    nv, nt, _, _, has_nrm = _counts(ctx)
-    if (n_verts is not None and n_verts != nv) or (n_tris is not None and n_tris != nt):
-        raise ValueError("the binding has %d vertices and %d triangles" % (nv, nt))
-    normals = normals and has_nrm
-    pos = np.empty((nv, 3), np.float32)
-    nrm = np.empty((3 * nt, 3), np.float32) if normals else None
-    ctx._chk(L.trg_morph_read(ctx.h_ctx, capi._ptr(pos), capi._ptr(nrm)))
-    return pos, nrm
+    return _binding.read(load(), ctx, "morph", n_verts, n_tris, normals)
 
 
 def release(ctx):
     """Frees the binding of a context, or of every context of a group (the refit scratch stays: refit.release)."""
-    L = load()
-    ctx._morph_counts = None
-    if isinstance(ctx, capi.Group):
-        for r in range(ctx.n):
-            L.trg_morph_release(L.trg_group_ctx(ctx.g, r))
-    elif getattr(ctx, "h_ctx", None):
-        L.trg_morph_release(ctx.h_ctx)
+    _binding.remember(ctx, "morph", None)
+    _binding.release(load(), ctx, "morph")
 
 
 def check_targets(target_first, entry_vertex, dpos, dnrm, n_verts, has_normals=True, bone_ids=None, bone_weights=None, n_bones=0, n_entries=None):

@@ -14,7 +14,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
+from . import _binding, capi
 
 _P = C.c_void_p
 _U = C.c_uint32
@@ -31,28 +31,10 @@ _SYMBOLS = [
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 
-_bound = None
-
 
 def load():
     """The library handle of capi.load() with the symbols of include/trg_pose.h bound.  No fallback: a library without them is an error."""
-    global _bound
-    L = capi.load()
-    if _bound is not L:
-        for name, res, args in _SYMBOLS:
-            fn = getattr(L, name)   # AttributeError if the .so lacks a declared symbol
-            fn.restype = res
-            fn.argtypes = args
-        _bound = L
-    return L
-
-
-def _group_chk(L, g, rc):
-    if rc != capi.OK:
-        msg = ""
-        for r in range(g.n):   # the text is the refusing context's
-            msg = msg or (L.trg_last_error(L.trg_group_ctx(g.g, r)) or b"").decode()
-        raise capi.TrgError(rc, msg)
+    return _binding.load(_SYMBOLS)
 
 
 def _tensor(t, what, dtypes, device):
@@ -90,32 +72,14 @@ def refit_scene_device(ctx, positions, normals, indices):
 def bind(ctx, positions, normals, indices, first, n_tris=None):
     """trg_pose_bind / trg_group_pose_bind.  first: n_objects + 1 triangle numbers.  n_tris: the count to pass (default: len(indices) / 3)."""
     L = load()
-    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
-    idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
     tab = np.ascontiguousarray(first, np.uint32).reshape(-1)
-    if idx.shape[0] % 3 or tab.shape[0] < 2:
-        raise ValueError("expected 3 indices per triangle and a table of n_objects + 1 entries")
-    nt = idx.shape[0] // 3 if n_tris is None else int(n_tris)
-    nrm = None
-    if normals is not None:
-        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
-        if nrm.shape[0] != idx.shape[0]:
-            raise ValueError("expected 3*n_tris normals for %d triangles" % (idx.shape[0] // 3))
-    args = (capi._ptr(pos), capi._ptr(nrm), capi._ptr(idx), pos.shape[0], nt, capi._ptr(tab), tab.shape[0] - 1)
-    ctx._pose_counts = None
-    if isinstance(ctx, capi.Group):
-        _group_chk(L, ctx, L.trg_group_pose_bind(ctx.g, *args))
-    else:
-        ctx._chk(L.trg_pose_bind(ctx.h_ctx, *args))
-    # the C calls that follow carry no counts: what was bound is remembered here, so that apply and read can size and check their host arrays
-    ctx._pose_counts = (pos.shape[0], nt, tab.shape[0] - 1, nrm is not None)
-
-
-def _counts(ctx):
-    counts = getattr(ctx, "_pose_counts", None)
-    if counts is None:
-        raise capi.TrgError(capi.ERR_INVALID, "pose: nothing bound (trg_pose_bind, through bind of this module, first)")
-    return counts
+    text = "expected 3 indices per triangle and a table of n_objects + 1 entries"
+    if tab.shape[0] < 2:
+        raise ValueError(text)
+    pos, nrm, idx, nt = _binding.geometry(positions, normals, indices, n_tris, text)
+    _binding.remember(ctx, "pose", None)
+    _binding.call(L, ctx, "pose_bind", capi._ptr(pos), capi._ptr(nrm), capi._ptr(idx), pos.shape[0], nt, capi._ptr(tab), tab.shape[0] - 1)
+    _binding.remember(ctx, "pose", (pos.shape[0], nt, tab.shape[0] - 1, nrm is not None))
 
 
 def apply(ctx, xforms):
@@ -123,46 +87,27 @@ def apply(ctx, xforms):
     the C call reads n_objects x 12 floats)."""
     L = load()
     x = np.ascontiguousarray(xforms, np.float32).reshape(-1, 12)
-    n_objects = _counts(ctx)[2]
+    n_objects = _binding.counts(ctx, "pose")[2]
     if x.shape[0] != n_objects:
         raise ValueError("expected %d transforms, one per bound object, got %d" % (n_objects, x.shape[0]))
-    if isinstance(ctx, capi.Group):
-        _group_chk(L, ctx, L.trg_group_pose_apply(ctx.g, capi._ptr(x)))
-    else:
-        ctx._chk(L.trg_pose_apply(ctx.h_ctx, capi._ptr(x)))
+    _binding.call(L, ctx, "pose_apply", capi._ptr(x))
 
 
 def buffers(ctx):
     """trg_pose_buffers: dict of device addresses (int, or None) -- pos, nrm, idx, prev_pos, prev_nrm."""
-    L = load()
-    out = [C.c_void_p() for _ in range(5)]
-    ctx._chk(L.trg_pose_buffers(ctx.h_ctx, *[C.byref(p) for p in out]))
-    return dict(zip(("pos", "nrm", "idx", "prev_pos", "prev_nrm"), (p.value for p in out)))
+    return _binding.buffers(load(), ctx, "pose")
 
 
 def read(ctx, n_verts=None, n_tris=None, normals=True):
     """trg_pose_read: (positions [n_verts, 3], normals [3 n_tris, 3] or None) of the current pose.  The arrays are sized by the counts bind
     remembered; n_verts / n_tris, if given, must be those (ValueError)."""
-    L = load()
-    nv, nt, _, has_nrm = _counts(ctx)
-    if (n_verts is not None and n_verts != nv) or (n_tris is not None and n_tris != nt):
-        raise ValueError("the binding has %d vertices and %d triangles" % (nv, nt))
-    n_verts, n_tris, normals = nv, nt, normals and has_nrm
-    pos = np.empty((n_verts, 3), np.float32)
-    nrm = np.empty((3 * n_tris, 3), np.float32) if normals else None
-    ctx._chk(L.trg_pose_read(ctx.h_ctx, capi._ptr(pos), capi._ptr(nrm)))
-    return pos, nrm
+    return _binding.read(load(), ctx, "pose", n_verts, n_tris, normals)
 
 
 def release(ctx):
     """Frees the binding of a context, or of every context of a group (the refit scratch stays: refit.release)."""
-    L = load()
-    ctx._pose_counts = None
-    if isinstance(ctx, capi.Group):
-        for r in range(ctx.n):
-            L.trg_pose_release(L.trg_group_ctx(ctx.g, r))
-    elif getattr(ctx, "h_ctx", None):
-        L.trg_pose_release(ctx.h_ctx)
+    _binding.remember(ctx, "pose", None)
+    _binding.release(load(), ctx, "pose")
 
 
 def object_maps(indices, first, n_verts):
@@ -218,27 +163,5 @@ def pose_reference(positions, normals, indices, first, xforms):
         if normals is None:
             return out, None
         nrm = np.ascontiguousarray(normals, f).reshape(-1, 3)
-        A = M[:, :, :3]
-
-        def cof(p_, q_, r_, s_):
-            return A[:, p_[0], p_[1]] * A[:, q_[0], q_[1]] - A[:, r_[0], r_[1]] * A[:, s_[0], s_[1]]
-        Cm = np.empty((M.shape[0], 3, 3), f)
-        Cm[:, 0, 0] = cof((1, 1), (2, 2), (1, 2), (2, 1))
-        Cm[:, 0, 1] = cof((1, 2), (2, 0), (1, 0), (2, 2))
-        Cm[:, 0, 2] = cof((1, 0), (2, 1), (1, 1), (2, 0))
-        Cm[:, 1, 0] = cof((0, 2), (2, 1), (0, 1), (2, 2))
-        Cm[:, 1, 1] = cof((0, 0), (2, 2), (0, 2), (2, 0))
-        Cm[:, 1, 2] = cof((0, 1), (2, 0), (0, 0), (2, 1))
-        Cm[:, 2, 0] = cof((0, 1), (1, 2), (0, 2), (1, 1))
-        Cm[:, 2, 1] = cof((0, 2), (1, 0), (0, 0), (1, 2))
-        Cm[:, 2, 2] = cof((0, 0), (1, 1), (0, 1), (1, 0))
-        det = (A[:, 0, 0] * Cm[:, 0, 0] + A[:, 0, 1] * Cm[:, 0, 1]) + A[:, 0, 2] * Cm[:, 0, 2]
-        sign = np.where(det < 0, f(-1), f(1)).astype(f)
-        obj = np.repeat(tri_obj, 3)
-        Cc, sc = Cm[obj], sign[obj]
-        v = np.stack([sc * ((Cc[:, i, 0] * nrm[:, 0] + Cc[:, i, 1] * nrm[:, 1]) + Cc[:, i, 2] * nrm[:, 2]) for i in range(3)], axis=1)
-        length = np.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
-        ok = (length > 0) & np.isfinite(length)
-        posed = np.where(ok[:, None], v / np.where(ok, length, f(1))[:, None], nrm)
-        assert posed.dtype == f and v.dtype == f and length.dtype == f
-    return out, np.ascontiguousarray(posed)
+        posed = _binding.transform_normals(M[:, :, :3], nrm, np.repeat(tri_obj, 3))   # the transform of the corner's triangle
+    return out, posed

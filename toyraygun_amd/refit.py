@@ -13,9 +13,7 @@ The context's refit scratch belongs to the context: ctx.close() frees it, releas
 """
 import ctypes as C
 
-import numpy as np
-
-from . import capi
+from . import _binding, capi
 
 NONE, DEVICE, REBUILD = 0, 1, 2
 PATH_NAMES = {NONE: "none", DEVICE: "device", REBUILD: "rebuild"}
@@ -37,50 +35,17 @@ _SYMBOLS = [
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 
-_bound = None
-
 
 def load():
     """The library handle of capi.load() with the symbols of include/trg_refit.h bound.  No fallback: a library without them is an error."""
-    global _bound
-    L = capi.load()
-    if _bound is not L:
-        for name, res, args in _SYMBOLS:
-            fn = getattr(L, name)   # AttributeError if the .so lacks a declared symbol
-            fn.restype = res
-            fn.argtypes = args
-        _bound = L
-    return L
-
-
-def _buffers(positions, normals, indices):
-    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
-    idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
-    if idx.shape[0] % 3:
-        raise ValueError("expected 3 indices per triangle")
-    nt = idx.shape[0] // 3
-    nrm = None
-    if normals is not None:
-        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
-        if nrm.shape[0] != 3 * nt:
-            raise ValueError("expected 3*n_tris normals for %d triangles" % nt)
-    return pos, nrm, idx, nt
+    return _binding.load(_SYMBOLS)
 
 
 def refit_scene(ctx, positions, normals, indices, n_tris=None):
     """trg_refit_scene / trg_group_refit_scene.  n_tris: the count to pass (default: len(indices) / 3)."""
     L = load()
-    pos, nrm, idx, nt = _buffers(positions, normals, indices)
-    nt = nt if n_tris is None else int(n_tris)
-    if isinstance(ctx, capi.Group):
-        rc = L.trg_group_refit_scene(ctx.g, capi._ptr(pos), capi._ptr(nrm), capi._ptr(idx), pos.shape[0], nt)
-        if rc != capi.OK:
-            msg = ""
-            for r in range(ctx.n):   # the text is the refusing context's
-                msg = msg or (L.trg_last_error(L.trg_group_ctx(ctx.g, r)) or b"").decode()
-            raise capi.TrgError(rc, msg)
-        return
-    ctx._chk(L.trg_refit_scene(ctx.h_ctx, capi._ptr(pos), capi._ptr(nrm), capi._ptr(idx), pos.shape[0], nt))
+    pos, nrm, idx, nt = _binding.geometry(positions, normals, indices, n_tris)
+    _binding.call(L, ctx, "refit_scene", capi._ptr(pos), capi._ptr(nrm), capi._ptr(idx), pos.shape[0], nt)
 
 
 def refit_last(ctx, rank=0):
@@ -99,9 +64,4 @@ def refit_last(ctx, rank=0):
 
 def release(ctx):
     """Frees the refit scratch of a context, or of every context of a group."""
-    L = load()
-    if isinstance(ctx, capi.Group):
-        for r in range(ctx.n):
-            L.trg_refit_release(L.trg_group_ctx(ctx.g, r))
-    elif getattr(ctx, "h_ctx", None):
-        L.trg_refit_release(ctx.h_ctx)
+    _binding.release(load(), ctx, "refit")
