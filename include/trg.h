@@ -85,6 +85,8 @@ typedef struct trg_stats {
     uint32_t bvh_quads;        /* host build: pairs of triangles the builder found to be parallelograms (one test each in the shipped build) */
     uint32_t bvh_boxes;        /* ... and groups of six such quads that bound a parallelepiped and are ONE leaf of the tree the shipped build walks: twelve
                                   triangle tests in the strict build (LDS node array; the strict HBM tree keeps the subtree), one slab test in the shipped one */
+    uint32_t bvh_room;         /* faces of the room of a scene staged in LDS (3..5 wall quads, faces of one parallelepiped, that the shipped build tests once
+                                  per traversal call ahead of the tree); 0 = none */
 } trg_stats;
 
 enum trg_option {
@@ -342,6 +344,17 @@ TRG_API int trg_debug_build_bvh4(const float *positions3, const uint32_t *indice
  * f = 2 k + (l_k > 0) the offset of its quad's first record (6).  Pass NULL to query the count. */
 TRG_API int trg_debug_boxes(const float *positions3, const uint32_t *indices, const uint32_t *material_ids, uint32_t n_verts, uint32_t n_tris,
                             float *boxes20_out, uint32_t boxes_cap, uint32_t *n_boxes);
+
+/* host-only: the ROOM trg_load_scene finds (scenes staged in LDS: 3, 4 or 5 consecutive quads of one material that are distinct faces of one
+ * parallelepiped -- Scene::addPlane's walls -- are tested once per traversal call by the shipped build, ahead of the tree; TRG_BVH_ROOM=0,
+ * TRG_BVH_BOXES=0 or TRG_BVH_QUADS=0 in the environment: none), and a digest of the device blob it builds.  room28_out (may be NULL), 28 floats:
+ * faces (0 = no room), first record, first triangle, present-face mask (bit f = 2 k + (l_k > 0)), what the walk over the rest starts at (0 nothing,
+ * 1 a node, 2 a leaf) and its node index / leaf code, that walk's depth and its primitives, centre (3), the rows a_k of the frame (9: l_k = a_k .
+ * (P - centre), the room is |l_k| <= 1), per face the offset of its quad's first record (6), material id, depth of the whole tree.  blob_hash =
+ * FNV-1a (64 bits) of the blob, blob_bytes its size, lds_candidate = 1 when the scene has the part a workgroup stages in LDS. */
+TRG_API int trg_debug_room(const float *positions3, const float *normals3, const float *colors3, const uint32_t *indices,
+                           const uint32_t *material_ids, uint32_t n_verts, uint32_t n_tris, float *room28_out, uint64_t *blob_hash,
+                           uint32_t *blob_bytes, uint32_t *lds_candidate);
 
 /* host-only: the same 4-wide nodes in the 64-byte quantised form the HBM kernels actually load (16 dwords per node:
  * origin.xyz scale.x | qlo.x qhi.x qlo.y qhi.y | qlo.z qhi.z scale.y scale.z | child[4]; one byte per child in each

@@ -9,6 +9,7 @@ from toyraygun_amd import capi
 from oracle import pyoracle as O
 sys.path.insert(0, "tests")
 from util import edge_flip_allowance
+import room_scenes
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
@@ -22,6 +23,19 @@ t_start = time.time()
 for case in range(cases):
     kind = rng.choice(["box", "small", "large"], p=[0.2, 0.45, 0.35])
     s = O.OracleScene.cornell_box() if kind != "large" or rng.random() < 0.5 else O.OracleScene()
+    # a ROOM of its own around half of the scenes (bvh_build.h RoomLeaf; tests/room_scenes.py): 3 to 5 faces, in any order, of a rotated, possibly
+    # sheared and mirrored parallelepiped that stands where the Cornell box does, of any material, in either index pattern -> the open-box test ahead
+    # of the tree where the scene is staged in LDS, wall quads of the tree everywhere else
+    if rng.random() < 0.5:
+        s = O.OracleScene()
+        q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+        sh = np.eye(3)
+        if rng.random() < 0.4:
+            sh[0, 1] = rng.uniform(-0.5, 0.5)
+        room_h = q @ sh @ np.diag(rng.uniform(0.8, 1.4, 3) * rng.choice([-1.0, 1.0], 3))
+        room_c = np.array([0.0, 1.0, 0.0]) + rng.uniform(-0.2, 0.2, 3)
+        room_faces = [int(f) for f in rng.permutation(6)[: int(rng.integers(3, 6))]]
+        room_scenes.add_room(s, room_c, room_h, room_faces, rng.uniform(0.2, 0.9, 3), int(rng.choice([1, 1, 1, 2, 3])), pattern=int(rng.integers(1, 3)))
     n = 0 if kind == "box" else int(rng.integers(1, 150)) if kind == "small" else int(rng.integers(400, 6000))
     if n:
         ctr = rng.uniform([-0.9, 0.1, -0.9], [0.9, 1.9, 0.9], (n, 3)).astype(np.float32)

@@ -45,7 +45,7 @@ class Stats(C.Structure):
         ("last_build_ms", C.c_double),
         ("gpu_built", C.c_uint32), ("bvh_nodes4", C.c_uint32), ("bvh_depth4", C.c_uint32), ("last_frame_split", C.c_uint32),
         ("last_tail_bounce", C.c_uint32), ("last_kernel", C.c_uint32), ("last_regen", C.c_uint32), ("last_tile_order", C.c_uint32),
-        ("bvh_quads", C.c_uint32), ("bvh_boxes", C.c_uint32),
+        ("bvh_quads", C.c_uint32), ("bvh_boxes", C.c_uint32), ("bvh_room", C.c_uint32),
     ]
 
     @property
@@ -132,6 +132,7 @@ _SYMBOLS = [
     ("trg_debug_build_bvh4q", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("trg_debug_boxes", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("trg_debug_flat_attributes", C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_int), _P]),
+    ("trg_debug_room", C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 
@@ -558,6 +559,27 @@ def debug_boxes(positions, indices, material_ids):
         if rc != OK:
             raise TrgError(rc, "trg_debug_boxes")
     return out
+
+
+def debug_room(positions, normals, colors, indices, material_ids):
+    """Host-only: the room trg_load_scene finds in the scene and a digest of the blob it builds (include/trg.h trg_debug_room): a dict with
+    n_faces (0: none), first_rec, first_tri, present (bit f = 2 k + (l_k > 0)), rest_kind (0 nothing, 1 node, 2 leaf), rest, rest_depth,
+    rest_prims, center[3] and axis[3, 3] (float32: l = axis (P - center)), face_rec[6], mask, depth, blob_hash, blob_bytes, lds_candidate."""
+    L = load()
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    nrm = np.ascontiguousarray(normals, np.float32).reshape(-1)
+    col = np.ascontiguousarray(colors, np.float32).reshape(-1)
+    idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+    mat = np.ascontiguousarray(material_ids, np.uint32).reshape(-1)
+    out = np.zeros(28, np.float32)
+    h, nb, cand = C.c_uint64(), C.c_uint32(), C.c_uint32()
+    rc = L.trg_debug_room(_ptr(pos), _ptr(nrm), _ptr(col), _ptr(idx), _ptr(mat), pos.shape[0], mat.shape[0], _ptr(out), C.byref(h), C.byref(nb), C.byref(cand))
+    if rc != OK:
+        raise TrgError(rc, "trg_debug_room")
+    i = lambda k: int(out[k])
+    return dict(n_faces=i(0), first_rec=i(1), first_tri=i(2), present=i(3), rest_kind=i(4), rest=i(5), rest_depth=i(6), rest_prims=i(7),
+                center=out[8:11].copy(), axis=out[11:20].reshape(3, 3).copy(), face_rec=out[20:26].astype(np.int64), mask=i(26), depth=i(27),
+                blob_hash=int(h.value), blob_bytes=int(nb.value), lds_candidate=int(cand.value))
 
 
 def debug_flat_attributes(normals, colors):

@@ -257,9 +257,107 @@ bool box_group(const float *pos, const uint32_t *idx, const uint32_t *masks, uin
     }
     return true;
 }
+
+// Are triangles k .. k + 2 nq - 1 (nq = 3, 4, 5) nq quads that are nq DISTINCT faces of one parallelepiped -- box_group's rule with faces absent?
+// The frame comes from the corners present, in double: the first quad's two half edges, the half edge of another quad that leaves their plane
+// (the edges of a parallelepiped have three directions, and any two faces that are not opposite show all three: three distinct faces always hold
+// such a pair), the centre = the first quad's centre moved along that third half edge to the side the other corners lie on.  Then, as for a box,
+// every corner of every quad must sit at local (+-1, +-1, +-1) to 1e-5, each quad on one side of one axis with the four sign pairs of the other
+// two, and no two quads on the same face.  The axes are numbered and signed by the world axis each one follows most (a room whose walls are
+// axis-aligned gets local x, y, z = world x, y, z).
+struct RoomGeom { double c[3], a[3][3]; uint32_t face_of_quad[5]; uint32_t present; };
+bool room_group(const float *pos, const uint32_t *idx, const uint32_t *masks, uint32_t ntris, uint32_t k, uint32_t nq, RoomGeom &g) {
+    if (nq < 3u || nq > 5u || (uint64_t)k + 2u * nq > ntris) return false;
+    auto vtx = [&](uint32_t t, int j) { return &pos[(size_t)idx[t * 3 + j] * 3]; };
+    double corner[5][4][3];
+    for (uint32_t q = 0; q < nq; ++q) {
+        uint32_t x = 0, y = 0;
+        if (masks[k + 2 * q] != masks[k] || !quad_pair(pos, idx, masks, ntris, k + 2 * q, x, y)) return false;
+        const float *p[4] = { vtx(x, 0), vtx(x, 1), vtx(x, 2), vtx(y, 2) };   // a, p1, the diagonal corner, p3 (quad_pair)
+        for (int j = 0; j < 4; ++j) for (int a = 0; a < 3; ++a) corner[q][j][a] = p[j][a];
+    }
+    auto cross = [](const double *u, const double *v, double *o) { o[0] = u[1] * v[2] - u[2] * v[1]; o[1] = u[2] * v[0] - u[0] * v[2]; o[2] = u[0] * v[1] - u[1] * v[0]; };
+    auto dot = [](const double *u, const double *v) { return u[0] * v[0] + u[1] * v[1] + u[2] * v[2]; };
+    double h[3][3], n01[3];
+    for (int a = 0; a < 3; ++a) { h[0][a] = 0.5 * (corner[0][1][a] - corner[0][0][a]); h[1][a] = 0.5 * (corner[0][3][a] - corner[0][0][a]); }
+    cross(h[0], h[1], n01);
+    const double nlen = std::sqrt(dot(n01, n01));
+    if (!(nlen > 0.0) || !std::isfinite(nlen)) return false;
+    double best = 0.0;
+    for (uint32_t q = 1; q < nq; ++q)
+        for (int e = 0; e < 2; ++e) {
+            double w[3];
+            for (int a = 0; a < 3; ++a) w[a] = 0.5 * (corner[q][e ? 3 : 1][a] - corner[q][0][a]);
+            const double wl = std::sqrt(dot(w, w)), out = wl > 0.0 ? std::fabs(dot(w, n01)) / (wl * nlen) : 0.0;
+            if (out > best) { best = out; for (int a = 0; a < 3; ++a) h[2][a] = w[a]; }
+        }
+    if (!(best > 1e-6)) return false;   // every quad parallel to the first: no third direction
+    // which side of the first quad the room lies on: the corner farthest out of its plane
+    double far = 0.0;
+    for (uint32_t q = 1; q < nq; ++q)
+        for (int j = 0; j < 4; ++j) {
+            double d[3];
+            for (int a = 0; a < 3; ++a) d[a] = corner[q][j][a] - corner[0][0][a];
+            const double o = dot(d, n01);
+            if (std::fabs(o) > std::fabs(far)) far = o;
+        }
+    if (far == 0.0) return false;
+    if ((far > 0.0) != (dot(h[2], n01) > 0.0)) for (int a = 0; a < 3; ++a) h[2][a] = -h[2][a];
+    double C[3];
+    for (int a = 0; a < 3; ++a) C[a] = corner[0][0][a] + h[0][a] + h[1][a] + h[2][a];
+    // number and sign the axes by the world axis each follows most
+    {
+        static const int perm[6][3] = { { 0, 1, 2 }, { 0, 2, 1 }, { 1, 0, 2 }, { 1, 2, 0 }, { 2, 0, 1 }, { 2, 1, 0 } };
+        int bp = 0; double bv = -1.0;
+        for (int p = 0; p < 6; ++p) {
+            double v = 1.0;
+            for (int a = 0; a < 3; ++a) v *= std::fabs(h[perm[p][a]][a]) / std::sqrt(dot(h[perm[p][a]], h[perm[p][a]]));
+            if (v > bv) { bv = v; bp = p; }
+        }
+        double hh[3][3];
+        for (int a = 0; a < 3; ++a) {
+            const double *src = h[perm[bp][a]];
+            double lead = src[a];
+            if (lead == 0.0) lead = src[0] != 0.0 ? src[0] : src[1] != 0.0 ? src[1] : src[2];
+            for (int b = 0; b < 3; ++b) hh[a][b] = lead < 0.0 ? -src[b] : src[b];
+        }
+        memcpy(h, hh, sizeof(h));
+    }
+    double scale = 0.0;
+    for (int ax = 0; ax < 3; ++ax) for (int a = 0; a < 3; ++a) scale = std::max(scale, std::fabs(h[ax][a]));
+    double c12[3], c20[3], c01[3];
+    cross(h[1], h[2], c12); cross(h[2], h[0], c20); cross(h[0], h[1], c01);
+    const double det = dot(h[0], c12);
+    if (!(std::fabs(det) > 1e-12 * scale * scale * scale) || !std::isfinite(det)) return false;
+    for (int a = 0; a < 3; ++a) { g.a[0][a] = c12[a] / det; g.a[1][a] = c20[a] / det; g.a[2][a] = c01[a] / det; g.c[a] = C[a]; }
+    g.present = 0u;
+    for (uint32_t q = 0; q < nq; ++q) {
+        double l[4][3], sum[3] = { 0, 0, 0 };
+        for (int j = 0; j < 4; ++j)
+            for (int ax = 0; ax < 3; ++ax) {
+                l[j][ax] = 0;
+                for (int a = 0; a < 3; ++a) l[j][ax] += g.a[ax][a] * (corner[q][j][a] - C[a]);
+                if (!(std::fabs(std::fabs(l[j][ax]) - 1.0) <= 1e-5)) return false;       // (also false for NaN)
+                sum[ax] += l[j][ax];
+            }
+        int kx = -1;
+        for (int ax = 0; ax < 3; ++ax) {
+            if (std::fabs(std::fabs(sum[ax]) - 4.0) <= 1e-3) { if (kx >= 0) return false; kx = ax; }   // all four corners on one side of this axis
+            else if (std::fabs(sum[ax]) > 1e-3) return false;                                        // the four sign pairs of the other two
+        }
+        if (kx < 0) return false;
+        const uint32_t f = 2u * (uint32_t)kx + (sum[kx] > 0.0 ? 1u : 0u);
+        if (g.present & (1u << f)) return false;   // the same face twice
+        g.present |= 1u << f;
+        g.face_of_quad[q] = f;
+    }
+    return true;
+}
 }  // namespace
 
-void build_bvh(const float *pos, const uint32_t *idx, const uint32_t *masks, uint32_t ntris, Bvh &out, bool want_wide8, bool want_boxes) {
+bool room_enabled() { const char *e = getenv("TRG_BVH_ROOM"); return !e || atoi(e) != 0; }
+
+void build_bvh(const float *pos, const uint32_t *idx, const uint32_t *masks, uint32_t ntris, Bvh &out, bool want_wide8, bool want_boxes, bool want_room) {
     if (const char *e = getenv("TRG_BVH_MAXLEAF")) kMaxLeaf = (uint32_t)std::min(6, std::max(1, atoi(e)));
     if (const char *e = getenv("TRG_BVH_TRAVCOST")) kTravCost = (float)atof(e);
     kQuads = quads_enabled();   // (read per build: the tests switch it)
@@ -272,11 +370,35 @@ void build_bvh(const float *pos, const uint32_t *idx, const uint32_t *masks, uin
     uint32_t n_prims = 0;
     std::vector<BoxGeom> box_geom;
     const bool boxes = want_boxes && kQuads && boxes_enabled();
+    // the room (bvh_build.h RoomLeaf): the first group of 5, 4 or 3 wall quads in index order; its quads wait in room_prims and go BEHIND the others
+    const bool rooms = want_room && boxes && ntris < 65536u && room_enabled();
+    RoomGeom room_geom;
+    uint32_t room_k0 = 0, room_nq = 0;
+    std::vector<Prim> room_prims;
     for (uint32_t k = 0; k < ntris; ++k) {
+        BoxGeom bg;
+        if (rooms && room_nq == 0u && !box_group(pos, idx, masks, ntris, k, bg)) {
+            for (uint32_t nq = 5; nq >= 3u && room_nq == 0u; --nq)
+                if (room_group(pos, idx, masks, ntris, k, nq, room_geom)) { room_k0 = k; room_nq = nq; }
+            if (room_nq) {
+                for (uint32_t q = 0; q < room_nq; ++q) {
+                    Prim p = Prim();
+                    uint32_t x = 0, y = 0;
+                    (void)quad_pair(pos, idx, masks, ntris, k + 2 * q, x, y);   // (room_group has checked it)
+                    p.id = x; p.id2 = y; p.box = ~0u;
+                    for (uint32_t t = k + 2 * q; t <= k + 2 * q + 1; ++t)
+                        for (int j = 0; j < 3; ++j) p.b.grow(vtx(t, j));
+                    for (int a = 0; a < 3; ++a) p.c[a] = 0.5f * (p.b.lo[a] + p.b.hi[a]);
+                    scene.grow(p.b);
+                    room_prims.push_back(p);
+                }
+                k += 2u * room_nq - 1u;
+                continue;
+            }
+        }
         Prim &p = B.prims[n_prims++];
         p = Prim();
         p.id = k; p.id2 = ~0u; p.box = ~0u;
-        BoxGeom bg;
         if (boxes && box_group(pos, idx, masks, ntris, k, bg)) {   // twelve triangles, one primitive
             p.box = (uint32_t)box_geom.size();
             box_geom.push_back(bg);
@@ -308,7 +430,27 @@ void build_bvh(const float *pos, const uint32_t *idx, const uint32_t *masks, uin
         B.cutoff = std::max(4096u, n_prims / (n_threads * 8u));
         B.tasks = &tasks;
     }
-    int32_t root = n_prims ? B.build(0, n_prims, 0) : -1;
+    int32_t root = -1, rest_root = -1;
+    const uint32_t n_rest = n_prims;
+    uint32_t rest_leaf_depth = 0;
+    if (room_nq) {
+        // the tree over everything else one level down, the room's quads behind them with a subtree of their own, and a new root over the two
+        // (a scene that is only a room: its subtree is the tree)
+        B.tasks = nullptr;
+        for (const Prim &p : room_prims) B.prims[n_prims++] = p;
+        if (n_rest) { rest_root = B.build(0, n_rest, 1); rest_leaf_depth = B.depth; }
+        const int32_t room_root = B.build(n_rest, room_nq, n_rest ? 1 : 0);
+        root = room_root;
+        if (n_rest) {
+            root = (int32_t)B.nodes.size();
+            B.nodes.emplace_back();
+            B.nodes[root].box = B.nodes[room_root].box;
+            B.nodes[root].box.grow(B.nodes[rest_root].box);
+            B.nodes[root].child[0] = room_root; B.nodes[root].child[1] = rest_root;
+        }
+    } else {
+        root = n_prims ? B.build(0, n_prims, 0) : -1;
+    }
     if (!tasks.empty()) {
         B.tasks = nullptr;
         std::vector<Builder> sub(tasks.size());
@@ -506,6 +648,22 @@ void build_bvh(const float *pos, const uint32_t *idx, const uint32_t *masks, uin
             }
         }
         out.boxes.push_back(bl);
+    }
+
+    out.room = RoomLeaf();
+    if (room_nq) {
+        RoomLeaf &rm = out.room;
+        rm.n_faces = room_nq; rm.first_rec = rec_first[n_rest]; rm.first_tri = room_k0; rm.mask = masks[room_k0]; rm.present = room_geom.present;
+        for (int a = 0; a < 3; ++a) { rm.center[a] = (float)room_geom.c[a]; for (int k = 0; k < 3; ++k) rm.axis[k][a] = (float)room_geom.a[k][a]; }
+        for (uint32_t j = 0; j < room_nq; ++j) {   // the quads in the order their subtree left them: records first_rec + 2 j, + 2 j + 1
+            const Prim &p = B.prims[n_rest + j];
+            rm.face_rec[room_geom.face_of_quad[(std::min(p.id, p.id2) - room_k0) / 2u]] = (uint8_t)(2u * j);
+        }
+        rm.rest_prims = n_rest;
+        if (rest_root >= 0) {
+            rm.rest = B.nodes[(size_t)rest_root].leaf ? leaf_of(B.nodes[(size_t)rest_root]) : dev_index[(size_t)rest_root];
+            rm.rest_depth = rest_leaf_depth - 1u;
+        }
     }
 
     // ---- 4-wide collapse (used for scenes that stay in HBM): each BVH2 inner node pulls up grandchildren,

@@ -53,8 +53,31 @@ struct BoxLeaf {
     uint32_t mask;          // the material id of its twelve triangles
 };
 
+// The ROOM (scenes staged in LDS only).  addPlane's walls (Scene.cpp:60-92) are k = 3, 4 or 5 quads, consecutive in the index buffer, that are k
+// distinct faces of ONE parallelepiped: a box with faces missing (the Cornell box: five, the camera looks in through the sixth).  Every inner node
+// that joins walls is as large as the room, so a ray walks them all.  With `want_room` the builder takes the first such group out of the tree:
+// the tree is built over everything else, the room's quads get a subtree of their own, and a NEW ROOT joins the two -- whoever walks from node 0
+// (the strict build, the BVH2 array, the 4-wide collapse) sees an ordinary tree.  The shipped build's LDS traversal tests the room once per
+// call, ahead of the loop -- one slab test in the room's frame whose entry and exit planes count only where their face is present -- and walks
+// from `rest`.  The nearest hit does not depend on the order primitives are tested in (ties go by index), so the result is the tree's.
+constexpr int32_t kRestNone = (int32_t)0x80000000;   // RoomLeaf::rest of a scene that is only a room (= the traversal's "finished" marker)
+struct RoomLeaf {
+    uint32_t n_faces = 0;   // 0: the scene has no room
+    uint32_t first_rec = 0; // its 2 n_faces records: n_faces quads, X then Y each
+    uint32_t first_tri = 0; // the original index of its first triangle
+    uint32_t mask = 0;      // the material id of its triangles
+    float center[3] = { 0, 0, 0 };   // the frame, as BoxLeaf's: l_k = axis[k] . (P - center), the room is |l_k| <= 1
+    float axis[3][3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };
+    uint32_t present = 0;   // bit f = 2 k + (l_k > 0 ? 1 : 0): the face is there
+    uint8_t face_rec[6] = { 0, 0, 0, 0, 0, 0 };   // a present face: offset (0, 2, ..) of its quad's X record from first_rec
+    int32_t rest = kRestNone;   // where the walk over everything else starts: an index into the BVH2 node array (>= 0), a leaf code (< 0), or kRestNone
+    uint32_t rest_prims = 0;    // primitives (triangles, quads, boxes) of that walk
+    uint32_t rest_depth = 0;    // its depth counted from `rest` (a box is a leaf): a stack for it needs rest_depth + 2 levels
+};
+
 struct Bvh {
-    std::vector<uint8_t> quad;   // per triangle record: 1 = record X of a quad leaf (the next record is its Y)
+    RoomLeaf room;
+    std::vector<uint8_t> quad;  // per triangle record: 1 = record X of a quad leaf (the next record is its Y)
     uint32_t n_quads = 0;
     std::vector<F4> nodes;   // 4 per node (BVH2)
     std::vector<F4> nodes4;  // 8 per node (BVH4 collapse of the same tree), float boxes: what the quantiser and the tests see
@@ -92,8 +115,10 @@ uint32_t pair_quads(const float *positions3, const uint32_t *indices, const uint
 
 // positions3: nverts*3 floats; indices: ntris*3; masks: ntris (the reference's materialID buffer,
 // MetalRenderer.mm:276).  Deterministic for a given input.
-void build_bvh(const float *positions3, const uint32_t *indices, const uint32_t *masks, uint32_t ntris, Bvh &out, bool want_wide8 = false, bool want_boxes = false);
+void build_bvh(const float *positions3, const uint32_t *indices, const uint32_t *masks, uint32_t ntris, Bvh &out, bool want_wide8 = false, bool want_boxes = false,
+               bool want_room = false);
 bool boxes_enabled();   // TRG_BVH_BOXES != 0 (default on), read at every call: the switch for A/B runs and tests
+bool room_enabled();    // TRG_BVH_ROOM != 0 (default on), read at every call; a room also needs the quads and the boxes on
 bool flat_shading_enabled();   // TRG_FLAT_SHADING != 0 (default on), read at every scene load: the flat-attribute records of trg_capi.cpp flat_attr_records
 
 }  // namespace trg

@@ -200,7 +200,10 @@ static bool plan_lds_as(const trg_ctx *c, LdsPlan &p, bool lds_scene, bool pool,
         // the sentinel at level 0 + BVH2, near child first: at most one pending entry per level + the scratch slot above the top
         // (BVH2: leaves sit at depth <= bvh_depth, so inner nodes at depths 0 .. bvh_depth - 1 hold at most bvh_depth pending entries in levels
         //  1 .. bvh_depth, and the step at an inner node of depth k stores its far child at level <= k + 1: bvh_depth + 1 levels are used, one is spare)
-        levels = c->bvh_depth + 2;
+        // (a scene with a room: the shipped build tests the room ahead of the loop and walks the REST of the tree from an empty stack, so its
+        //  launches need the levels of that part only -- the new root over room and rest must not cost a level; the strict build walks from node 0)
+        //  (the experiments library keeps the full depth: the schedules kept there have traversal loops of their own that start at node 0)
+        levels = ((c->bvh_room && !c->opt_strict && !TRG_EXPERIMENTS) ? c->bvh_walk_depth : c->bvh_depth) + 2;
         p.klds = levels;
     } else {
         // the sentinel at level 0; 4-wide: up to three pending entries per level.  (TRG_WIDE8: one two-word node group per level of the 8-wide tree,
@@ -454,7 +457,7 @@ static int load_scene_gpu_build(trg_ctx *c, const float *pos, const float *nrm, 
     HIPCHK(c, hipStreamSynchronize(c->stream));
     sc.blob = c->blob;
     c->sc = sc;
-    c->bvh_nodes = 0; c->bvh_depth = 2 * depth4; c->bvh_leaves = n_tris; c->bvh_quads = 0; c->bvh_boxes = 0;   // (device builds: the quads are paired on the device, not counted)
+    c->bvh_nodes = 0; c->bvh_depth = 2 * depth4; c->bvh_leaves = n_tris; c->bvh_quads = 0; c->bvh_boxes = 0; c->bvh_room = 0; c->bvh_walk_depth = 0;   // (device builds: the quads are paired on the device, not counted)
     c->bvh_nodes4 = n4; c->bvh_depth4 = depth4;
     c->scene_loaded = true;
     LdsPlan plan;
@@ -470,6 +473,7 @@ struct HostScene {
     std::vector<unsigned char> blob;   // the image of the device allocation (plan_scene_layout)
     SceneDesc sc{};                    // offsets; sc.blob is filled in per context
     uint32_t bvh_nodes = 0, bvh_depth = 0, bvh_leaves = 0, bvh_nodes4 = 0, bvh_depth4 = 0, bvh_quads = 0, bvh_boxes = 0;
+    uint32_t bvh_room = 0, bvh_walk_depth = 0;   // faces of the room (0: none) and the depth of the part the shipped build walks behind it (bvh_build.h RoomLeaf)
     double build_ms = 0.0;
     float lo[3] = { 0.f, 0.f, 0.f }, hi[3] = { 1.f, 1.f, 1.f };   // bounds of the triangles
 };
@@ -581,6 +585,13 @@ static void box_frame_rows(const BoxLeaf &bl, const float *center, float *rows) 
     }
 }
 
+// is the scene small enough to be staged in LDS: [ nodes | 48-byte records + u16 each | attributes | Halton tables ] within kMaxLdsScene
+static bool lds_candidate_scene(const Bvh &bvh, uint32_t n_tris) {
+    const uint32_t nt_rec = (uint32_t)(bvh.tris.size() / 3), attr_tris = std::max(n_tris, 1u);
+    const uint64_t small_bytes = (uint64_t)bvh.n_nodes * kLdsNodeBytes + (uint64_t)nt_rec * 50u + (uint64_t)attr_tris * 76u + 80u + kHtabBytes;
+    return small_bytes <= kMaxLdsScene && n_tris < (1u << 14);   // (u16 per record: index << 2 | mask)
+}
+
 int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float *col, const uint32_t *idx, const uint32_t *mat, uint32_t n_verts,
                      uint32_t n_tris, HostScene **out) {
     if (!c || !out) return TRG_ERR_INVALID;
@@ -590,7 +601,18 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
     if (!hs) return fail(c, TRG_ERR_NOMEM, "trg_load_scene: out of host memory");
     const auto host_t0 = std::chrono::steady_clock::now();
     Bvh bvh;
-    build_bvh(pos, idx, mat, n_tris, bvh, TRG_WIDE8 != 0, !TRG_WIDE8);
+    // a room (bvh_build.h RoomLeaf) is for scenes staged in LDS: one is looked for only where the triangle count leaves that open (126 staged bytes per
+    // triangle at least), and a scene that has one and turns out not to be an LDS candidate is built again without -- its blob is then the one a
+    // builder that knows no rooms makes
+    const bool try_room = !TRG_WIDE8 && (uint64_t)n_tris * 126u <= kMaxLdsScene;
+    build_bvh(pos, idx, mat, n_tris, bvh, TRG_WIDE8 != 0, !TRG_WIDE8, try_room);
+    if (bvh.room.n_faces && !lds_candidate_scene(bvh, n_tris)) build_bvh(pos, idx, mat, n_tris, bvh, TRG_WIDE8 != 0, !TRG_WIDE8, false);
+    // ... and what a scene with a room is traversed through from HBM (TRG_OPT_FORCE_GLOBAL, a tree too deep for LDS stacks) comes from the tree
+    // WITHOUT the room: a subtree of walls as large as the scene beside the rest is a poor tree to walk, and nothing there tests the room first.  The
+    // two parts of the blob do not refer to each other (each has its own records, in its own leaf order)
+    Bvh bvh_plain;
+    if (bvh.room.n_faces) build_bvh(pos, idx, mat, n_tris, bvh_plain, false, true, false);
+    const Bvh &hb = bvh.room.n_faces ? bvh_plain : bvh;
     if (TRG_WIDE8 && !bvh.wide8_ok) { delete hs; return fail(c, TRG_ERR_RANGE, "trg_load_scene: the 8-wide layout of this build needs leaves of at most two records (TRG_BVH_MAXLEAF <= 2)"); }
     hs->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
     if (n_tris) {
@@ -610,8 +632,7 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
     // The first bracket is what a workgroup stages into LDS; only a scene small enough for that has it.  The other two are what
     // the HBM kernels traverse (a small scene kept in HBM -- TRG_OPT_FORCE_GLOBAL, a tree too deep for LDS stacks -- uses them too).
     const uint32_t lds_nodes = bvh.n_nodes;
-    const uint64_t small_bytes = (uint64_t)lds_nodes * kLdsNodeBytes + (uint64_t)nt_rec * 50u + (uint64_t)attr_tris * 76u + 80u + kHtabBytes;
-    const bool lds_candidate = small_bytes <= kMaxLdsScene && n_tris < (1u << 14);   // (u16 per record: index << 2 | mask)
+    const bool lds_candidate = lds_candidate_scene(bvh, n_tris);
     SceneDesc sc{};
     sc.n_nodes = lds_candidate ? lds_nodes : 0u; sc.n_tris = n_tris;
     sc.n_tris_rec = lds_candidate ? nt_rec : 0u;
@@ -625,13 +646,13 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
         if (n_tris && prims <= kFlatMaxPrims) n_flat = prims;
     }
     sc.n_flat = n_flat;
-    sc.n_nodes4 = TRG_WIDE8 ? bvh.n_nodes8 : bvh.n_nodes4;
+    sc.n_nodes4 = TRG_WIDE8 ? bvh.n_nodes8 : hb.n_nodes4;
     const uint32_t n_fat = TRG_WIDE8 ? (uint32_t)bvh.rec8.size() : nt_rec;   // (TRG_WIDE8: two entries per leaf, in the order the 8-wide tree addresses them)
     uint64_t total = 0;
     // the box-leaf flavour of the HBM tree (shipped build): TRG_BVH_BOXES_HBM=0 leaves it out (A/B runs: the kernels then never meet a box code)
-    const bool hbm_boxes = !TRG_WIDE8 && bvh.n_nodes4_box != 0 && !(getenv("TRG_BVH_BOXES_HBM") && atoi(getenv("TRG_BVH_BOXES_HBM")) == 0);
+    const bool hbm_boxes = !TRG_WIDE8 && hb.n_nodes4_box != 0 && !(getenv("TRG_BVH_BOXES_HBM") && atoi(getenv("TRG_BVH_BOXES_HBM")) == 0);
     if (!plan_scene_layout(sc.n_nodes, node_bytes, lds_candidate ? nt_rec : 0u, lds_candidate ? attr_tris : 0u, lds_candidate, sc.n_nodes4, n_fat, sc, total,
-                           hbm_boxes ? bvh.n_nodes4_box : 0u, hbm_boxes ? bvh.boxes.size() : 0u)) {
+                           hbm_boxes ? hb.n_nodes4_box : 0u, hbm_boxes ? hb.boxes.size() : 0u)) {
         delete hs;
         return fail(c, TRG_ERR_RANGE, "trg_load_scene: scene needs %llu B on the device (limit 4 GiB)", (unsigned long long)total);
     }
@@ -686,7 +707,30 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
             memcpy(&host[sc.off_tris_alt + (size_t)(bl.first_rec + 1u) * 48u], rec, 48);
             uint32_t faces[12] = { 0 };
             for (int f = 0; f < 6; ++f) faces[f] = ((uint32_t)bl.face_rec[f] << 16) | ((uint32_t)bl.face_rec[f] * 48u);
+            faces[6] = 63u;   // every face is present (lds_box_hit_resolve reads the mask of a box and of the room alike)
             memcpy(&host[sc.off_tris_alt + (size_t)(bl.first_rec + 3u) * 48u], faces, 48);
+        }
+        // the room (bvh_build.h RoomLeaf, trg_kernels.h SceneDesc::room_first1): the same two Y slots, the mask of the faces that are there, and
+        // where the walk over the rest of the scene starts
+        if (bvh.room.n_faces) {
+            const RoomLeaf &rm = bvh.room;
+            BoxLeaf fr{};
+            memcpy(fr.center, rm.center, sizeof(fr.center)); memcpy(fr.axis, rm.axis, sizeof(fr.axis));
+            float rec[12];
+            box_frame_rows(fr, sc.center, rec);
+            memcpy(&host[sc.off_tris_alt + (size_t)(rm.first_rec + 1u) * 48u], rec, 48);
+            uint32_t faces[12] = { 0 };
+            for (int f = 0; f < 6; ++f)
+                if (rm.present & (1u << f)) faces[f] = ((uint32_t)rm.face_rec[f] << 16) | ((uint32_t)rm.face_rec[f] * 48u);
+            int32_t start = rm.rest;
+            for (const BoxLeaf &bl : bvh.boxes)   // (the rest is one box: its leaf, as the node array above names it)
+                if (start >= 0 && (uint32_t)start == bl.node) start = ~(int32_t)((bl.first_rec << 3) | kLeafBox);
+            if (start >= 0) start *= (int32_t)kLdsNodeBytes;
+            faces[6] = rm.present;
+            faces[7] = (uint32_t)start;   // (the kernels read the walk's start here, next to the mask: trg_device.h trav_room_planes)
+            memcpy(&host[sc.off_tris_alt + (size_t)(rm.first_rec + 3u) * 48u], faces, 48);
+            sc.room_first1 = rm.first_rec + 1u;
+            sc.walk_start = start;
         }
         if (sc.n_flat) {   // the flat list: the same plane records, one entry per primitive, + who it is -- in ASCENDING order of original index (traverse_flat's tie rule)
             struct FP { uint32_t key, rec; bool quad; };
@@ -742,9 +786,9 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
     }
 #else
     for (uint32_t i = 0; i < nt_rec; ++i) {
-        fill_fat_record(&host[sc.off_fat + (size_t)i * kFatRecBytes], &bvh.tris[(size_t)i * 3], nrm, col, n_tris);
-        fill_fat_record_planes(&host[sc.off_fat_planes + (size_t)i * kFatRecBytes], &bvh.tris[(size_t)i * 3], nrm, col, n_tris, sc.center,
-                               (i < bvh.quad.size() && bvh.quad[i]) ? &bvh.tris[(size_t)(i + 1) * 3] : nullptr);
+        fill_fat_record(&host[sc.off_fat + (size_t)i * kFatRecBytes], &hb.tris[(size_t)i * 3], nrm, col, n_tris);
+        fill_fat_record_planes(&host[sc.off_fat_planes + (size_t)i * kFatRecBytes], &hb.tris[(size_t)i * 3], nrm, col, n_tris, sc.center,
+                               (i < hb.quad.size() && hb.quad[i]) ? &hb.tris[(size_t)(i + 1) * 3] : nullptr);
     }
 #endif
     if (lds_candidate) {  // Halton group tables (trg_kernels.h kHtab)
@@ -760,13 +804,13 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
 #if TRG_WIDE8
     if (sc.n_nodes4) memcpy(&host[sc.off_nodes4], bvh.nodes8.data(), (size_t)sc.n_nodes4 * kQ8NodeBytes);
 #else
-    if (sc.n_nodes4) memcpy(&host[sc.off_nodes4], bvh.nodes4q.data(), (size_t)sc.n_nodes4 * kQ4NodeBytes);
+    if (sc.n_nodes4) memcpy(&host[sc.off_nodes4], hb.nodes4q.data(), (size_t)sc.n_nodes4 * kQ4NodeBytes);
 #endif
 
     if (hbm_boxes) {
-        memcpy(&host[sc.off_nodes4_box], bvh.nodes4q_box.data(), (size_t)bvh.n_nodes4_box * kQ4NodeBytes);
-        for (size_t b = 0; b < bvh.boxes.size(); ++b) {
-            const BoxLeaf &bl = bvh.boxes[b];
+        memcpy(&host[sc.off_nodes4_box], hb.nodes4q_box.data(), (size_t)hb.n_nodes4_box * kQ4NodeBytes);
+        for (size_t b = 0; b < hb.boxes.size(); ++b) {
+            const BoxLeaf &bl = hb.boxes[b];
             float rec[16];
             box_frame_rows(bl, sc.center, rec);
             uint32_t row3[4] = { bl.first_rec, bl.mask, 0u, 0u };
@@ -783,9 +827,10 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
     hs->sc = sc;
     hs->bvh_nodes = bvh.n_nodes; hs->bvh_depth = bvh.depth; hs->bvh_leaves = bvh.n_leaves;
     hs->bvh_quads = bvh.n_quads; hs->bvh_boxes = (lds_candidate || hbm_boxes) ? bvh.n_boxes_real : 0u;
-    hs->bvh_nodes4 = TRG_WIDE8 ? bvh.n_nodes8 : bvh.n_nodes4; hs->bvh_depth4 = TRG_WIDE8 ? bvh.depth8 : bvh.depth4;
+    hs->bvh_room = bvh.room.n_faces; hs->bvh_walk_depth = bvh.room.rest_depth;
+    hs->bvh_nodes4 = TRG_WIDE8 ? bvh.n_nodes8 : hb.n_nodes4; hs->bvh_depth4 = TRG_WIDE8 ? bvh.depth8 : hb.depth4;
     // the stack is sized by the tree the kernels walk (plan_lds_as): with box leaves in HBM that is the box flavour, another collapse of the same BVH2
-    if (!TRG_WIDE8 && hbm_boxes) hs->bvh_depth4 = std::max(bvh.depth4, bvh.depth4_box);
+    if (!TRG_WIDE8 && hbm_boxes) hs->bvh_depth4 = std::max(hb.depth4, hb.depth4_box);
     *out = hs;
     return TRG_OK;
 }
@@ -807,6 +852,7 @@ int host_scene_upload(trg_ctx *c, const HostScene *hs) {
     c->gpu_built = false;
     c->bvh_nodes = hs->bvh_nodes; c->bvh_depth = hs->bvh_depth; c->bvh_leaves = hs->bvh_leaves;
     c->bvh_quads = hs->bvh_quads; c->bvh_boxes = hs->bvh_boxes;
+    c->bvh_room = hs->bvh_room; c->bvh_walk_depth = hs->bvh_walk_depth;
     c->bvh_nodes4 = hs->bvh_nodes4; c->bvh_depth4 = hs->bvh_depth4;
     c->scene_loaded = true;
     LdsPlan plan;
@@ -1159,7 +1205,7 @@ int trg_get_stats(trg_ctx *c, trg_stats *out) {
     out->wave_node_iters = sum[6]; out->wave_tri_iters = sum[7];
     out->last_render_ms = c->last_ms; out->total_render_ms = c->total_ms; out->renders = c->renders;
     out->bvh_nodes = c->bvh_nodes; out->bvh_depth = c->bvh_depth; out->bvh_leaves = c->bvh_leaves;
-    out->bvh_quads = c->bvh_quads; out->bvh_boxes = c->bvh_boxes;
+    out->bvh_quads = c->bvh_quads; out->bvh_boxes = c->bvh_boxes; out->bvh_room = c->bvh_room;
     out->scene_bytes = c->sc.blob_bytes;
     out->last_build_ms = c->last_build_ms; out->gpu_built = c->gpu_built ? 1u : 0u;
     out->bvh_nodes4 = c->bvh_nodes4; out->bvh_depth4 = c->bvh_depth4;
@@ -1367,6 +1413,39 @@ int trg_debug_boxes(const float *positions3, const uint32_t *indices, const uint
             for (int a = 0; a < 3; ++a) { o[2 + a] = bl.center[a]; for (int k = 0; k < 3; ++k) o[5 + k * 3 + a] = bl.axis[k][a]; }
             for (int f = 0; f < 6; ++f) o[14 + f] = (float)bl.face_rec[f];
         }
+    }
+    return TRG_OK;
+}
+
+int trg_debug_room(const float *positions3, const float *normals3, const float *colors3, const uint32_t *indices, const uint32_t *material_ids,
+                   uint32_t n_verts, uint32_t n_tris, float *room28_out, uint64_t *blob_hash, uint32_t *blob_bytes, uint32_t *lds_candidate) {
+    if (n_tris && (!positions3 || !normals3 || !colors3 || !indices || !material_ids)) return TRG_ERR_INVALID;
+    trg_ctx tmp;   // (host_scene_build reports errors into a context; it touches no device)
+    HostScene *hs = nullptr;
+    if (int rc = host_scene_build(&tmp, positions3, normals3, colors3, indices, material_ids, n_verts, n_tris, &hs)) return rc;
+    if (blob_hash) {   // FNV-1a, 64 bits
+        uint64_t h = 1469598103934665603ull;
+        for (unsigned char b : hs->blob) { h ^= b; h *= 1099511628211ull; }
+        *blob_hash = h;
+    }
+    if (blob_bytes) *blob_bytes = (uint32_t)hs->blob.size();
+    if (lds_candidate) *lds_candidate = hs->sc.n_nodes != 0u ? 1u : 0u;
+    const bool had_room = hs->bvh_room != 0u;
+    host_scene_free(hs);
+    if (room28_out) {
+        // the room itself from the builder, asked the way host_scene_build asks (a scene that is no LDS candidate has none)
+        Bvh bvh;
+        if (had_room) build_bvh(positions3, indices, material_ids, n_tris, bvh, false, true, true);
+        const RoomLeaf &rm = bvh.room;
+        float *o = room28_out;
+        memset(o, 0, 28 * sizeof(float));
+        o[0] = (float)rm.n_faces; o[1] = (float)rm.first_rec; o[2] = (float)rm.first_tri; o[3] = (float)rm.present;
+        o[4] = rm.rest == kRestNone ? 0.f : rm.rest >= 0 ? 1.f : 2.f;                       // the walk starts at: nothing, a node, a leaf
+        o[5] = rm.rest == kRestNone ? 0.f : rm.rest >= 0 ? (float)rm.rest : (float)(uint32_t)~rm.rest;   // ... the node's index / the leaf's code (first record << 3 | kind)
+        o[6] = (float)rm.rest_depth; o[7] = (float)rm.rest_prims;
+        for (int a = 0; a < 3; ++a) { o[8 + a] = rm.center[a]; for (int k = 0; k < 3; ++k) o[11 + k * 3 + a] = rm.axis[k][a]; }
+        for (int f = 0; f < 6; ++f) o[20 + f] = (float)rm.face_rec[f];
+        o[26] = (float)rm.mask; o[27] = (float)bvh.depth;
     }
     return TRG_OK;
 }

@@ -65,6 +65,7 @@ struct trg_ctx {
     double last_build_ms = 0.0;
     bool gpu_built = false;
     uint32_t bvh_nodes = 0, bvh_depth = 0, bvh_leaves = 0, bvh_quads = 0, bvh_boxes = 0;
+    uint32_t bvh_room = 0, bvh_walk_depth = 0;   // the room of an LDS-resident scene: its faces (0 = none), and the depth of the part the shipped build walks behind it
     double last_ms = 0.0, total_ms = 0.0;
     uint32_t renders = 0;
     uint32_t last_fsplit = 1;

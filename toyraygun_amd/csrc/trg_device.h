@@ -539,6 +539,7 @@ struct SceneView {
     uint32_t n_rec;         // HBM scene: its leaf records; an index from here on names a BOX record (shipped build: SceneDesc::off_boxrec sits right behind them)
     const v4f *flat;        // shipped build, tiny LDS-resident scene: the flat primitive list in global memory (trg_kernels.h SceneDesc::off_flat), wave-uniform
     uint32_t n_flat;        // its entries; 0: walk the tree
+    uint32_t room_first1;   // shipped build, LDS scene: first record of the ROOM + 1 (trg_kernels.h SceneDesc::room_first1), 0 = none; wave-uniform
 };
 // original index / material id of leaf record r of an HBM-resident scene: the .w of rows 0 / 1 (Moeller-Trumbore records), or the last two
 // words of the record (plane records, whose rows 0..2 are full)
@@ -880,6 +881,61 @@ TRG_DEV bool trav_box_planes(const SceneView &sc, const v4f *tr, uint32_t first,
     return any && ok;
 }
 TRG_DEV const v4f *lds_records(const SceneView &sc, uint32_t first);
+// The ROOM of an LDS-resident scene (shipped build; bvh_build.h RoomLeaf, trg_kernels.h SceneDesc::room_first1): 3 to 5 wall quads that are faces of
+// one parallelepiped, tested ONCE per traversal call, ahead of the node loop, by every live lane together -- no stack, no divergence -- instead of
+// a leaf step each behind inner nodes as large as the room.  The slab test of trav_box_planes in the room's frame, with two candidates: the plane
+// the ray enters the slabs by (tnear) and the plane it leaves by (tfar).  A candidate counts when the slabs are met at all (tnear <= tfar), its t lies
+// in [0, best] and its FACE IS PRESENT; the nearer one that counts is the hit (the quads are two-sided).  From outside into a wall: tnear.  From
+// inside: tfar, or nothing when that face is absent.  In through an absent face: tfar.  In and out through absent faces: nothing.  The entry face on
+// axis k is the one at l_k = -1 when the ray runs towards +l_k (f = 2 k), else f = 2 k + 1; the exit face is the other.  A ray parallel to a pair of
+// faces has +-1e30 for that reciprocal (rcp3_parallel_safe): outside that slab a miss, inside no constraint, and never a hit ON one of the pair.
+// Called AHEAD of trav_begin, on the ray alone (o relative to the scene's centre, rmask its two low bits: trav_begin): the reciprocals and the
+// rest of the traversal state are not alive yet, which is what keeps the render kernels within their registers.  Returns whether the room is hit
+// within [0, tmax], t, the code the hit is held by -- -(first + 2), "a box, still to be named", exactly what a box leaf leaves behind:
+// lds_box_hit_resolve names the triangle from the face's own quad rows -- or -1, and `start`, where the walk over the rest begins (word 7 of the
+// face table, read with the mask).  Code and start come out of per-call VGPRs on purpose: as selects on launch constants the compiler keeps each
+// in a register of its own across the whole frame loop, two more than the render kernels have.
+template <bool COUNT>
+TRG_DEV bool trav_room_planes(const SceneView &sc, V3 o, V3 d, float tmax, uint32_t rmask, float &t, int &held, int &start, Counters &cnt) {
+    // opaque copy: the room's rows sit at one LDS address for the whole launch, and LICM would hoist their thirteen words out of the bounce and
+    // frame loops and keep them in VGPRs across every shading event (the render kernels then spill); re-read per call, as a leaf's are
+    uint32_t first = sc.room_first1 - 1u;
+    asm volatile("" : "+v"(first));
+    const v4f *tr = lds_records(sc, first);
+    const uint32_t meta0 = sc.meta[first];
+    const bool masked_in = (meta0 & rmask) != 0u;   // (one material for all the walls: bvh_build.cpp room_group)
+    // counted as one NODE step (a slab test ahead of the walk, paid by every call like a root's), not as a primitive test: one of those per call would
+    // put a room scene's primitive tests per ray above 1, and the counters' users compare them between trees (fewer with box leaves than without)
+    if (COUNT) { cnt.nodes++; if (mbcnt64(__ballot(1)) == 0) cnt.wnodes++; }
+    const v4f b0 = tr[3], b1 = tr[4], b2 = tr[5];
+    typedef uint32_t v2u_t __attribute__((ext_vector_type(2)));
+    const v2u_t pw = reinterpret_cast<const v2u_t *>(tr + 9)[3];   // words 6, 7 of the face table: the present-face mask, the walk's start
+    const uint32_t present = pw.x;
+    start = (int)pw.y;
+    const float lox = b0.x * o.x + (b0.y * o.y + (b0.z * o.z + b0.w)), ldx = b0.x * d.x + (b0.y * d.y + b0.z * d.z);
+    const float loy = b1.x * o.x + (b1.y * o.y + (b1.z * o.z + b1.w)), ldy = b1.x * d.x + (b1.y * d.y + b1.z * d.z);
+    const float loz = b2.x * o.x + (b2.y * o.y + (b2.z * o.z + b2.w)), ldz = b2.x * d.x + (b2.y * d.y + b2.z * d.z);
+    float ix, iy, iz;
+    rcp3_parallel_safe(ldx, ldy, ldz, ix, iy, iz, true);
+    const float mx = -lox * ix, my = -loy * iy, mz = -loz * iz;              // the ray meets the planes l_k = -1, +1 at m_k -+ |1 / ld_k|
+    const float ax = fabsf(ix), ay = fabsf(iy), az = fabsf(iz);
+    const float nx = mx - ax, ny = my - ay, nz = mz - az, fx = mx + ax, fy = my + ay, fz = mz + az;
+    const float tnear = fmaxf(fmaxf(nx, ny), nz), tfar = fminf(fminf(fx, fy), fz);
+    const uint32_t sx = __float_as_uint(ix) >> 31, sy = __float_as_uint(iy) >> 31, sz = __float_as_uint(iz) >> 31;   // 1: the ray runs towards -l_k
+    const bool nisx = nx >= tnear, nisy = ny >= tnear, fisx = fx <= tfar, fisy = fy <= tfar;
+    const uint32_t fnear = nisx ? sx : nisy ? 2u + sy : 4u + sz;
+    const uint32_t ffar = fisx ? (sx ^ 1u) : fisy ? 2u + (sy ^ 1u) : 4u + (sz ^ 1u);
+    // a ray PARALLEL to a face misses it, also one that lies in its plane (the intersection contract: Moeller-Trumbore's det == 0; trav_box_rec says
+    // the same of a lone quad): with the origin exactly on l_k = +-1 the held reciprocal puts one plane of that slab at t = 0, and that plane
+    // would be the entry or the exit -- a candidate on an axis whose reciprocal is held does not count
+    const float anear = nisx ? ax : nisy ? ay : az, afar = fisx ? ax : fisy ? ay : az;
+    const bool cn = (tnear >= 0.0f) && (tnear <= tmax) && ((present >> fnear) & 1u) != 0u && (anear < kRcpParallel);
+    const bool cf = (tfar >= 0.0f) && (tfar <= tmax) && ((present >> ffar) & 1u) != 0u && (afar < kRcpParallel);
+    t = cn ? tnear : tfar;
+    const bool ok = (tnear <= tfar) && (cn || cf) && masked_in;
+    held = ok ? -(int)(first + 2u) : -1;
+    return ok;
+}
 // the triangle and the weights of a hit that is still a box (h.prim <= -2): the hit point in the box's frame, the face = the axis along which it lies
 // farthest out, that face's own quad planes for (s, t) -- exactly what its quad test would have computed there
 TRG_DEV void lds_box_hit_resolve(const SceneView &sc, const Trav &tv, Hit &h) {
@@ -890,10 +946,13 @@ TRG_DEV void lds_box_hit_resolve(const SceneView &sc, const Trav &tv, Hit &h) {
     const V3 o = tv.o, d = tv.d;
     const V3 P = mk(o.x + h.t * d.x, o.y + h.t * d.y, o.z + h.t * d.z);
     const float lx = b0.x * P.x + (b0.y * P.y + (b0.z * P.z + b0.w)), ly = b1.x * P.x + (b1.y * P.y + (b1.z * P.z + b1.w)), lz = b2.x * P.x + (b2.y * P.y + (b2.z * P.z + b2.w));
-    const float fx = fabsf(lx), fy = fabsf(ly), fz = fabsf(lz);
+    // (the ROOM, trav_room_planes: a box with faces absent -- word 6 of the face table is the mask of those present, 63 for a box.  At a seam next
+    //  to an absent face the largest |l_k| may be the absent face's by rounding, and that one must never be named: it has no quad)
+    const uint32_t present = reinterpret_cast<const uint32_t *>(tr + 9)[6];
+    const uint32_t sx = lx > 0.0f ? 1u : 0u, sy = ly > 0.0f ? 3u : 2u, sz = lz > 0.0f ? 5u : 4u;
+    const float fx = ((present >> sx) & 1u) ? fabsf(lx) : -1.0f, fy = ((present >> sy) & 1u) ? fabsf(ly) : -1.0f, fz = ((present >> sz) & 1u) ? fabsf(lz) : -1.0f;
     const bool isz = fz >= fx && fz >= fy, isy = !isz && fy >= fx, isx = !isz && !isy;
-    const float lk = isx ? lx : isy ? ly : lz;
-    const uint32_t f = (isx ? 0u : isy ? 2u : 4u) + (lk > 0.0f ? 1u : 0u);
+    const uint32_t f = isx ? sx : isy ? sy : sz;
     const uint32_t fw = reinterpret_cast<const uint32_t *>(tr + 9)[f];
     const v4f *q = reinterpret_cast<const v4f *>(reinterpret_cast<const char *>(tr) + (fw & 0xFFFFu));
     const v4f q1 = q[1], q2 = q[2];
@@ -1189,10 +1248,20 @@ TRG_DEV bool traverse(const SceneView &sc, V3 o, V3 d, float tmax_ray, uint32_t 
     if (!UNIFIED && kShipped && sc.n_flat != 0u) return traverse_flat<ANY, COUNT>(sc, o, d, tmax_ray, rmask, hit, cnt);   // (wave-uniform: a property of the scene)
 #endif
     Trav tv;
+    const bool room = !UNIFIED && kShipped && sc.room_first1 != 0u;   // (wave-uniform: a property of the scene) the room first, then the walk over the rest
+    bool in_room = false;
+    int held = -1, start = 0;
+    if (room) {
+        float t;
+        in_room = trav_room_planes<COUNT>(sc, o - sc.center, d, tmax_ray, rmask & 3u, t, held, start, cnt);
+        tmax_ray = in_room ? t : tmax_ray;
+        asm volatile("" : "+v"(tmax_ray), "+v"(d.x), "+v"(d.y), "+v"(d.z));   // (the reciprocals of trav_begin are formed BEHIND the room test, not next to it)
+    }
     trav_begin(sc, tv, o, d, tmax_ray, rmask, stk.first(), lds_node_base<UNIFIED>(sc), !UNIFIED);
+    if (room) { tv.found = in_room; tv.hit.prim = held; tv.node = start; }
     if (UNIFIED) {
         while (tv.node != kNodeDone) trav_step_hbm<COUNT, BLOCK>(sc, tv, ANY, stk, cnt);
-    } else {
+    } else if (!(ANY && in_room)) {   // (an any-hit query that the room satisfies does not walk)
         for (;;) {
             while (tv.node >= 0) trav_node_step_signed<COUNT, BLOCK>(sc, tv, stk, cnt);
             if (tv.node == kNodeDone) break;
@@ -1214,6 +1283,7 @@ TRG_DEV bool traverse(const SceneView &sc, V3 o, V3 d, float tmax_ray, uint32_t 
 template <bool COUNT, int BLOCK, bool UNIFIED, typename STK>
 TRG_DEV void traverse_pair(const SceneView &sc, V3 org, bool has_shadow, V3 sdir, float smax, bool has_next, V3 ndir,
                            uint32_t nmask, bool &occluded, Hit &nhit, bool &nfound, STK stk, Counters &cnt) {
+    static_assert(UNIFIED, "the LDS form of the ray pair walks from node 0 and does not test a scene's room first (traverse does): HBM scenes only");
     occluded = false; nfound = false;
     nhit.t = -1.0f; nhit.prim = -1; nhit.u = 0.0f; nhit.v = 0.0f;
     int phase = has_shadow ? 0 : (has_next ? 1 : 2);

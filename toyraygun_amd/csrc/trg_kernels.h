@@ -76,6 +76,13 @@ struct SceneDesc {
     // the planes are stored relative to this point (the centre of the scene's bounding box) and a ray's origin is shifted by it when its
     // traversal begins: n . o - d0 then cancels numbers of the size of the scene instead of its distance from the coordinate origin
     float center[3];
+    // The ROOM of an LDS-resident scene (bvh_build.h RoomLeaf; shipped build): room_first1 = its first record + 1, 0 = the scene has none.  Its
+    // plane records are 3 to 5 quads X, Y, X, Y ..., and like a box leaf's the free Y slots hold the frame rows (a_k, d_k) (record first + 1) and one
+    // word per face f = 2 k + (l_k > 0): (X-record offset << 16) | its byte offset (record first + 3), then the present-face mask as word 6 (a box
+    // leaf's says 63) and walk_start as word 7, where the kernels read it.  walk_start = where the traversal continues once the room is tested: the
+    // byte offset of a node of the LDS node array, a leaf code, or 0x80000000 (the traversal's "finished" marker) for a scene that is only a room.
+    uint32_t room_first1;
+    int32_t walk_start;
 };
 constexpr uint32_t kFatRecBytes = 128u;
 #ifndef TRG_FLAT_MAX_PRIMS

@@ -82,6 +82,7 @@ TRG_DEV SceneView scene_view(const trg::SceneDesc &sc, unsigned char *smem) {
     }
     v.flat = reinterpret_cast<const v4f *>(sc.blob + sc.off_flat);
     v.n_flat = (LDS_SCENE && kShipped) ? sc.n_flat : 0u;
+    v.room_first1 = (LDS_SCENE && kShipped) ? sc.room_first1 : 0u;
     v.center = mk(sc.center[0], sc.center[1], sc.center[2]);
     v.tex.uv = nullptr; v.tex.ids = nullptr; v.tex.table = nullptr; v.tex.texels = nullptr;
     v.n_rec = sc.n_fat;
