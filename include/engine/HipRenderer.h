@@ -61,6 +61,17 @@ public:
                    const float *entryDnrm3, const uint32_t *boneIds4, const float *boneWeights4, unsigned int nBones);
     bool poseMorph(const float *targetWeights, const float *bones12);
     unsigned int getMorphCount() const { return m_morphs; }    // poseMorph calls that succeeded
+    // Rigs (include/trg_rig.h): the bones themselves made on the device, from a keyframed joint forest.  bindRig, any time after create (a rig holds
+    // no geometry and survives loadScene): joint j is bone j; parent[j] is 0xFFFFFFFF or < j; joint j's keys are the 12-float records
+    // [keyFirst[j], keyFirst[j + 1]) of keys12, {time, T | R | S, 0}; clockOf[j] < nClocks; invBind12 nJoints x 12 floats or null.  animateSkin:
+    // nClocks floats -- the rig is evaluated and the skin binding (bindSkin, as many bones as the rig has joints) is applied from its bones, which
+    // never leave the device.  animateMorph: the same for the morph binding (bound with bones), with its target weights.  The temporal hand-over
+    // is poseSkin's and poseMorph's.  A call the library refuses says so on stdout, changes nothing and arms nothing.  All return false when refused.
+    bool bindRig(const uint32_t *parent, unsigned int nJoints, const uint32_t *keyFirst, const float *keys12, const uint32_t *clockOf, unsigned int nClocks,
+                 const float *invBind12);
+    bool animateSkin(const float *clocks);
+    bool animateMorph(const float *targetWeights, const float *clocks);
+    unsigned int getRigCount() const { return m_rigs; }        // animateSkin and animateMorph calls that succeeded
     // One more sample per pixel into the running average.  ASYNCHRONOUS like the reference's (MetalRenderer.mm:373-552: encode,
     // commit, return; three frames in flight behind a semaphore, :33,377,385-387): the call never waits for the GPU to finish
     // a frame.  It takes a snapshot of the uniforms and either launches at once (GPU idle) or -- while earlier launches are
@@ -168,6 +179,7 @@ protected:
     uint32_t m_skinVerts = 0;    // the vertex count bound by bindSkin
     unsigned int m_morphs = 0;   // morphs applied
     uint32_t m_morphVerts = 0;   // the vertex count bound by bindMorph
+    unsigned int m_rigs = 0;     // rigs applied
     void afterPose(int (*buffers)(trg_ctx *, void **, void **, void **, void **, void **), uint32_t nVerts);   // the history follows an apply
 };
 

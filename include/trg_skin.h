@@ -29,7 +29,7 @@
  * The arithmetic, operation by operation, is toyraygun_amd/csrc/trg_skin_math.h.  Equal inputs give equal outputs: the copies of a shared corner
  * stay bitwise equal.  A vertex with weights (1, 0, 0, 0) gets values equal under == to trg_pose_apply's with that bone as its object's matrix.
  *
- * Out of scope: dual-quaternion blending; more than four bones per vertex; bones that live on the device; blend shapes (trg_morph.h has them, in front of this skin); changed topology; the
+ * Out of scope: dual-quaternion blending; more than four bones per vertex; bones that live on the device (trg_rig.h has them: a keyframed joint forest, or the caller's device memory); blend shapes (trg_morph.h has them, in front of this skin); changed topology; the
  * 8-wide experiments build, which refuses these calls.
  */
 #ifndef TRG_SKIN_H

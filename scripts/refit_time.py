@@ -1,6 +1,6 @@
 """Update time and render time of a refitted scene against a reloaded one (include/trg_refit.h).
 
-    python scripts/refit_time.py [--n 44] [--reps 5] [--w 1024 --h 768 --spp 4] [--legs refit,pose,skin,morph] [--parent-so FILE] [--out FILE]
+    python scripts/refit_time.py [--n 44] [--reps 5] [--w 1024 --h 768 --spp 4] [--legs refit,pose,skin,morph,rig] [--parent-so FILE] [--out FILE]
 
 The Cornell box + n^3 cubes (n = 44: 1,022,244 triangles, n = 96: 10,616,868).  In ONE process, alternating, medians over `reps`:
 
@@ -31,6 +31,13 @@ medians over `reps`, each call followed by a wait, both libraries straight throu
 same morphed geometry; with --parent-so that library's trg_refit_scene -- what a caller with blend shapes pays today, before the CPU morph itself.
 rf_morph_kernel's own time: the same kernel-trace run, with --legs morph.
 
+The rig leg (include/trg_rig.h; device builder): the skin leg's binding, and a rig of one five-joint chain per five bones (n = 44: 17,037 chains,
+85,185 joints), two keys per joint, one clock per chain, no inverse binds; two clock vectors alternate.  Alternating, medians over `reps`, each call
+followed by a wait, both libraries straight through ctypes: trg_rig_skin_apply; trg_rig_skin_apply_device from a torch tensor of the same bones;
+this library's trg_skin_apply and -- with --parent-so -- the parent's, given those bones PRECOMPUTED on the host: what a caller pays today, not
+counting the CPU evaluation of the skeleton.  rig_skin_apply_not_slower_than_parent_skin_apply compares the medians.  rf_rig_level_kernel's own
+time: the same kernel-trace run, with --legs rig.
+
 Every apply and every trg_refit_scene is called straight through ctypes, as the parent's are (the wrappers' argument checks cost about 10 us, the
 size of the differences looked for; the skin leg times refit.py's wrapper beside them).  With --parent-so every leg
 also binds the same data on the parent library, when it exports the leg's symbols, and times ITS trg_{pose,skin,morph}_apply in the same alternation:
@@ -47,7 +54,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from toyraygun_amd import capi, host, morph, pose, refit, skin  # noqa: E402
+from toyraygun_amd import capi, host, morph, pose, refit, rig, skin  # noqa: E402
 
 
 def parent_context(path, w, h, pos, nrm, col, idx, mat):
@@ -313,6 +320,54 @@ def main():
             morph.release(c)
             skin.release(c)
             res["morph"] = r
+        if "rig" in a.legs.split(","):
+            import torch
+            GL = rig.load()
+            assert n_bones % 5 == 0
+            n_chains = n_bones // 5
+            j = np.arange(n_bones)
+            par = np.where(j % 5 == 0, rig.NO_PARENT, j - 1).astype(np.uint32)
+            keys = np.zeros((2 * n_bones, 12), np.float32)
+            keys[:, 7] = 1.0                                                # no rotation
+            keys[:, 8:11] = 1.0
+            keys[1::2, 0] = 1.0                                             # key 0 at time 0: rest; key 1 at time 1: a small translation per joint
+            keys[1::2, 1:4] = rng.integers(-4, 5, (n_bones, 3)).astype(np.float32) * np.float32(2.0 ** -11)
+            kfirst = (2 * np.arange(n_bones + 1)).astype(np.uint32)
+            clock_of = (j // 5).astype(np.uint32)
+            clocks = [np.full(n_chains, 1.0, np.float32), np.linspace(0.25, 0.75, n_chains).astype(np.float32)]
+            bones = [rig.rig_reference(par, kfirst, keys, clock_of, t)[0] for t in clocks]     # the caller's CPU evaluation, outside every timing
+            load(1, pos0)
+            skin.bind(c, pos0, nrm, idx, ids, wts, n_bones)
+            rig.bind(c, par, kfirst, keys, clock_of, n_chains)
+            rig.skin_apply(c, clocks[0])
+            got = rig.read(c)[0], skin.read(c)[0]
+            assert np.array_equal(got[0].view(np.uint32), bones[0].view(np.uint32))
+            skin.apply(c, bones[0])
+            assert np.array_equal(skin.read(c)[0].view(np.uint32), got[1].view(np.uint32))     # the same skinned geometry either way
+            tensors = [torch.from_numpy(x).cuda() for x in bones]
+            torch.cuda.synchronize()
+            parent = parent_context(a.parent_so, a.w, a.h, pos0, nrm, col, idx, mat) if a.parent_so else None
+            calls = {"rig_skin_apply": lambda k: raw(GL, c.h_ctx, "trg_rig_skin_apply", clocks[k % 2]),
+                     "rig_skin_apply_device": lambda k: raw(GL, c.h_ctx, "trg_rig_skin_apply_device", tensors[k % 2].data_ptr()),
+                     "skin_apply": lambda k: raw(SL, c.h_ctx, "trg_skin_apply", bones[k % 2])}
+            if parent:
+                raw(parent[0], parent[1], "trg_skin_bind", pos0, nrm, idx, nv, nt, ids, wts, n_bones)
+                calls["parent_skin_apply"] = lambda k: raw(parent[0], parent[1], "trg_skin_apply", bones[k % 2])
+            t = alternate(calls, a.reps, timed)
+            r = medians(t)
+            r.update({"joints": int(n_bones), "chains": int(n_chains), "levels": 5, "keys": int(keys.shape[0]), "vertices": int(nv)})
+            r["upload_bytes"] = {"rig_skin_apply": int(4 * n_chains), "rig_skin_apply_device": 0, "skin_apply": int(48 * n_bones)}
+            # what rf_rig_level_kernel moves per joint: order, clock id, two key-range words, two 48-byte keys, world and bone rows out -- and from
+            # level 1 on the parent's id and its world rows (the clocks come from cache; there are no inverse binds here)
+            r["kernel_moved_bytes"] = int((4 + 4 + 8 + 96 + 96) * n_bones + (4 + 48) * (n_bones - n_chains))
+            r["evaluation_on_top_of_the_device_form_ms"] = r["rig_skin_apply_ms"] - r["rig_skin_apply_device_ms"]
+            if parent:
+                r["rig_skin_apply_not_slower_than_parent_skin_apply"] = bool(r["rig_skin_apply_ms"] <= r["parent_skin_apply_ms"])
+                r["skin_apply_within_parent_spread"] = within_spread(t, "skin_apply", "parent_skin_apply")
+                parent[0].trg_destroy(parent[1])
+            rig.release(c)
+            skin.release(c)
+            res["rig"] = r
     finally:
         refit.release(c)
         c.close()

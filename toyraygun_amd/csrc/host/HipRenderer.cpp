@@ -12,6 +12,7 @@
 #include "trg_denoise.h"
 #include "trg_morph.h"
 #include "trg_pose.h"
+#include "trg_rig.h"
 #include "trg_skin.h"
 #include "trg_refit.h"
 
@@ -326,6 +327,46 @@ bool HipRenderer::poseMorph(const float *targetWeights, const float *bones12) {
         return false;
     }
     ++m_morphs;
+    afterPose(trg_morph_buffers, m_morphVerts);
+    return true;
+}
+
+bool HipRenderer::bindRig(const uint32_t *parent, unsigned int nJoints, const uint32_t *keyFirst, const float *keys12, const uint32_t *clockOf, unsigned int nClocks,
+                          const float *invBind12) {
+    if (!m_ctx || !parent || !keyFirst || !keys12 || !clockOf || !nJoints) return false;
+    flush();
+    const char *text = "";
+    const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) { return trg_rig_bind(c, parent, nJoints, keyFirst, keys12, keyFirst[nJoints], clockOf, nClocks, invBind12); }, &text);
+    if (rc != TRG_OK) { printf("HipRenderer: rig not bound (%s)\n", text); fflush(stdout); }
+    return rc == TRG_OK;
+}
+
+bool HipRenderer::animateSkin(const float *clocks) {
+    if (!m_ctx || !m_sceneLoaded || !clocks) return false;
+    flush();   // frames queued so far are rendered with the pose they were queued under
+    const char *text = "";
+    const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) { return trg_rig_skin_apply(c, clocks); }, &text);
+    if (rc != TRG_OK) {
+        printf("HipRenderer: rig refused (%s); nothing changed\n", text);
+        fflush(stdout);
+        return false;
+    }
+    ++m_rigs;
+    afterPose(trg_skin_buffers, m_skinVerts);
+    return true;
+}
+
+bool HipRenderer::animateMorph(const float *targetWeights, const float *clocks) {
+    if (!m_ctx || !m_sceneLoaded || !targetWeights || !clocks) return false;
+    flush();   // frames queued so far are rendered with the pose they were queued under
+    const char *text = "";
+    const int rc = poseEach(m_group, m_ctx, [&](trg_ctx *c) { return trg_rig_morph_apply(c, targetWeights, clocks); }, &text);
+    if (rc != TRG_OK) {
+        printf("HipRenderer: rig refused (%s); nothing changed\n", text);
+        fflush(stdout);
+        return false;
+    }
+    ++m_rigs;
     afterPose(trg_morph_buffers, m_morphVerts);
     return true;
 }

@@ -1,6 +1,6 @@
 // main_cornell.cpp -- headless demo following the reference app's call order (reference src/main.cpp:16-98):
 // engine init -> three shaders -> renderer init -> camera -> Cornell box -> frame loop; then writes a PNG.
-//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [twist=DEG] [bulge=W] [refit|pose|skin|morph]]
+//   toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [twist=DEG] [bulge=W] [bend=DEG] [refit|pose|skin|morph|rig]]
 //     denoise=N    a-trous iterations of the written image, 0 = off (default)
 //     ,var         the variance-guided filter from two half-sample buffers
 //     ,temporal    the frames are rendered as `frames` calls of 1 spp, each a temporal step (reprojected history, temporal variance); the
@@ -28,6 +28,14 @@
 //                  axis -- and, with twist=DEG, with the two bones of the skin option behind it.  Before call k the target gets the weight k * W
 //                  and bone 1 turns by k * DEG degrees (HipRenderer::poseMorph, include/trg_morph.h): the top of the box bulges, and twists.
 //                  bulge=0 without a twist applies nothing.  The last line of output counts the morphs applied
+//     rig          (with bend=DEG; not with refit, pose, skin or morph) the short box is bound to a chain of three joints up its vertical axis -- at
+//                  its foot, half way up and at its top, each the child of the one below; a corner leans on joint k by max(0, 1 - |2 h - k|), h
+//                  its height within the box -- and everything else to a fourth joint that rests (HipRenderer::bindSkin, four bones).  The clip
+//                  (HipRenderer::bindRig, include/trg_rig.h) has two keys per chain joint: rest at time 0, and at time 1 every joint turned by
+//                  DEG x (calls - 1) degrees about the x axis through its origin.  Before call k the clock is k / (calls - 1)
+//                  (HipRenderer::animateSkin): 4 bytes go to the device and the box bends over.  bend=0 applies nothing.  Not with slide=D: a
+//                  slid box is a reloaded scene, and the skin binding would be stale.  The last line of output
+//                  counts the rigs applied
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -76,9 +84,9 @@ int main(int argc, char **argv) {
     int denoise = 0;
     bool denoiseVar = false, denoiseTemporal = false, varianceOfMean = false;
     double orbit = 0.0, slide = 0.0, lagGate = -1.0, coverMin = -1.0;
-    double twist = 0.0, bulge = 0.0;
-    bool refit = false, pose = false, skin = false, morph = false;
-    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [twist=DEG] [bulge=W] [refit|pose|skin|morph]]";
+    double twist = 0.0, bulge = 0.0, bend = 0.0;
+    bool refit = false, pose = false, skin = false, morph = false, rig = false;
+    const char *usage = "usage: toyraygun_cornell [width height frames bounces out.png [denoise=N[,var|,temporal[,lag[=G]][,vmean][,cover[=C]]]] [orbit=DEG] [slide=D] [twist=DEG] [bulge=W] [bend=DEG] [refit|pose|skin|morph|rig]]";
     for (int a = 6; a < argc; ++a) {
         if (strncmp(argv[a], "slide=", 6) == 0) {
             char *end = nullptr;
@@ -90,6 +98,13 @@ int main(int argc, char **argv) {
         if (strcmp(argv[a], "pose") == 0) { pose = true; continue; }
         if (strcmp(argv[a], "skin") == 0) { skin = true; continue; }
         if (strcmp(argv[a], "morph") == 0) { morph = true; continue; }
+        if (strcmp(argv[a], "rig") == 0) { rig = true; continue; }
+        if (strncmp(argv[a], "bend=", 5) == 0) {
+            char *end = nullptr;
+            bend = strtod(argv[a] + 5, &end);
+            if (end == argv[a] + 5 || *end != 0) { std::cout << usage << std::endl; return -1; }
+            continue;
+        }
         if (strncmp(argv[a], "bulge=", 6) == 0) {
             char *end = nullptr;
             bulge = strtod(argv[a] + 6, &end);
@@ -144,7 +159,7 @@ int main(int argc, char **argv) {
         }
     }
 
-    if ((pose && refit) || (skin && (pose || refit)) || (morph && (pose || refit || skin))) { std::cout << usage << std::endl; return -1; }
+    if ((pose && refit) || (skin && (pose || refit)) || (morph && (pose || refit || skin)) || (rig && (pose || refit || skin || morph || slide != 0.0))) { std::cout << usage << std::endl; return -1; }
 
     Engine *engine = Engine::instance();
     engine->init(width, height);
@@ -219,6 +234,46 @@ int main(int argc, char **argv) {
             }
         }
     }
+    // rig: joints 0, 1, 2 up the short box's vertical axis, joint 3 at rest for everything else; two keys per chain joint
+    if (rig) {
+        const size_t nVerts = scene->m_vertexBuffer.size();
+        if (nVerts < 36) { std::cout << "the rig was refused" << std::endl; return -1; }
+        double lo = scene->m_vertexBuffer[0].y, hi = lo, x0 = scene->m_vertexBuffer[0].x, x1 = x0, z0 = scene->m_vertexBuffer[0].z, z1 = z0;
+        for (size_t v = 0; v < 36; ++v) {
+            lo = fmin(lo, (double)scene->m_vertexBuffer[v].y); hi = fmax(hi, (double)scene->m_vertexBuffer[v].y);
+            x0 = fmin(x0, (double)scene->m_vertexBuffer[v].x); x1 = fmax(x1, (double)scene->m_vertexBuffer[v].x);
+            z0 = fmin(z0, (double)scene->m_vertexBuffer[v].z); z1 = fmax(z1, (double)scene->m_vertexBuffer[v].z);
+        }
+        double origin[4][3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };
+        for (int k = 0; k < 3; ++k) { origin[k][0] = (x0 + x1) / 2; origin[k][1] = lo + (hi - lo) * (double)k / 2; origin[k][2] = (z0 + z1) / 2; }
+        std::vector<uint32_t> ids(nVerts * 4);
+        std::vector<float> weights(nVerts * 4, 0.0f);
+        for (size_t v = 0; v < nVerts; ++v) {
+            for (uint32_t k = 0; k < 4; ++k) ids[v * 4 + k] = k;
+            if (v >= 36 || !(hi > lo)) { weights[v * 4 + 3] = 1.0f; continue; }
+            const double h = ((double)scene->m_vertexBuffer[v].y - lo) / (hi - lo);
+            for (int k = 0; k < 3; ++k) weights[v * 4 + k] = (float)fmax(0.0, 1.0 - fabs(2.0 * h - (double)k));
+        }
+        const double a = bend * (double)(frames - 1) * 3.14159265358979323846 / 180.0;
+        const uint32_t parent[4] = { 0xFFFFFFFFu, 0u, 1u, 0xFFFFFFFFu }, keyFirst[5] = { 0u, 2u, 4u, 6u, 7u }, clockOf[4] = { 0u, 0u, 0u, 0u };
+        float keys[7 * 12] = { 0 }, invBind[4 * 12] = { 0 };
+        for (int k = 0; k < 4; ++k) {
+            for (int i = 0; i < (k < 3 ? 2 : 1); ++i) {
+                float *key = keys + (keyFirst[k] + i) * 12;
+                key[0] = (float)i;
+                for (int e = 0; e < 3; ++e) key[1 + e] = k < 3 ? (float)(origin[k][e] - (k ? origin[k - 1][e] : 0.0)) : 0.0f;
+                key[4] = i ? (float)sin(a / 2) : 0.0f;
+                key[7] = i ? (float)cos(a / 2) : 1.0f;
+                key[8] = key[9] = key[10] = 1.0f;
+            }
+            invBind[k * 12] = invBind[k * 12 + 5] = invBind[k * 12 + 10] = 1.0f;
+            for (int e = 0; e < 3; ++e) invBind[k * 12 + 4 * e + 3] = (float)-origin[k][e];
+        }
+        if (!hip->bindSkin(scene, ids.data(), weights.data(), 4) || !hip->bindRig(parent, 4, keyFirst, keys, clockOf, 1, invBind)) {
+            std::cout << "the rig was refused" << std::endl;
+            return -1;
+        }
+    }
     const bx::Vec3 eye0(0.0f, 1.0f, 3.38f), at(0.0f, 1.0f, -1.0f);
     int call = 0;
     while (!engine->hasQuit()) {
@@ -238,6 +293,9 @@ int main(int argc, char **argv) {
             const float weight = (float)call * (float)bulge;
             if (skin) hip->poseSkin(bones);
             else hip->poseMorph(&weight, twist != 0.0 ? bones : nullptr);
+        } else if (rig && bend != 0.0 && call > 0 && frames > 1) {
+            const float clock = (float)((double)call / (double)(frames - 1));
+            hip->animateSkin(&clock);
         } else if (pose && slide != 0.0 && call > 0) {
             float x[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
             x[3] = (float)((double)call * slide);
@@ -257,5 +315,6 @@ int main(int argc, char **argv) {
     if (pose) printf("%u poses applied\n", hip->getPoseCount());
     if (skin) printf("%u skins applied\n", hip->getSkinCount());
     if (morph) printf("%u morphs applied\n", hip->getMorphCount());
+    if (rig) printf("%u rigs applied\n", hip->getRigCount());
     return 0;
 }

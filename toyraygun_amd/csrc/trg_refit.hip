@@ -4,6 +4,7 @@
 // refit_device and the context's RefitState -- the same refit from buffers already on the device, and the per-object poses that feed it
 // (arithmetic: trg_pose_math.h).  So does include/trg_skin.h: blended bone matrices per vertex in front of the same refit (trg_skin_math.h).
 // And include/trg_morph.h: blend shapes in front of that skin (trg_morph_math.h).  The three keep one binding protocol: RefitState::Binding.
+// And include/trg_rig.h: a keyframed joint forest evaluated into the bones those two read (trg_rig_math.h) -- RefitState::Rig, which is no Binding.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -17,6 +18,7 @@
 #include "../../include/trg_pose.h"
 #include "../../include/trg_skin.h"
 #include "../../include/trg_refit.h"
+#include "../../include/trg_rig.h"
 #include "trg_ctx.h"
 #include "trg_internal.h"
 #include "trg_kernels.h"
@@ -24,6 +26,7 @@
 #include "trg_pose_math.h"
 #include "trg_skin_math.h"
 #include "trg_refit_math.h"
+#include "trg_rig_math.h"
 
 using namespace trg;
 
@@ -420,6 +423,52 @@ __global__ void rf_morph_kernel(const float *rest_pos, const uint32_t *vfirst, c
     for (int j = 0; j < 3; ++j) nrm_out[(size_t)k * 3 + j] = q[j];
 }
 
+// ---- include/trg_rig.h: one launch per LEVEL of the joint forest, one thread per joint of that level, reached through `order` (the level table of
+//      trg_rig_math.h).  A thread finds its key pair (the search reads only the times), loads the two records as three 16-byte rows each, samples,
+//      builds its local matrix, reads its parent's world rows -- which the launch BEFORE this one wrote: no thread ever waits on another thread's
+//      store, the order between levels is the stream's --, composes, writes its world rows, composes with its inverse bind and writes its bone rows.
+//      kRoot: the level is level 0 and nobody has a parent; kInv: there are inverse binds.  No LDS, no atomics, no grid stride ----
+__device__ inline void rf_rows_get(const float4 *src, float *m) {
+    const float4 r0 = src[0], r1 = src[1], r2 = src[2];
+    m[0] = r0.x; m[1] = r0.y; m[2] = r0.z; m[3] = r0.w; m[4] = r1.x; m[5] = r1.y; m[6] = r1.z; m[7] = r1.w; m[8] = r2.x; m[9] = r2.y; m[10] = r2.z; m[11] = r2.w;
+}
+__device__ inline void rf_rows_put(float4 *dst, const float *m) {
+    dst[0] = make_float4(m[0], m[1], m[2], m[3]);
+    dst[1] = make_float4(m[4], m[5], m[6], m[7]);
+    dst[2] = make_float4(m[8], m[9], m[10], m[11]);
+}
+template <bool kRoot, bool kInv>
+__global__ void rf_rig_level_kernel(const uint32_t *order, uint32_t first, uint32_t count, const uint32_t *parent, const uint32_t *kfirst, const float4 *keys,
+                                    const uint32_t *clock_of, const float *clocks, const float4 *inv_bind, float4 *world, float4 *bones) {
+    const uint32_t k = blockIdx.x * kT + threadIdx.x;
+    if (k >= count) return;
+    const uint32_t j = order[first + k];
+    const float t = clocks[clock_of[j]];
+    uint32_t ia, ib;
+    rig::key_pair(reinterpret_cast<const float *>(keys), kfirst[j], kfirst[j + 1] - 1u, t, &ia, &ib);
+    float ka[12], kb[12], T[3], R[4], S[3], L[12], W[12];
+    rf_rows_get(keys + (size_t)ia * 3, ka);
+    rf_rows_get(keys + (size_t)ib * 3, kb);
+    rig::sample(ka, kb, ia == ib, t, T, R, S);
+    rig::local(T, R, S, L);
+    if (kRoot) {
+        for (int e = 0; e < 12; ++e) W[e] = L[e];
+    } else {
+        float P[12];
+        rf_rows_get(world + (size_t)parent[j] * 3, P);
+        rig::compose(P, L, W);
+    }
+    rf_rows_put(world + (size_t)j * 3, W);
+    if (kInv) {
+        float I[12], B[12];
+        rf_rows_get(inv_bind + (size_t)j * 3, I);
+        rig::compose(W, I, B);
+        rf_rows_put(bones + (size_t)j * 3, B);
+    } else {
+        rf_rows_put(bones + (size_t)j * 3, W);
+    }
+}
+
 // ---- per-context scratch (grow-only): trg_ctx::refit, created on first use, freed by refit_state_free ----
 struct Buf {
     void *p = nullptr;
@@ -486,6 +535,16 @@ struct trg::RefitState {
         bool has_dnrm = false, has_bones = false;
         template <typename F> void each_own(F f) { for (Buf *b : { &vfirst, &pos_recs, &nrm_recs, &tw, &ids, &weights, &bones }) f(*b); }
     } morph;
+    // include/trg_rig.h.  NOT a Binding: it holds no geometry, knows no scene and survives trg_load_scene.  keys are 48-byte records, world and bones
+    // 48 bytes per joint (hipMalloc aligns them far beyond the 16 bytes their float4 rows need); the level table stays on the host, which launches
+    // level by level.  evaluated: world and bones hold an evaluation
+    struct Rig {
+        Buf parent, order, keys, kfirst, clock_of, inv_bind, clocks, world, bones;
+        uint32_t n_joints = 0, n_keys = 0, n_clocks = 0, n_levels = 0;
+        uint32_t level_first[rig::kMaxLevels + 1] = {};
+        bool bound = false, has_inv = false, evaluated = false;
+        template <typename F> void each_own(F f) { for (Buf *b : { &parent, &order, &keys, &kfirst, &clock_of, &inv_bind, &clocks, &world, &bones }) f(*b); }
+    } rig;
 };
 
 namespace {
@@ -501,6 +560,7 @@ void each_buffer(RefitState &s, F f) {
     each_binding_buffer(s.pose, f);
     each_binding_buffer(s.skin, f);
     each_binding_buffer(s.morph, f);
+    s.rig.each_own(f);
 }
 int grow(trg_ctx *c, Buf &b, size_t need, const char *what) {
     if (need <= b.bytes && b.p) return TRG_OK;
@@ -693,23 +753,23 @@ int refit_arguments(trg_ctx *c, const void *positions3, const void *indices, uin
 
 // ---- include/trg_pose.h: trg_refit_scene_device ----
 // `need` bytes from p on: device memory of the context's device, by the runtime's own records; nothing is enqueued
-int device_span(trg_ctx *c, const void *p, size_t need, const char *what) {
+int device_span(trg_ctx *c, const void *p, size_t need, const char *what, const char *who = "trg_refit_scene_device") {
     hipPointerAttribute_t attr{};
     if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(c, TRG_ERR_INVALID, "trg_refit_scene_device: %s: %p is not memory the device runtime knows", what, p);
+        return fail(c, TRG_ERR_INVALID, "%s: %s: %p is not memory the device runtime knows", who, what, p);
     }
     if (attr.type != hipMemoryTypeDevice || attr.device != c->device)
-        return fail(c, TRG_ERR_INVALID, "trg_refit_scene_device: %s: %p is not device memory of device %d", what, p, c->device);
+        return fail(c, TRG_ERR_INVALID, "%s: %s: %p is not device memory of device %d", who, what, p, c->device);
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
     if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess || !base) {
         (void)hipGetLastError();
-        return fail(c, TRG_ERR_INVALID, "trg_refit_scene_device: %s: no allocation holds %p", what, p);
+        return fail(c, TRG_ERR_INVALID, "%s: %s: no allocation holds %p", who, what, p);
     }
     const size_t at = (size_t)(static_cast<const char *>(p) - static_cast<const char *>(base));
     if (at > size || size - at < need)
-        return fail(c, TRG_ERR_INVALID, "trg_refit_scene_device: %s: the allocation holds %zu bytes from %p on, the call reads %zu", what, at > size ? (size_t)0 : size - at, p, need);
+        return fail(c, TRG_ERR_INVALID, "%s: %s: the allocation holds %zu bytes from %p on, the call reads %zu", who, what, at > size ? (size_t)0 : size - at, p, need);
     return TRG_OK;
 }
 
@@ -882,6 +942,94 @@ int morph_launch(trg_ctx *c, RefitState::Morph &m, uint32_t blocks, float *pos_o
     return TRG_OK;
 }
 
+// ---- the second half of an apply of the skin and the morph unit: the binding's `bones` buffer (and the morph's weights) hold this call's values
+//      -- uploaded by trg_skin_apply / trg_morph_apply, copied device to device by include/trg_rig.h's calls --; launch, refit, rotate ----
+int skin_run(trg_ctx *c, RefitState::Skin &p) {
+    RF_LAUNCH(c, rf_skin_kernel, dim3(p.blocks(p.has_nrm)), p.rest_pos.as<float>(), p.ids.as<uint4>(), p.weights.as<float4>(), p.n_verts, p.rest_nrm.as<float>(),
+              p.idx.as<uint32_t>(), p.n_tris * 3u, p.bones.as<float4>(), p.pos_of(p.spare()), p.nrm_of(p.spare()));
+    return apply_finish(c, p);
+}
+int morph_run(trg_ctx *c, RefitState::Morph &m) {
+    float *pos_out = m.pos_of(m.spare()), *nrm_out = m.nrm_of(m.spare());
+    // no corner can change without normal deltas and without bones: that copy holds the rest normals since bind, and the range is left out
+    const uint32_t blocks = m.blocks(m.has_nrm && (m.has_dnrm || m.has_bones));
+    int rc = TRG_OK;
+    if (m.has_bones) rc = m.has_dnrm ? morph_launch<true, true>(c, m, blocks, pos_out, nrm_out) : morph_launch<true, false>(c, m, blocks, pos_out, nrm_out);
+    else rc = m.has_dnrm ? morph_launch<false, true>(c, m, blocks, pos_out, nrm_out) : morph_launch<false, false>(c, m, blocks, pos_out, nrm_out);
+    if (rc) return rc;
+    return apply_finish(c, m);
+}
+// what trg_morph_apply checks of its weights
+int morph_weights(trg_ctx *c, const char *who, const RefitState::Morph &m, const float *target_weights) {
+    if (!target_weights) return fail(c, TRG_ERR_INVALID, "%s: null target weights", who);
+    for (uint32_t k = 0; k < m.n_targets; ++k)
+        if (!std::isfinite(target_weights[k])) return fail(c, TRG_ERR_INVALID, "%s: the weight of target %u is not finite", who, k);
+    return TRG_OK;
+}
+
+// ---- include/trg_rig.h ----
+// the context's rig, or why there is none to use
+int rig_of(trg_ctx *c, const char *who, RefitState::Rig **out) {
+    if (!c) return TRG_ERR_INVALID;
+#if TRG_WIDE8
+    return fail(c, TRG_ERR_INVALID, "%s: an 8-wide experiments build has no rigs", who);
+#endif
+    if (!c->refit || !c->refit->rig.bound) return fail(c, TRG_ERR_INVALID, "%s: no rig bound (trg_rig_bind first)", who);
+    RF_HIPCHK(c, hipSetDevice(c->device));
+    *out = &c->refit->rig;
+    return TRG_OK;
+}
+int clocks_finite(trg_ctx *c, const char *who, const RefitState::Rig &r, const float *clocks) {
+    if (!clocks) return fail(c, TRG_ERR_INVALID, "%s: null clocks", who);
+    for (uint32_t k = 0; k < r.n_clocks; ++k)
+        if (!std::isfinite(clocks[k])) return fail(c, TRG_ERR_INVALID, "%s: clock %u is not finite", who, k);
+    return TRG_OK;
+}
+template <bool kRoot>
+int rig_level(trg_ctx *c, RefitState::Rig &r, uint32_t first, uint32_t count) {
+    if (r.has_inv)
+        RF_LAUNCH(c, (rf_rig_level_kernel<kRoot, true>), blocks_for(count), r.order.as<uint32_t>(), first, count, r.parent.as<uint32_t>(), r.kfirst.as<uint32_t>(),
+                  r.keys.as<float4>(), r.clock_of.as<uint32_t>(), r.clocks.as<float>(), r.inv_bind.as<float4>(), r.world.as<float4>(), r.bones.as<float4>());
+    else
+        RF_LAUNCH(c, (rf_rig_level_kernel<kRoot, false>), blocks_for(count), r.order.as<uint32_t>(), first, count, r.parent.as<uint32_t>(), r.kfirst.as<uint32_t>(),
+                  r.keys.as<float4>(), r.clock_of.as<uint32_t>(), r.clocks.as<float>(), nullptr, r.world.as<float4>(), r.bones.as<float4>());
+    return TRG_OK;
+}
+// the clocks (checked by the caller) to the device and one launch per level, enqueued; nobody waits
+int rig_evaluate(trg_ctx *c, RefitState::Rig &r, const float *clocks) {
+    RF_HIPCHK(c, hipMemcpyAsync(r.clocks.p, clocks, (size_t)r.n_clocks * 4, hipMemcpyHostToDevice, c->stream));
+    for (uint32_t l = 0; l < r.n_levels; ++l) {
+        const uint32_t first = r.level_first[l], count = r.level_first[l + 1] - first;
+        if (int rc = l == 0 ? rig_level<true>(c, r, first, count) : rig_level<false>(c, r, first, count)) return rc;
+    }
+    r.evaluated = true;
+    return TRG_OK;
+}
+// the rig and the binding of an apply from the rig's bones: both bound, the binding's scene still loaded, as many joints as bones
+template <typename B>
+int rig_target(trg_ctx *c, const char *who, B RefitState::*unit, const char *bind_name, RefitState::Rig **r, B **b) {
+    int rc = TRG_OK;
+    if ((rc = rig_of(c, who, r)) || (rc = binding_of(c, who, unit, bind_name, b))) return rc;
+    return TRG_OK;
+}
+int rig_counts(trg_ctx *c, const char *who, const RefitState::Rig &r, uint32_t n_bones) {
+    if (r.n_joints != n_bones) return fail(c, TRG_ERR_INVALID, "%s: the rig has %u joints, the binding %u bones (joint j is bone j)", who, r.n_joints, n_bones);
+    return TRG_OK;
+}
+int morph_has_bones(trg_ctx *c, const char *who, const RefitState::Morph &m) {
+    if (!m.has_bones) return fail(c, TRG_ERR_INVALID, "%s: the morph binding has no bones (trg_morph_bind with bone ids and weights)", who);
+    return TRG_OK;
+}
+// the 8-wide refusal and the binding of the _device forms, which need no rig
+template <typename B>
+int device_target(trg_ctx *c, const char *who, B RefitState::*unit, const char *bind_name, B **b) {
+    if (!c) return TRG_ERR_INVALID;
+#if TRG_WIDE8
+    return fail(c, TRG_ERR_INVALID, "%s: an 8-wide experiments build has no rigs", who);
+#endif
+    return binding_of(c, who, unit, bind_name, b);
+}
+
 }  // namespace
 
 void trg::refit_state_free(trg_ctx *c) {
@@ -1012,9 +1160,7 @@ int trg_skin_apply(trg_ctx *c, const float *bones12) {
     if (!bones12) return fail(c, TRG_ERR_INVALID, "trg_skin_apply: null bones");
     if (int rc = bones_finite(c, "trg_skin_apply", bones12, p.n_bones)) return rc;
     RF_HIPCHK(c, hipMemcpyAsync(p.bones.p, bones12, (size_t)p.n_bones * 48, hipMemcpyHostToDevice, c->stream));
-    RF_LAUNCH(c, rf_skin_kernel, dim3(p.blocks(p.has_nrm)), p.rest_pos.as<float>(), p.ids.as<uint4>(), p.weights.as<float4>(), p.n_verts, p.rest_nrm.as<float>(),
-              p.idx.as<uint32_t>(), p.n_tris * 3u, p.bones.as<float4>(), p.pos_of(p.spare()), p.nrm_of(p.spare()));
-    return apply_finish(c, p);
+    return skin_run(c, p);
 }
 
 int trg_skin_read(trg_ctx *c, float *positions3_host, float *normals3_host) {
@@ -1099,22 +1245,13 @@ int trg_morph_apply(trg_ctx *c, const float *target_weights, const float *bones1
     RefitState::Morph *mp = nullptr;
     if (int rc = binding_of(c, "trg_morph_apply", &RefitState::morph, "trg_morph_bind", &mp)) return rc;
     RefitState::Morph &m = *mp;
-    if (!target_weights) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: null target weights");
-    for (uint32_t k = 0; k < m.n_targets; ++k)
-        if (!std::isfinite(target_weights[k])) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: the weight of target %u is not finite", k);
+    if (int rc = morph_weights(c, "trg_morph_apply", m, target_weights)) return rc;
     if (m.has_bones && !bones12) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: null bones, the binding has %u", m.n_bones);
     if (!m.has_bones && bones12) return fail(c, TRG_ERR_INVALID, "trg_morph_apply: bones given, the binding has none");
     if (int rc = bones_finite(c, "trg_morph_apply", bones12, m.n_bones)) return rc;
-    float *pos_out = m.pos_of(m.spare()), *nrm_out = m.nrm_of(m.spare());
     RF_HIPCHK(c, hipMemcpyAsync(m.tw.p, target_weights, (size_t)m.n_targets * 4, hipMemcpyHostToDevice, c->stream));
     if (m.has_bones) RF_HIPCHK(c, hipMemcpyAsync(m.bones.p, bones12, (size_t)m.n_bones * 48, hipMemcpyHostToDevice, c->stream));
-    // no corner can change without normal deltas and without bones: that copy holds the rest normals since bind, and the range is left out
-    const uint32_t blocks = m.blocks(m.has_nrm && (m.has_dnrm || m.has_bones));
-    int rc = TRG_OK;
-    if (m.has_bones) rc = m.has_dnrm ? morph_launch<true, true>(c, m, blocks, pos_out, nrm_out) : morph_launch<true, false>(c, m, blocks, pos_out, nrm_out);
-    else rc = m.has_dnrm ? morph_launch<false, true>(c, m, blocks, pos_out, nrm_out) : morph_launch<false, false>(c, m, blocks, pos_out, nrm_out);
-    if (rc) return rc;
-    return apply_finish(c, m);
+    return morph_run(c, m);
 }
 
 int trg_morph_read(trg_ctx *c, float *positions3_host, float *normals3_host) {
@@ -1137,6 +1274,154 @@ int trg_group_morph_bind(trg_group *g, const float *positions3, const float *nor
 
 int trg_group_morph_apply(trg_group *g, const float *target_weights, const float *bones12) {
     return group_each(g, [&](trg_ctx *c) { return trg_morph_apply(c, target_weights, bones12); });
+}
+
+int trg_rig_bind(trg_ctx *c, const uint32_t *parent, uint32_t n_joints, const uint32_t *key_first, const float *keys12, uint32_t n_keys, const uint32_t *clock_of,
+                 uint32_t n_clocks, const float *inv_bind12) {
+    if (!c) return TRG_ERR_INVALID;
+#if TRG_WIDE8
+    return fail(c, TRG_ERR_INVALID, "trg_rig_bind: an 8-wide experiments build has no rigs");
+#endif
+    uint32_t j = 0, k = 0;
+    const bool counts = n_joints != 0 && n_keys != 0 && n_clocks != 0;
+    if (counts && (!parent || !key_first || !keys12 || !clock_of)) return fail(c, TRG_ERR_INVALID, "trg_rig_bind: null table");
+    const int what = !counts ? (int)rig::kRigCounts : rig::check(parent, n_joints, key_first, keys12, n_keys, clock_of, n_clocks, inv_bind12, &j, &k);
+    switch (what) {
+    case rig::kRigCounts: return fail(c, TRG_ERR_INVALID, "trg_rig_bind: %u joints, %u keys, %u clocks: none of them may be zero", n_joints, n_keys, n_clocks);
+    case rig::kRigParent: return fail(c, TRG_ERR_INVALID, "trg_rig_bind: joint %u names parent %u: a parent comes before its children (or is 0xFFFFFFFF, a root)", j, parent[j]);
+    case rig::kRigTableFirst: return fail(c, TRG_ERR_INVALID, "trg_rig_bind: joint 0 begins at key %u, not at 0", key_first[0]);
+    case rig::kRigTableOrder: return fail(c, TRG_ERR_INVALID, "trg_rig_bind: joint %u begins at key %u and ends at %u: every joint has a key and the table is strictly ascending", j, key_first[j], key_first[j + 1]);
+    case rig::kRigTableEnd: return fail(c, TRG_ERR_INVALID, "trg_rig_bind: joint %u ends at key %u, there are %u keys", j, key_first[n_joints], n_keys);
+    case rig::kRigTime: return fail(c, TRG_ERR_INVALID, "trg_rig_bind: key %u of joint %u has a time that is not finite or not after the key before it", k, j);
+    case rig::kRigTS: return fail(c, TRG_ERR_INVALID, "trg_rig_bind: key %u of joint %u has a translation or a scale that is not finite", k, j);
+    case rig::kRigQuat: return fail(c, TRG_ERR_INVALID, "trg_rig_bind: key %u of joint %u has a rotation that is not finite or not of unit length within 1e-3", k, j);
+    case rig::kRigClock: return fail(c, TRG_ERR_INVALID, "trg_rig_bind: joint %u names clock %u, there are %u clocks", j, clock_of[j], n_clocks);
+    case rig::kRigInvBind: return fail(c, TRG_ERR_INVALID, "trg_rig_bind: the inverse bind matrix of joint %u is not finite", j);
+    default: break;
+    }
+    std::vector<uint32_t> depth(n_joints), order(n_joints);
+    uint32_t level_first[rig::kMaxLevels + 1], n_levels = 0;
+    if (rig::levels(parent, n_joints, depth.data(), order.data(), level_first, &n_levels, &j) != rig::kRigOk)
+        return fail(c, TRG_ERR_RANGE, "trg_rig_bind: joint %u lies deeper than %u levels (TRG_RIG_MAX_LEVELS)", j, (uint32_t)TRG_RIG_MAX_LEVELS);
+
+    RF_HIPCHK(c, hipSetDevice(c->device));
+    RefitState::Rig &r = state_of(c).rig;
+    r.bound = false; r.evaluated = false;
+    const size_t words = (size_t)n_joints * 4, mats = (size_t)n_joints * 48;
+    int rc = TRG_OK;
+    if ((rc = grow(c, r.parent, words, "rig parents")) || (rc = grow(c, r.order, words, "rig order")) || (rc = grow(c, r.keys, (size_t)n_keys * 48, "rig keys")) ||
+        (rc = grow(c, r.kfirst, words + 4, "rig key ranges")) || (rc = grow(c, r.clock_of, words, "rig clock ids")) || (inv_bind12 && (rc = grow(c, r.inv_bind, mats, "inverse binds"))) ||
+        (rc = grow(c, r.clocks, (size_t)n_clocks * 4, "rig clocks")) || (rc = grow(c, r.world, mats, "world matrices")) || (rc = grow(c, r.bones, mats, "rig bones")))
+        return rc;
+    RF_HIPCHK(c, hipMemcpyAsync(r.parent.p, parent, words, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(r.order.p, order.data(), words, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(r.keys.p, keys12, (size_t)n_keys * 48, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(r.kfirst.p, key_first, words + 4, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(r.clock_of.p, clock_of, words, hipMemcpyHostToDevice, c->stream));
+    if (inv_bind12) RF_HIPCHK(c, hipMemcpyAsync(r.inv_bind.p, inv_bind12, mats, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipStreamSynchronize(c->stream));   // (the caller's arrays, and the bind's own, are free again on return)
+    r.n_joints = n_joints; r.n_keys = n_keys; r.n_clocks = n_clocks; r.n_levels = n_levels;
+    for (uint32_t l = 0; l <= rig::kMaxLevels; ++l) r.level_first[l] = level_first[l];
+    r.has_inv = inv_bind12 != nullptr;
+    r.bound = true;
+    return TRG_OK;
+}
+
+int trg_rig_evaluate(trg_ctx *c, const float *clocks) {
+    RefitState::Rig *r = nullptr;
+    int rc = TRG_OK;
+    if ((rc = rig_of(c, "trg_rig_evaluate", &r)) || (rc = clocks_finite(c, "trg_rig_evaluate", *r, clocks))) return rc;
+    return rig_evaluate(c, *r, clocks);
+}
+
+int trg_rig_read(trg_ctx *c, float *bones12_host, float *world12_host) {
+    RefitState::Rig *r = nullptr;
+    if (int rc = rig_of(c, "trg_rig_read", &r)) return rc;
+    if (!r->evaluated) return fail(c, TRG_ERR_INVALID, "trg_rig_read: the rig has not been evaluated since it was bound");
+    const size_t mats = (size_t)r->n_joints * 48;
+    if (bones12_host) RF_HIPCHK(c, hipMemcpyAsync(bones12_host, r->bones.p, mats, hipMemcpyDeviceToHost, c->stream));
+    if (world12_host) RF_HIPCHK(c, hipMemcpyAsync(world12_host, r->world.p, mats, hipMemcpyDeviceToHost, c->stream));
+    RF_HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TRG_OK;
+}
+
+int trg_rig_buffers(trg_ctx *c, void **bones_dev, void **world_dev) {
+    RefitState::Rig *r = nullptr;
+    if (int rc = rig_of(c, "trg_rig_buffers", &r)) return rc;
+    if (bones_dev) *bones_dev = r->bones.p;
+    if (world_dev) *world_dev = r->world.p;
+    return TRG_OK;
+}
+
+int trg_rig_release(trg_ctx *c) {
+    if (!c) return TRG_ERR_INVALID;
+    if (!c->refit) return TRG_OK;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    RefitState::Rig &r = c->refit->rig;
+    r.each_own([](Buf &buf) { if (buf.p) (void)hipFree(buf.p); buf.p = nullptr; buf.bytes = 0; });
+    r.bound = false; r.evaluated = false;
+    return TRG_OK;
+}
+
+int trg_rig_skin_apply(trg_ctx *c, const float *clocks) {
+    const char *who = "trg_rig_skin_apply";
+    RefitState::Rig *r = nullptr;
+    RefitState::Skin *p = nullptr;
+    int rc = TRG_OK;
+    if ((rc = rig_target(c, who, &RefitState::skin, "trg_skin_bind", &r, &p)) || (rc = rig_counts(c, who, *r, p->n_bones)) || (rc = clocks_finite(c, who, *r, clocks)) ||
+        (rc = rig_evaluate(c, *r, clocks)))
+        return rc;
+    RF_HIPCHK(c, hipMemcpyAsync(p->bones.p, r->bones.p, (size_t)p->n_bones * 48, hipMemcpyDeviceToDevice, c->stream));
+    return skin_run(c, *p);
+}
+
+int trg_rig_morph_apply(trg_ctx *c, const float *target_weights, const float *clocks) {
+    const char *who = "trg_rig_morph_apply";
+    RefitState::Rig *r = nullptr;
+    RefitState::Morph *m = nullptr;
+    int rc = TRG_OK;
+    if ((rc = rig_target(c, who, &RefitState::morph, "trg_morph_bind", &r, &m)) || (rc = morph_has_bones(c, who, *m)) || (rc = rig_counts(c, who, *r, m->n_bones)) ||
+        (rc = morph_weights(c, who, *m, target_weights)) || (rc = clocks_finite(c, who, *r, clocks)) || (rc = rig_evaluate(c, *r, clocks)))
+        return rc;
+    RF_HIPCHK(c, hipMemcpyAsync(m->tw.p, target_weights, (size_t)m->n_targets * 4, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(m->bones.p, r->bones.p, (size_t)m->n_bones * 48, hipMemcpyDeviceToDevice, c->stream));
+    return morph_run(c, *m);
+}
+
+int trg_rig_skin_apply_device(trg_ctx *c, const void *bones12_dev) {
+    const char *who = "trg_rig_skin_apply_device";
+    RefitState::Skin *p = nullptr;
+    if (int rc = device_target(c, who, &RefitState::skin, "trg_skin_bind", &p)) return rc;
+    if (!bones12_dev) return fail(c, TRG_ERR_INVALID, "%s: null bones", who);
+    if (int rc = device_span(c, bones12_dev, (size_t)p->n_bones * 48, "bones", who)) return rc;
+    RF_HIPCHK(c, hipMemcpyAsync(p->bones.p, bones12_dev, (size_t)p->n_bones * 48, hipMemcpyDeviceToDevice, c->stream));
+    return skin_run(c, *p);
+}
+
+int trg_rig_morph_apply_device(trg_ctx *c, const float *target_weights, const void *bones12_dev) {
+    const char *who = "trg_rig_morph_apply_device";
+    RefitState::Morph *m = nullptr;
+    int rc = TRG_OK;
+    if ((rc = device_target(c, who, &RefitState::morph, "trg_morph_bind", &m)) || (rc = morph_has_bones(c, who, *m)) || (rc = morph_weights(c, who, *m, target_weights))) return rc;
+    if (!bones12_dev) return fail(c, TRG_ERR_INVALID, "%s: null bones", who);
+    if ((rc = device_span(c, bones12_dev, (size_t)m->n_bones * 48, "bones", who))) return rc;
+    RF_HIPCHK(c, hipMemcpyAsync(m->tw.p, target_weights, (size_t)m->n_targets * 4, hipMemcpyHostToDevice, c->stream));
+    RF_HIPCHK(c, hipMemcpyAsync(m->bones.p, bones12_dev, (size_t)m->n_bones * 48, hipMemcpyDeviceToDevice, c->stream));
+    return morph_run(c, *m);
+}
+
+int trg_group_rig_bind(trg_group *g, const uint32_t *parent, uint32_t n_joints, const uint32_t *key_first, const float *keys12, uint32_t n_keys, const uint32_t *clock_of,
+                       uint32_t n_clocks, const float *inv_bind12) {
+    return group_each(g, [&](trg_ctx *c) { return trg_rig_bind(c, parent, n_joints, key_first, keys12, n_keys, clock_of, n_clocks, inv_bind12); });
+}
+
+int trg_group_rig_skin_apply(trg_group *g, const float *clocks) {
+    return group_each(g, [&](trg_ctx *c) { return trg_rig_skin_apply(c, clocks); });
+}
+
+int trg_group_rig_morph_apply(trg_group *g, const float *target_weights, const float *clocks) {
+    return group_each(g, [&](trg_ctx *c) { return trg_rig_morph_apply(c, target_weights, clocks); });
 }
 
 int trg_refit_last(trg_ctx *c, trg_refit_info *out) {
