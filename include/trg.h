@@ -356,6 +356,13 @@ TRG_API int trg_debug_room(const float *positions3, const float *normals3, const
                            const uint32_t *material_ids, uint32_t n_verts, uint32_t n_tris, float *room28_out, uint64_t *blob_hash,
                            uint32_t *blob_bytes, uint32_t *lds_candidate);
 
+/* host-only: the rule by which a render launch decides that its light lies inside the scene's room (centre and rows as trg_debug_room reports
+ * them): 1 when all four corners light_pos +- light_right +- light_up of `u` have |l_k| + 2.001e-3 |a_k| <= 1 - 1e-4 on every axis of the frame, in
+ * double, else 0 (a shadow ray ends up to 2e-3 world units from its light sample: it is aimed from the hit point and traced from 1e-3 off it).
+ * The shipped build's any-hit rays then skip the room test in wavefronts whose origins all lie inside the room (TRG_ROOM_INSIDE=0 in the
+ * environment, read at every launch: never). */
+TRG_API int trg_debug_room_light_inside(const float *center3, const float *axis9, const trg_uniforms *u);
+
 /* host-only: the same 4-wide nodes in the 64-byte quantised form the HBM kernels actually load (16 dwords per node:
  * origin.xyz scale.x | qlo.x qhi.x qlo.y qhi.y | qlo.z qhi.z scale.y scale.z | child[4]; one byte per child in each
  * q dword; plane = origin + q * scale).  Node i of this array is node i of trg_debug_build_bvh4. */

@@ -133,6 +133,7 @@ _SYMBOLS = [
     ("trg_debug_boxes", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("trg_debug_flat_attributes", C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_int), _P]),
     ("trg_debug_room", C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("trg_debug_room_light_inside", C.c_int, [_P, _P, _P]),
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 
@@ -580,6 +581,21 @@ def debug_room(positions, normals, colors, indices, material_ids):
     return dict(n_faces=i(0), first_rec=i(1), first_tri=i(2), present=i(3), rest_kind=i(4), rest=i(5), rest_depth=i(6), rest_prims=i(7),
                 center=out[8:11].copy(), axis=out[11:20].reshape(3, 3).copy(), face_rec=out[20:26].astype(np.int64), mask=i(26), depth=i(27),
                 blob_hash=int(h.value), blob_bytes=int(nb.value), lds_candidate=int(cand.value))
+
+
+def debug_room_light_inside(center, axis, uniforms_bytes):
+    """Host-only: does the light rectangle of a 176-byte uniform block lie inside the room with this frame (debug_room's center and axis), by the
+    rule a render launch uses (include/trg.h trg_debug_room_light_inside)?"""
+    L = load()
+    cen = np.ascontiguousarray(center, np.float32).reshape(3)
+    ax = np.ascontiguousarray(axis, np.float32).reshape(9)
+    u = np.frombuffer(bytes(uniforms_bytes), np.uint8).copy()
+    if u.size != 176:
+        raise ValueError("uniforms: 176 bytes expected, got %d" % u.size)
+    rc = L.trg_debug_room_light_inside(_ptr(cen), _ptr(ax), _ptr(u))
+    if rc < 0:
+        raise TrgError(rc, "trg_debug_room_light_inside")
+    return bool(rc)
 
 
 def debug_flat_attributes(normals, colors):

@@ -474,6 +474,7 @@ struct HostScene {
     SceneDesc sc{};                    // offsets; sc.blob is filled in per context
     uint32_t bvh_nodes = 0, bvh_depth = 0, bvh_leaves = 0, bvh_nodes4 = 0, bvh_depth4 = 0, bvh_quads = 0, bvh_boxes = 0;
     uint32_t bvh_room = 0, bvh_walk_depth = 0;   // faces of the room (0: none) and the depth of the part the shipped build walks behind it (bvh_build.h RoomLeaf)
+    float room_center[3] = { 0.f, 0.f, 0.f }, room_axis[3][3] = {};   // the room's frame (RoomLeaf::center, ::axis), as trg_debug_room reports it
     double build_ms = 0.0;
     float lo[3] = { 0.f, 0.f, 0.f }, hi[3] = { 1.f, 1.f, 1.f };   // bounds of the triangles
 };
@@ -828,6 +829,7 @@ int host_scene_build(trg_ctx *c, const float *pos, const float *nrm, const float
     hs->bvh_nodes = bvh.n_nodes; hs->bvh_depth = bvh.depth; hs->bvh_leaves = bvh.n_leaves;
     hs->bvh_quads = bvh.n_quads; hs->bvh_boxes = (lds_candidate || hbm_boxes) ? bvh.n_boxes_real : 0u;
     hs->bvh_room = bvh.room.n_faces; hs->bvh_walk_depth = bvh.room.rest_depth;
+    memcpy(hs->room_center, bvh.room.center, sizeof(hs->room_center)); memcpy(hs->room_axis, bvh.room.axis, sizeof(hs->room_axis));
     hs->bvh_nodes4 = TRG_WIDE8 ? bvh.n_nodes8 : hb.n_nodes4; hs->bvh_depth4 = TRG_WIDE8 ? bvh.depth8 : hb.depth4;
     // the stack is sized by the tree the kernels walk (plan_lds_as): with box leaves in HBM that is the box flavour, another collapse of the same BVH2
     if (!TRG_WIDE8 && hbm_boxes) hs->bvh_depth4 = std::max(hb.depth4, hb.depth4_box);
@@ -853,6 +855,7 @@ int host_scene_upload(trg_ctx *c, const HostScene *hs) {
     c->bvh_nodes = hs->bvh_nodes; c->bvh_depth = hs->bvh_depth; c->bvh_leaves = hs->bvh_leaves;
     c->bvh_quads = hs->bvh_quads; c->bvh_boxes = hs->bvh_boxes;
     c->bvh_room = hs->bvh_room; c->bvh_walk_depth = hs->bvh_walk_depth;
+    memcpy(c->room_center, hs->room_center, sizeof(c->room_center)); memcpy(c->room_axis, hs->room_axis, sizeof(c->room_axis));
     c->bvh_nodes4 = hs->bvh_nodes4; c->bvh_depth4 = hs->bvh_depth4;
     c->scene_loaded = true;
     LdsPlan plan;
@@ -1004,6 +1007,36 @@ static int render_done(trg_ctx *c) {
     return TRG_OK;
 }
 
+// May the shadow rays of a launch under `u` leave the room test out (room frame: l_k = axis[k] . (P - center), the room is |l_k| <= 1)?  A shadow
+// ray does NOT end at its light sample S: the shading event measures direction and distance from the hit point P and traces from o = P + nrm * 1e-3
+// to dist - 1e-3 (trg_kernels.hip shade_event), so the ray ends at E = S + 1e-3 (nrm - dir), up to 2e-3 world units from S in any direction --
+// kRayEndOffset, with 0.05 % for the fp32 lengths of nrm and dir -- which is 2e-3 |axis[k]| on axis k of the frame, more the smaller the room.  The
+// rule, in double: all four corners light_pos +- light_right +- light_up have |l_k| + kRayEndOffset |axis[k]| <= 1 - 1e-4 on every axis.  S is a convex
+// combination of the corners, so every E then has |l_k(E)| <= 1 - 1e-4: the ray of an origin inside the room ends inside it, and its exit plane lies
+// beyond its end by at least 5e-5 of its length at any scene scale (t_exit / t_end = (1 - lo_k) / (l_k(E) - lo_k) >= 1 + 1e-4 / 2), farther than the
+// fp32 rounding of tfar reaches (trg_device.h trav_room_planes).  (The Cornell box's light sits at l_y = 0.98, |axis| = 1.)  NaN anywhere: no.
+constexpr double kRayEndOffset = 2.001e-3;
+static bool room_light_inside(const float center[3], const float axis[3][3], const trg_uniforms &u) {
+    for (int corner = 0; corner < 4; ++corner) {
+        const double sr = (corner & 1) ? 1.0 : -1.0, su = (corner & 2) ? 1.0 : -1.0;
+        double P[3];
+        for (int a = 0; a < 3; ++a) P[a] = (double)u.light_pos[a] + sr * (double)u.light_right[a] + su * (double)u.light_up[a] - (double)center[a];
+        for (int k = 0; k < 3; ++k) {
+            const double ax = axis[k][0], ay = axis[k][1], az = axis[k][2];
+            const double l = ax * P[0] + ay * P[1] + az * P[2];
+            if (!(std::fabs(l) + kRayEndOffset * std::sqrt(ax * ax + ay * ay + az * az) <= 1.0 - 1e-4)) return false;
+        }
+    }
+    return true;
+}
+// RenderParams::room_inside of a launch.  TRG_ROOM_INSIDE=0 in the environment, read per launch as TRG_BVH_ROOM is per scene load: never.
+static uint32_t room_inside_flag(const trg_ctx *c, bool lds_scene) {
+    if (!lds_scene || c->opt_strict || TRG_EXPERIMENTS || c->sc.room_first1 == 0u) return 0u;
+    const char *e = getenv("TRG_ROOM_INSIDE");
+    if (e && atoi(e) == 0) return 0u;
+    return room_light_inside(c->room_center, c->room_axis, c->u) ? 1u : 0u;
+}
+
 static int render_impl(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint32_t bounces, uint32_t row0, uint32_t rows, uint32_t il_n, uint32_t il_r) {
     if (!c->scene_loaded) return fail(c, TRG_ERR_INVALID, "trg_render: no scene loaded");
     if (!c->have_uniforms) return fail(c, TRG_ERR_INVALID, "trg_render: uniforms not set");
@@ -1061,6 +1094,7 @@ static int render_impl(trg_ctx *c, uint32_t frame_begin, uint32_t spp, uint32_t 
     p.fsplit = fsplit; p.fp_rounds = fp_rounds; p.acc_off = plan.acc_off;
     p.il_n = il_n > 1u ? il_n : 0u; p.il_r = il_n > 1u ? il_r : 0u;
     p.tex = c->tex;
+    p.room_inside = room_inside_flag(c, plan.lds_scene);
     // workgroup tile: 16x16 pixels, or (4/fsplit) 8x8 sub-tiles side by side when the frames are split over waves
     const uint32_t tile_w = fsplit > 1 ? 8u * (kWaves / fsplit) : (uint32_t)kTileW, tile_h = fsplit > 1 ? 8u : (uint32_t)kTileH;
     p.tiles_x = (c->w + tile_w - 1) / tile_w;
@@ -1448,6 +1482,13 @@ int trg_debug_room(const float *positions3, const float *normals3, const float *
         o[26] = (float)rm.mask; o[27] = (float)bvh.depth;
     }
     return TRG_OK;
+}
+
+int trg_debug_room_light_inside(const float *center3, const float *axis9, const trg_uniforms *u) {
+    if (!center3 || !axis9 || !u) return TRG_ERR_INVALID;
+    float axis[3][3];
+    memcpy(axis, axis9, sizeof(axis));
+    return room_light_inside(center3, axis, *u) ? 1 : 0;
 }
 
 int trg_debug_build_bvh4q(const float *positions3, const uint32_t *indices, const uint32_t *material_ids, uint32_t n_verts,

@@ -66,6 +66,7 @@ struct trg_ctx {
     bool gpu_built = false;
     uint32_t bvh_nodes = 0, bvh_depth = 0, bvh_leaves = 0, bvh_quads = 0, bvh_boxes = 0;
     uint32_t bvh_room = 0, bvh_walk_depth = 0;   // the room of an LDS-resident scene: its faces (0 = none), and the depth of the part the shipped build walks behind it
+    float room_center[3] = { 0.f, 0.f, 0.f }, room_axis[3][3] = {};   // its frame: l_k = room_axis[k] . (P - room_center), the room is |l_k| <= 1 (render_impl: is the light inside?)
     double last_ms = 0.0, total_ms = 0.0;
     uint32_t renders = 0;
     uint32_t last_fsplit = 1;

@@ -895,26 +895,42 @@ TRG_DEV const v4f *lds_records(const SceneView &sc, uint32_t first);
 // lds_box_hit_resolve names the triangle from the face's own quad rows -- or -1, and `start`, where the walk over the rest begins (word 7 of the
 // face table, read with the mask).  Code and start come out of per-call VGPRs on purpose: as selects on launch constants the compiler keeps each
 // in a register of its own across the whole frame loop, two more than the render kernels have.
-template <bool COUNT>
-TRG_DEV bool trav_room_planes(const SceneView &sc, V3 o, V3 d, float tmax, uint32_t rmask, float &t, int &held, int &start, Counters &cnt) {
+//
+// ANY-HIT RAYS BETWEEN TWO POINTS INSIDE the room (skip_inside, wave-uniform: RenderParams::room_inside).  Every any-hit ray of a render kernel is
+// aimed from a hit point P at a sample S of the light rectangle and traced from P + nrm * 1e-3 to dist - 1e-3: it ends at S + 1e-3 (nrm - dir), up to
+// 2e-3 world units from S.  The host has checked that the launch's light rectangle, grown by that much, lies within |l_k| <= 1 - 1e-4 of this frame
+// (trg_capi.cpp room_light_inside): every such ray ENDS inside the room.  The origin comes into the room's frame first (9 fma, which the test needs
+// anyway), and one ballot asks whether every live lane of the wavefront has |lo_k| <= 1 - 2^-20 on all three axes.  If so the test's answer is known:
+// with that margin |rounded(lo_k ix_k)| < |ix_k| on every axis (a held reciprocal too), so every entry plane lies at t < 0 and the entry candidate is
+// false; the ray is a segment between two points inside a convex body, so its exit plane lies beyond tmax -- by 5e-5 of its length at least, the host's
+// margin, farther than the rounding of tfar reaches -- and the exit candidate is false, whether the face is there or not.  "No hit", the walk's start
+// read as always, and nothing else: no reciprocals, no planes, no face selects.  Otherwise the whole wavefront runs the whole test: no lane diverges
+// and the test has one copy.  A test left out is not counted as a node step (the counters show that it was left out).  Nearest-hit rays and every ray
+// of trg_trace and of the denoiser's guides run the whole test, always.
+constexpr float kRoomInside = 1.0f - 0x1p-20f;
+template <bool ANY, bool COUNT>
+TRG_DEV bool trav_room_planes(const SceneView &sc, V3 o, V3 d, float tmax, uint32_t rmask, bool skip_inside, float &t, int &held, int &start, Counters &cnt) {
     // opaque copy: the room's rows sit at one LDS address for the whole launch, and LICM would hoist their thirteen words out of the bounce and
     // frame loops and keep them in VGPRs across every shading event (the render kernels then spill); re-read per call, as a leaf's are
     uint32_t first = sc.room_first1 - 1u;
     asm volatile("" : "+v"(first));
     const v4f *tr = lds_records(sc, first);
-    const uint32_t meta0 = sc.meta[first];
-    const bool masked_in = (meta0 & rmask) != 0u;   // (one material for all the walls: bvh_build.cpp room_group)
-    // counted as one NODE step (a slab test ahead of the walk, paid by every call like a root's), not as a primitive test: one of those per call would
-    // put a room scene's primitive tests per ray above 1, and the counters' users compare them between trees (fewer with box leaves than without)
-    if (COUNT) { cnt.nodes++; if (mbcnt64(__ballot(1)) == 0) cnt.wnodes++; }
     const v4f b0 = tr[3], b1 = tr[4], b2 = tr[5];
     typedef uint32_t v2u_t __attribute__((ext_vector_type(2)));
     const v2u_t pw = reinterpret_cast<const v2u_t *>(tr + 9)[3];   // words 6, 7 of the face table: the present-face mask, the walk's start
     const uint32_t present = pw.x;
     start = (int)pw.y;
-    const float lox = b0.x * o.x + (b0.y * o.y + (b0.z * o.z + b0.w)), ldx = b0.x * d.x + (b0.y * d.y + b0.z * d.z);
-    const float loy = b1.x * o.x + (b1.y * o.y + (b1.z * o.z + b1.w)), ldy = b1.x * d.x + (b1.y * d.y + b1.z * d.z);
-    const float loz = b2.x * o.x + (b2.y * o.y + (b2.z * o.z + b2.w)), ldz = b2.x * d.x + (b2.y * d.y + b2.z * d.z);
+    const float lox = b0.x * o.x + (b0.y * o.y + (b0.z * o.z + b0.w)), loy = b1.x * o.x + (b1.y * o.y + (b1.z * o.z + b1.w)), loz = b2.x * o.x + (b2.y * o.y + (b2.z * o.z + b2.w));
+    if (ANY && skip_inside && __ballot(!(fmaxf(fmaxf(fabsf(lox), fabsf(loy)), fabsf(loz)) <= kRoomInside)) == 0ull) {   // (a NaN origin is not inside)
+        t = tmax; held = -1;
+        return false;
+    }
+    const uint32_t meta0 = sc.meta[first];
+    const bool masked_in = (meta0 & rmask) != 0u;   // (one material for all the walls: bvh_build.cpp room_group)
+    // counted as one NODE step (a slab test ahead of the walk, paid by every call like a root's), not as a primitive test: one of those per call would
+    // put a room scene's primitive tests per ray above 1, and the counters' users compare them between trees (fewer with box leaves than without)
+    if (COUNT) { cnt.nodes++; if (mbcnt64(__ballot(1)) == 0) cnt.wnodes++; }
+    const float ldx = b0.x * d.x + (b0.y * d.y + b0.z * d.z), ldy = b1.x * d.x + (b1.y * d.y + b1.z * d.z), ldz = b2.x * d.x + (b2.y * d.y + b2.z * d.z);
     float ix, iy, iz;
     rcp3_parallel_safe(ldx, ldy, ldz, ix, iy, iz, true);
     const float mx = -lox * ix, my = -loy * iy, mz = -loz * iz;              // the ray meets the planes l_k = -1, +1 at m_k -+ |1 / ld_k|
@@ -1241,9 +1257,11 @@ TRG_DEV uint32_t lds_node_base(const SceneView &sc) {
 #endif
 
 // Nearest-hit (ANY=false) or any-hit (ANY=true) query for one ray per lane.
+// room_inside (wave-uniform, the any-hit rays of the render kernels only: RenderParams::room_inside): every any-hit ray of this launch ends inside the
+// scene's room, so a wavefront of them that starts inside it leaves the room test out (trav_room_planes); false = the whole test, always
 template <bool ANY, bool COUNT, int BLOCK, bool UNIFIED = false, typename STK>
 TRG_DEV bool traverse(const SceneView &sc, V3 o, V3 d, float tmax_ray, uint32_t rmask, Hit &hit, STK stk,
-                      Counters &cnt) {
+                      Counters &cnt, bool room_inside = false) {
 #if TRG_EXPERIMENTS
     if (!UNIFIED && kShipped && sc.n_flat != 0u) return traverse_flat<ANY, COUNT>(sc, o, d, tmax_ray, rmask, hit, cnt);   // (wave-uniform: a property of the scene)
 #endif
@@ -1253,7 +1271,7 @@ TRG_DEV bool traverse(const SceneView &sc, V3 o, V3 d, float tmax_ray, uint32_t 
     int held = -1, start = 0;
     if (room) {
         float t;
-        in_room = trav_room_planes<COUNT>(sc, o - sc.center, d, tmax_ray, rmask & 3u, t, held, start, cnt);
+        in_room = trav_room_planes<ANY, COUNT>(sc, o - sc.center, d, tmax_ray, rmask & 3u, room_inside, t, held, start, cnt);
         tmax_ray = in_room ? t : tmax_ray;
         asm volatile("" : "+v"(tmax_ray), "+v"(d.x), "+v"(d.y), "+v"(d.z));   // (the reciprocals of trav_begin are formed BEHIND the room test, not next to it)
     }

@@ -141,6 +141,10 @@ struct RenderParams {
     // hands a workgroup to, and no XCD idles behind a slower one.  xq: 8 counters, zeroed before the launch.
     uint32_t *xq;
     uint32_t xq_jobs;
+    // LDS-resident scene with a room, shipped build: 1 = the light rectangle of THIS launch's uniforms lies so far inside the room that every shadow
+    // ray ends inside it (trg_capi.cpp room_light_inside: the ray ends up to 2e-3 from its light sample), so one that starts inside the room cannot
+    // meet it and a wavefront of such rays leaves the room test out (trg_device.h trav_room_planes).  0: the whole test, always (no room, strict build, HBM traversal, TRG_ROOM_INSIDE=0 in the environment).
+    uint32_t room_inside;
 };
 constexpr uint32_t kMicroBandRows = 8;   // = the rows of a wavefront's 8x8 sub-tile: a wavefront never straddles two micro-bands
 constexpr uint32_t kXcdPersist = 64;   // tile order 64 + n: persistent workgroups popping from per-XCD queues over the n x (8 / n) regions (regeneration kernel)

@@ -35,7 +35,7 @@ TRG_DEV void path_segment_lds(const trg::RenderParams &p, const SceneView &sc, S
             primary_ray = rmask == 3u;
             if (so.want_shadow) {
                 Hit sh;
-                const bool occluded = traverse<true, COUNT, trg::kBlock, false>(sc, o, so.sdir, so.smax, 1u, sh, stk, cnt);
+                const bool occluded = traverse<true, COUNT, trg::kBlock, false>(sc, o, so.sdir, so.smax, 1u, sh, stk, cnt, p.room_inside != 0u);
                 if (!occluded) rad = rad + so.scol;
             }
         }
