@@ -95,11 +95,11 @@ def _strict_bars(capi, O, c, scene, rays, what, kernels=HBM_KERNELS, uniforms=No
         c.set_option(capi.OPT_STRICT, 0)
 
 
-def _shipped_bars(capi, O, c, scene, b, rays, what, gpu_build=0, uniforms=None):
+def _shipped_bars(capi, O, c, scene, b, rays, what, gpu_build=0, uniforms=None, w=W, h=H):
     """Shipped build: the frame inside fast_bar against the oracle; trace records against a fresh trg_load_scene of the moved geometry within
     DESIGN section 2's figures (distance 3e-6, weights 2e-5) wherever the two name the same primitive -- and they may name another one only where
-    double precision cannot decide (margin below 1e-5, the rule of tests/test_gpu_parity.py test_intersector)."""
-    ref, _ = O.render(scene, W, H, SPP, BOUNCES, uniforms=uniforms)
+    double precision cannot decide (margin below 1e-5, the rule of tests/test_gpu_parity.py test_intersector).  w, h: the context's size."""
+    ref, _ = O.render(scene, w, h, SPP, BOUNCES, uniforms=uniforms)
     c.set_option(capi.OPT_STRICT, 0)
     c.reset_stats()
     c.render(0, SPP, BOUNCES)
@@ -297,6 +297,9 @@ def test_small_scene_is_rebuilt_and_keeps_its_textures(capi, refit, O):
                     c.set_option(capi.OPT_FORCE_GLOBAL, force_global)
                     assert c.stats().scene_in_lds == 1 - force_global
                     _strict_bars(capi, O, c, scene, rays, "cornell step %d global %d" % (s, force_global), kernels=(("direct", 0, 1),))
+                    if force_global == 0:                                    # the shipped LDS kernels test the room ahead of the tree: the strict build does not know it
+                        assert c.stats().bvh_room == 5
+                        _shipped_bars(capi, O, c, scene, b, rays, "cornell step %d" % s)
                 c.set_option(capi.OPT_FORCE_GLOBAL, 0)
             with pytest.raises(capi.TrgError) as e:                          # the small path refuses what it cannot build from, by name
                 bad = RS.cornell_moved(O, 3)

@@ -460,6 +460,8 @@ def test_cornell_box_bends_through_the_rebuild_and_hands_its_previous_pose_to_th
         want, _ = O.render(RS.oracle_scene(O, moved), w, h, SPP, BOUNCES, offsets=O.pixel_offsets(w, h))
         O.set_trig_mode(O.TRIG_LIBM)
         assert np.array_equal(_bits(got), _bits(want))
+        assert c.stats().bvh_room == 5                                           # the shipped LDS kernels test the room ahead of the tree: the strict build does not know it
+        _shipped_bars(capi, O, c, RS.oracle_scene(O, moved), moved, _rays(O, 291, lo=(-0.95, 0.05, -0.95), hi=(0.95, 1.9, 3.0)), "bent cornell", w=w, h=h)
         dn.temporal_set_previous_scene(c, first[0], first[1], b["indices"])
         want = dn.guides_motion(c, 0)
         dn.temporal_set_previous_scene(c, None, None, None)
